@@ -20,11 +20,19 @@ For the fixed-F workloads the blocks are dealt to the ranks by longest-processin
 GAR.py:76-126; the sum MFGP_ver2023May/ResGP.py:232-246); a rank that owns several blocks overlaps them on its GPU
 (functional.concurrent_blocks from one host thread; the HOGP blocks, whose eigensolver waits on the host after its bulge chasing,
 from `--hogp-slots` host threads with a handle and a stream each: functional.threaded_blocks); one all-reduce(SUM) of the F-vector
-per step.  The default run also times both fixed-F
-workloads for a few steps after the headline and reports them under "sharded", so that one `--gpus N` sweep carries the
-GAR-8 / CIGAR-4 curve next to the headline.
+per step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W]
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and nothing else.  `--full` adds what
+else the benchmark measures and checks: the roofline kernel's launch statistics (event pairs inside the timed region), stage
+times, the same steps again without the event pairs, and -- for the stock headline -- both fixed-F workloads for a few steps
+(reported under "sharded", so that one `--gpus N` sweep carries the GAR-8 / CIGAR-4 curve next to the headline), the training
+step, the per-GPU unit, the small-model training loop, the parity values, the vendor factorisation and the torch-CPU baseline.
+`--dump-outputs DIR` writes what the last timed step handed its caller as DIR/<name>.npy (float64): the F-vector of block values
+(`nll`, or `block_loss` for gar8_hogp) and, with --with-grad, the gradients of rank 0's blocks (`grad_Y`, `grad_w`, `grad_amp`,
+`grad_diag_add`); an array of more than DUMP_MAX_ELEMS entries as a fixed, seeded sample of them.  The inputs are seeded: the
+same arguments give the same inputs in every run.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload W] [--full] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script launches its own N ranks (child processes, one per GPU,
 rendezvous on 127.0.0.1) BEFORE importing torch or touching the GPU; under `python -m torch.distributed.run
@@ -56,6 +64,7 @@ WORKLOADS = {   # name: (F or None = one block per rank, N, D, d, BASELINE confi
     "gar8_hogp": (8, 8192, 8, 4096, 4),
 }
 HOGP_MODES = (64, 64)   # output shape of a gar8_hogp block (prod = d)
+DUMP_MAX_ELEMS = 1 << 20   # --dump-outputs: entries written per array (8 MB of float64); a larger output is sampled
 
 
 def parse_args(argv=None):
@@ -68,8 +77,11 @@ def parse_args(argv=None):
     ap.add_argument("--D", type=int, default=None)
     ap.add_argument("--d", type=int, default=None)
     ap.add_argument("--blocks", type=int, default=None, help="override F of a fixed-F workload (development / --dry)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sharded", action="store_true", help="skip the fixed-F legs after the headline")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beside the headline figure "
+                    "(roofline statistics, stage times, the extra legs, parity, vendor factorisation, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the parity values, vendor factorisation and CPU baseline")
+    ap.add_argument("--no-sharded", action="store_true", help="--full: skip the fixed-F and other legs after the headline")
     ap.add_argument("--cpu-budget-s", type=float, default=40.0, help="wall-clock bound of the CPU baseline leg")
     ap.add_argument("--with-grad", action="store_true", help="time forward + closed-form gradients instead")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl")
@@ -276,6 +288,19 @@ def rel_err(a, b):
     import numpy as np
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(float(np.abs(b).max()), 1e-300))
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  One of more than DUMP_MAX_ELEMS entries is written as the entries
+    at a fixed, seeded, sorted set of flat indices (the same set for the same size), so that two builds compare entry for entry."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def gpu_parity_values(dev, names):
@@ -511,6 +536,7 @@ def run_rank(args):
         return w, amp, dadd
 
     deal = {}     # workload name -> how its blocks were dealt (owner of every block, the evaluation path of every rank)
+    grads_of = {}  # workload name -> () -> the gradients its last step handed the caller, rank's blocks only (--dump-outputs)
 
     def make_workload(name, n=None, D=None, d=None, blocks=None, with_grad=None):
         """-> (step(), F_total, n, D, d, scaling): step() evaluates this rank's blocks and all-reduces the F-vector.
@@ -576,6 +602,7 @@ def run_rank(args):
         nslots = max(1, min(args.slots, len(mine)))
 
         path = block_path(len(mine), args.no_chain_batch)
+        last = {}
 
         def step():
             vals = {}
@@ -595,12 +622,24 @@ def run_rank(args):
                     for i, f in enumerate(mine):
                         with cb.slot(i):
                             vals[f] = F.nlml(data[f][0], data[f][1], w, amp, diag_add=dadd, clamp=1e-30, **F._slot_args())
+            if with_grad:
+                last["vals"] = vals
             joint.zero_()
             for f, v in vals.items():
                 joint[f] = v.detach()
             if world > 1:
                 dist.all_reduce(joint)      # the joint NLML: one 8*F-byte sum over xGMI
             return joint
+
+        def grads():
+            """what `backward()` of the last step's values hands the caller: the gradients the fused call computed in that step"""
+            if not mine:
+                return {}
+            ys = [data[f][1] for f in mine]
+            g = torch.autograd.grad([last["vals"][f] for f in mine], ys + [w, amp, dadd])
+            return {"grad_Y": torch.stack(g[:len(mine)]), "grad_w": g[-3], "grad_amp": g[-2], "grad_diag_add": g[-1]}
+        if with_grad:
+            grads_of[name] = grads
         return step, F_total, n, D, d, scaling
 
     def timed(step, steps, warmup):
@@ -625,24 +664,29 @@ def run_rank(args):
             for kv in args.opt:   # again, now that the handles of the concurrent slots exist
                 key, val = kv.split("=")
                 _lib.set_option(key, float(val), local_rank, all_slots=True)
-    if not args.dry:
+    if args.full and not args.dry:
         # event pairs around every trailing-update launch, on the stream the kernel runs on, inside the timed region (no host
-        # syncs): the contract's live roofline measurement; costs ~0.1 ms of the 29 ms step by A/B (tools/ab_forward.py)
+        # syncs): the live roofline measurement; costs ~0.1 ms of the 29 ms step by A/B (tools/ab_forward.py)
         _lib.set_option("timing", 2, local_rank, all_slots=True)
         _lib.syrk_stats(reset=True, device_index=local_rank, all_slots=True)
     dt, joint = timed(step, args.steps, 0)
     stats, stages = {"flops": 0.0, "ms": 0.0, "launches": 0}, {}
-    if not args.dry:
+    if args.full and not args.dry:
         stats = _lib.syrk_stats(reset=True, device_index=local_rank, all_slots=True)
         _lib.set_option("timing", 0, local_rank, all_slots=True)
-        if WORKLOADS[args.workload][0] is None:
-            _lib.set_option("timing", 1, local_rank)
-            step()
-            stages = _lib.last_timings(local_rank)
-            _lib.set_option("timing", 0, local_rank)
+    if args.dump_outputs and rank == 0:
+        outs = {"block_loss" if args.workload == "gar8_hogp" else "nll": joint.cpu().numpy()}
+        if args.workload in grads_of:
+            outs.update({k: v.detach().cpu().numpy() for k, v in grads_of[args.workload]().items()})
+        dump_outputs(args.dump_outputs, outs)
+    if args.full and not args.dry and WORKLOADS[args.workload][0] is None:
+        _lib.set_option("timing", 1, local_rank)
+        step()
+        stages = _lib.last_timings(local_rank)
+        _lib.set_option("timing", 0, local_rank)
     ms_per_step = dt / args.steps * 1e3
     ms_no_events = None
-    if not args.dry and args.steps >= 4:
+    if args.full and not args.dry and args.steps >= 4:
         # the same steps once more WITHOUT the per-launch event pairs of the live roofline measurement (timing = 0): what the event
         # pairs cost the timed region is stated, not assumed -- `value` stays the timed region's, events included
         dt0, _ = timed(step, args.steps, 0)
@@ -654,9 +698,9 @@ def run_rank(args):
     stock = args.n is None and args.D is None and args.d is None and args.blocks is None
     gpu_ref, vendor = {}, None
 
-    # ---- the fixed-F sharding workloads, a few steps each (default run only) ----------------------------------------
+    # ---- the fixed-F sharding workloads, a few steps each (--full only) ----------------------------------------------
     sharded = {}
-    if args.workload == "headline" and not args.no_sharded and not args.with_grad and (stock or args.dry):
+    if args.full and args.workload == "headline" and not args.no_sharded and not args.with_grad and (stock or args.dry):
         del step
         if not args.dry:
             torch.cuda.empty_cache()
@@ -689,7 +733,7 @@ def run_rank(args):
 
     # ---- the reference's training iteration (forward + every gradient) at C2, C3 and configs[3], a few steps each ------------------
     train_step = {}
-    if args.workload == "headline" and not args.no_sharded and not args.with_grad and stock and not args.dry:
+    if args.full and args.workload == "headline" and not args.no_sharded and not args.with_grad and stock and not args.dry:
         for name in ("c2", "headline", "cigar4"):
             t_step, tF, tn, tD, td, _ = make_workload(name, with_grad=True)
             tsteps, twarm = (10, 3) if name == "c2" else (4, 3)      # (eight hardware queues: the first steps of a chained leg place its streams)
@@ -708,7 +752,7 @@ def run_rank(args):
     # ---- the per-GPU unit of the sharded configs and C2, forward, one block per rank (what one GPU of an 8-GPU gar8 / 4-GPU cigar4
     #      run executes per step: the single-block F.nlml path) --------------------------------------------------------------------
     blocks_leg = {}
-    if args.workload == "headline" and not args.no_sharded and not args.with_grad and stock and not args.dry:
+    if args.full and args.workload == "headline" and not args.no_sharded and not args.with_grad and stock and not args.dry:
         for key, (bn, bD, bd, cfg) in (("c2", (4096, 8, 1, 1)), ("n8192_d1", (8192, 8, 1, None)), ("n8192_d1024", (8192, 8, 1024, 3)),
                                        ("n8192_d4096", (8192, 8, 4096, 4))):
             b_step, bF, _, _, _, _ = make_workload("c2", n=bn, D=bD, d=bd, with_grad=False)
@@ -725,7 +769,7 @@ def run_rank(args):
 
     # ---- the reference's training loop at the sizes its experiments run: K Adam steps per library call, small models in ONE launch ----
     train_small = {}
-    if args.workload == "headline" and not args.no_sharded and not args.with_grad and stock and not args.dry:
+    if args.full and args.workload == "headline" and not args.no_sharded and not args.with_grad and stock and not args.dry:
         from fidelityfusion_amd import kernel as K_
         from fidelityfusion_amd.cigp_v10 import cigp, train_many
         for key, (tn, tD, td, tFm) in (("n128", (128, 5, 1, 1)), ("n32", (32, 5, 1, 1)), ("n64_x16", (64, 5, 1, 16))):
@@ -746,26 +790,18 @@ def run_rank(args):
                                 "what": "cigp_v10.train_many -> ffgp_train_raw: 200 iterations of zero_grad / loss = -negative_log_likelihood / "
                                         "backward / Adam step (FidelityFusion_Models/ResGP.py:78-112) as ONE call, wall clock around the call"}
 
-    if not args.dry and not args.no_cpu_baseline and world == 1 and stock and args.workload in ("headline", "c2"):
+    if args.full and not args.dry and not args.no_cpu_baseline and world == 1 and stock and args.workload in ("headline", "c2"):
         # after every timed leg: the GPU side of the parity columns, and the vendor factorisation as a stated side number
         gpu_ref = gpu_parity_values(dev, ("c2", "headline") if args.workload == "headline" else ("c2",))
         if args.workload in gpu_ref and abs(gpu_ref[args.workload]["ll"] + float(joint[0])) > 1e-9 * abs(float(joint[0])):
             raise SystemExit("bench.py: the timed step's value %r and the drop-in module's %r differ" % (float(joint[0]), gpu_ref[args.workload]["ll"]))
         vendor = vendor_potrf_ms(dev)
     if rank == 0:
-        achieved = stats["flops"] / (stats["ms"] * 1e-3) / 1e12 if stats["ms"] > 0 else 0.0
-        traffic, traffic_src, traffic_err = None, None, None
-        if not args.dry:
-            try:    # a replayed annotation must never cost the measured line (or leave the other ranks in the barrier)
-                traffic, traffic_src = recorded_traffic(n)
-            except Exception as e:   # noqa: BLE001
-                traffic_err = "%s: %s" % (type(e).__name__, e)
         cfg_idx = WORKLOADS[args.workload][4] if stock else None
         out = {
             "metric": "GP NLML+Cholesky throughput (NxN fp64 GF/s, %%MFMA-roofline) at N=%d" % n,
             "value": round(value, 1), "unit": "GF/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3),
-            "ms_per_step_without_launch_events": None if ms_no_events is None else round(ms_no_events, 3),
             "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": "%s: %s NLML %s, ARD kernel, %d block%s of N=%d D=%d d=%d%s"
@@ -783,21 +819,30 @@ def run_rank(args):
             "cpu_affinity": (None if pinned is None else {"rank0_cpus": len(pinned), "first": pinned[0], "last": pinned[-1],
                                                           "source": "NUMA node of the rank's GPU (sysfs)" if gpu_numa_cpus(local_rank) else "even split"}),
             "rccl_ranks": coll["ranks"] if coll["backend"] == "nccl" else 0,
-            "roofline": {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(achieved / FP64_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                         "traffic_unit": "bytes/launch (PMC pass of this command, replayed from the committed profile)",
-                         "traffic_source": traffic_src, "traffic_error": traffic_err,
-                         "traffic_calibration": "2 x FETCH_SIZE checked on this kernel's own loads (profiles/r05a_traffic_calibration.txt): a "
-                                                "k = 16 launch at m = 16384 reads 1082 MB of C tiles by construction and reports 2 x FETCH = "
-                                                "1123 MB (TCC_EA0_RDREQ x 128 B, no 32-B requests); WRITE_SIZE exact (1074.0 vs 1073.7 MB)",
-                         "algorithmic_bytes_per_launch": round(8.0 * stats["flops"] / max(stats["launches"], 1) / 512.0 * (1.0 + 1.0 / 16.0)),
-                         "kernel": ROOFLINE_KERNEL + " (trailing SYRK update of the blocked Cholesky, K = 512)",
-                         "launches": stats["launches"], "avg_launch_ms": round(stats["ms"] / max(stats["launches"], 1), 4),
-                         "avg_launch_gflop": round(stats["flops"] / max(stats["launches"], 1) / 1e9, 3)},
             "whole_path_frac_of_mfma_peak": round(value / world / 1e3 / FP64_MFMA_PEAK_TFLOPS, 4),
-            "stage_ms": {k: round(v, 3) for k, v in stages.items()},
             "nll": float(joint[0]), "joint_nll": float(joint.sum()),
         }
+        if args.full:
+            achieved = stats["flops"] / (stats["ms"] * 1e-3) / 1e12 if stats["ms"] > 0 else 0.0
+            traffic, traffic_src, traffic_err = None, None, None
+            if not args.dry:
+                try:    # a replayed annotation must never cost the measured line (or leave the other ranks in the barrier)
+                    traffic, traffic_src = recorded_traffic(n)
+                except Exception as e:   # noqa: BLE001
+                    traffic_err = "%s: %s" % (type(e).__name__, e)
+            out["ms_per_step_without_launch_events"] = None if ms_no_events is None else round(ms_no_events, 3)
+            out["roofline"] = {"bound": "mfma", "achieved": round(achieved, 2), "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(achieved / FP64_MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+                               "traffic_unit": "bytes/launch (PMC pass of this command, replayed from the committed profile)",
+                               "traffic_source": traffic_src, "traffic_error": traffic_err,
+                               "traffic_calibration": "2 x FETCH_SIZE checked on this kernel's own loads (profiles/r05a_traffic_calibration.txt): a "
+                                                      "k = 16 launch at m = 16384 reads 1082 MB of C tiles by construction and reports 2 x FETCH = "
+                                                      "1123 MB (TCC_EA0_RDREQ x 128 B, no 32-B requests); WRITE_SIZE exact (1074.0 vs 1073.7 MB)",
+                               "algorithmic_bytes_per_launch": round(8.0 * stats["flops"] / max(stats["launches"], 1) / 512.0 * (1.0 + 1.0 / 16.0)),
+                               "kernel": ROOFLINE_KERNEL + " (trailing SYRK update of the blocked Cholesky, K = 512)",
+                               "launches": stats["launches"], "avg_launch_ms": round(stats["ms"] / max(stats["launches"], 1), 4),
+                               "avg_launch_gflop": round(stats["flops"] / max(stats["launches"], 1) / 1e9, 3)}
+            out["stage_ms"] = {k: round(v, 3) for k, v in stages.items()}
         if args.workload == "gar8_hogp":   # blocks return +NLL / (N prod d) each (hogp_simple.py:92-117); s/step is the primary figure
             out["sum_block_loss"] = out.pop("joint_nll")
             out.pop("nll")
@@ -815,7 +860,7 @@ def run_rank(args):
         if vendor is not None:
             out["vendor_potrf_ms"] = dict(vendor, note="torch.linalg.cholesky on this GPU (the reference's own .cuda() path, MFGP_ver2023May/"
                                           "mfgp_demo.py:88-94) vs ffgp_potrf on the same matrix; outside the timed region, never on the product path")
-        if not args.no_cpu_baseline and world == 1 and not args.dry:   # reported on rank 0 of the single-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.dry:   # reported on rank 0 of the single-GPU run only
             out["cpu_baseline"] = cpu_baseline(args.cpu_budget_s, gpu_ref)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -30,7 +30,7 @@ def _expected_joint(F_, n, D, d):
 
 
 def test_self_launch_two_ranks_weak_and_sharded_legs():
-    out = _run("--gpus", "2", "--n", "96")
+    out = _run("--gpus", "2", "--n", "96", "--full")
     assert out["n_gpus"] == 2 and out["scaling"] == "weak" and out["config"]["blocks"] == 2
     assert out["collective"] == {"backend": "gloo", "ranks": 2}
     # every rank of a multi-rank run pins itself to its own slice of the host's CPUs before it touches the GPU (bench.pin_rank)
@@ -77,6 +77,37 @@ def test_runs_as_a_rank_under_an_external_launcher():
     out = _run("--gpus", "1", "--n", "64", env_extra={"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1",
                                                       "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29591"})
     assert out["n_gpus"] == 1
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """without --full the line carries the headline figure and none of the other legs; --dump-outputs writes the F-vector the last
+    timed step computed, the same numbers in every run (seeded inputs)"""
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("out%d" % k))
+        out = _run("--gpus", "2", "--n", "96", "--dump-outputs", d)
+        for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"):
+            assert key in out
+        assert out["steps"] == 2 and out["warmup"] == 1
+        for key in ("sharded", "roofline", "stage_ms", "cpu_baseline"):
+            assert key not in out
+        nll = np.load(os.path.join(d, "nll.npy"))
+        assert nll.dtype == np.float64 and nll.shape == (2,)
+        assert abs(nll.sum() - out["joint_nll"]) <= 1e-12 * abs(out["joint_nll"])
+        assert abs(nll.sum() - _expected_joint(2, 96, 16, 1)) < 1e-9 * abs(out["joint_nll"])
+        dumps.append(nll)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_samples_a_large_array_the_same_way_every_time(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    big = np.arange(3 * bench.DUMP_MAX_ELEMS, dtype=np.float64).reshape(3, -1)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {"big": big, "small": big[0, :5]})
+    a, b = (np.load(str(tmp_path / str(k) / "big.npy")) for k in range(2))
+    assert a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b) and np.all(np.diff(a) > 0)   # distinct entries, in order
+    assert np.array_equal(np.load(str(tmp_path / "0" / "small.npy")), big[0, :5])
 
 
 def test_world_size_mismatch_is_an_error_not_a_hang():
@@ -194,7 +225,7 @@ def test_eight_rank_dry_run_deals_one_block_per_gpu():
     """`bench.py --gpus 8 --dry --backend gloo`: the launch the driver makes on an 8-GPU node, on CPU.  gar8 (BASELINE configs[4]) puts
     exactly ONE block on every rank and every rank takes the single-block path (F.nlml -- the `blocks` leg of the 1-GPU line prices
     that unit); cigar4 (configs[3]) gives four ranks one block each and leaves four idle; the joint values are the 1-rank values"""
-    out = _run("--gpus", "8", "--n", "64")
+    out = _run("--gpus", "8", "--n", "64", "--full")
     assert out["n_gpus"] == 8 and out["collective"] == {"backend": "gloo", "ranks": 8}
     assert out["config"]["owner"] == list(range(8)) and out["config"]["rank_paths"] == ["single"] * 8
     g8, c4, hg = out["sharded"]["gar8"], out["sharded"]["cigar4"], out["sharded"]["gar8_hogp"]
@@ -204,7 +235,7 @@ def test_eight_rank_dry_run_deals_one_block_per_gpu():
     assert abs(g8["joint_nll"] - _expected_joint(8, 64, 8, 8)) < 1e-9 * abs(g8["joint_nll"])
     assert abs(c4["joint_nll"] - _expected_joint(4, 64, 8, 8)) < 1e-9 * abs(c4["joint_nll"])
     # four ranks: cigar4 one block per GPU, gar8 two per GPU through ONE shared chain
-    out = _run("--gpus", "4", "--n", "64")
+    out = _run("--gpus", "4", "--n", "64", "--full")
     assert out["sharded"]["cigar4"]["rank_paths"] == ["single"] * 4
     assert out["sharded"]["gar8"]["rank_paths"] == ["chain"] * 4 and out["sharded"]["gar8_hogp"]["rank_paths"] == ["threads"] * 4
 
@@ -234,7 +265,7 @@ def test_roofline_flops_count_every_block_of_a_shared_chain():
         for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cigar4", "--blocks", str(blocks), "--steps", "2",
-                            "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                            "--warmup", "1", "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, p.stderr[-2000:]
         return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
     one, four = run(1), run(4)

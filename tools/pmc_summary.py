@@ -21,7 +21,7 @@ def main(out, dirs):
         for k in c.values():
             k["per_launch"] = k["sum"] / max(1, k["launches"])
     doc = {
-        "command": "rocprofv3 --pmc <counters> --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline "
+        "command": "rocprofv3 --pmc <counters> --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
                    "(separate passes: FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE)",
         "units": "FETCH_SIZE/WRITE_SIZE in KiB as reported by rocprofv3; on gfx950 FETCH_SIZE counts 64 B per 128-B request "
                  "for 16-B/lane streams: double it (MI355X_MICROARCH.md, HBM)",
