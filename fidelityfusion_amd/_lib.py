@@ -18,7 +18,7 @@ log = logging.getLogger("fidelityfusion_amd")
 import torch  # noqa: F401  (device memory, streams)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.environ.get("FFGP_LIB") or os.path.join(_HERE, "libffgp.so")   # FFGP_LIB: development builds (tools/)
+_SO = os.environ.get("FFGP_LIB") or os.path.join(_HERE, "libffgp.so")   # FFGP_LIB: another build of the library (tools/)
 
 FFGP_LL_V1, FFGP_LL_V2 = 1, 2
 FFGP_VAR_FULL, FFGP_VAR_DIAG = 0, 1
@@ -174,8 +174,7 @@ lib = _load()
 
 
 def has_dev_options():
-    """True for the development build (`make -C fidelityfusion_amd/csrc dev`, loaded through FFGP_LIB): the switches of
-    measured-and-rejected experiments are compiled in; the shipped library refuses their keys"""
+    """Always False: ffgp_has_dev_options() returns 0 since the development build was retired (kept for existing callers)"""
     return bool(lib.ffgp_has_dev_options())
 
 _handles = {}

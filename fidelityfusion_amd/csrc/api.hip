@@ -123,28 +123,19 @@ static void stage_collect(ffgp_handle* h) {
 
 extern "C" {
 
-#ifdef FFGP_DEV_OPTIONS
-const char* ffgp_version(void) { return "ffgp 0.6-dev (gfx950, fp64 MFMA; development build: the options of measured-and-rejected experiments are compiled in)"; }
-int ffgp_has_dev_options(void) { return 1; }
-#else
 const char* ffgp_version(void) { return "ffgp 0.6 (gfx950, fp64 MFMA)"; }
-int ffgp_has_dev_options(void) { return 0; }
-#endif
+int ffgp_has_dev_options(void) { return 0; }   // (always 0: kept for existing bindings)
 
 long ffgp_graph_replays(const ffgp_handle* h) { return h ? h->graph_replays : -1; }
 
-struct RawGraph {
+struct RawGraph {          // the captured forward call (option "fwd_graph", nlml_fused_enqueue)
   ffgp_problem p;
-  ffgp_links l;
-  long off[6];            // offsets (doubles) of g_w, g_amp, g_diag_add, g_kparam, g_Y, g_diag_vec inside the caller's block; -1 = absent
-  long len;               // length of the caller's gradient block
   unsigned long epoch;
   int seen;               // 1 = this signature was enqueued plainly last time (buffers are warm): capture next
   hipGraph_t graph;
   hipGraphExec_t exec;
   bool valid;
-  double* stage;          // [1 + len]: value | gradient block
-  long stage_len;
+  double* stage;          // the value the graph writes
 };
 
 static void rawg_drop_one(RawGraph* r) {
@@ -157,10 +148,7 @@ static void rawg_drop_one(RawGraph* r) {
   r->seen = 0;
 }
 
-static void rawg_drop(ffgp_handle* h) {
-  rawg_drop_one(h->rawg);
-  rawg_drop_one(h->fwdg);
-}
+static void rawg_drop(ffgp_handle* h) { rawg_drop_one(h->fwdg); }
 
 static int create_resources(ffgp_handle* h) {
   FFGP_HIP(hipStreamCreate(&h->stream));
@@ -280,20 +268,15 @@ int ffgp_create(int device, ffgp_handle** out) {
   h->batch_grad_ob = 1;
   h->tile32_threshold = 1024;
   h->polite_m = 6144;
-  h->polite_pad_kb = 40;
   h->split_rem_max = 180;
-  h->band_log2 = 3;
   h->super_block = 1024;
   h->splitk_min_k = 1024;
   h->skinny_max_n = 8;
   h->super_min_n = 2048;
-  h->la_split = 1;
   h->la_carry = 2;
   h->la_carry_n = 12288;
   h->la_carry_rows = 8192;
   h->la_min_n = 1024;
-  h->pass_split_min = 0;        // (measured and lost, docs/experiments.md: 0 = the passenger rows ride in the chain's launches)
-  h->tail_mask_cus = 8;
   h->chase_xl = 1;
   h->chase_xl_max_n = 2048;
   {   // (handles of one process prefer different XCDs: blocks in flight from several host threads do not crowd one)
@@ -319,14 +302,11 @@ int ffgp_create(int device, ffgp_handle** out) {
   h->trsm128_max_m = 8192;
   h->trtri_overlap = 1;
   h->trtri_fill = 0;
-  h->raw_graph_max_n = 0;
   h->fwd_graph = 0;
   h->graph_replays = 0;
   h->fwdg = nullptr;
   h->small2_off = 1;
-  h->q2_wave4 = 1;
   h->q2_split_min_cols = 8192;
-  h->sb_qr4 = 0;
   h->sb_lower = 1;
   h->sb_lower_min_n = 6144;
   h->sb_sym_wg = 2048;
@@ -362,14 +342,9 @@ int ffgp_destroy(ffgp_handle* h) {
   if (h->d_link) hipFree(h->d_link);
   if (h->aux2) hipStreamDestroy(h->aux2);
   if (h->aux3) hipStreamDestroy(h->aux3);
-  if (h->masked) hipStreamDestroy(h->masked);
   if (h->ev_switch) hipEventDestroy(h->ev_switch);
-  for (int i = 0; i < 4; ++i)
-    if (h->sb_ev[i]) hipEventDestroy(h->sb_ev[i]);
   for (int i = 0; i < 2; ++i)
     if (h->tri_ev[i]) hipEventDestroy(h->tri_ev[i]);
-  for (int i = 0; i < 12; ++i)
-    if (h->eig_ev[i]) hipEventDestroy(h->eig_ev[i]);
   if (h->d_info) hipFree(h->d_info);
   if (h->ho_mem) hipFree(h->ho_mem);
   if (h->bt_info) hipFree(h->bt_info);
@@ -382,7 +357,6 @@ int ffgp_destroy(ffgp_handle* h) {
   if (h->small_kbuf) hipFree(h->small_kbuf);
   if (h->train_tab) hipFree(h->train_tab);
   if (h->train_host) hipHostFree(h->train_host);
-  if (h->pack_buf) hipFree(h->pack_buf);
   ffgp_assemble_collect_free(h);
   if (h->bt_info_host) hipHostFree(h->bt_info_host);
   if (h->d_scal) hipFree(h->d_scal);
@@ -392,11 +366,6 @@ int ffgp_destroy(ffgp_handle* h) {
     if (h->fwdg->stage) hipFree(h->fwdg->stage);
     delete h->fwdg;
     h->fwdg = nullptr;
-  }
-  if (h->rawg) {
-    if (h->rawg->stage) hipFree(h->rawg->stage);
-    delete h->rawg;
-    h->rawg = nullptr;
   }
   if (h->h_info) hipHostFree(h->h_info);
   if (h->h_scal) hipHostFree(h->h_scal);
@@ -433,19 +402,7 @@ int ffgp_set_stream(ffgp_handle* h, void* s) {
 int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
   if (!h || !key) return FFGP_ERR_ARG;
   rawg_drop(h);      // a captured call baked the old options in
-#ifndef FFGP_DEV_OPTIONS
-  // The shipped library keeps the switches a binding or a deployment tunes (thresholds, block sizes, the on-device cross-check,
-  // timing).  The switches of experiments that were measured and lost (docs/experiments.md) exist in the development build only
-  // (`make dev` -> libffgp_dev.so, ffgp_has_dev_options() == 1); here their keys are refused like any unknown key.
-  static const char* const dev_only[] = {"raw_graph_max_n", "diag_dbg", "la_split", "nb_big", "nb_big_until", "sb_lookahead", "sb_av_gemm", "sb_qr4", "q2_wave4", "eig_overlap", "band_log2", "polite_pad_kb", "pass_split_min", "tail_mask_m", "tail_mask_cus", "syrk_h64", "syrk_direct"};
-  for (const char* k : dev_only)
-    if (!strcmp(key, k)) return FFGP_ERR_ARG;
-  if (!strcmp(key, "diag_v2") && value != 4.0 && value != 0.0) return FFGP_ERR_ARG;   // (the round-3 pipelines: development build)
-#endif
-  if (!strcmp(key, "raw_graph_max_n")) {
-    h->raw_graph_max_n = (int)value;
-    return FFGP_OK;
-  }
+  // (the switches of experiments that were measured and lost, docs/experiments.md, are gone: their keys are refused like any unknown key)
   if (!strcmp(key, "timing")) {
     h->timing = (int)value;
   } else if (!strcmp(key, "nb_outer")) {
@@ -496,11 +453,8 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
   } else if (!strcmp(key, "trsm128_max_m")) {
     h->trsm128_max_m = (int)value;
   } else if (!strcmp(key, "diag_v2")) {
+    if (value != 4.0 && value != 0.0) return FFGP_ERR_ARG;
     h->diag_v2 = (int)value;
-  } else if (!strcmp(key, "diag_dbg")) {
-    h->diag_dbg = (int)value;
-  } else if (!strcmp(key, "la_split")) {
-    h->la_split = (int)value;
   } else if (!strcmp(key, "la_min_n")) {
     h->la_min_n = (int)value;
   } else if (!strcmp(key, "chase_xl")) {
@@ -515,22 +469,6 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
   } else if (!strcmp(key, "chase_xcc")) {
     if (value < 0 || value > 15) return FFGP_ERR_ARG;
     h->chase_xcc = (int)value;
-  } else if (!strcmp(key, "syrk_direct")) {
-    h->syrk_direct = (int)value;
-  } else if (!strcmp(key, "syrk_h64")) {
-    h->syrk_h64 = (int)value;
-  } else if (!strcmp(key, "tail_mask_m")) {
-    h->tail_mask_m = (int)value;
-  } else if (!strcmp(key, "tail_mask_cus")) {
-    if (value < 1 || value > 31) return FFGP_ERR_ARG;
-    if ((int)value != h->tail_mask_cus && h->masked) {      // another mask: the stream is rebuilt at its next use
-      hipStreamSynchronize(h->masked);
-      hipStreamDestroy(h->masked);
-      h->masked = nullptr;
-    }
-    h->tail_mask_cus = (int)value;
-  } else if (!strcmp(key, "pass_split_min")) {
-    h->pass_split_min = (int)value;
   } else if (!strcmp(key, "la_carry")) {
     h->la_carry = (int)value;
   } else if (!strcmp(key, "la_carry_n")) {
@@ -543,17 +481,8 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
     h->lookahead = (int)value;
   } else if (!strcmp(key, "polite_m")) {
     h->polite_m = (int)value;
-  } else if (!strcmp(key, "polite_pad_kb")) {
-    if (value < 17 || value > 90) return FFGP_ERR_ARG;   // > 16: two padded workgroups must not fit a CU (2 x (64 + pad) > 160)
-    h->polite_pad_kb = (int)value;
   } else if (!strcmp(key, "split_rem_max")) {
     h->split_rem_max = (int)value;
-  } else if (!strcmp(key, "nb_big")) {
-    const int v = (int)value;
-    if (v != 0 && (v < FFGP_NB || v % FFGP_NB)) return FFGP_ERR_ARG;
-    h->nb_big = v;
-  } else if (!strcmp(key, "nb_big_until")) {
-    h->nb_big_until = (int)value;
   } else if (!strcmp(key, "super_block")) {
     const int v = (int)value;
     if (v != 0 && (v < 2 * FFGP_NB || (v & (v - 1)))) return FFGP_ERR_ARG;   // 0, or a power of two >= 256
@@ -566,8 +495,6 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
     h->asm_mm_grid = (int)value;
   } else if (!strcmp(key, "asm_mm_min")) {
     h->asm_mm_min = (int)value;
-  } else if (!strcmp(key, "sb_lookahead")) {
-    h->sb_lookahead = (int)value;
   } else if (!strcmp(key, "trtri_fill")) {
     h->trtri_fill = (int)value;
   } else if (!strcmp(key, "trtri_overlap")) {
@@ -582,20 +509,12 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
   } else if (!strcmp(key, "sb_sym_wg")) {
     if (value < 64 || value > 65536) return FFGP_ERR_ARG;
     h->sb_sym_wg = (int)value;
-  } else if (!strcmp(key, "sb_av_gemm")) {
-    h->sb_av_gemm = (int)value;
-  } else if (!strcmp(key, "sb_qr4")) {
-    h->sb_qr4 = (int)value;
   } else if (!strcmp(key, "q2_split_min_cols")) {
     h->q2_split_min_cols = (int)value;
-  } else if (!strcmp(key, "q2_wave4")) {
-    h->q2_wave4 = (int)value;
   } else if (!strcmp(key, "small_finish")) {
     h->small2_off = (value == 0.0) ? 1 : 0;
   } else if (!strcmp(key, "small_fused")) {
     h->small_off = (value == 0.0) ? 1 : 0;
-  } else if (!strcmp(key, "eig_overlap")) {
-    h->eig_overlap = (int)value;
   } else if (!strcmp(key, "chase_pack")) {
     h->chase_pack = (int)value;
   } else if (!strcmp(key, "skinny_max_n")) {
@@ -604,10 +523,6 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
     h->splitk_min_k = (int)value;
   } else if (!strcmp(key, "super_min_n")) {
     h->super_min_n = (int)value;
-  } else if (!strcmp(key, "band_log2")) {
-    if (value < 0 || value > 6) return FFGP_ERR_ARG;
-    h->band_log2 = (int)value;
-
   } else {
     return FFGP_ERR_ARG;
   }
@@ -998,7 +913,7 @@ static int ffgp_grad_lanes_prepare(ffgp_handle* h, int nl) {
 int ffgp_nlml_fused_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g,
                           int* status) {
   if (!h || !p || !nll_dev || F < 2 || F > 256) return FFGP_ERR_ARG;
-  if (h->use_naive || h->diag_v2 != 4 || h->diag_dbg) return FFGP_ERR_ARG;
+  if (h->use_naive || h->diag_v2 != 4) return FFGP_ERR_ARG;
   bool want_grad = false, uniform = true;
   for (int f = 0; f < F; ++f) {
     const ffgp_problem& q = p[f];
@@ -1013,7 +928,6 @@ int ffgp_nlml_fused_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ff
     }
   }
   if (!uniform) {      // members of different sizes: the ragged chain's own limits (ffgp_potrf_ragged)
-    if (h->nb_big > h->nb_outer) return FFGP_ERR_ARG;
     for (int f = 0; f < F; ++f)
       if (h->lookahead && p[f].n > h->nb_outer && p[f].n > h->la_min_n && !(h->la_carry == 1 || (h->la_carry == 2 && p[f].n <= h->la_carry_n)))
         return FFGP_ERR_ARG;
@@ -1308,8 +1222,6 @@ int ffgp_nlml_fused_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ff
 // mul + addcmul, bias corrections computed on the host with the C library's pow as Python does, sqrt / div / add eps, addcdiv) and
 // stores the step's loss in the trace.  No host synchronisation inside the loop; the factorisation status is sticky and read once
 // at the end (the first step whose Sigma was not positive definite; the parameters stop moving from that step on).
-static int nlml_fused_raw_plain(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g);
-
 __global__ void ffgp_adam_kernel(int F, ffgp_train_slot sl, const double* __restrict__ gbuf, double* __restrict__ state, long state_stride,
                                  double lr, double b1, double b2, double eps, double bc1, double bc2_sqrt, const double* __restrict__ loss,
                                  double* __restrict__ trace, long trace_stride, int step, int* __restrict__ info, int fold,
@@ -1410,7 +1322,7 @@ int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_link
       if ((lrc = ffgp_small_batch_enqueue(h, F, p, lk.data(), loss, g.data())) != FFGP_OK) break;
       hipLaunchKernelGGL(ffgp_sticky_info_kernel, dim3(1), dim3(1), 0, h->stream, h->d_info);
     } else {
-      for (int f = 0; f < F && lrc == FFGP_OK; ++f) lrc = nlml_fused_raw_plain(h, p + f, &lk[f], loss + f, &g[f]);
+      for (int f = 0; f < F && lrc == FFGP_OK; ++f) lrc = nlml_fused_raw_enqueue(h, p + f, &lk[f], loss + f, &g[f]);
       if (lrc != FFGP_OK) break;
     }
     const double t = (double)(step0 + k + 1);
@@ -1432,120 +1344,12 @@ int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_link
   return ffgp_wait(h);
 }
 
-// ---- launch-bound sizes: the whole call as one captured graph ---------------------------------------------------------------
-// At N = 128 a likelihood + gradient call is 21 launches of 2-30 us kernels: the host's launch cost (~5 us each) and the gaps
-// between dependent kernels are most of it.  When the SAME call (same inputs, sizes, links, options -- a training loop) arrives
-// a second time it is captured into a hipGraph writing to a handle-owned staging block, and from then on replayed with one
-// hipGraphLaunch plus one small copy into the caller's (fresh) output buffers.  The cache holds one graph per handle and is
-// dropped when the signature, an option or any of the handle's device buffers changes.
-// MEASURED (tools/raw_graph_bench.py, ROCm 7.2): the replay is no faster than the launches it replaces -- a training step at
-// N = 64 / 128 / 256 / 512 takes 0.316 / 0.260 / 0.341 / 0.498 ms with it against 0.244 / 0.249 / 0.337 / 0.484 ms without
-// (this runtime issues a graph's kernel nodes one by one with its own barriers) -- so it is OFF by default
-// (option "raw_graph_max_n" = 0); the values are bit-identical either way (test_raw_graph_replay).
+// copies a captured graph's staged outputs (value, then an optional gradient block) into the caller's buffers (the forward graph
+// below)
 __global__ void ffgp_rawg_copy_out(const double* __restrict__ stage, long len, double* __restrict__ nll, double* __restrict__ gbase) {
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   if (t == 0) nll[0] = stage[0];
   if (t < len) gbase[t] = stage[1 + t];
-}
-
-static int nlml_fused_raw_plain(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g);
-
-// the caller's gradient pointers as one block [base, base + len): true when they are laid out in the order w | amp | diag_add |
-// kparam | Y | diag_vec without overlap (functional._NLMLRaw allocates them that way)
-static bool rawg_block(const ffgp_problem* p, const ffgp_grads* g, long off[6], long* len, double** base) {
-  if (!g || g->g_cov_dev || g->g_pair) return false;
-  double* ptr[6] = {g->g_w_dev, g->g_amp_dev, g->g_diag_add_dev, g->g_kparam_dev, g->g_Y_dev, g->g_diag_vec_dev};
-  const long cnt[6] = {p->D, 1, 1, 1, (long)p->n * p->d, p->n};
-  double* b = nullptr;
-  long end = 0;
-  for (int i = 0; i < 6; ++i) {
-    off[i] = -1;
-    if (!ptr[i]) continue;
-    if (!b) b = ptr[i];
-    const long o = (long)(ptr[i] - b);
-    if (o < end || o > end + 4096) return false;
-    off[i] = o;
-    end = o + cnt[i];
-  }
-  if (!b) return false;
-  *base = b;
-  *len = end;
-  return true;
-}
-
-static int nlml_fused_raw_enqueue(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g) {
-  if (!h || !p || !l || !nll_dev) return FFGP_ERR_ARG;
-  long off[6], len = 0;
-  double* base = nullptr;
-  const bool eligible = h->raw_graph_max_n > 0 && p->n <= h->raw_graph_max_n && h->timing == 0 && !p->cov_dev && !p->pair && !p->tree &&
-                        !ffgp_small_ok(h, p, g) && rawg_block(p, g, off, &len, &base);
-  if (!eligible) return nlml_fused_raw_plain(h, p, l, nll_dev, g);
-  if (!h->rawg) {
-    h->rawg = new RawGraph();
-    memset(h->rawg, 0, sizeof(RawGraph));
-  }
-  RawGraph* r = h->rawg;
-  const bool same = (r->seen || r->valid) && !memcmp(&r->p, p, sizeof(ffgp_problem)) && !memcmp(&r->l, l, sizeof(ffgp_links)) &&
-                    !memcmp(r->off, off, sizeof(off)) && r->len == len && r->epoch == h->alloc_epoch;
-  if (same && r->valid) {
-    FFGP_HIP(hipSetDevice(h->device));
-    FFGP_HIP(hipGraphLaunch(r->exec, h->stream));
-    hipLaunchKernelGGL(ffgp_rawg_copy_out, dim3((unsigned)((len > 0 ? len : 1) + 255) / 256), dim3(256), 0, h->stream, r->stage, len, nll_dev,
-                       base);
-    ffgp_invalidate(h);     // the replay rebuilt the handle's cached inverses on the device; the host-side keys do not know
-    if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-    return FFGP_OK;
-  }
-  if (!same) {              // first sight of this call: run it plainly (sizes every buffer), remember it
-    rawg_drop(h);
-    const int rc = nlml_fused_raw_plain(h, p, l, nll_dev, g);
-    r->p = *p;
-    r->l = *l;
-    memcpy(r->off, off, sizeof(off));
-    r->len = len;
-    r->epoch = h->alloc_epoch;
-    r->seen = (rc == FFGP_OK) ? 1 : 0;
-    return rc;
-  }
-  // second sight: capture
-  FFGP_HIP(hipSetDevice(h->device));
-  if (r->stage_len < len + 1) {
-    if (r->stage) hipFree(r->stage);
-    r->stage = nullptr;
-    r->stage_len = 0;
-    FFGP_HIP(hipMalloc(&r->stage, (size_t)(len + 1) * sizeof(double)));
-    r->stage_len = len + 1;
-  }
-  ffgp_grads gs = *g;
-  double** gp[6] = {&gs.g_w_dev, &gs.g_amp_dev, &gs.g_diag_add_dev, &gs.g_kparam_dev, &gs.g_Y_dev, &gs.g_diag_vec_dev};
-  for (int i = 0; i < 6; ++i) *gp[i] = (off[i] >= 0) ? r->stage + 1 + off[i] : nullptr;
-  r->seen = 0;
-  if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();
-    return nlml_fused_raw_plain(h, p, l, nll_dev, g);
-  }
-  const int rc = nlml_fused_raw_plain(h, p, l, r->stage, &gs);
-  hipGraph_t graph = nullptr;
-  const hipError_t ec = hipStreamEndCapture(h->stream, &graph);
-  if (rc != FFGP_OK || ec != hipSuccess || !graph || r->epoch != h->alloc_epoch) {
-    (void)hipGetLastError();
-    if (graph) hipGraphDestroy(graph);
-    return nlml_fused_raw_plain(h, p, l, nll_dev, g);
-  }
-  hipGraphExec_t exec = nullptr;
-  if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-    (void)hipGetLastError();
-    hipGraphDestroy(graph);
-    return nlml_fused_raw_plain(h, p, l, nll_dev, g);
-  }
-  r->graph = graph;
-  r->exec = exec;
-  r->valid = true;
-  FFGP_HIP(hipGraphLaunch(r->exec, h->stream));
-  hipLaunchKernelGGL(ffgp_rawg_copy_out, dim3((unsigned)((len > 0 ? len : 1) + 255) / 256), dim3(256), 0, h->stream, r->stage, len, nll_dev, base);
-  ffgp_invalidate(h);
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-  return FFGP_OK;
 }
 
 // 40 < n <= 128 (one diagonal block): assemble and factor with the blocked path's kernels, then ONE finishing kernel (small.hip,
@@ -1575,7 +1379,7 @@ static int small2_enqueue(ffgp_handle* h, const ffgp_problem* p, const ffgp_link
   return FFGP_OK;
 }
 
-static int nlml_fused_raw_plain(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g) {
+static int nlml_fused_raw_enqueue(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g) {
   if (!h || !p || !l || !nll_dev) return FFGP_ERR_ARG;
   if (p->cov_dev || p->pair || p->tree || !p->w_dev || !p->amp_dev || p->D <= 0 || p->D > 128) return FFGP_ERR_ARG;
   FFGP_HIP(hipSetDevice(h->device));
@@ -1678,7 +1482,6 @@ static int nlml_fused_enqueue(ffgp_handle* h, const ffgp_problem* p, double* nll
   }
   if (!r->stage) {
     FFGP_HIP(hipMalloc(&r->stage, 2 * sizeof(double)));
-    r->stage_len = 2;
   }
   r->seen = 0;
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
@@ -1776,7 +1579,7 @@ static int nlml_fused_plain(ffgp_handle* h, const ffgp_problem* p, double* nll_d
   // forward + gradients of a large block: the head of the triangular inverse (everything that only needs the factor's first n1s
   // columns: 3/4 of its flops) runs on a third stream under the factorisation's chain-bound tail
   int n1s = 0;
-  if (want_grad && h->trtri_overlap && h->lookahead && !h->use_naive && n >= 4096 && n > h->la_min_n && h->nb_big <= h->nb_outer) {
+  if (want_grad && h->trtri_overlap && h->lookahead && !h->use_naive && n >= 4096 && n > h->la_min_n) {
     n1s = FFGP_NB;
     while (2 * n1s < n) n1s *= 2;
     if (n1s % h->nb_outer != 0) n1s = 0;

@@ -1,4 +1,4 @@
-// The in-register 16 x 16 pivot step of the diagonal-block kernel (potrf.hip, ffgp_potrf_diag128_v2) and its lane primitives: a header
+// The in-register 16 x 16 pivot step of the diagonal-block kernel (potrf.hip, the pipelined kernels) and its lane primitives: a header
 // of their own so that tools/native/f16_probe.hip can time the bare pivot loop with the very same code.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -152,7 +152,7 @@ struct ffgp_handle {
   hipStream_t stream;   // stream work is enqueued on (caller's, or `own`)
   hipStream_t own;      // the handle's own stream
   hipStream_t aux;      // high-priority side stream for the look-ahead panel factorisation
-  hipEvent_t la_ev[10]; // look-ahead hand-off events ([7], [8]: carry mode's "strip Z(k) has run", main -> side stream)
+  hipEvent_t la_ev[10]; // look-ahead hand-off events ([0..5]: eb / eg / ei of two iterations, [6]: the chain's start; [7..9] unused)
   unsigned* ho_mem;     // one word (64 bytes apart) per look-ahead event: the hand-off as hipStreamWriteValue32 / hipStreamWaitValue32 (potrf.hip)
   unsigned ho_seq[10];  // ... the number its latest "record" wrote
   unsigned ho_launched[10];   // ... the newest number whose producing operation has been ENQUEUED (submission-order rule, la_wait)
@@ -185,9 +185,7 @@ struct ffgp_handle {
   int polite64_pad_kb;  // unused LDS (KiB) requested by the look-ahead's 64-tile trailing updates (default 60: two workgroups per CU instead of four)
   int trsm128;          // 1 = the chain's full-block TRSM runs on its own kernel (ffgp_trsm128_kernel; same values as the general GEMM)
   int trsm128_max_m;    // ... for panels of at most this many rows (taller ones stay on the general GEMM)
-  int diag_dbg;         // timing-only ablation mask of potrf_diag128 (0 in production)
-  int diag_v2;          // diagonal-block kernel: 4 = round-4 kernel (default: owner-computes helpers, wave 0's SIMD partner steps aside), 1 = round-3 pipeline with the DP-ALU DPP pivot step, 3 = round-3 pipeline as it was, 0 = barrier version
-  int la_split;         // 1 = issue the look-ahead part of the trailing update in two launches (first 128 columns first)
+  int diag_v2;          // diagonal-block kernel: 4 = round-4 kernel (default: owner-computes helpers, wave 0's SIMD partner steps aside), 0 = barrier version
   int lookahead;        // 1 = overlap panel k+1 with the trailing update of step k
   int la_min_n;         // blocks up to this size are factored in order (no side stream): default 1024 since the look-ahead's hand-offs are values
                         // (2 - 6 % at 1280 ... 3584 rows; 3584 while they were event pairs)
@@ -197,9 +195,7 @@ struct ffgp_handle {
   int la_carry_n;       // ... (default 12288; also the largest member a ragged chain accepts)
   int la_carry_rows;    // ... (default 8192)
   int diag_attr_set;    // dynamic-LDS attribute of potrf_diag128 set on this handle's device
-  int band_log2;        // GEMM tile order: band height 2^band_log2 tile rows (default 3)
   int split_rem_max;    // split tail of the 128-tile launches: quarter the last (tiles mod 256) tiles when that is <= this (0 = off)
-  int polite_pad_kb;    // LDS padding (KiB) of a polite trailing-update workgroup
   int polite_m;         // trailing updates with fewer rows than this run one workgroup per CU (0 = never)
   bool own_stream;
   // workspace (grown on demand, never shrunk)
@@ -221,18 +217,10 @@ struct ffgp_handle {
   size_t skw_bytes;
   double* ews;       // workspace of the symmetric eigensolver (syevd.hip)
   size_t ews_bytes;
-  hipEvent_t eig_ev[12];   // hand-offs between the chase (side stream) and the back-transformation (main stream) of ffgp_syevd
-  hipStream_t masked;   // CU-masked stream for the trailing updates of the chain-bound tail (tail_mask_m > 0)
-  int masked_failed, tail_mask_m, tail_mask_cus;
   int chase_xl_max_n;
   int chase_xcc;        // the XCD this handle's XCD-local chases run on
   int chase_xl;         // bulge chase with every working wave on one XCD, hand-overs through that XCD's L2 (sb2st.hip)
-  int syrk_direct;      // trailing update's interior tiles in the direct form (no LDS, no barriers; gemm_tile_direct)
-  double* pack_buf;
-  size_t pack_bytes;
-  int syrk_h64;         // experiment: trailing update on 128 x 64 half tiles, three workgroups per CU
-  hipStream_t aux3;     // fourth stream: the passenger rows of a look-ahead factorisation, one panel behind the chain (ffgp_potrf_impl)
-  int pass_split_min;   // passenger rows (right-hand sides riding in the factorisation) from this many on leave the chain's launches; 0 = never
+  hipStream_t aux3;     // fourth stream: gradient lane 2 of ffgp_nlml_fused_batch (created with aux2)
   hipStream_t aux2;     // third stream: the head of the triangular inverse under the factorisation's tail (nlml_fused_enqueue)
   hipEvent_t tri_ev[2]; // [0] factor columns < tri_hook_col are final (recorded by ffgp_potrf_impl on the side stream); [1] head done
   int tri_hook_col, tri_hook_fired;
@@ -268,12 +256,9 @@ struct ffgp_handle {
   int trtri_overlap;    // option (default 1)
   int trtri_fill;       // option "trtri_fill" (default 0): 1 = zero the whole inverse buffer before the head of the triangular inverse; 0 = only the diagonal blocks' upper parts; 2 = NaN-fill it (test)
   hipEvent_t ev_switch; // ffgp_set_stream: recorded on the stream the handle leaves, waited for by the one it moves to
-  hipEvent_t sb_ev[4];  // sy2sb: hand-offs between the trailing update (main stream) and the next panel's QR chain (side stream)
-  int sb_lookahead;     // option (default 0: measured 103 -> 108 ms at N = 8192 -- the event hand-offs cost more than the QR chain hides)
   int small_max_n;   // largest n that takes the one-kernel path (0 = the measured default, 40)
   int small_off;     // 1: never take the one-kernel path of small.hip (option "small_fused" = 0)
   double* d_link;    // effective parameters / their gradients of ffgp_nlml_fused_raw (2 x 256 doubles)
-  int eig_overlap;   // ffgp_syevd: 1 = chase on the side stream with the Q2^T accumulation behind it (see syevd.hip), 0 = stage after stage
   int chase_pack;    // bulge chasing: every chase_pack-th workgroup works (8 = all on one XCD; 1 = spread over the chip)
   int splitk_min_k;  // thin products (<= 64 tiles of 64 x 64) with k >= this are cut along k (0 = never)
   int skinny_max_n;  // products with at most this many output columns (<= 8) take the matrix-vector kernels (0 = never)
@@ -281,20 +266,13 @@ struct ffgp_handle {
   int super_min_n;   // factors smaller than this keep the 128-block sweep
   int* d_info;       // device status word(s)
   double* d_scal;    // small device scalar scratch (64 doubles)
-  // launch-bound sizes: the raw-parameter likelihood call replayed as a captured graph (api.hip, nlml_fused_raw_enqueue)
   int sb_lower;                // option "sb_lower" (default 1): the band reduction keeps and reads only the LOWER triangle of the trailing matrix (sy2sb_av_sym) ...
   int sb_lower_min_n;          // ... for matrices of at least this many rows (option "sb_lower_min_n", default 6144: below, the full form is as fast or faster)
   int sb_sym_wg;               // option "sb_sym_wg" (default 2048): workgroups the lower-triangle A Y launch aims for (half of them exit: chunks right of the diagonal)
-  int sb_av_gemm;              // option "sb_av_gemm" (default 0): 1 = the band reduction's A Y product on the general GEMM again
-  int q2_blocks_lanes;         // how the last q2_prep wrote its blocks (1: lane order for q2_apply_wave4)
-  int sb_qr4;                  // option "sb_qr4" (default 0): 1 = the band reduction's leaf QRs on 256 threads, four columns per half-wave (sy2sb_leaf_qr4)
   int q2_split_min_cols;       // option "q2_split_min_cols" (default 8192): from this many columns of Z on, Z <- Q2 Z runs 32-column slabs on eight waves
-  int q2_wave4;                // option "q2_wave4" (default 1): Z <- Q2 Z with four sweep groups per pass over Z (sb2st.hip)
   int small2_off;              // option "small_finish" (default 0 = off): 1 = 40 < n <= 128 runs assembly + the blocked diagonal-block
                                // factorisation + ONE finishing kernel (7 launches instead of 21); measured +-5-10 % per training step
   unsigned long alloc_epoch;   // bumped whenever one of the handle's device buffers is re-allocated (captured pointers go stale)
-  int raw_graph_max_n;         // option "raw_graph_max_n" (default 0 = never capture: measured no faster, see api.hip)
-  struct RawGraph* rawg;
   int fwd_graph;               // option "fwd_graph" (default 0): forward-only calls replay a captured hipGraph (api.hip)
   struct RawGraph* fwdg;
   long graph_replays;
@@ -319,7 +297,6 @@ struct ffgp_handle {
   int syrk_pool_used;
   // tuning knobs
   int nb_outer;      // outer (trailing-update) block size, multiple of FFGP_NB
-  int nb_big, nb_big_until;  // wider outer block while more than nb_big_until columns remain (0 = off)
   int use_naive;     // debug: route potrf through the naive kernels
 };
 

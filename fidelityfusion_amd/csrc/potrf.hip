@@ -387,7 +387,8 @@ __global__ __launch_bounds__(DIAG_THREADS) void ffgp_potrf_diag128(double* __res
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// potrf_diag128_v2: the same factor + inverse as a wave-specialised PIPELINE instead of barrier-separated phases.
+// The pipelined diagonal-block kernels (round 3; v3 and v4 below keep its chain): the same factor + inverse as a wave-specialised
+// PIPELINE instead of barrier-separated phases.
 //
 // The old kernel spends 8 x (3 workgroup barriers + a ~1.7 us in-register 16x16 factor + two short MFMA phases); every wave
 // waits for every other wave three times per 16 columns.  Here wave 0 never meets a barrier after the load phase:
@@ -475,253 +476,6 @@ __device__ __forceinline__ bool d2_wait_ge(volatile int* p, int target, volatile
   D2_COMPILER_FENCE();
   return true;
 }
-
-#ifdef FFGP_DEV_OPTIONS   // the round-3 pipelines (diag_v2 = 1, 3): development build only
-template <int NW, bool DPP64>
-__global__ __launch_bounds__(NW * 64, NW / 2) void ffgp_potrf_diag128_v2(double* __restrict__ A, int lda, int nb, double* __restrict__ Dinv,
-                                                                 int* info, int row_base, int prio) {
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* S = lds;
-  volatile D2Flags* fl = reinterpret_cast<volatile D2Flags*>(lds + NBLK_LOWER * BLKSZ);
-  constexpr int NT = NW * 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (wave == 0) D2_TRACE(0);
-  if (tid == 0) {
-    d2_st(&fl->seqF, 0); d2_st(&fl->seqX, 0); d2_st(&fl->doneU, 0); d2_st(&fl->sb, 0); d2_st(&fl->abort, 0);
-  }
-  // ---- load phase (as in the barrier version): lower blocks, diagonal blocks completed symmetrically, identity padding
-  {
-    // two rounds of 8 loads per thread (all of a round in flight before its LDS stores): the kernel is held to 128 VGPRs
-    // so that it fits on a CU BESIDE a resident trailing-update workgroup (the barrier version needs 256 -- a whole CU)
-    constexpr int NLOAD = 8192 / NT, CH = NLOAD / 2;
-    const bool vec = !(lda & 1) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      d2_t lv[CH];
-#pragma unroll
-      for (int it = 0; it < CH; ++it) {
-        const int idx = tid + NT * (half * CH + it);
-        const int r = min(idx >> 6, nb - 1), c = min((idx & 63) * 2, (nb - 1) & ~1);
-        const double* src = A + (size_t)r * lda + c;
-        if (vec) {
-          lv[it] = *reinterpret_cast<const d2_t*>(src);
-        } else {
-          lv[it].x = src[0];
-          lv[it].y = (c + 1 < nb) ? src[1] : 0.0;
-        }
-      }
-#pragma unroll
-      for (int it = 0; it < CH; ++it) {
-        const int idx = tid + NT * (half * CH + it);
-        const int r = idx >> 6, c = (idx & 63) * 2;
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-          const int cc = c + e;
-          if (cc <= r) {
-            double x = (r == cc) ? 1.0 : 0.0;
-            if (r < nb) x = e ? lv[it].y : lv[it].x;
-            S[blk_off(r >> 4, cc >> 4) + (r & 15) * BLD + (cc & 15)] = x;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < 8 * 256; idx += NT) {
-      const int jj = idx >> 8, i = (idx >> 4) & 15, c = idx & 15;
-      double* Dj = S + blk_off(jj, jj);
-      if (c > i) Dj[i * BLD + c] = Dj[c * BLD + i];
-    }
-  }
-  // helper roles: every wave but wave 0.  (Keeping the helpers off wave 0's SIMD -- so that no MFMA shares a pipe with
-  // the pivot chain's fp64 operations -- was measured: no difference.)
-  const int hidx = wave - 1;
-  constexpr int NH = NW - 1;
-  __syncthreads();
-  volatile int* ab = &fl->abort;
-  const int g = lane >> 4, c = lane & 15;
-
-  if (wave == 0) {
-    // ================================ the serial chain ================================
-    if (prio) __builtin_amdgcn_s_setprio(3);
-    D2_TRACE(1);
-    double v[4], w[4];
-    {
-      const double* D0 = S + blk_off(0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = D0[(g + 4 * r) * BLD + c];
-    }
-    for (int jj = 0; jj < 8; ++jj) {
-      // ---- F(jj)
-      // (lane coordinates made opaque per iteration: otherwise every lane-derived constant of the 16 unrolled pivots is
-      //  hoisted out of this loop and the kernel spills ~60 registers around its serial chain)
-      int cc = c, gg = g;
-      asm volatile("" : "+v"(cc), "+v"(gg));
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w[r] = (gg + 4 * r == cc) ? 1.0 : 0.0;
-      double rowA = bperm_d(v[0], cc);           // row 0: lanes (0, c)
-      double rowW = (cc == 0) ? 1.0 : 0.0;
-      if constexpr (DPP64) {
-        double hA = bperm_d(v[0], 16 + cc), hW = (cc == 1) ? 1.0 : 0.0;    // row 1 (lanes (1, c), register 0), one step ahead at the start only
-        double pRow = 0.0, pt = 0.0, ptw = 0.0;
-        double dcur = row_bcast64<0>(rowA), ycur = __builtin_amdgcn_rcp(dcur);
-#define F16_S(JJ) f16_step_dpp<JJ>(v, w, rowA, rowW, hA, hW, pRow, pt, ptw, dcur, ycur, cc, gg);
-        F16_S(0) F16_S(1) F16_S(2) F16_S(3) F16_S(4) F16_S(5) F16_S(6) F16_S(7) F16_S(8) F16_S(9) F16_S(10) F16_S(11) F16_S(12) F16_S(13)
-        F16_S(14) F16_S(15)
-#undef F16_S
-      } else {
-#define F16_S(JJ) f16_step<JJ>(v, w, rowA, rowW, cc, gg);
-        F16_S(0) F16_S(1) F16_S(2) F16_S(3) F16_S(4) F16_S(5) F16_S(6) F16_S(7) F16_S(8) F16_S(9) F16_S(10) F16_S(11) F16_S(12) F16_S(13)
-        F16_S(14) F16_S(15)
-#undef F16_S
-      }
-      // operands of G(jj) that do not depend on this block's result are fetched now, under the post-processing below:
-      // the helpers' updates of iteration jj-1 must have landed in S[jj+1][jj] and S[jj+1][jj+1]
-      double sb[4];
-      d4_t D;
-      if (jj < 7) {
-        if (jj > 0 && !d2_wait_ge(&fl->doneU, NH * jj, ab, info)) break;
-        const double* Sb = S + blk_off(jj + 1, jj);
-        const double* Sd = S + blk_off(jj + 1, jj + 1);
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq) sb[kq] = Sb[c * BLD + kq * 4 + g];       // B operand of Y = inv(L_jj) S[jj+1][jj]^T
-#pragma unroll
-        for (int r = 0; r < 4; ++r) D[r] = Sd[(g + 4 * r) * BLD + c];
-      }
-      D2_TRACE(3 + 3 * jj);
-      // the pivot of column c sits, unscaled, on the parked column's diagonal: lane (c & 3, c), register c >> 2
-      const int q = c >> 2;
-      const double dsel = (q == 0) ? v[0] : (q == 1) ? v[1] : (q == 2) ? v[2] : v[3];
-      const double dcol = bperm_d(dsel, 16 * (c & 3) + c);
-      const double rs = rsqrt_nr(dcol);          // 1 / sqrt(pivot of column c)
-      // first non-positive pivot of the block (a NaN counts): lanes 0..15 carry columns 0..15
-      const unsigned long long nonpos = __ballot(!(dcol > 0.0)) & 0xffffull;
-      const int bad = nonpos ? __ffsll((long long)nonpos) : 0;
-      double* Dj = S + blk_off(jj, jj);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = g + 4 * r;
-        const double rsi = bperm_d(rs, i);       // 1 / sqrt(pivot of column i): the row scaling of the inverse
-        const double x = (i >= c) ? w[r] * rsi : 0.0;
-        Dj[i * BLD + c] = x;                                              // inv(L_jj) for the helpers and for G
-        const int gr = jj * 16 + i, gc = jj * 16 + c;
-        if (i >= c) {
-          Dinv[(size_t)gr * NB + gc] = x;
-          if (gr < nb) A[(size_t)gr * lda + gc] = v[r] * rs;              // L_jj
-        }
-      }
-      if (bad && lane == 0 && (jj * 16 + bad) <= nb) atomicCAS(info, 0, row_base + jj * 16 + bad);
-      D2_LDS_FENCE();
-      if (lane == 0) d2_st(&fl->seqF, jj + 1);
-      D2_TRACE(2 + 3 * jj);
-      if (jj == 7) break;
-      // ---- G(jj)
-      d4_t Y = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) Y = __builtin_amdgcn_mfma_f64_16x16x4f64(Dj[c * BLD + kq * 4 + g], sb[kq], Y, 0, 0, 0);
-      {
-        double* Xb = S + blk_off(jj + 1, jj);                  // L[jj+1][jj] = Y^T  (its old content sits in sb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int k = g + 4 * r;                             // Y[k][c] -> X[c][k]
-          Xb[c * BLD + k] = Y[r];
-          const int gr = (jj + 1) * 16 + c;
-          if (gr < nb) A[(size_t)gr * lda + jj * 16 + k] = Y[r];
-        }
-      }
-      D2_LDS_FENCE();
-      if (lane == 0) d2_st(&fl->seqX, jj + 1);
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) D = __builtin_amdgcn_mfma_f64_16x16x4f64(Y[kq], Y[kq], D, 0, 0, 1);   // D -= Y^T Y
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = D[r];
-      D2_TRACE(4 + 3 * jj);
-    }
-    return;
-  }
-
-  // ================================ helpers ================================
-  int sb_target = 0;
-  auto helper_barrier = [&]() -> bool {
-    sb_target += NH;
-    D2_LDS_FENCE();
-    if (lane == 0) atomicAdd(const_cast<int*>(&fl->sb), 1);
-    return d2_wait_ge(&fl->sb, sb_target, ab, info);
-  };
-  d4_t T[2];                                   // T_j for the columns j = hidx, hidx + NH of the inverse's next row block
-  T[0] = (d4_t){0.0, 0.0, 0.0, 0.0};
-  T[1] = T[0];
-  for (int jj = 0; jj < 8; ++jj) {
-    if (!d2_wait_ge(&fl->seqF, jj + 1, ab, info)) return;
-    if (hidx == 0) D2_TRACE(32 + 4 * jj);
-    const double* Wj = S + blk_off(jj, jj);    // inv(L_jj)
-    // A1: L[i][jj] = S[i][jj] inv(L_jj)^T for the block rows wave 0 does not take itself
-    for (int i = jj + 2 + hidx; i < 8; i += NH) {
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
-      double* Bij = S + blk_off(i, jj);
-      mma16<true>(acc, Bij, BLD, Wj, BLD, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        Bij[(g + 4 * r) * BLD + c] = acc[r];
-        const int gr = i * 16 + g + 4 * r;
-        if (gr < nb) A[(size_t)gr * lda + jj * 16 + c] = acc[r];
-      }
-    }
-    // A2: X[jj][j] = -inv(L_jj) T_j (T from B3 of the previous iteration; accumulator layout = B-operand layout)
-    for (int s = 0; s < 2; ++s) {
-      const int j = hidx + s * NH;
-      if (j < jj) {
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Wj[c * BLD + kq * 4 + g], s ? T[1][kq] : T[0][kq], acc, 0, 0, 0);
-        double* dst = S + blk_off(jj, j);
-        double* gd = Dinv + (size_t)(jj * 16 + g) * NB + j * 16 + c;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          dst[(g + 4 * r) * BLD + c] = -acc[r];
-          gd[(size_t)4 * r * NB] = -acc[r];
-        }
-      }
-    }
-    if (hidx == 0) D2_TRACE(33 + 4 * jj);
-    if (jj == 7) break;
-    if (!helper_barrier()) return;
-    if (!d2_wait_ge(&fl->seqX, jj + 1, ab, info)) return;
-    // B1 / B2, dealt round-robin in priority order: (B1 i, B2 i) for i = jj+2 .. 7
-    {
-      const int nrows = 6 - jj;                // block rows jj+2 .. 7
-      for (int q = hidx; q < 2 * nrows; q += NH) {
-        const int i = jj + 2 + (q >> 1);
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-        double* dst;
-        if ((q & 1) == 0) {                    // B1: column jj+1 receives block column jj
-          mma16<true>(acc, S + blk_off(i, jj), BLD, S + blk_off(jj + 1, jj), BLD, lane);
-          dst = S + blk_off(i, jj + 1);
-        } else {                               // B2: column jj+2 receives block columns 0 .. jj
-          for (int p = 0; p <= jj; ++p) mma16<true>(acc, S + blk_off(i, p), BLD, S + blk_off(jj + 2, p), BLD, lane);
-          dst = S + blk_off(i, jj + 2);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[(g + 4 * r) * BLD + c] -= acc[r];
-      }
-    }
-    D2_LDS_FENCE();
-    if (lane == 0) atomicAdd(const_cast<int*>(&fl->doneU), 1);
-    if (hidx == 0) D2_TRACE(34 + 4 * jj);
-    // B3: T_j = sum_{k=j}^{jj} L[jj+1][k] X[k][j] for the owned columns j <= jj of the inverse's row block jj+1
-    for (int s = 0; s < 2; ++s) {
-      const int j = hidx + s * NH;
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
-      if (j <= jj)
-        for (int k = j; k <= jj; ++k) mma16<false>(acc, S + blk_off(jj + 1, k), BLD, S + blk_off(k, j), BLD, lane);
-      if (s) T[1] = acc; else T[0] = acc;
-    }
-    if (hidx == 0) D2_TRACE(35 + 4 * jj);
-    if (!helper_barrier()) return;             // row block jj+1 of L is dead now: A2 of the next iteration overwrites it
-  }
-}
-
-#endif   // FFGP_DEV_OPTIONS
 
 // ------------------------------------------------------------------------------------------------------------
 // potrf_diag128_v3 (round 4): the same chain, with the helpers reorganised around what tools/native/f16_probe.hip measured.
@@ -1667,90 +1421,72 @@ static int launch_trsm128_set(ffgp_handle* h, const TrsmSet& set, int cnt, int m
 // ------------------------------------------------------------------------------------------------------------
 static inline void la_take_deferred(ffgp_handle* h, DiagRag& dr);
 static int launch_diag(ffgp_handle* h, double* Ablk, int lda, int nb, double* Dinv_blk, int row_base, int do_factor) {
-  if (h->bt_F > 1 && !(do_factor && h->diag_v2 == 4 && !h->diag_dbg)) return FFGP_ERR_ARG;   // only the round-4 kernel is batched
+  if (h->bt_F > 1 && !(do_factor && h->diag_v2 == 4)) return FFGP_ERR_ARG;   // only the round-4 kernel is batched
   if (!(h->diag_attr_set & 1)) {   // per handle = per device (the attribute lives in the device's context)
     FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
     h->diag_attr_set |= 1;
   }
-  if (do_factor && h->diag_v2 && !h->diag_dbg) {   // the pipelined kernel (the barrier version keeps the inverse-only entry)
-#ifdef FFGP_DEV_OPTIONS
-    if (!(h->diag_attr_set & 2)) {
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v2<8, true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v2<8, false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
-      h->diag_attr_set |= 2;
+  if (do_factor && h->diag_v2 == 4) {   // round 4: owner-computes helpers, wave 0's SIMD partner steps aside (the barrier version keeps
+                                       // the inverse-only entry)
+    if (!(h->diag_attr_set & 4)) {
+      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   DIAG_LDS_BYTES));
+      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   DIAG_LDS_BYTES));
+      h->diag_attr_set |= 4;
     }
-#endif
-    if (h->diag_v2 == 4) {   // round 4: owner-computes helpers, wave 0's SIMD partner steps aside
-      if (!(h->diag_attr_set & 4)) {
-        FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     DIAG_LDS_BYTES));
-        FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     DIAG_LDS_BYTES));
-        h->diag_attr_set |= 4;
+    // (diag_excl: the panel's FIRST diagonal block of a chain-bound carry iteration asks for a whole CU's LDS, so the S_bz workgroups that
+    //  start the moment it publishes cannot land beside it -- see ffgp_potrf_impl.  Only where a workgroup may have that much: the
+    //  limit is asked for once, and a device or runtime that says less simply keeps the ordinary launch)
+    if (!h->lds_cap_known) {
+      int cap = 0;
+      if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess) {
+        (void)hipGetLastError();
+        cap = 64 * 1024;
       }
-      // (diag_excl: the panel's FIRST diagonal block of a chain-bound carry iteration asks for a whole CU's LDS, so the S_bz workgroups that
-      //  start the moment it publishes cannot land beside it -- see ffgp_potrf_impl.  Only where a workgroup may have that much: the
-      //  limit is asked for once, and a device or runtime that says less simply keeps the ordinary launch)
-      if (!h->lds_cap_known) {
-        int cap = 0;
-        if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess) {
-          (void)hipGetLastError();
-          cap = 64 * 1024;
-        }
-        h->lds_cap = cap;
-        h->lds_cap_known = 1;
-      }
-      const bool excl = h->diag_excl_now && h->bt_F <= 1 && h->lds_cap >= 160 * 1024;
-      const int lds_bytes = excl ? 160 * 1024 : DIAG_LDS_BYTES;
-      if (excl && !h->diag_v4 && !(h->diag_attr_set & 8)) {
-        FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024));
-        h->diag_attr_set |= 8;
-      }
-      if (h->diag_v4 && !(h->diag_attr_set & 16)) {
-        const int want = h->lds_cap >= 160 * 1024 ? 160 * 1024 : DIAG4_LDS_BYTES;
-        FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-        h->diag_attr_set |= 16;
-      }
-      // the pending "panel complete" publication is taken only now, when nothing can fail between here and the launch that carries it
-      DiagRag dr = DiagRag();
-      la_take_deferred(h, dr);
-      if (h->diag_v4) {      // round 6: two barriers per stage (ffgp_potrf_diag128_v4)
-        const int lds4 = excl ? lds_bytes : DIAG4_LDS_BYTES;
-        auto kern = ffgp_potrf_diag128_v4<false>;
-        if (h->bt_F > 1)
-          hipLaunchKernelGGL(kern, dim3(h->bt_F), dim3(512), DIAG4_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
-                             h->bt_info, row_base, h->aux_prio, h->bt_sA, h->bt_sD, 1, dr);
-        else
-          hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds4, h->stream, Ablk, lda, nb, Dinv_blk, h->d_info,
-                             row_base, h->aux_prio, 0L, 0L, 0, dr);
-      } else if (h->bt_F > 1)
-        hipLaunchKernelGGL(ffgp_potrf_diag128_v3<false>, dim3(h->bt_F), dim3(512), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
+      h->lds_cap = cap;
+      h->lds_cap_known = 1;
+    }
+    const bool excl = h->diag_excl_now && h->bt_F <= 1 && h->lds_cap >= 160 * 1024;
+    const int lds_bytes = excl ? 160 * 1024 : DIAG_LDS_BYTES;
+    if (excl && !h->diag_v4 && !(h->diag_attr_set & 8)) {
+      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   160 * 1024));
+      h->diag_attr_set |= 8;
+    }
+    if (h->diag_v4 && !(h->diag_attr_set & 16)) {
+      const int want = h->lds_cap >= 160 * 1024 ? 160 * 1024 : DIAG4_LDS_BYTES;
+      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
+      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
+      h->diag_attr_set |= 16;
+    }
+    // the pending "panel complete" publication is taken only now, when nothing can fail between here and the launch that carries it
+    DiagRag dr = DiagRag();
+    la_take_deferred(h, dr);
+    if (h->diag_v4) {      // round 6: two barriers per stage (ffgp_potrf_diag128_v4)
+      const int lds4 = excl ? lds_bytes : DIAG4_LDS_BYTES;
+      auto kern = ffgp_potrf_diag128_v4<false>;
+      if (h->bt_F > 1)
+        hipLaunchKernelGGL(kern, dim3(h->bt_F), dim3(512), DIAG4_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
                            h->bt_info, row_base, h->aux_prio, h->bt_sA, h->bt_sD, 1, dr);
       else
-        hipLaunchKernelGGL(ffgp_potrf_diag128_v3<false>, dim3(1), dim3(512), lds_bytes, h->stream, Ablk, lda, nb, Dinv_blk, h->d_info,
+        hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds4, h->stream, Ablk, lda, nb, Dinv_blk, h->d_info,
                            row_base, h->aux_prio, 0L, 0L, 0, dr);
-      if (hipGetLastError() != hipSuccess) {      // the launch that carried the publication did not happen: write it plainly, report
-        if (dr.pub) (void)hipStreamWriteValue32(h->stream, dr.pub, dr.pub_val, 0);
-        return FFGP_ERR_HIP;
-      }
-    }
-#ifdef FFGP_DEV_OPTIONS
-    else if (h->diag_v2 == 3)   // the round-3 pivot step (32-bit DPP moves), kept for A/B runs
-      hipLaunchKernelGGL((ffgp_potrf_diag128_v2<8, false>), dim3(1), dim3(512), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
-                         h->d_info, row_base, h->aux_prio);
+    } else if (h->bt_F > 1)
+      hipLaunchKernelGGL(ffgp_potrf_diag128_v3<false>, dim3(h->bt_F), dim3(512), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
+                         h->bt_info, row_base, h->aux_prio, h->bt_sA, h->bt_sD, 1, dr);
     else
-      hipLaunchKernelGGL((ffgp_potrf_diag128_v2<8, true>), dim3(1), dim3(512), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
-                         h->d_info, row_base, h->aux_prio);
-#endif
+      hipLaunchKernelGGL(ffgp_potrf_diag128_v3<false>, dim3(1), dim3(512), lds_bytes, h->stream, Ablk, lda, nb, Dinv_blk, h->d_info,
+                         row_base, h->aux_prio, 0L, 0L, 0, dr);
+    if (hipGetLastError() != hipSuccess) {      // the launch that carried the publication did not happen: write it plainly, report
+      if (dr.pub) (void)hipStreamWriteValue32(h->stream, dr.pub, dr.pub_val, 0);
+      return FFGP_ERR_HIP;
+    }
     return FFGP_OK;
   }
   hipLaunchKernelGGL(ffgp_potrf_diag128, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
-                     h->d_info, row_base, do_factor, h->diag_dbg, h->aux_prio);
+                     h->d_info, row_base, do_factor, /*dbg=*/0, h->aux_prio);
   return FFGP_OK;
 }
 
@@ -1875,7 +1611,7 @@ static inline bool la_withheld(ffgp_handle* h) {
 }
 // submission-order rule (see ffgp_potrf_impl): a wait is only ever ENQUEUED after the launch that satisfies it, so that polling gates in
 // shared in-order hardware queues cannot form a cycle.  ho_launched[slot] = the newest sequence number whose producing operation has
-// been enqueued; la_wait checks it (development build: an error; product: counted in ho_order_violations).
+// been enqueued; la_wait checks it (a violation is counted in ho_order_violations).
 static inline void la_mark_launched(ffgp_handle* h, int slot) { h->ho_launched[slot] = h->ho_seq[slot]; }
 static int la_record(ffgp_handle* h, hipEvent_t ev, hipStream_t s) {
   const int slot = la_slot(h, ev);
@@ -1895,14 +1631,7 @@ static int la_wait(ffgp_handle* h, hipStream_t s, hipEvent_t ev) {
     FFGP_HIP(hipStreamWaitEvent(s, ev, 0));
     return FFGP_OK;
   }
-  if (h->ho_launched[slot] != h->ho_seq[slot]) {      // the producer of this number has not been enqueued yet
-    h->ho_order_violations += 1;
-#ifdef FFGP_DEV_OPTIONS
-    fprintf(stderr, "[ffgp] look-ahead: wait for hand-off %d #%u enqueued before its producer (#%u launched)\n", slot, h->ho_seq[slot],
-            h->ho_launched[slot]);
-    return FFGP_ERR_HIP;
-#endif
-  }
+  if (h->ho_launched[slot] != h->ho_seq[slot]) h->ho_order_violations += 1;      // the producer of this number has not been enqueued yet
   if (h->ho_gate) {
     int* info = h->ho_info ? h->ho_info : h->d_info;
     hipLaunchKernelGGL(ffgp_handoff_gate, dim3(1), dim3(64), 0, s, h->ho_mem + slot * 16, h->ho_seq[slot], info,
@@ -1948,7 +1677,7 @@ static int la_record_deferred(ffgp_handle* h, hipEvent_t ev, hipStream_t s) {
   const int slot = la_slot(h, ev);
   // (only ffgp_potrf_diag128_v3 publishes: with another diagonal-block kernel selected -- option diag_v2 -- nobody would pick the word up, and
   //  the plain write at the end of the factorisation would sit behind kernels that wait for it; found by the suite's barrier-kernel case)
-  if (slot < 0 || !h->ho_defer || h->diag_v2 != 4 || h->diag_dbg || h->use_naive) return la_record(h, ev, s);
+  if (slot < 0 || !h->ho_defer || h->diag_v2 != 4 || h->use_naive) return la_record(h, ev, s);
   FFGP_CHECK(la_flush(h));
   h->ho_seq[slot] += 1;
   h->ho_defer_slot = slot;
@@ -2000,7 +1729,6 @@ static int la_begin(ffgp_handle* h) {
     FFGP_HIP(hipStreamSynchronize(h->aux));
     if (h->aux2) FFGP_HIP(hipStreamSynchronize(h->aux2));
     if (h->aux3) FFGP_HIP(hipStreamSynchronize(h->aux3));
-    if (h->masked) FFGP_HIP(hipStreamSynchronize(h->masked));
     FFGP_HIP(hipMemsetAsync(h->ho_mem, 0, 10 * 16 * sizeof(unsigned), h->stream));
     FFGP_HIP(hipStreamSynchronize(h->stream));
     for (int i = 0; i < 10; ++i) h->ho_seq[i] = 0;
@@ -2064,28 +1792,6 @@ static int factor_panel_first_diag(ffgp_handle* h, double* A, int n, int lda, in
   return launch_diag(h, A + (size_t)k0 * lda + k0, lda, min(NB, n - k0), h->dinv + (size_t)(k0 / NB) * NB * NB, k0, 1);
 }
 
-// the handle's CU-masked stream (tail_mask_m): every CU except the first tail_mask_cus of each XCD.  Mask bit i <-> XCD i % 8, CU
-// i / 8 of that XCD (tools/native/cumask_probe.hip); a mask that leaves an XCD empty is ignored by the runtime.
-int ffgp_ensure_masked(ffgp_handle* h) {
-  if (h->masked) return FFGP_OK;
-  if (h->masked_failed) return FFGP_ERR_HIP;
-  uint32_t mask[8];
-  for (int i = 0; i < 8; ++i) mask[i] = 0xffffffffu;
-  const int cut = h->tail_mask_cus > 0 && h->tail_mask_cus < 32 ? h->tail_mask_cus : 8;
-  for (int x = 0; x < 8; ++x)
-    for (int c = 0; c < cut; ++c) {
-      const int bit = c * 8 + x;
-      mask[bit / 32] &= ~(1u << (bit % 32));
-    }
-  if (hipExtStreamCreateWithCUMask(&h->masked, 8, mask) != hipSuccess) {
-    (void)hipGetLastError();
-    h->masked = nullptr;
-    h->masked_failed = 1;
-    return FFGP_ERR_HIP;
-  }
-  return FFGP_OK;
-}
-
 // Factor the leading n x n block of A in place; rows n..mtot-1 (if any) are "passenger" rows that receive the
 // same right-hand transformations and come out as  A[n:, :] * L^-T  -- i.e. (L^-1 B)^T for B^T stored below
 // Sigma.  The fused NLML/predict paths put Y^T and K_*^T there, so the triangular solves ride inside the
@@ -2110,54 +1816,10 @@ int ffgp_potrf_impl(ffgp_handle* h, double* A, int n, int mtot, int lda, int syn
     if (mtot > n) hipLaunchKernelGGL(ffgp_trsm_rows_naive, dim3(mtot - n), dim3(64), 0, h->stream, A, lda, n);
   } else {
     const int NB1 = h->nb_outer;
-    // panel width at column k0: the wide block while more than nb_big_until columns remain (the SYRK's fixed per-tile
-    // cost is amortised over a longer k loop where the chain still hides under it), nb_outer after that
-    auto pw = [&](int k0) { return (h->nb_big > NB1 && n - k0 > h->nb_big_until) ? h->nb_big : NB1; };
     const bool in_order = !h->lookahead || n <= NB1 || n <= h->la_min_n;
-    // Passenger rows off the chain (round 5).  Riding in the chain's own launches, the right-hand sides made every TRSM and
-    // panel update of the dependency chain (n - j) + d rows tall: at N = 8192, d = 4096 a third of the chain's kernel time, on the
-    // latency tiles, while most of the chip idled in the chain-bound tail.  With many of them (>= pass_split_min) and a look-ahead
-    // form, the chain and the trailing updates cover the n x n matrix only, and the passenger rows follow ONE PANEL BEHIND on a
-    // stream of their own: per panel the same operations as before (per 128-column block the product with the inverted diagonal
-    // block and the update of the panel's remaining columns, then the K = panel-width update of the columns to the right), which
-    // read the panel's finished columns of L and write passenger rows only -- they fill the CUs the chain leaves idle.
-    const int npass = mtot - n;
-    const bool split_pass = !in_order && h->pass_split_min > 0 && npass >= h->pass_split_min;
-    const int mch = split_pass ? n : mtot;       // rows the chain's and the trailing updates' launches cover
-    hipEvent_t pass_done = nullptr;
-    if (split_pass) FFGP_CHECK(ffgp_ensure_aux2(h));
-    auto pass_panel = [&](int k0, int w1, hipEvent_t ready) -> int {
-      // `ready`: the panel's columns of L are final.  Runs on h->aux3; h->stream is restored by the caller's bookkeeping.
-      hipStream_t keep = h->stream;
-      FFGP_CHECK(la_wait(h, h->aux3, ready));
-      h->stream = h->aux3;
-      int rc = FFGP_OK;
-      const int pend = k0 + w1;
-      double* Ap0 = A + (size_t)n * lda;           // first passenger row
-      for (int j0 = k0; j0 < pend && rc == FFGP_OK; j0 += NB) {
-        const int jb = min(NB, n - j0);
-        double* Ap = Ap0 + j0;
-        double* Dj = h->dinv + (size_t)(j0 / NB) * NB * NB;
-        rc = potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_FULL, 0, Ap, lda, Dj, NB, Ap, lda, npass, jb, jb, 1.0, 0.0, 0, ALIAS_A, true);
-        const int wrem = pend - (j0 + jb);
-        if (rc == FFGP_OK && wrem > 0)
-          rc = potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_FULL, 0, Ap, lda, A + (size_t)(j0 + jb) * lda + j0, lda, Ap0 + (j0 + jb), lda, npass,
-                          wrem, jb, -1.0, 1.0);
-      }
-      const int mt = n - pend;
-      if (rc == FFGP_OK && mt > 0)
-        rc = potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_FULL, 0, Ap0 + k0, lda, A + (size_t)pend * lda + k0, lda, Ap0 + pend, lda, npass, mt, w1,
-                        -1.0, 1.0);
-      h->stream = keep;
-      if (rc == FFGP_OK) {
-        FFGP_CHECK(la_record(h, h->la_ev[9], h->aux3));
-        pass_done = h->la_ev[9];
-      }
-      return rc;
-    };
     if (in_order) {
-      for (int k0 = 0; k0 < n; k0 += pw(k0)) {
-        const int w1 = min(pw(k0), n - k0);
+      for (int k0 = 0; k0 < n; k0 += NB1) {
+        const int w1 = min(NB1, n - k0);
         const int pend = k0 + w1;  // end column of this outer panel
         FFGP_CHECK(factor_panel(h, A, n, mtot, lda, k0, w1));
         const int mt = n - pend;  // trailing columns; trailing rows include the passenger rows
@@ -2196,44 +1858,33 @@ int ffgp_potrf_impl(ffgp_handle* h, double* A, int n, int mtot, int lda, int syn
         ~Polite64() { f = 0; }
       } polite64(h->polite64_active);
       auto carry_of = [&](int pend_) { return max(0, min(NB, n - pend_)); };   // columns of the next panel's first block (0 at the end)
-      const int w0 = min(pw(0), n);
+      const int w0 = min(NB1, n);
       bool carried = (h->la_carry == 1) || (h->la_carry == 2 && n <= h->la_carry_n);      // does the complete panel carry Z(k+1)?  (blocks up to la_carry_n rows: carry form throughout)
-      FFGP_CHECK(factor_panel(h, A, n, mch, lda, 0, w0, nullptr, carried ? carry_of(w0) : 0));
+      FFGP_CHECK(factor_panel(h, A, n, mtot, lda, 0, w0, nullptr, carried ? carry_of(w0) : 0));
       FFGP_CHECK(la_record(h, h->la_ev[6], main_s));
       FFGP_CHECK(la_wait(h, h->aux, h->la_ev[6]));
-      if (split_pass) FFGP_CHECK(pass_panel(0, w0, h->la_ev[6]));
       int it = 0;
       hipEvent_t eb_prev = nullptr, ei_prev = nullptr;
-      // Chain-bound tail on a CU-masked stream (option tail_mask_m): once the trailing matrix has fewer rows than that, the trailing
-      // updates are issued to a stream that may not use tail_mask_cus CUs of every XCD -- those CUs stay free of trailing-update
-      // workgroups, so the chain's kernels (unmasked side stream) start at once and run undisturbed instead of waiting for slots and
-      // sharing SIMDs with the update's MFMA stream; the update loses a quarter of the chip where it has slack anyway.
-      hipStream_t syrk_s = main_s;
-      for (int k0 = 0; k0 < n; k0 += pw(k0), ++it) {
-        const int w1 = min(pw(k0), n - k0);
+      for (int k0 = 0; k0 < n; k0 += NB1, ++it) {
+        const int w1 = min(NB1, n - k0);
         const int pend = k0 + w1;
         const int mt = n - pend;
         if (mt <= 0) break;
         // carry iteration: panel k+1 is factored carrying Z(k+2) (every later iteration is one too: the trailing matrix only shrinks)
         const bool cm = (h->la_carry == 1) || (h->la_carry == 2 && (carried || mt <= h->la_carry_rows));
         h->polite64_active = cm ? 1 : 0;
-        if (cm && h->tail_mask_m > 0 && mch - pend < h->tail_mask_m && syrk_s == main_s && ffgp_ensure_masked(h) == FFGP_OK) {
-          FFGP_CHECK(la_record(h, h->la_ev[7], main_s));
-          FFGP_CHECK(la_wait(h, h->masked, h->la_ev[7]));
-          syrk_s = h->masked;
-        }
-        const int wn = min(pw(pend), mt);  // width of the next panel
+        const int wn = min(NB1, mt);       // width of the next panel
         const int q = pend + wn;           // first column of panel k+2
         const int wz = cm ? carry_of(q) : 0;
         hipEvent_t eb = h->la_ev[(it & 1) * 3], eg = h->la_ev[(it & 1) * 3 + 1], ei = h->la_ev[(it & 1) * 3 + 2];
-        const int wa = (cm || h->la_split) ? min(NB, wn) : wn;     // Z(k+1)
+        const int wa = min(NB, wn);        // Z(k+1)
         // side stream: S_a(k) unless panel k carried it (after S_ii(k-1), which carried panel k-1 into these columns)
         if (!carried) {
           if (ei_prev) FFGP_CHECK(la_wait(h, h->aux, ei_prev));
           double* P = A + (size_t)pend * lda + k0;
           double* C = A + (size_t)pend * lda + pend;
           h->stream = h->aux;
-          const int arc = potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_LOWER, 1, P, lda, P, lda, C, lda, mch - pend, wa, w1, -1.0, 1.0);
+          const int arc = potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_LOWER, 1, P, lda, P, lda, C, lda, mtot - pend, wa, w1, -1.0, 1.0);
           h->stream = main_s;
           FFGP_CHECK(arc);
         }
@@ -2257,17 +1908,14 @@ int ffgp_potrf_impl(ffgp_handle* h, double* A, int n, int mtot, int lda, int syn
         h->stream = main_s;
         FFGP_CHECK(drc);
         // main stream, once panel k is complete: S_b(k) (and S_z(k), its right-hand neighbour: columns pend+wa .. q+wz, one launch)
-        if (eb_prev) FFGP_CHECK(la_wait(h, syrk_s, eb_prev));
+        if (eb_prev) FFGP_CHECK(la_wait(h, main_s, eb_prev));
         hipEvent_t gate = nullptr;
         if (wn - wa + wz > 0) {
           double* Pb = A + (size_t)(pend + wa) * lda + k0;
           double* Cb = A + (size_t)(pend + wa) * lda + (pend + wa);
-          h->stream = syrk_s;
-          const int brc = potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_LOWER, 1, Pb, lda, Pb, lda, Cb, lda, mch - pend - wa,
-                                     wn - wa + wz, w1, -1.0, 1.0);
-          h->stream = main_s;
-          FFGP_CHECK(brc);
-          FFGP_CHECK(la_record_on_next_gemm(h, eg, syrk_s));     // (published by S_ii(k), the next launch on that stream)
+          FFGP_CHECK(potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_LOWER, 1, Pb, lda, Pb, lda, Cb, lda, mtot - pend - wa, wn - wa + wz, w1,
+                                -1.0, 1.0));
+          FFGP_CHECK(la_record_on_next_gemm(h, eg, main_s));     // (published by S_ii(k), the next launch on that stream)
           gate = eg;
         }
         // main stream: S_ii(k), everything right of panel k+1 and of Z(k+2)
@@ -2276,27 +1924,23 @@ int ffgp_potrf_impl(ffgp_handle* h, double* A, int n, int mtot, int lda, int syn
         if (mt2 > 0) {
           double* P2 = A + (size_t)(q + wz) * lda + k0;
           double* C2 = A + (size_t)(q + wz) * lda + (q + wz);
-          h->stream = syrk_s;
-          const int irc = potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_LOWER, 1, P2, lda, P2, lda, C2, lda, mch - q - wz, mt2, w1, -1.0, 1.0);
-          h->stream = main_s;
-          FFGP_CHECK(irc);
+          FFGP_CHECK(potrf_gemm(h, OP_KMAJOR, OP_KMAJOR, TILES_LOWER, 1, P2, lda, P2, lda, C2, lda, mtot - q - wz, mt2, w1, -1.0, 1.0));
           if (!cm) {                                          // (the next iteration's S_a waits for it)
-            FFGP_CHECK(la_record(h, ei, syrk_s));
+            FFGP_CHECK(la_record(h, ei, main_s));
             ei_prev = ei;
           }
         }
         FFGP_CHECK(la_flush_gemm(h));                         // (no S_ii: the hand-off of S_bz is written plainly)
         // side stream: the rest of panel k+1 (carrying Z(k+2) in a carry iteration)
         h->stream = h->aux;
-        const int rc = factor_panel(h, A, n, mch, lda, pend, wn, gate, wz, nullptr, true);
+        const int rc = factor_panel(h, A, n, mtot, lda, pend, wn, gate, wz, nullptr, true);
         h->stream = main_s;
         FFGP_CHECK(rc);
-        if (cm && !split_pass)
+        if (cm)
           FFGP_CHECK(la_record_deferred(h, eb, h->aux));     // (published by the next panel's first diagonal-block kernel)
         else
-          FFGP_CHECK(la_record(h, eb, h->aux));              // (the next kernel on the side stream is S_a(k+1); pass_panel waits at once)
+          FFGP_CHECK(la_record(h, eb, h->aux));              // (the next kernel on the side stream is S_a(k+1))
         eb_prev = eb;
-        if (split_pass) FFGP_CHECK(pass_panel(pend, wn, eb));
         if (h->tri_hook_col > 0 && pend + wn == h->tri_hook_col) {   // the factor's columns < tri_hook_col are final from here on
           FFGP_CHECK(la_record(h, h->tri_ev[0], h->aux));
           h->tri_hook_fired = 1;
@@ -2304,12 +1948,7 @@ int ffgp_potrf_impl(ffgp_handle* h, double* A, int n, int mtot, int lda, int syn
         carried = cm;
       }
       FFGP_CHECK(la_flush(h));
-      if (syrk_s != main_s) {
-        FFGP_CHECK(la_record(h, h->la_ev[8], syrk_s));
-        FFGP_CHECK(la_wait(h, main_s, h->la_ev[8]));
-      }
       if (eb_prev) FFGP_CHECK(la_wait(h, main_s, eb_prev));
-      if (pass_done) FFGP_CHECK(la_wait(h, main_s, pass_done));
     }
     h->dinv_L = A;
     h->dinv_n = n;
@@ -2332,11 +1971,11 @@ int ffgp_potrf_impl(ffgp_handle* h, double* A, int n, int mtot, int lda, int syn
 // the side stream; trailing updates of in-order members follow their panel on the chain's stream (as in their single call), those
 // of look-ahead members run on the main stream behind the same two events per panel as in ffgp_potrf_impl's carry form.
 // Not covered (FFGP_ERR_ARG, the caller evaluates such sets block by block): members above 12288 rows (their single call uses the
-// round-1 look-ahead form), the naive / barrier-kernel modes, wide early panels (nb_big).
+// round-1 look-ahead form), the naive / barrier-kernel modes.
 // ------------------------------------------------------------------------------------------------------------
 int ffgp_potrf_ragged(ffgp_handle* h, int R, const ffgp_rag_block* mem) {
   if (R <= 0) return FFGP_OK;
-  if (!mem || h->use_naive || h->diag_v2 != 4 || h->diag_dbg || h->nb_big > h->nb_outer) return FFGP_ERR_ARG;
+  if (!mem || h->use_naive || h->diag_v2 != 4) return FFGP_ERR_ARG;
   const int NB1 = h->nb_outer;
   std::vector<int> form(R);
   bool any_la = false;

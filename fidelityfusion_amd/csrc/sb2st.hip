@@ -14,9 +14,9 @@
 //   -> status word), so the grid always drains.
 // q2_prep: the reflectors of 32 consecutive sweeps at the same step k form a 63 x 32 staircase V; its compact-WY T comes from
 //   T^-1 = striu(V^T V) + diag(1 / tau); stored per block: V (64 x 32) and (V T)^T (32 x 64).
-// q2_apply: Z <- Q2 Z.  One workgroup per slab of 32 columns of Z walks the blocks in the order (sweep group descending,
-//   step ascending -- the only order in which overlapping blocks commute into place, see the numpy model) with a sliding 64-row
-//   window in LDS: X = V^T Zw, Zw -= W X on the fp64 matrix cores.
+// q2_apply_wave4: Z <- Q2 Z.  One workgroup per slab of 16 or 32 columns of Z walks the blocks in the order (sweep group
+//   descending, step ascending -- the only order in which overlapping blocks commute into place, see the numpy model), four sweep
+//   groups per pass, with a sliding window in LDS: X = V^T Zw, Zw -= W X on the fp64 matrix cores.
 #include "ffgp_internal.h"
 #include "syevd_internal.h"
 
@@ -436,22 +436,16 @@ __global__ void sb2st_tail(const double* __restrict__ AB, int n, double* d, doub
 
 static inline int chase_K(int n) { return n / 32 + 1; }
 
-// AB [n, 64] band in (destroyed), d [n], e [n] out, V2 [n * K * 32], tau2 [n * K], prog [n + 1] ints (last: status word).
-// init clears the stores; chunk runs the sweeps [s_begin, s_end) (sweeps of later launches find their predecessors' counters at
-// CH_DONE); finish writes the last two diagonal entries.  All on stream st.
-int ffgp_sb2st_init(ffgp_handle* h, hipStream_t st, int n, double* V2, double* tau2, int* prog) {
+// AB [n, 64] band in (destroyed), d [n], e [n] out, V2 [n * K * 32], tau2 [n * K], prog [n + 1] ints (last: status word), all on the
+// handle's stream: the stores are cleared, the n - 2 sweeps chased, the last two diagonal entries written.
+int ffgp_sb2st_impl(ffgp_handle* h, double* AB, int n, double* d, double* e, double* V2, double* tau2, int* prog) {
   if (n < 64 || n % 32) return FFGP_ERR_ARG;
+  hipStream_t st = h->stream;
   const int K = chase_K(n);
   FFGP_HIP(hipMemsetAsync(prog, 0, (size_t)(n + 1) * sizeof(int), st));
   FFGP_HIP(hipMemsetAsync(V2, 0, (size_t)n * K * 32 * sizeof(double), st));
   FFGP_HIP(hipMemsetAsync(tau2, 0, (size_t)n * K * sizeof(double), st));
-  return FFGP_OK;
-}
-
-int ffgp_sb2st_chunk(ffgp_handle* h, hipStream_t st, double* AB, int n, double* d, double* e, double* V2, double* tau2, int* prog, int s_begin,
-                     int s_end) {
-  s_end = min(s_end, n - 2);
-  if (s_begin >= s_end) return FFGP_OK;
+  const int s_begin = 0, s_end = n - 2;
   ChaseArgs a;
   a.AB = AB; a.n = n; a.d = d; a.e = e; a.V2 = V2; a.tau2 = tau2; a.K = chase_K(n); a.prog = prog; a.err = prog + n;
   a.s_begin = s_begin; a.s_end = s_end;
@@ -475,27 +469,15 @@ int ffgp_sb2st_chunk(ffgp_handle* h, hipStream_t st, double* AB, int n, double* 
     hipLaunchKernelGGL(sb2st_ticket_init, dim3(1), dim3(1), 0, st, a.ticket, s_begin);
     const int grid = min(s_end - s_begin, max(16, n / 64)) * 8;
     hipLaunchKernelGGL(sb2st_chase<true>, dim3(grid), dim3(64), 0, st, a);
-    // ... and the sweeps the ticket did not reach (none, unless no wave landed on XCD `xcc`) on the chip-wide form: the chase is
-    // complete when this returns, wherever the runtime placed the XL launch's waves
     a.begin_from = a.ticket;
     a.ticket = nullptr;
-    hipLaunchKernelGGL(sb2st_chase<false>, dim3(min(s_end - s_begin, 256) * a.pack), dim3(64), 0, st, a);
-    return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
   }
-  const int grid = min(s_end - s_begin, 256) * a.pack;
-  hipLaunchKernelGGL(sb2st_chase<false>, dim3(grid), dim3(64), 0, st, a);
-  return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
-}
-
-int ffgp_sb2st_finish(ffgp_handle* h, hipStream_t st, const double* AB, int n, double* d, double* e) {
+  // the chip-wide form: every sweep, or after the XL launch the sweeps its ticket did not reach (none, unless no wave landed on XCD
+  // `xcc`) -- the chase is complete when this returns, wherever the runtime placed the XL launch's waves
+  hipLaunchKernelGGL(sb2st_chase<false>, dim3(min(s_end - s_begin, 256) * a.pack), dim3(64), 0, st, a);
+  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
   hipLaunchKernelGGL(sb2st_tail, dim3(1), dim3(64), 0, st, AB, n, d, e);
   return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
-}
-
-int ffgp_sb2st_impl(ffgp_handle* h, double* AB, int n, double* d, double* e, double* V2, double* tau2, int* prog) {
-  FFGP_CHECK(ffgp_sb2st_init(h, h->stream, n, V2, tau2, prog));
-  FFGP_CHECK(ffgp_sb2st_chunk(h, h->stream, AB, n, d, e, V2, tau2, prog, 0, n - 2));
-  return ffgp_sb2st_finish(h, h->stream, AB, n, d, e);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -599,162 +581,29 @@ __global__ __launch_bounds__(256) void q2_prep(PrepArgs p) {
   }
 }
 
-int ffgp_q2_prep_impl(ffgp_handle* h, const double* V2, const double* tau2, int n, double* blocks, int G0, int G1, int trans) {
-  if (G1 <= G0) return FFGP_OK;
+// the blocks of Q2 (W = V T) of every sweep group, both factors in the lane order of q2_apply_wave4
+int ffgp_q2_prep_impl(ffgp_handle* h, const double* V2, const double* tau2, int n, double* blocks) {
   PrepArgs a;
-  a.V2 = V2; a.tau2 = tau2; a.n = n; a.K = chase_K(n); a.blocks = blocks; a.G0 = G0; a.trans = trans;
-  a.lanes = (!trans && h->q2_wave4) ? 1 : 0;
-  h->q2_blocks_lanes = a.lanes;     // (the apply launch must read the blocks the way they were written)
-  hipLaunchKernelGGL(q2_prep, dim3(a.K, G1 - G0), dim3(256), 0, h->stream, a);
+  a.V2 = V2; a.tau2 = tau2; a.n = n; a.K = chase_K(n); a.blocks = blocks; a.G0 = 0; a.trans = 0; a.lanes = 1;
+  hipLaunchKernelGGL(q2_prep, dim3(a.K, n / 32), dim3(256), 0, h->stream, a);
   return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
 }
 
 struct ApplyArgs {
   const double* blocks; int n, K;
-  double* Z; int ldz; int ncols; int dbg;
+  double* Z; int ldz; int ncols; int dbg;   // (dbg: read by no kernel, always 0)
   int G0, G1;   // sweep groups of this launch
-  int skip8;    // 1: workgroups with blockIdx % 8 == 0 (the XCD the chase runs on) leave at once, the others share the slabs
+  int skip8;    // (read by no kernel, always 0)
 };
 
-// One workgroup of 4 waves per slab of 16 columns of Z; several workgroups share a CU (16 KB of LDS, <= 128 VGPRs), so one
-// slab's barriers and memory latencies are filled with another slab's arithmetic.  The 64-row window lives in LDS as two 32-row
-// halves whose roles swap from block to block (no copying when the window slides); per block X = V^T Zw (32 x 16, k = 64: wave
-// (xa, xk) one 16 x 16 tile over half of k, the two halves summed when X is read) and Zw -= W X (64 x 16: one tile per wave),
-// 16 MFMAs per wave.  V and W^T come straight from global memory (L2) in the MFMA lane layout, one block ahead -- every wave
-// loads a different quarter of them; the 32 new rows of the window are requested before the block's arithmetic and land in LDS
-// after it.
 #define XLD 16   // 4 consecutive rows of 16 doubles: the 64 lanes of an operand read cover 64 consecutive doubles, no conflicts
 // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every outstanding global load of the wave
 // (loads and stores share one counter on this ISA), which would serialise the operand / window prefetches with the arithmetic
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// FWD = false: Z <- Q2 Z (groups descending, steps ascending, window slides down);  FWD = true: Z <- Q2^T Z with blocks prepared as
-// V, (V T^T)^T (groups ascending -- the order the chase produces them --, steps descending, window slides up)
-template <bool FWD>
-__global__ __launch_bounds__(256, 4) void q2_apply(ApplyArgs p) {
-  __shared__ double Zs[2][32 * XLD];      // physical halves of the window
-  __shared__ double Xs[2][32 * XLD];      // the two k-halves of X
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n = p.n;
-  int slab = blockIdx.x;
-  if (p.skip8) {
-    if ((blockIdx.x & 7) == 0) return;
-    slab = blockIdx.x - (blockIdx.x >> 3) - 1;
-  }
-  const int col0 = slab * 16;
-  if (col0 >= p.ncols) return;
-  double* __restrict__ Zg = p.Z + col0;
-  const int lr = lane & 15, lq = lane >> 4;
-  const int trow = tid >> 3, tc2 = (tid & 7) * 2;   // window <-> global map: 256 threads, 32 rows x 8 column pairs
-  const int ncv = min(16, p.ncols - col0);
-  const bool cok0 = tc2 < ncv, cok1 = tc2 + 1 < ncv;
-  // X tile of this wave: rows 16 xa.., k half xk;   Zw tile: logical rows 16 zr.. (half zr >> 1)
-  const int xa = wave & 1, xk = wave >> 1;
-  const int zr = wave;
-  auto load_ops = [&](const double* __restrict__ blk, double (&va)[8], double (&wa)[8]) {
-#pragma unroll
-    for (int kq = 0; kq < 8; ++kq) va[kq] = blk[(32 * xk + kq * 4 + lq) * 32 + xa * 16 + lr];
-#pragma unroll
-    for (int kq = 0; kq < 8; ++kq) wa[kq] = blk[2048 + (kq * 4 + lq) * 64 + zr * 16 + lr];
-  };
-  auto load_rows = [&](int grow) {   // two doubles of one row of the slab (zero beyond the matrix / the live columns)
-    d2_t v = {0.0, 0.0};
-    if (grow < n) {
-      const double* src = Zg + (size_t)grow * p.ldz + tc2;
-      if (cok1) v = *reinterpret_cast<const d2_t*>(src);
-      else if (cok0) v.x = src[0];
-    }
-    return v;
-  };
-  auto store_rows = [&](int grow, d2_t v) {
-    if (grow < n) {
-      double* dst = Zg + (size_t)grow * p.ldz + tc2;
-      if (cok1) *reinterpret_cast<d2_t*>(dst) = v;
-      else if (cok0) dst[0] = v.x;
-    }
-  };
-  for (int gi = 0; gi < p.G1 - p.G0; ++gi) {
-    const int G = FWD ? p.G0 + gi : p.G1 - 1 - gi;
-    const int s0 = 32 * G;
-    const int nk = q2_nsteps(n, s0);
-    if (nk == 0) continue;
-    const int kfirst = FWD ? nk - 1 : 0, kstep = FWD ? -1 : 1;
-    double va[8], wa[8];
-    load_ops(p.blocks + ((size_t)G * p.K + kfirst) * 4096, va, wa);
-    int cur = 0;   // physical half that holds the window's rows 0..31
-    {
-      const int rb = s0 + 1 + 32 * kfirst;
-      __syncthreads();   // the previous group's last reads of Zs are done, its last stores to Z visible to the whole workgroup
-      const d2_t a0 = load_rows(rb + trow), a1 = load_rows(rb + 32 + trow);
-      *reinterpret_cast<d2_t*>(&Zs[0][trow * XLD + tc2]) = a0;
-      *reinterpret_cast<d2_t*>(&Zs[1][trow * XLD + tc2]) = a1;
-    }
-    for (int ki = 0; ki < nk; ++ki) {
-      const int k = kfirst + kstep * ki;
-      const int rb = s0 + 1 + 32 * k;
-      const bool last = (ki == nk - 1);
-      double vn[8], wn[8];
-      d2_t znew = {0.0, 0.0};
-      if (!last) {
-        load_ops(p.blocks + ((size_t)G * p.K + k + kstep) * 4096, vn, wn);
-        // the rows that enter the window at the next step: below it when it slides down, above it when it slides up
-        znew = load_rows(FWD ? rb - 32 + trow : rb + 64 + trow);
-      }
-      lds_barrier();   // window complete
-      {
-        const double* zh = Zs[xk ^ cur];
-        double zb[8];
-#pragma unroll
-        for (int kq = 0; kq < 8; ++kq) zb[kq] = zh[(kq * 4 + lq) * XLD + lr];   // all operand reads first, then the MFMA chain
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kq = 0; kq < 8; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(va[kq], zb[kq], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Xs[xk][(xa * 16 + 4 * r + lq) * XLD + lr] = acc[r];
-      }
-      lds_barrier();
-      {
-        double* zh = Zs[(zr >> 1) ^ cur] + ((zr & 1) * 16) * XLD;
-        d4_t acc;
-        double xb[8];
-#pragma unroll
-        for (int kq = 0; kq < 8; ++kq) {
-          const int o = (kq * 4 + lq) * XLD + lr;
-          xb[kq] = Xs[0][o] + Xs[1][o];
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = zh[(4 * r + lq) * XLD + lr];
-#pragma unroll
-        for (int kq = 0; kq < 8; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(wa[kq], xb[kq], acc, 0, 0, 1);   // -A
-#pragma unroll
-        for (int r = 0; r < 4; ++r) zh[(4 * r + lq) * XLD + lr] = acc[r];
-      }
-      lds_barrier();
-      // the half the window leaves behind (its first 32 rows when it slides down, its last 32 when it slides up) is final for
-      // this group; that half receives the incoming rows (the last step writes both halves).  The LDS write of the incoming rows
-      // comes BEFORE the global stores: waiting for the incoming rows' load must not also wait for stores issued a moment ago
-      // (loads and stores share one counter).
-      const int hout = FWD ? (cur ^ 1) : cur;          // physical half that leaves
-      const int rout = FWD ? rb + 32 : rb;
-      const d2_t fin = *reinterpret_cast<const d2_t*>(&Zs[hout][trow * XLD + tc2]);
-      if (last) {
-        const d2_t fin2 = *reinterpret_cast<const d2_t*>(&Zs[hout ^ 1][trow * XLD + tc2]);
-        store_rows(rout + trow, fin);
-        store_rows((FWD ? rb : rb + 32) + trow, fin2);
-      } else {
-        *reinterpret_cast<d2_t*>(&Zs[hout][trow * XLD + tc2]) = znew;
-        store_rows(rout + trow, fin);
-        cur ^= 1;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) va[q] = vn[q], wa[q] = wn[q];
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Z <- Q2 Z, four sweep groups per pass over Z (round 3, second half).  The kernel above streams the whole slab through its
-// window once per sweep group: n / 32 passes over Z, 8 flops per byte of HBM traffic -- at N = 8192 it ran at 14 TFLOP/s, bound
+// Z <- Q2 Z, four sweep groups per pass over Z (round 3, second half).  The kernel this replaced streamed the whole slab through
+// its window once per sweep group: n / 32 passes over Z, 8 flops per byte of HBM traffic -- at N = 8192 it ran at 14 TFLOP/s, bound
 // by that traffic and by three barriers per 63 x 32 block.  Blocks of different groups commute when their rows are disjoint,
 // and block (G, k) covers the row bands G + k and G + k + 1 (32 rows each), so four consecutive groups can travel down the slab
 // TOGETHER as a wavefront: wave w of the workgroup owns group Gtop - w and runs two steps behind wave w - 1, which puts it three
@@ -986,43 +835,31 @@ __global__ __launch_bounds__(SPLIT ? 512 : 256, (NC == 1 && !SPLIT) ? 2 : 1) voi
   }
 }
 
-// Z [n, ldz] (first ncols columns) <- Q2 Z (fwd = 0; blocks prepared with trans = 0) or Q2^T Z (fwd = 1; trans = 1), the sweep
-// groups [G0, G1) only.  skip8: leave the XCD the chase runs on alone.
-int ffgp_q2_apply_impl(ffgp_handle* h, const double* blocks, int n, double* Z, int ldz, int ncols, int G0, int G1, int fwd, int skip8) {
-  if (G1 <= G0) return FFGP_OK;
+// Z [n, ldz] (first ncols columns) <- Q2 Z, blocks prepared by ffgp_q2_prep_impl
+int ffgp_q2_apply_impl(ffgp_handle* h, const double* blocks, int n, double* Z, int ldz, int ncols) {
   ApplyArgs a;
-  a.blocks = blocks; a.n = n; a.K = chase_K(n); a.Z = Z; a.ldz = ldz; a.ncols = ncols; a.dbg = h->diag_dbg;
-  a.G0 = G0; a.G1 = G1; a.skip8 = skip8;
-  const int nslab = (ncols + 15) / 16;
-  if (!fwd && h->q2_blocks_lanes) {
-    if (skip8) return FFGP_ERR_ARG;
-    static bool attr_set[64] = {false};
-    if (h->device >= 0 && h->device < 64 && !attr_set[h->device]) {
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(q2_apply_wave4<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   Q2W_LDS_DOUBLES(1) * (int)sizeof(double)));
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(q2_apply_wave4<2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   Q2W_LDS_DOUBLES(2) * (int)sizeof(double)));
-      attr_set[h->device] = true;
-    }
-    // 16-column slabs (two workgroups per CU) measured faster than 32-column ones at every size: N = 8192 51.9 / 57.4 ms,
-    // N = 16384 401 / 424 ms (the old kernel: 80.4 / 712); option value 2 selects the wide form
-    const bool wide = (h->q2_wave4 == 2);
-    // 32-column slabs on eight waves (the SPLIT form) once there are enough of them to fill the chip: N = 8192 45.4 -> 38.9 ms (256 slabs:
-    // one per CU); at N = 4096 its 128 workgroups leave half the CUs empty (7.2 -> 10.2 ms), so smaller matrices keep the 16-column form
-    if (h->q2_wave4 == 3 || (h->q2_wave4 == 1 && ncols >= h->q2_split_min_cols)) {
-      static bool attr3[64] = {false};
-      if (h->device >= 0 && h->device < 64 && !attr3[h->device]) {
-        FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(q2_apply_wave4<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     Q2W_LDS_DOUBLES(2) * (int)sizeof(double)));
-        attr3[h->device] = true;
-      }
-      hipLaunchKernelGGL((q2_apply_wave4<2, true>), dim3((ncols + 31) / 32), dim3(512), Q2W_LDS_DOUBLES(2) * sizeof(double), h->stream, a);
-    } else if (wide) hipLaunchKernelGGL(q2_apply_wave4<2>, dim3((ncols + 31) / 32), dim3(256), Q2W_LDS_DOUBLES(2) * sizeof(double), h->stream, a);
-    else hipLaunchKernelGGL(q2_apply_wave4<1>, dim3(nslab), dim3(256), Q2W_LDS_DOUBLES(1) * sizeof(double), h->stream, a);
-    return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
+  a.blocks = blocks; a.n = n; a.K = chase_K(n); a.Z = Z; a.ldz = ldz; a.ncols = ncols; a.dbg = 0;
+  a.G0 = 0; a.G1 = n / 32; a.skip8 = 0;
+  static bool attr_set[64] = {false};
+  if (h->device >= 0 && h->device < 64 && !attr_set[h->device]) {
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(q2_apply_wave4<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 Q2W_LDS_DOUBLES(1) * (int)sizeof(double)));
+    attr_set[h->device] = true;
   }
-  const int grid = skip8 ? nslab + (nslab + 6) / 7 + 1 : nslab;
-  if (fwd) hipLaunchKernelGGL(q2_apply<true>, dim3(grid), dim3(256), 0, h->stream, a);
-  else hipLaunchKernelGGL(q2_apply<false>, dim3(grid), dim3(256), 0, h->stream, a);
+  // 16-column slabs (two workgroups per CU) measured faster than 32-column ones on four waves at every size: N = 8192 51.9 / 57.4 ms,
+  // N = 16384 401 / 424 ms (the old kernel: 80.4 / 712).
+  // 32-column slabs on eight waves (the SPLIT form) once there are enough of them to fill the chip: N = 8192 45.4 -> 38.9 ms (256 slabs:
+  // one per CU); at N = 4096 its 128 workgroups leave half the CUs empty (7.2 -> 10.2 ms), so smaller matrices keep the 16-column form
+  if (ncols >= h->q2_split_min_cols) {
+    static bool attr3[64] = {false};
+    if (h->device >= 0 && h->device < 64 && !attr3[h->device]) {
+      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(q2_apply_wave4<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   Q2W_LDS_DOUBLES(2) * (int)sizeof(double)));
+      attr3[h->device] = true;
+    }
+    hipLaunchKernelGGL((q2_apply_wave4<2, true>), dim3((ncols + 31) / 32), dim3(512), Q2W_LDS_DOUBLES(2) * sizeof(double), h->stream, a);
+  } else {
+    hipLaunchKernelGGL(q2_apply_wave4<1>, dim3((ncols + 15) / 16), dim3(256), Q2W_LDS_DOUBLES(1) * sizeof(double), h->stream, a);
+  }
   return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
 }

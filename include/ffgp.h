@@ -178,7 +178,6 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
                         overlap did not pay for its hand-offs below ~3500 rows; with value hand-offs -- "ho_values" -- it does from two
                         panels on: N = 1280 / 1536 / 2048 / 2560 / 3072 / 3584 -3.4 / -2.1 / -4.3 / -4.2 / -5.0 / -6.1 %; 0 = look ahead at
                         every size),
-            "la_split" (default 1: the look-ahead column update covers the next panel's first 128 columns only),
             "la_carry" / "la_carry_n" / "la_carry_rows" (a panel's own update kernels also cover the next panel's first 128 columns, so
                         no strip update sits between two panels on the dependency chain: 1 = always, 0 = never (the S_a / S_b / S_ii
                         form), default 2 = throughout for blocks of at most la_carry_n rows (default 12288), and for larger blocks in
@@ -203,46 +202,30 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
             "tile32_threshold" (default 1024: K-major launches with fewer 64-tiles use 32-row tiles),
             "polite_m" (default 6144: trailing updates with fewer rows run one workgroup per CU so that the side
                         stream's kernels always find free registers and LDS),
-            "polite_pad_kb" (default 40: the LDS padding of a polite workgroup; 17 would leave room for the diagonal-block kernel
-                        beside it -- measured neutral),
             "split_rem_max" (default 180: a 128-tile launch whose tile count leaves a remainder <= this modulo the 256 CUs
                         hands those last tiles out as 64 x 64 quarters -- same bits, a shorter last round; 0 = never),
-            "nb_big" / "nb_big_until" (default 0: a wider outer block while more than nb_big_until columns remain; measured
-                        neutral at N = 16384 -- tools/ab_forward.py),
             "super_block" / "super_min_n" (default 1024 / 2048: triangular sweeps on factors of at least super_min_n rows go
                         through inverted super_block x super_block diagonal blocks; 0 = always block by block),
             "skinny_max_n" (default 8: products with at most this many output columns run on the matrix-vector kernels; 0 = never),
             "splitk_min_k" (default 1024: products with <= 64 tiles of 64 x 64 and k >= this are cut along k; 0 = never),
-            "band_log2" (default 3: the GEMM tile order walks bands of 2^k tile rows, column-major inside a band),
-            "diag_dbg" (timing-only ablation mask of the diagonal-block kernel; results are wrong when non-zero),
             "asm_mm" / "asm_mm_min" / "asm_mm_grid" (default 1 / 6144 / 768: squared-exponential assemblies whose geometric-mean size
                         is at least asm_mm_min evaluate their interior 64 x 64 tiles on the matrix cores -- norm expansion, guarded
                         per 32 x 32 block by a fall-back to the difference form wherever a distance is below 1e-6 of the
                         squared norms -- with asm_mm_grid persistent workgroups; 0 = the difference kernel alone),
-            "q2_wave4" (default 1: ffgp_syevd / ffgp_ormq2 apply Q2 with four sweep groups per pass over Z; 2 = the same on
-                        32-column slabs; 0 = one group per pass -- blocks are prepared in the matching layout by ffgp_sb2st),
             "small_finish" (default 0; 1: 40 < n <= 128 runs assembly + blocked factorisation + ONE finishing kernel, 7 launches
                         instead of 21 -- measured +-5-10 % per training step),
-            "raw_graph_max_n" (default 0; > 0: ffgp_nlml_fused_raw calls with n <= this are captured into a hipGraph on their
-                        second identical occurrence and replayed afterwards -- measured no faster on ROCm 7.2),
             "trtri_fill" (default 0: the gradient path's triangular inverse, when its head runs under the factorisation, zeroes only the
                         diagonal blocks' upper parts of its N x N buffer -- every consumer reads it tile-wise below the diagonal;
                         1 = zero-fill the whole buffer first (2 GB per step at N = 16384; +0.2 ms); 2 = fill it with NaN, a test mode),
-            "sb_av_gemm" (default 0: the band reduction forms A * Y with its own 128-row kernel; 1 = the general GEMM -- measured
-                        sy2sb 104 -> 91 ms at n = 8192, equal below n = 4096),
             "sb_lower" (default 1) / "sb_lower_min_n" (default 6144): for matrices of at least that many rows ffgp_syevd's band
                         reduction keeps only the LOWER triangle of the trailing matrix up to date (the rank-64 update is bound by
                         HBM: half the bytes) and forms A * Y from that triangle alone (every element serves the product and its
                         transpose); results agree with the full form to rounding.  n = 8192: update 21.8 -> 12.3 ms, A * Y and its
                         sums 16.1 -> 20.6 ms, eigh 234.3 -> 229.7 ms; below ~6000 rows the full form is as fast.  "sb_sym_wg"
                         (default 2048): workgroups the lower-triangle A * Y launch aims for,
-            "sb_qr4" (default 0; 1: the band reduction's leaf QRs on 256-thread workgroups, four columns per half-wave -- 58.9 us per
-                        panel against 54.4 us on 1024 threads at n = 8192; with "sb_lookahead" the only form whose leaves overlap
-                        the trailing update, stage time equal either way),
             "diag_v2" (default 4: the round-4 diagonal-block kernel ffgp_potrf_diag128_v3 -- owner-computes helper waves, no
                         barrier; 0 = the barrier version (ffgp_nlml_fused_batch then returns FFGP_ERR_ARG: only the default kernel
-                        is batched).  The shipped library accepts 0 and 4 only; 1 and 3, the round-3 pipelines, exist in the
-                        development build),
+                        is batched).  Any other value is refused),
             "chase_pack" (placement of the bulge chase's 256 working wavefronts: every pack-th workgroup works.  Default 1 = one per
                         compute unit over the whole chip (N = 8192: 64.6 ms; 2 = on every other XCD: 69.4, 4: 92, 8: 166); beside
                         other blocks' kernels 1 and 2 measure the same (config 5's eight blocks: 1.43-1.47 s per step either way),
@@ -288,19 +271,17 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
                         chase; a value no wave of the launch reports leaves the whole chase to the chip-wide launch behind it: a test mode),
             "batch_grad_ob" (default 1: the shared chain's gradient stage inverts all blocks in one outer-batched sequence of launches),
             "trtri_overlap", "small_fused", "small_max_n" (round-3 experiment switches).
-   Keys the SHIPPED library refuses with FFGP_ERR_ARG (they are accepted by the development build only, `make dev`,
-   ffgp_has_dev_options() == 1): "raw_graph_max_n", "diag_dbg", "la_split", "nb_big", "nb_big_until", "sb_lookahead", "sb_av_gemm",
-   "sb_qr4", "q2_wave4", "eig_overlap", "band_log2", "polite_pad_kb", "pass_split_min", "tail_mask_m", "tail_mask_cus", "syrk_h64", "syrk_direct" (the
-   round-5 experiments on the factorisation's chain, docs/experiments.md), and every value of "diag_v2" other than 0 and 4.  An unknown
-   key is FFGP_ERR_ARG in both builds.    */
+   Retired keys, refused with FFGP_ERR_ARG like any unknown key: "raw_graph_max_n", "diag_dbg", "la_split", "nb_big", "nb_big_until",
+   "sb_lookahead", "sb_av_gemm", "sb_qr4", "q2_wave4", "eig_overlap", "band_log2", "polite_pad_kb", "pass_split_min", "tail_mask_m",
+   "tail_mask_cus", "syrk_h64", "syrk_direct" (switches of experiments that were measured and lost, docs/experiments.md; the library
+   runs with the values they had by default), and the values 1 and 3 of "diag_v2".    */
 int ffgp_set_option(ffgp_handle* h, const char* key, double value);
 /* Create the handle's side streams now and use each once, so that they bind their hardware queues before streams the process creates
    later (ROCm binds at first use; a late stream shares a queue with an earlier one and runs in line with it).  For the main handle of
    a process that puts several blocks in flight on one GPU: call it before creating the worker streams.  No reference counterpart. */
 int ffgp_prepare_streams(ffgp_handle* h);
 const char* ffgp_version(void);
-/* 1 in the development build (`make dev`: the switches of measured-and-rejected experiments are accepted by ffgp_set_option), 0 in
-   the shipped library */
+/* Always 0; kept for existing bindings. */
 int ffgp_has_dev_options(void);
 /* Number of forward calls this handle has served by replaying a captured graph since it was created (option "fwd_graph" of
    ffgp_set_option: the second identical forward-only call -- same problem struct, so the same device buffers; their CONTENTS may

@@ -1121,42 +1121,6 @@ def test_raw_path_defers_not_pd_to_backward():
     assert torch.isfinite(m.negative_log_likelihood(X, Y))
 
 
-def test_raw_graph_replay():
-    """option raw_graph_max_n: the third identical raw-parameter call replays a captured graph (off by default -- no faster on this
-    runtime); values and gradients are bit-identical, a changed input or option drops the graph"""
-    from conftest import need_dev_options
-    need_dev_options()
-    from fidelityfusion_amd import _lib, kernel
-    from fidelityfusion_amd.cigp_v10 import cigp
-    rng = np.random.default_rng(6)
-    X, Y = T(rng.uniform(0, 1, (150, 3))), T(rng.standard_normal((150, 2)))
-    m = cigp(kernel.ARDKernel(3), 0.8).double().to(DEV)
-    h = _lib.handle(0)
-
-    def step(x):
-        for p_ in m.parameters():
-            p_.grad = None
-        v = m.negative_log_likelihood(x, Y)
-        v.backward()
-        return v.detach().clone(), [p_.grad.clone() for p_ in m.parameters()]
-
-    ref = step(X)
-    X2 = X.clone() * 0.9
-    ref2 = step(X2)
-    assert _lib.lib.ffgp_set_option(h, b"raw_graph_max_n", 1024.0) == 0
-    try:
-        for i in range(4):                       # plain, capture + launch, replay, replay
-            v, gr = step(X)
-            assert torch.equal(v, ref[0]) and all(torch.equal(a, b) for a, b in zip(gr, ref[1])), i
-        v, gr = step(X2)                         # other inputs: the graph is dropped, not replayed on them
-        assert torch.equal(v, ref2[0]) and all(torch.equal(a, b) for a, b in zip(gr, ref2[1]))
-        for i in range(3):
-            v, gr = step(X)
-            assert torch.equal(v, ref[0]) and all(torch.equal(a, b) for a, b in zip(gr, ref[1])), i
-    finally:
-        _lib.lib.ffgp_set_option(h, b"raw_graph_max_n", 0.0)
-
-
 @pytest.mark.parametrize("n,d", [(900, 2), (1536, 3), (4000, 1)])
 def test_forward_graph_replay(n, d):
     """option fwd_graph: from its third identical occurrence a forward-only likelihood call is ONE hipGraphLaunch (both streams of the

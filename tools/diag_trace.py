@@ -1,4 +1,4 @@
-"""Phase timeline of the pipelined diagonal-block kernel (ffgp_potrf_diag128_v2): builds fidelityfusion_amd/libffgp_dtrace.so
+"""Phase timeline of the pipelined diagonal-block kernel (option diag_v2 = 4): builds fidelityfusion_amd/libffgp_dtrace.so
 with -DFFGP_DIAG_TRACE (wave 0 and helper 0 stamp wall_clock64 -- 100 MHz -- at their phase boundaries) and prints the
 stamps of one 128 x 128 factorisation in microseconds."""
 import ctypes as C
@@ -35,7 +35,7 @@ if __name__ == "__main__":
     X = torch.rand((n, 8), generator=g, device=dev, dtype=torch.float64)
     A = torch.exp(-0.5 * torch.cdist(X, X) ** 2) + 0.37 * torch.eye(n, device=dev, dtype=torch.float64)
     buf = torch.zeros(128, dtype=torch.int64, device=dev)
-    mode = int(sys.argv[1]) if len(sys.argv) > 1 else 1
+    mode = int(sys.argv[1]) if len(sys.argv) > 1 else 4
     lib.ffgp_set_option(h, b"diag_v2", C.c_double(mode))
     for rep in range(3):
         W = A.clone()

@@ -5,11 +5,10 @@ import sys
 import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _devlib  # noqa: F401,E402  (development build: these switches are not in the shipped library)
 import torch
 from fidelityfusion_amd import eigh as E
 from fidelityfusion_amd import _lib as _opt_lib
-for _kv in os.environ.get("FFGP_EIGH_OPTS", "").split(","):     # e.g. FFGP_EIGH_OPTS=q2_wave4=0
+for _kv in os.environ.get("FFGP_EIGH_OPTS", "").split(","):     # e.g. FFGP_EIGH_OPTS=sb_lower=0
     if _kv:
         _opt_lib.check(_opt_lib.lib.ffgp_set_option(_opt_lib.handle(0), _kv.split("=")[0].encode(), float(_kv.split("=")[1])), "ffgp_set_option")
 
@@ -34,18 +33,14 @@ for n in sizes:
             torch.cuda.synchronize()
             best = min(best, time.perf_counter() - t0)
         return best * 1e3, out
-    from fidelityfusion_amd import _lib
-    _lib.set_option("eig_overlap", 1)
-    t_ovl, _ = timed(lambda: E.eigh(K))
-    _lib.set_option("eig_overlap", 0)
     t_own, (ev, U) = timed(lambda: E.eigh(K))
     t_roc, (ev_r, U_r) = timed(lambda: torch.linalg.eigh(K))
     nrm = float(torch.linalg.matrix_norm(K))
     rec = float(torch.linalg.matrix_norm((U * ev) @ U.T - K)) / nrm
     rec_r = float(torch.linalg.matrix_norm((U_r * ev_r) @ U_r.T - K)) / nrm
     orth = float((U.T @ U - torch.eye(n, device=dev, dtype=torch.float64)).abs().max())
-    print("eigh n=%5d D=%d: own %8.1f ms (overlapped driver %8.1f ms)  rocSOLVER %8.1f ms   |K-ULU'|/|K| own %.1e roc %.1e  orth %.1e  max|dlam|/lam_max %.1e"
-          % (n, D, t_own, t_ovl, t_roc, rec, rec_r, orth, float((ev - ev_r).abs().max() / ev_r.abs().max())), flush=True)
+    print("eigh n=%5d D=%d: own %8.1f ms  rocSOLVER %8.1f ms   |K-ULU'|/|K| own %.1e roc %.1e  orth %.1e  max|dlam|/lam_max %.1e"
+          % (n, D, t_own, t_roc, rec, rec_r, orth, float((ev - ev_r).abs().max() / ev_r.abs().max())), flush=True)
     if n % 64 == 0:
         t1, (AB, Y) = timed(lambda: E.sy2sb(K), 1)
         t2, (dd, ee, refl) = timed(lambda: E.sb2st(AB), 1)

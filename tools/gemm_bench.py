@@ -9,7 +9,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _devlib  # noqa: F401,E402  (development build: these switches are not in the shipped library)
 
 import numpy as np
 import torch
@@ -90,67 +89,6 @@ if __name__ == "__main__":
     main()
 
 
-def diag_ablation():
-    """time potrf_diag128 alone (inverse-only and factor entry) with phases masked out"""
-    h = _lib.handle(0)
-    _lib.bind_stream(h, 0)
-    n = 128 * 64
-    dev = "cuda:0"
-    g = torch.Generator(device=dev).manual_seed(0)
-    X = torch.rand((n, 8), generator=g, device=dev, dtype=torch.float64)
-    w = torch.ones(8, device=dev, dtype=torch.float64)
-    amp = torch.ones(1, device=dev, dtype=torch.float64)
-    dadd = torch.full((1,), 0.37, device=dev, dtype=torch.float64)
-    W = torch.empty((n, n), device=dev, dtype=torch.float64)
-    _lib.lib.ffgp_assemble(h, p(X), n, p(X), n, 8, p(w), p(amp), 1e-30, p(dadd), None, 0, None, 0, 0.0, 0.0, p(W), n, 1, 0, 1.0)
-    assert _lib.lib.ffgp_potrf(h, p(W), n, n) == 0
-    # 64 sequential launches of the inverse-only entry (phases 0,3,4,5)
-    for mask in (0, 8, 16, 32, 128, 8 + 16 + 32 + 128):
-        _lib.set_option("diag_dbg", mask, 0)
-        fn = lambda: _lib.lib.ffgp_trtri_diag(h, p(W), n, n)
-        fn()
-        tmin, _ = timeit(fn)
-        print("diag inverse-only entry, mask %3d: %.1f us per launch" % (mask, tmin * 1e3 / 64))
-    _lib.set_option("diag_dbg", 0, 0)
-
-
-if "diag" in sys.argv[1:]:
-    diag_ablation()
-
-
-def diag_factor_ablation():
-    h = _lib.handle(0)
-    _lib.bind_stream(h, 0)
-    dev = "cuda:0"
-    n = 128
-    g = torch.Generator(device=dev).manual_seed(0)
-    X = torch.rand((n, 8), generator=g, device=dev, dtype=torch.float64)
-    w = torch.ones(8, device=dev, dtype=torch.float64)
-    amp = torch.ones(1, device=dev, dtype=torch.float64)
-    dadd = torch.full((1,), 0.37, device=dev, dtype=torch.float64)
-    W0 = torch.empty((n, n), device=dev, dtype=torch.float64)
-    _lib.lib.ffgp_assemble(h, p(X), n, p(X), n, 8, p(w), p(amp), 1e-30, p(dadd), None, 0, None, 0, 0.0, 0.0, p(W0), n, 1, 0, 1.0)
-    Ws = [W0.clone() for _ in range(50)]
-    _lib.set_option("lookahead", 0, 0)
-    for mask in (0, 1, 2, 4, 64, 1 + 2 + 4 + 64, 255):
-        _lib.set_option("diag_dbg", mask, 0)
-
-        def fn():
-            for Wt in Ws:
-                Wt.copy_(W0)
-            for Wt in Ws:
-                _lib.lib.ffgp_potrf(h, p(Wt), n, n)
-        fn()
-        tmin, _ = timeit(fn)
-        print("potrf(n=128) x50 incl. host sync, mask %3d: %.1f us per call" % (mask, tmin * 1e3 / 50))
-    _lib.set_option("diag_dbg", 0, 0)
-    _lib.set_option("lookahead", 1, 0)
-
-
-if "diagf" in sys.argv[1:]:
-    diag_factor_ablation()
-
-
 def potrf_sweep():
     h = _lib.handle(0)
     _lib.bind_stream(h, 0)
@@ -163,22 +101,19 @@ def potrf_sweep():
         dadd = torch.full((1,), 0.37, device=dev, dtype=torch.float64)
         W = torch.empty((n, n), device=dev, dtype=torch.float64)
         for nbo in (512, 768, 1024):
-            for split in (0, 1):
-                for thr in (256, 384, 640):
-                    _lib.set_option("nb_outer", nbo, 0)
-                    _lib.set_option("la_split", split, 0)
-                    _lib.set_option("small_tile_threshold", thr, 0)
+            for thr in (256, 384, 640):
+                _lib.set_option("nb_outer", nbo, 0)
+                _lib.set_option("small_tile_threshold", thr, 0)
 
-                    def fn():
-                        _lib.lib.ffgp_assemble(h, p(X), n, p(X), n, 16, p(w), p(amp), 1e-30, p(dadd), None, 0, None, 0, 0.0,
-                                               0.0, p(W), n, 1, 0, 1.0)
-                        assert _lib.lib.ffgp_potrf(h, p(W), n, n) == 0
-                    fn()
-                    tmin, tmed = timeit(fn, rounds=3)
-                    print("n=%d nb_outer=%d split=%d thr=%d: %.2f ms (%.1f TF/s)" % (n, nbo, split, thr, tmin, n ** 3 / 3.0 / tmin / 1e9))
+                def fn():
+                    _lib.lib.ffgp_assemble(h, p(X), n, p(X), n, 16, p(w), p(amp), 1e-30, p(dadd), None, 0, None, 0, 0.0,
+                                           0.0, p(W), n, 1, 0, 1.0)
+                    assert _lib.lib.ffgp_potrf(h, p(W), n, n) == 0
+                fn()
+                tmin, tmed = timeit(fn, rounds=3)
+                print("n=%d nb_outer=%d thr=%d: %.2f ms (%.1f TF/s)" % (n, nbo, thr, tmin, n ** 3 / 3.0 / tmin / 1e9))
     _lib.set_option("nb_outer", 512, 0)
-    _lib.set_option("la_split", 0, 0)
-    _lib.set_option("small_tile_threshold", 384, 0)
+    _lib.set_option("small_tile_threshold", 640, 0)
 
 
 if "sweep" in sys.argv[1:]:

@@ -9,14 +9,10 @@
 #define sb2st_chase probe_sb2st_chase
 #define sb2st_tail probe_sb2st_tail
 #define ffgp_sb2st_impl probe_sb2st_impl
-#define ffgp_sb2st_init probe_sb2st_init
-#define ffgp_sb2st_chunk probe_sb2st_chunk
-#define ffgp_sb2st_finish probe_sb2st_finish
 #define ffgp_q2_prep_impl probe_q2_prep_impl
 #define ffgp_q2_apply_impl probe_q2_apply_impl
 #define ffgp_q2_block_doubles probe_q2_block_doubles
 #define q2_prep probe_q2_prep
-#define q2_apply probe_q2_apply
 #define q2_apply_wave4 probe_q2_apply_wave4
 #include "../../fidelityfusion_amd/csrc/sb2st.hip"
 #include <cstdio>

@@ -13,14 +13,10 @@
 #define sb2st_chase probe_sb2st_chase
 #define sb2st_tail probe_sb2st_tail
 #define ffgp_sb2st_impl probe_sb2st_impl
-#define ffgp_sb2st_init probe_sb2st_init
-#define ffgp_sb2st_chunk probe_sb2st_chunk
-#define ffgp_sb2st_finish probe_sb2st_finish
 #define ffgp_q2_prep_impl probe_q2_prep_impl
 #define ffgp_q2_apply_impl probe_q2_apply_impl
 #define ffgp_q2_block_doubles probe_q2_block_doubles
 #define q2_prep probe_q2_prep
-#define q2_apply probe_q2_apply
 #define q2_apply_wave4 probe_q2_apply_wave4
 #include "../../fidelityfusion_amd/csrc/sb2st.hip"
 #include <cstdio>
@@ -45,14 +41,13 @@ int main() {
   CK(hipMalloc(&Z, (size_t)n * n * sizeof(double)));
   CK(hipMemset(blocks, 0, nb * sizeof(double)));
   CK(hipMemset(Z, 0, (size_t)n * n * sizeof(double)));
-  h->q2_blocks_lanes = 1;
   hipEvent_t e0, e1;
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
   float best = 1e9f;
   for (int rep = 0; rep < 3; ++rep) {
     CK(hipEventRecord(e0, h->stream));
-    if (probe_q2_apply_impl(h, blocks, n, Z, n, n, 0, n / 32, 0, 0) != FFGP_OK) { printf("apply failed\n"); return 1; }
+    if (probe_q2_apply_impl(h, blocks, n, Z, n, n) != FFGP_OK) { printf("apply failed\n"); return 1; }
     CK(hipEventRecord(e1, h->stream));
     CK(hipDeviceSynchronize());
     float ms;

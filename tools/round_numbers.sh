@@ -20,16 +20,13 @@ python3 bench.py --full --n 32768 --steps 3 --warmup 1 --no-cpu-baseline --no-sh
 python3 bench.py --full --workload gar8_hogp --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_gar8_hogp.json 2>> $OUT/bench.err
 fi
 if [ "$PART" != "bench" ]; then
-# (the development library -- switches of rejected experiments that diag_bench / eigh_bench / raw_graph_bench A/B -- does not travel to
-#  the box: built here, ~1 min; tools/_devlib.py picks it up)
-make -C fidelityfusion_amd/csrc -j16 dev > $OUT/make_dev.log 2>&1
 {
 echo "## tools/train_bench.py 200"; timeout 300 python3 tools/train_bench.py 200 2>&1 | grep -v amdgpu.ids | tail -8
 for sz in "300,300,250 1" "300,300,250 1 grad" "8192,4096,2048,1024 1" "8192,4096,2048,1024 1 grad" "8192,4096,2048,1024 256"; do
   echo "## tools/ragged_probe.py $sz"; timeout 300 python3 tools/ragged_probe.py $sz 2>&1 | grep -v amdgpu.ids | tail -7
 done
 echo "## tools/batch_chain_bench.py 4096 8"; timeout 300 python3 tools/batch_chain_bench.py 4096 8 2>&1 | grep -v amdgpu.ids | tail -8
-for t in posterior_bench hogp_bench c4_step small_n_latency small_kernel_bench v2_bench diag_bench assemble_bench chase_dbg step_stages raw_graph_bench; do
+for t in posterior_bench hogp_bench c4_step small_n_latency small_kernel_bench v2_bench assemble_bench chase_dbg step_stages; do
   echo "## tools/$t.py"; timeout 300 python3 tools/$t.py 2>&1 | grep -v amdgpu.ids | tail -12
 done
 echo "## tools/eigh_bench.py full big"; timeout 600 python3 tools/eigh_bench.py full big 2>&1 | grep -v amdgpu.ids | tail -12

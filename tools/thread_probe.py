@@ -5,7 +5,6 @@ import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _devlib  # noqa: F401,E402  (development build: these switches are not in the shipped library)
 import torch
 from fidelityfusion_amd import eigh as E
 from fidelityfusion_amd import functional as F
@@ -80,12 +79,7 @@ with torch.no_grad():
         torch.cuda.synchronize()
         print("sy2sb from threads, concurrent (repeat %d): %s" % (rep, ["same" if all(torch.equal(a, b) for a, b in zip(ref[f], got[f])) else "DIFFERENT" for f in range(nb)]), flush=True)
 
-# --- which kernel?  toggle the band reduction's alternative kernels on every handle in use ------------------------------------------
-def set_all(key, val):
-    for s_ in range(0, nslots + 1):
-        _lib.set_option_handle(_lib.handle(0, s_), key, val)
-
-
+# --- the band reduction from threads against the sequential run ---------------------------------------------------------------------
 def concurrent_ok(label, reps=3):
     with torch.no_grad():
         ref_ = [E.sy2sb(Ks[f]) for f in range(nb)]
@@ -99,15 +93,6 @@ def concurrent_ok(label, reps=3):
 
 
 concurrent_ok("defaults")
-set_all("sb_av_gemm", 1)
-concurrent_ok("A Y on the general GEMM (sb_av_gemm=1)")
-set_all("sb_av_gemm", 0)
-set_all("sb_qr4", 1)
-concurrent_ok("256-thread leaf QR (sb_qr4=1)")
-set_all("sb_av_gemm", 1)
-concurrent_ok("both")
-set_all("sb_av_gemm", 0)
-set_all("sb_qr4", 0)
 
 # --- where does a concurrent band reduction first leave the sequential one? -----------------------------------------------------------
 with torch.no_grad():
