@@ -285,14 +285,12 @@ int ffgp_create(int device, ffgp_handle** out) {
   }
   h->aux_prio = 1;
   h->nb_outer = 512;
-  h->diag_v2 = 4;
   h->trsm128 = 1;
   h->polite64_pad_kb = 60;
   h->polite32_pad_kb = 46;
   h->ho_values = default_ho_values();
   h->ho_defer = 2;
   h->ho_gate = 1;
-  h->diag_v4 = 1;
   h->grad_lanes = 3;
   h->ho_timeout_ms = 2000;
   h->ho_defer_slot = -1;
@@ -428,8 +426,6 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
   } else if (!strcmp(key, "ho_values")) {
     if (value != 0.0 && h->ho_selftest_failed) return FFGP_ERR_ARG;      // (this process runs its kernels one at a time: see ffgp_handoff_selftest)
     h->ho_values = value != 0.0;
-  } else if (!strcmp(key, "diag_v4")) {
-    h->diag_v4 = value != 0.0;
   } else if (!strcmp(key, "ho_gate")) {
     h->ho_gate = value != 0.0;
   } else if (!strcmp(key, "ho_timeout_ms")) {
@@ -452,9 +448,6 @@ int ffgp_set_option(ffgp_handle* h, const char* key, double value) {
     h->trsm128 = value != 0.0;
   } else if (!strcmp(key, "trsm128_max_m")) {
     h->trsm128_max_m = (int)value;
-  } else if (!strcmp(key, "diag_v2")) {
-    if (value != 4.0 && value != 0.0) return FFGP_ERR_ARG;
-    h->diag_v2 = (int)value;
   } else if (!strcmp(key, "la_min_n")) {
     h->la_min_n = (int)value;
   } else if (!strcmp(key, "chase_xl")) {
@@ -905,7 +898,7 @@ static int ffgp_grad_lanes_prepare(ffgp_handle* h, int nl) {
 // and fill its gaps with F times the matrix-core work.  The per-block arithmetic is the single call's, instruction for instruction
 // (same kernels, same k order): the values are bit-identical to F separate calls.
 // Conditions (else FFGP_ERR_ARG, and the caller falls back to separate calls): 2 <= F <= 256 blocks with n > 128, V1
-// likelihood, one radial-profile kernel each (no pair / tree / caller-built covariance), the round-4 diagonal-block kernel.
+// likelihood, one radial-profile kernel each (no pair / tree / caller-built covariance), not the naive kernels.
 // Round 5: the blocks may have DIFFERENT n and d (the reference's fidelities are ragged by nature, FidelityFusion_Models/ResGP.py:121-136):
 // every member follows its own single call's launch sequence and launches of the same kind at the same chain step are merged
 // (ffgp_potrf_ragged, ffgp_gemm_launch_rag), members drop out as their columns run out; members above 12288 rows are refused.
@@ -913,7 +906,7 @@ static int ffgp_grad_lanes_prepare(ffgp_handle* h, int nl) {
 int ffgp_nlml_fused_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g,
                           int* status) {
   if (!h || !p || !nll_dev || F < 2 || F > 256) return FFGP_ERR_ARG;
-  if (h->use_naive || h->diag_v2 != 4) return FFGP_ERR_ARG;
+  if (h->use_naive) return FFGP_ERR_ARG;
   bool want_grad = false, uniform = true;
   for (int f = 0; f < F; ++f) {
     const ffgp_problem& q = p[f];

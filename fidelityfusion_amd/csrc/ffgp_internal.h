@@ -158,7 +158,6 @@ struct ffgp_handle {
   unsigned ho_launched[10];   // ... the newest number whose producing operation has been ENQUEUED (submission-order rule, la_wait)
   long ho_order_violations;   // waits enqueued before their producers (must stay 0)
   int lds_cap, lds_cap_known;   // hipDeviceAttributeMaxSharedMemoryPerBlock, asked for once (launch_diag)
-  int diag_v4;          // option "diag_v4": the diagonal-block kernel with two barriers per stage (ffgp_potrf_diag128_v4) in place of v3
   int ho_gate;          // option "ho_gate" (default 1): waits are the library's own gate kernel with a watchdog; 0 = hipStreamWaitValue32
   int ho_timeout_ms;    // option "ho_timeout_ms" (default 2000): the gate gives up after this long (FFGP_ERR_HANDOFF)
   int* ho_info;         // the status word a gate that gives up writes to (set by the factorisation entry points)
@@ -185,7 +184,6 @@ struct ffgp_handle {
   int polite64_pad_kb;  // unused LDS (KiB) requested by the look-ahead's 64-tile trailing updates (default 60: two workgroups per CU instead of four)
   int trsm128;          // 1 = the chain's full-block TRSM runs on its own kernel (ffgp_trsm128_kernel; same values as the general GEMM)
   int trsm128_max_m;    // ... for panels of at most this many rows (taller ones stay on the general GEMM)
-  int diag_v2;          // diagonal-block kernel: 4 = round-4 kernel (default: owner-computes helpers, wave 0's SIMD partner steps aside), 0 = barrier version
   int lookahead;        // 1 = overlap panel k+1 with the trailing update of step k
   int la_min_n;         // blocks up to this size are factored in order (no side stream): default 1024 since the look-ahead's hand-offs are values
                         // (2 - 6 % at 1280 ... 3584 rows; 3584 while they were event pairs)
@@ -194,7 +192,7 @@ struct ffgp_handle {
                         // the iterations whose trailing matrix has at most la_carry_rows rows
   int la_carry_n;       // ... (default 12288; also the largest member a ragged chain accepts)
   int la_carry_rows;    // ... (default 8192)
-  int diag_attr_set;    // dynamic-LDS attribute of potrf_diag128 set on this handle's device
+  int diag_attr_set;    // dynamic-LDS attributes set on this handle's device (launch_diag, ffgp_potrf_ragged): 1 inverse-only kernel, 2 / 4 v4
   int split_rem_max;    // split tail of the 128-tile launches: quarter the last (tiles mod 256) tiles when that is <= this (0 = off)
   int polite_m;         // trailing updates with fewer rows than this run one workgroup per CU (0 = never)
   bool own_stream;

@@ -2,10 +2,9 @@
 //
 //   outer step (width nb_outer, default 512):
 //     panel: for each 128-wide sub-block
-//        potrf_diag128   one workgroup, the 128x128 diagonal block LDS-resident (padded [128][130] image):
-//                        left-looking over 16-column blocks -- MFMA updates, a register/readlane 16x16 factor in
-//                        one wave, substitution TRSM with one lane per row -- then the block's INVERSE is formed
-//                        in place (16x16 inverses + MFMA products) and written to the handle's Dinv store;
+//        potrf_diag128_v4  one workgroup, the 128x128 diagonal block LDS-resident (36 packed 16x16 blocks, diag_block.h):
+//                        16-column stages -- a register 16x16 factor + inverse in one wave, MFMA updates, solves and
+//                        the rows of the block's INVERSE in the others -- L to A, the inverse to the handle's Dinv store;
 //        TRSM            A21 <- A21 * inv(L11)^T      = one NT GEMM on the matrix cores (in place);
 //        panel update    A22p -= A21 * A21p^T         = one NT GEMM (lower-trapezoid tiles);
 //     trailing update    A22 -= P * P^T  (K = nb_outer) = the SYRK instantiation of the GEMM kernel -- the
@@ -15,106 +14,20 @@
 // global index (first failure wins) and the factorisation continues with a unit pivot so that no NaN/Inf
 // propagates into later kernels' control flow.
 #include "ffgp_internal.h"
-#include "f16_steps.h"
+#include "diag_block.h"
 
 #define NB FFGP_NB
-// LDS image of the 128x128 diagonal block: only the 36 lower 16x16 blocks, each [16][17] doubles (the pad makes
-// the MFMA operand reads bank-conflict-free).  78 KiB instead of 130 KiB for the dense image: the kernel must
-// fit beside ONE resident GEMM workgroup (72 KiB of the CU's 160 KiB), otherwise the look-ahead panel factor
-// would never be scheduled while the trailing update occupies the chip.
-#define BLD 17
-#define BLKSZ (16 * BLD)
-#define NBLK_LOWER 36
+// LDS of the inverse-only kernel: the block image (diag_block.h) and the reciprocals of the diagonal of L
 #define DIAG_LDS_DOUBLES (NBLK_LOWER * BLKSZ + 128)
 #define DIAG_LDS_BYTES (DIAG_LDS_DOUBLES * 8)
-// 8 waves: wave 0 runs the serial 16x16 factor chain, the other seven do the MFMA work in its shadow
 #define DIAG_THREADS 512
-#define DIAG_WAVES (DIAG_THREADS / 64)
-
-__device__ __forceinline__ int blk_off(int bi, int bj) { return (bi * (bi + 1) / 2 + bj) * BLKSZ; }
-
-__device__ __forceinline__ double rsqrt_nr(double d) {
-  double y = __builtin_amdgcn_rsq(d);
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const double e = __builtin_fma(-d * y, y, 1.0);
-    y = __builtin_fma(0.5 * y, e, y);
-  }
-  return y;
-}
-
-__device__ __forceinline__ double rcp_nr(double d) {
-  double y = __builtin_amdgcn_rcp(d);
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {  // v_rcp_f64 is good to ~2^-26; two Newton steps reach fp64 rounding level
-    const double e = __builtin_fma(-d, y, 1.0);
-    y = __builtin_fma(y, e, y);
-  }
-  return y;
-}
-
-// 16x16 MFMA tile product helper: acc += Arows(16 x 16, K-major at pa[row*lda_ + k]) * B
-//   KB = true : B given K-major  (B^T stored: element (n,k) at pb[n*ldb_ + k])
-//   KB = false: B given N-major  (element (k,n) at pb[k*ldb_ + n])
-template <bool KB>
-__device__ __forceinline__ void mma16(d4_t& acc, const double* pa, int lda_, const double* pb, int ldb_, int lane) {
-#pragma unroll
-  for (int kq = 0; kq < 4; ++kq) {
-    const int k = kq * 4 + (lane >> 4);
-    const double a = pa[(lane & 15) * lda_ + k];
-    const double b = KB ? pb[(lane & 15) * ldb_ + k] : pb[k * ldb_ + (lane & 15)];
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-  }
-}
-
-// one step of the in-register 16x16 Cholesky: the block is symmetric-full, lane (g = lane>>4, c = lane&15) holds
-// rows g+4r (r = 0..3) of column c.  Pivot J: rank-1 downdate of the whole block with column J / d.
-// The pivot-to-pivot dependency chain is  readlane -> rcp -> 3 fma -> fma  (fp64 VALU ops have ~24-cycle dependent
-// latency, so every op removed from the chain is ~10 % of the block's factor time):
-//   * 1/d = y0 (1 + e + e^2), e = 1 - d y0, with y0 = v_rcp_f64(d) (~2^-26): t = u + u*(e + e^2), u = A[J][c]*y0 --
-//     three dependent fmas after the rcp instead of two Newton steps plus a multiply;
-//   * the pivot is not sanitised on the chain: a non-positive pivot is flagged on the side and the block's
-//     results are then garbage (as LAPACK's are), but no control flow depends on them;
-//   * the lanes of column J park their unscaled column and pivot; 1/sqrt(d) scaling happens after the 16 steps;
-//   * the same eliminations are applied to an identity block W (off the chain, in its issue gaps), so that
-//     inv(L_jj) = diag(1/sqrt(d)) * W comes out with the factor and the rows below are solved on the matrix cores.
-template <int J>
-__device__ __forceinline__ void chol16_step(double (&v)[4], double (&w)[4], double (&out)[4], double& dmine, int lane,
-                                            int& bad) {
-  constexpr int PL = 16 * (J & 3) + J, PR = J >> 2;
-  const double d = readlane_d(v[PR], PL);
-  bad = (!(d > 0.0) && bad == 0) ? J + 1 : bad;
-  const double y0 = __builtin_amdgcn_rcp(d);
-  const double rowj = bperm_d(v[PR], 16 * (J & 3) + (lane & 15));  // A[J][c]
-  const double wrow = bperm_d(w[PR], 16 * (J & 3) + (lane & 15));  // W[J][c]
-  double colj[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) colj[r] = row_bcast_d<J>(v[r]);      // A[g+4r][J]
-  const bool mine = (lane & 15) == J;
-  dmine = mine ? d : dmine;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) out[r] = mine ? v[r] : out[r];
-  const double e = __builtin_fma(-d, y0, 1.0);
-  const double f = __builtin_fma(e, e, e);
-  const double u = rowj * y0;
-  const double t = __builtin_fma(u, f, u);          // A[J][c] / d
-  const double uw = wrow * y0;
-  const double tw = __builtin_fma(uw, f, uw);       // W[J][c] / d
-#pragma unroll
-  for (int r = 0; r < 4; ++r) v[r] = __builtin_fma(-colj[r], t, v[r]);
-  // W rows above the pivot see multipliers that are rounding residue of already-eliminated entries (~1e-16 relative:
-  // harmless); only the pivot row itself must be left alone
-  colj[PR] = ((lane >> 4) == (J & 3)) ? 0.0 : colj[PR];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) w[r] = __builtin_fma(-colj[r], tw, w[r]);
-}
 
 // one level of the in-place blocked inversion by recursive doubling: pairs of inverted S-block-wide diagonal
 // blocks (S in units of 16) are merged,  X21 = -X22 * (L21 * X11).  Four (pair, block column) work items per
 // level = one per wave; a wave keeps its column of T = L21*X11 in registers across the barrier that protects
 // L21 from being overwritten while other waves still read it.
 template <int S_>
-__device__ __forceinline__ void inv_merge_level(double* S, int wave, int lane, double* __restrict__ Dinv, bool wr) {
+__device__ __forceinline__ void inv_merge_level(double* S, int wave, int lane, double* __restrict__ Dinv) {
   const bool act = wave < 4;   // four work items per level; any further waves only take part in the barriers
   const int pair = wave / S_, jl = wave % S_;
   const int b0 = pair * 2 * S_;
@@ -151,24 +64,20 @@ __device__ __forceinline__ void inv_merge_level(double* S, int wave, int lane, d
 #pragma unroll
       for (int r = 0; r < 4; ++r) dst[((lane >> 4) + 4 * r) * BLD + (lane & 15)] = -R[ii][r];
       // the block is final: it also goes straight to the Dinv store (no separate write-out pass)
-      if (wr) {
-        double* g = Dinv + (size_t)((b0 + S_ + ii) * 16 + (lane >> 4)) * NB + j * 16 + (lane & 15);
+      double* g = Dinv + (size_t)((b0 + S_ + ii) * 16 + (lane >> 4)) * NB + j * 16 + (lane & 15);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) g[(size_t)4 * r * NB] = -R[ii][r];
-      }
+      for (int r = 0; r < 4; ++r) g[(size_t)4 * r * NB] = -R[ii][r];
     }
   }
   __syncthreads();
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// potrf_diag128: factor one diagonal block (nb <= 128 valid rows/cols, identity-padded) and invert it.
+// potrf_diag128: invert one diagonal block of a factor produced elsewhere (nb <= 128 valid rows/cols of L,
+// identity-padded) into the handle's Dinv store -- the factorisation itself inverts on the way (ffgp_potrf_diag128_v4).
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(DIAG_THREADS) void ffgp_potrf_diag128(double* __restrict__ A, int lda, int nb,
-                                                          double* __restrict__ Dinv, int* info, int row_base,
-                                                          int do_factor, int dbg, int prio) {
-  // dbg: timing-only ablation mask (results are wrong when non-zero): 1 skip (b), 2 skip (c), 4 skip (a),
-  //      8 skip phase 3, 16 skip phase 4, 32 skip phase 5, 64 skip phase 2, 128 skip phase 0
+__global__ __launch_bounds__(DIAG_THREADS) void ffgp_potrf_diag128(const double* __restrict__ A, int lda, int nb,
+                                                          double* __restrict__ Dinv, int prio) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* S = lds;                      // 36 lower blocks [16][17]
   double* rd = lds + NBLK_LOWER * BLKSZ;  // [128] reciprocals of the diagonal of L
@@ -177,7 +86,7 @@ __global__ __launch_bounds__(DIAG_THREADS) void ffgp_potrf_diag128(double* __res
 
   // ---- phase 0: load the lower blocks; diagonal blocks are completed symmetrically (mirror of the lower part),
   //      rows/cols beyond nb are identity
-  if (!(dbg & 128)) {
+  {
     // 32 unconditional 16-byte loads per thread, all in flight before the first LDS store (rows are clamped into
     // the valid block; entries above the diagonal are fetched but never used)
     constexpr int NLOAD = 8192 / DIAG_THREADS;
@@ -218,140 +127,12 @@ __global__ __launch_bounds__(DIAG_THREADS) void ffgp_potrf_diag128(double* __res
   }
   __syncthreads();
 
-  if (do_factor) {
-    // ---- phase 1: left-looking factorisation over 16-column blocks, with one block column of look-ahead:
-    //      while wave 0 factors the 16x16 diagonal block jj in registers, waves 1-3 already apply blocks p < jj to
-    //      block column jj+1, so that step jj+1 only has the single product with block column jj left on the chain
-    const bool wr = !(dbg & 64);
-    for (int jj = 0; jj < 8; ++jj) {
-      d4_t T = {0.0, 0.0, 0.0, 0.0};   // this wave's block (j = wave - 1) of L[jj][:] * X, see the shadow work in (b)
-      // (a) the one missing term: S[i][jj] -= S[i][jj-1] * S[jj][jj-1]^T   for block rows i = jj..7 (MFMA)
-      if (jj > 0 && !(dbg & 4)) {
-        for (int i = jj + wave; i < 8; i += DIAG_WAVES) {
-          d4_t acc = {0.0, 0.0, 0.0, 0.0};
-          mma16<true>(acc, S + blk_off(i, jj - 1), BLD, S + blk_off(jj, jj - 1), BLD, lane);
-          double* dst = S + blk_off(i, jj);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dst[((lane >> 4) + 4 * r) * BLD + (lane & 15)] -= acc[r];
-        }
-      }
-      __syncthreads();
-      // (b) wave 0: in-register 16x16 Cholesky + inverse (4 entries per lane, DPP / bpermute broadcasts).  L_jj goes
-      //     straight to global memory; its LDS slot receives inv(L_jj), which is all that (c) and the block
-      //     inversion need from it.
-      if (wave == 0 && !(dbg & 1)) {
-        double* Dj = S + blk_off(jj, jj);
-        const int g = lane >> 4, c = lane & 15;
-        double v[4], w[4], out[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] = Dj[(g + 4 * r) * BLD + c];
-          w[r] = (g + 4 * r == c) ? 1.0 : 0.0;
-          out[r] = 0.0;
-        }
-        int bad = 0;
-        double dmine = 1.0;
-        chol16_step<0>(v, w, out, dmine, lane, bad);
-        chol16_step<1>(v, w, out, dmine, lane, bad);
-        chol16_step<2>(v, w, out, dmine, lane, bad);
-        chol16_step<3>(v, w, out, dmine, lane, bad);
-        chol16_step<4>(v, w, out, dmine, lane, bad);
-        chol16_step<5>(v, w, out, dmine, lane, bad);
-        chol16_step<6>(v, w, out, dmine, lane, bad);
-        chol16_step<7>(v, w, out, dmine, lane, bad);
-        chol16_step<8>(v, w, out, dmine, lane, bad);
-        chol16_step<9>(v, w, out, dmine, lane, bad);
-        chol16_step<10>(v, w, out, dmine, lane, bad);
-        chol16_step<11>(v, w, out, dmine, lane, bad);
-        chol16_step<12>(v, w, out, dmine, lane, bad);
-        chol16_step<13>(v, w, out, dmine, lane, bad);
-        chol16_step<14>(v, w, out, dmine, lane, bad);
-        chol16_step<15>(v, w, out, dmine, lane, bad);
-        const double rs = rsqrt_nr(dmine);  // 1/sqrt(pivot) of this lane's column
-        if (g == 0) rd[jj * 16 + c] = rs;
-        // L[i][c] = out * rs (rows >= c) -> global
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = g + 4 * r;
-          const int gr = jj * 16 + i, gc = jj * 16 + c;
-          if (i >= c && gr < nb && wr) A[(size_t)gr * lda + gc] = out[r] * rs;
-        }
-        // inv(L_jj)[i][c] = rs_i * W[i][c]; rs_i comes back through the LDS slot just written
-        __builtin_amdgcn_s_waitcnt(0);       // rd[] visible to the whole wave (same-wave LDS write -> read)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = g + 4 * r;
-          const double x = (i >= c) ? w[r] * rd[jj * 16 + i] : 0.0;
-          Dj[i * BLD + c] = x;
-          if (i >= c && !(dbg & 32)) Dinv[(size_t)(jj * 16 + i) * NB + jj * 16 + c] = x;
-        }
-        if (bad && lane == 0 && (jj * 16 + bad) <= nb) atomicCAS(info, 0, row_base + jj * 16 + bad);
-      } else if (wave != 0 && jj > 0) {
-        // in the shadow of the 16x16 factor (waves 1..3):
-        // look-ahead: S[i][jj+1] -= sum_{p<jj} S[i][p] * S[jj+1][p]^T  for block rows i = jj+1..7
-        if (jj < 7 && !(dbg & 4)) {
-          for (int i = jj + 1 + (wave - 1); i < 8; i += DIAG_WAVES - 1) {
-            d4_t acc = {0.0, 0.0, 0.0, 0.0};
-            for (int p = 0; p < jj; ++p) mma16<true>(acc, S + blk_off(i, p), BLD, S + blk_off(jj + 1, p), BLD, lane);
-            double* dst = S + blk_off(i, jj + 1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dst[((lane >> 4) + 4 * r) * BLD + (lane & 15)] -= acc[r];
-          }
-        }
-        // incremental inverse, row block jj: T[jj][j] = sum_{k=j}^{jj-1} L[jj][k] * X[k][j]  (X = inv(L), rows < jj
-        // already sit in place of L's); the products with inv(L_jj) follow in (c).  T stays in registers.
-        if (!(dbg & 16) && wave - 1 < jj) {
-          const int j = wave - 1;
-          for (int k = j; k < jj; ++k) mma16<false>(T, S + blk_off(jj, k), BLD, S + blk_off(k, j), BLD, lane);
-        }
-      }
-      __syncthreads();
-      // (c) rows below: X = B * inv(L_jj)^T on the matrix cores (4 MFMAs per 16-row block); the finished block of L
-      //     goes to LDS (later steps read it) and straight to global memory
-      if (!(dbg & 2)) {
-        for (int i = jj + 1 + wave; i < 8; i += DIAG_WAVES) {
-          d4_t acc = {0.0, 0.0, 0.0, 0.0};
-          double* Bij = S + blk_off(i, jj);
-          mma16<true>(acc, Bij, BLD, S + blk_off(jj, jj), BLD, lane);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) Bij[((lane >> 4) + 4 * r) * BLD + (lane & 15)] = acc[r];
-          if (wr) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int gr = i * 16 + (lane >> 4) + 4 * r;
-              if (gr < nb) A[(size_t)gr * lda + jj * 16 + (lane & 15)] = acc[r];
-            }
-          }
-        }
-      }
-      // (c') inverse, row block jj: X[jj][j] = -inv(L_jj) * T[jj][j].  The accumulator layout of T (lane group g,
-      //      register r <-> row g + 4r) IS the MFMA B-operand layout of k-step r, so T never leaves its registers.
-      if (wave != 0 && wave - 1 < jj && !(dbg & 16)) {
-        const double* Wj = S + blk_off(jj, jj);
-        const int j = wave - 1;
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Wj[(lane & 15) * BLD + kq * 4 + (lane >> 4)], T[kq], acc, 0, 0, 0);
-        double* dst = S + blk_off(jj, j);
-        double* g = Dinv + (size_t)(jj * 16 + (lane >> 4)) * NB + j * 16 + (lane & 15);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          dst[((lane >> 4) + 4 * r) * BLD + (lane & 15)] = -acc[r];
-          if (!(dbg & 32)) g[(size_t)4 * r * NB] = -acc[r];
-        }
-      }
-      __syncthreads();
-    }
-  } else {
-    // inverse-only entry (Dinv refresh for a factor produced elsewhere): reciprocals of the diagonal
-    if (tid < NB) rd[tid] = 1.0 / S[blk_off(tid >> 4, tid >> 4) + (tid & 15) * BLD + (tid & 15)];
-  }
+  // ---- reciprocals of the diagonal
+  if (tid < NB) rd[tid] = 1.0 / S[blk_off(tid >> 4, tid >> 4) + (tid & 15) * BLD + (tid & 15)];
   __syncthreads();
 
-  // ---- phase 3 (inverse-only entry; the factor entry already left inv(L_jj) in the diagonal slots):
-  //      inverses of the eight 16x16 diagonal blocks, in place; 16 lanes per block (one per column)
-  if (!do_factor && wave < 2 && !(dbg & 8)) {
+  // ---- phase 1: inverses of the eight 16x16 diagonal blocks, in place; 16 lanes per block (one per column)
+  if (wave < 2) {
     const int jj = wave * 4 + (lane >> 4), c = lane & 15;
     double* Lj = S + blk_off(jj, jj);
     double x[16];
@@ -367,266 +148,26 @@ __global__ __launch_bounds__(DIAG_THREADS) void ffgp_potrf_diag128(double* __res
     // every lane of the wave has finished reading L_jj (same instruction stream) before the block is overwritten
 #pragma unroll
     for (int i = 0; i < 16; ++i) Lj[i * BLD + c] = x[i];
-    if (!(dbg & 32)) {
 #pragma unroll
-      for (int i = 0; i < 16; ++i)
-        if (i >= c) Dinv[(size_t)(jj * 16 + i) * NB + jj * 16 + c] = x[i];
-    }
+    for (int i = 0; i < 16; ++i)
+      if (i >= c) Dinv[(size_t)(jj * 16 + i) * NB + jj * 16 + c] = x[i];
   }
   __syncthreads();
 
-  // ---- phase 4: in-place blocked inversion by recursive doubling (16 -> 32 -> 64 -> 128), 2 barriers per level;
+  // ---- phase 2: in-place blocked inversion by recursive doubling (16 -> 32 -> 64 -> 128), 2 barriers per level;
   //      every block is written to the Dinv store the moment it is final (the strictly-upper part of the store is
   //      zero from allocation)
-  if (!do_factor && !(dbg & 16)) {   // (the factor entry built the inverse row block by row block, see (c'))
-    const bool wi = !(dbg & 32);
-    inv_merge_level<1>(S, wave, lane, Dinv, wi);   // (4 work items per level: waves 4..7 only keep the barriers)
-    inv_merge_level<2>(S, wave, lane, Dinv, wi);
-    inv_merge_level<4>(S, wave, lane, Dinv, wi);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// The pipelined diagonal-block kernels (round 3; v3 and v4 below keep its chain): the same factor + inverse as a wave-specialised
-// PIPELINE instead of barrier-separated phases.
-//
-// The old kernel spends 8 x (3 workgroup barriers + a ~1.7 us in-register 16x16 factor + two short MFMA phases); every wave
-// waits for every other wave three times per 16 columns.  Here wave 0 never meets a barrier after the load phase:
-//
-//   wave 0   F(jj): in-register 16x16 Cholesky + inverse of the diagonal block (16 pivots)
-//            G(jj): Y = inv(L_jj) S[jj+1][jj]^T on the matrix cores (4 MFMAs); L[jj+1][jj] = Y^T goes to LDS / global;
-//                   D = S[jj+1][jj+1] - Y^T Y (4 MFMAs with a = b = the Y registers: the accumulator layout is both the
-//                   A layout of Y^T and the B layout of Y) -> the next diagonal block, already in the factor's layout
-//            ... F(jj+1) ...                       serial chain: 8 x (F + G), nothing else
-//   helpers  iteration jj, triggered by wave 0's flags in LDS (seqF: inv(L_jj) is in LDS; seqX: L[jj+1][jj] is):
-//            A1 TRSM of the block rows jj+2.. of column jj          A2 row block jj of the inverse (from T, see B3)
-//            B1 column jj+1 receives block column jj   B2 column jj+2 receives block columns 0..jj (left-looking,
-//            one block column of look-ahead -- so G(jj+1) finds S[jj+2][jj+1], S[jj+2][jj+2] complete)  -> doneU
-//            B3 T_j = sum_k L[jj+1][k] X[k][j] for the inverse's next row block (kept in registers)
-//   Helpers synchronise among themselves with a counter barrier in LDS (two per iteration); wave 0 waits for doneU of
-//   iteration jj-1 before G(jj) -- by then it has spent a whole F on its own, so it normally does not wait at all.
-//
-// The 16x16 factor itself is restructured so that no LDS-latency operation sits on the pivot-to-pivot chain: every lane
-// keeps the CURRENT pivot row for its column (rowA, rowW); the next pivot row is fetched (ds_bpermute) one step ahead,
-// before this step's update, and patched locally with this step's rank-1 term; pivot and multiplier broadcasts are DPP
-// row shares.  Finished columns are parked in place (their multiplier is masked to 0), so no select instructions
-// capture them.  Every polling loop is bounded: on a timeout the kernel raises `abort`, every wave leaves, and the host
-// sees FFGP_DIAG_WATCHDOG in the status word instead of a hung queue.
-// ------------------------------------------------------------------------------------------------------------
-#define FFGP_DIAG_WATCHDOG 0x7ffffff0
-#define FFGP_HANDOFF_WATCHDOG 0x7fffffe0     // a look-ahead gate gave up waiting for its hand-off (ffgp_handoff_gate)
-
-// tools/diag_trace.py builds a second library with -DFFGP_DIAG_TRACE: wave 0 and helper 0 stamp the cycle counter at their
-// phase boundaries (never compiled into libffgp.so)
-#ifdef FFGP_DIAG_TRACE
-__device__ unsigned long long* ffgp_diag_trace_buf = nullptr;
-__device__ int ffgp_diag_trace_row = -1;          // -1: every launch stamps (the last one stays); else only the launch at this row
-extern "C" int ffgp_debug_set_diag_trace(void* p) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(ffgp_diag_trace_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-extern "C" int ffgp_debug_set_diag_trace_row(int row) {
-  return hipMemcpyToSymbol(HIP_SYMBOL(ffgp_diag_trace_row), &row, sizeof(row)) == hipSuccess ? 0 : -1;
-}
-#define D2_TRACE(slot)                                                                          \
-  do {                                                                                          \
-    if (lane == 0 && ffgp_diag_trace_buf && (ffgp_diag_trace_row < 0 || ffgp_diag_trace_row == row_base))  \
-    {                                                                                           \
-      ffgp_diag_trace_buf[(slot)] = wall_clock64();                                             \
-      if ((slot) == 0 || (slot) == 23) ffgp_diag_trace_buf[120 + ((slot) != 0)] = __builtin_readcyclecounter();   /* shader clock */ \
-    }                                                                                           \
-  } while (0)
-#else
-#define D2_TRACE(slot)
-#endif
-
-struct D2Flags {      // ints in LDS, behind the block image
-  int seqF, seqX, doneU, sb, abort, pad[3];
-};
-
-#define D2_LDS_FENCE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define D2_COMPILER_FENCE() asm volatile("" ::: "memory")
-
-// The flags live in LDS and are touched with explicit DS instructions.  A `volatile` access through the generic pointer
-// compiles to flat_load / flat_store with `s_waitcnt vmcnt(0)`: every poll would first wait for all of the wave's
-// outstanding GLOBAL stores (the L / inverse blocks it has just written -- a memory round trip per hand-off).
-__device__ __forceinline__ int d2_ld(const volatile int* p) {
-  int v;
-  const unsigned off = (unsigned)(uintptr_t)p;          // low half of a generic LDS address = the LDS offset
-  asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(off) : "memory");
-  // every lane read the same word: saying so (v_readfirstlane) lets the compiler keep the polling loops, the loop counters compared
-  // with the flags and every branch on them SCALAR -- without it the whole helper section was compiled as divergent control flow
-  // (exec-mask juggling around every task, loop counters in vector registers)
-  return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ void d2_st(volatile int* p, int v) {
-  const unsigned off = (unsigned)(uintptr_t)p;
-  asm volatile("ds_write_b32 %0, %1" : : "v"(off), "v"(v) : "memory");
-}
-
-__device__ __forceinline__ bool d2_wait_ge(volatile int* p, int target, volatile int* abort_flag, int* info, int site = 0) {
-  int spins = 0;
-  while (d2_ld(p) < target) {
-    __builtin_amdgcn_s_sleep(1);
-    if ((++spins & 63) == 0 && (spins > (1 << 21) || d2_ld(abort_flag))) {   // ~1 s of polling: something upstream died
-      if (!d2_ld(abort_flag)) atomicExch(info, FFGP_DIAG_WATCHDOG + site);    // (site: which hand-off; ffgp_map_info prints it)
-      d2_st(abort_flag, 1);
-      return false;
-    }
-  }
-  D2_COMPILER_FENCE();
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// potrf_diag128_v3 (round 4): the same chain, with the helpers reorganised around what tools/native/f16_probe.hip measured.
-//
-//  * fp64 MFMAs and fp64 vector instructions share a SIMD's double-precision pipe: ONE MFMA-streaming wave on wave 0's own SIMD
-//    takes the pivot loop from 148 to 270-280 cycles per pivot (s_setprio does not help: an issued 64-cycle MFMA is not
-//    pre-empted); six streaming waves on the three OTHER SIMDs cost nothing (150).  An 8-wave workgroup puts two waves on each
-//    SIMD, so the wave that shares wave 0's SIMD (found by HW_ID.SIMD_ID, not assumed) takes no part in the arithmetic: it leaves
-//    at once.  Six helpers remain.
-//  * No load phase and no workgroup barrier after the role hand-out: wave 0 reads its first diagonal block straight from global
-//    memory into the factor's register layout and starts; every other 16 x 16 block has an OWNER wave (column-major round
-//    robin) that loads it from global memory, keeps its running value in the block's LDS home as a REGISTER IMAGE of the
-//    transposed block (lane (g, c), register r = S[c][g + 4r]: exactly the B operand of the triangular solve and of wave 0's
-//    G, so no product ever needs a layout change), applies every update of that block itself, in order -- right-looking:
-//    column s of L updates all later columns as soon as it exists -- and finally solves it (or hands it to wave 0).  No two
-//    waves ever write the same block, so there are no barriers: a bit per block says "L[i][k] is final" (rows[k], bit i), two counters
-//    hand wave 0 its next operands (hs, hd).  The round-3 kernel ran left-looking with one column of look-ahead and two
-//    7-wave counter barriers per iteration: its helpers needed 3.0-3.3 us per iteration in the middle of the block, more than
-//    wave 0's 2.6 -- the chain waited for them.
-//  * The inverse's row block s, X[s][j] = -inv(L_s) sum_k L[s][k] X[k][j], overwrites row s of L in place; every helper counts
-//    itself in (cntA[s]) once it has finished reading that row, and a row block is stored only when all six have.
-// Stage s of a helper (s = 0 .. 7), after seqF >= s + 1 (inv(L_s) is in LDS):
-//    (1) L[i][s]^T = inv(L_s) S[i][s]^T for its blocks of column s, i >= s + 2 (row s + 1 is wave 0's G)            -> rows[s] bit i
-//    (2) S[i][k]^T -= L[k][s] L[i][s]^T for its blocks with k > s (column s + 1 first); a block whose updates are complete and
-//        that wave 0 needs next is announced: (s + 2, s + 1) -> hs, the diagonal block (s + 2, s + 2) -> hd
-//    (3) its columns of the inverse's row block s
-// ------------------------------------------------------------------------------------------------------------
-struct D3Flags {      // ints in LDS, behind the block image
-  int seqF, h2, hs, hd, abort, roles, pad0[2];
-  int simd[8];
-  int cntA[8];
-  int rows[8];        // rows[s]: bit i = L[i][s] is final and in LDS (bit s + 1 is set by wave 0's G(s), the others by the blocks' owners)
-  int prog[8];        // [0] wave 0: 16 jj + phase; [1 + hidx]: the helper's current task index (post-mortem of a timed-out hand-off)
-};
-
-#define D3_NH 6
-// The helpers' work as a STATIC task list per helper (the block structure is fixed, so is the schedule).  A first version walked
-// nested loops over (stage, pass, owned block) with the ownership tests inline: on this machine a not-taken scalar branch costs as
-// much as four vector instructions, and a stage with nothing to do took 2.5 us of pure control flow.  Now lane t of a helper holds
-// descriptor t of its list (one load at the start), v_readlane fetches the next one, and one switch dispatches it.
-//   descriptor: bits 1:0 type, 4:2 i, 7:5 k, 9:8 flag to raise (0 none, 1 hs, 2 hd, 3 h2), 12:10 stage s, 15:13 first column p0 of an
-//   update (it applies columns p0 .. s); 0xffff ends the list
-// Ownership: block t of the column-major enumeration (k = 0..7, i = k..7, without (0, 0)) belongs to helper t % 6.
-// WHEN a block receives column p.  Right-looking (at stage p, the moment column p exists) puts 28 + 21 + 15 of the 77 updates into the
-// first three stages, where the helpers then lag behind wave 0; left-looking (everything at stage k - 1) starves them early and
-// makes the last stages long.  In between: block (i, k) takes column p at stage max(p, k - 3) -- the two columns wave 0 needs next
-// stay current, column s + 3 catches up on columns 0 .. s in ONE task (one read and one write of the image, 4 (s + 1) products),
-// later columns wait: 18, 19, 18, 15, 10, 3, 1 block visits per stage instead of 28, 21, 15, 10, 6, 3, 1.
-// Order inside a stage s (what wave 0's G(s + 1) waits for comes first -- it needs (s + 2, s + 1), (s + 2, s + 2) and (s + 3, s + 1)
-// with column s applied): STAGE (wait for inv(L_s)); the solve of (s + 3, s), the one operand of those three that wave 0 does not
-// produce itself; those three updates; the other solves of column s; the other updates, next column first; the inverse's row s.
-enum { D3_STAGE = 0, D3_TRSM = 1, D3_UPDATE = 2, D3_INVERSE = 3, D3_END = 0xffff, D3_MAXTASKS = 64 };
-struct D3TaskTable { unsigned short t[D3_NH][D3_MAXTASKS]; };
-constexpr int d3_owner(int i, int k) { return (k == 0 ? i - 1 : 8 * k - 1 - k * (k - 1) / 2 + (i - k)) % D3_NH; }
-constexpr unsigned short d3_desc(int type, int i, int k, int flag, int s, int p0 = 0) {
-  return (unsigned short)(type | (i << 2) | (k << 5) | (flag << 8) | (s << 10) | (p0 << 13));
-}
-constexpr int d3_flag_of(int i, int k, int s) {      // which of wave 0's next operands block (i, k) is once column s is applied
-  return (k == s + 1 && i == s + 2) ? 1 : (k == s + 2 && i == k) ? 2 : (k == s + 1 && i == s + 3) ? 3 : 0;
-}
-constexpr D3TaskTable d3_make_tasks() {
-  D3TaskTable T{};
-  for (int h = 0; h < D3_NH; ++h) {
-    int n = 0;
-    for (int s = 0; s < 8; ++s) {
-      T.t[h][n++] = d3_desc(D3_STAGE, 0, 0, 0, s);
-      if (s + 3 < 8 && d3_owner(s + 3, s) == h) T.t[h][n++] = d3_desc(D3_TRSM, s + 3, s, 0, s);
-      for (int pass = 0; pass < 2; ++pass) {            // pass 0: the three urgent updates; pass 1: the other solves, the other updates
-        if (pass == 1)
-          for (int i = s + 4; i < 8; ++i)
-            if (d3_owner(i, s) == h) T.t[h][n++] = d3_desc(D3_TRSM, i, s, 0, s);
-        for (int k = s + 1; k < 8 && k <= s + 3; ++k)
-          for (int i = k; i < 8; ++i) {
-            if (d3_owner(i, k) != h || (i == k && k == s + 1)) continue;      // (the diagonal block of column s + 1 is wave 0's)
-            const int fl = d3_flag_of(i, k, s);
-            if ((fl != 0) == (pass == 0)) T.t[h][n++] = d3_desc(D3_UPDATE, i, k, fl, s, (k == s + 3) ? 0 : s);
-          }
-      }
-      if (s >= 1) T.t[h][n++] = d3_desc(D3_INVERSE, 0, 0, 0, s);
-    }
-    for (; n < D3_MAXTASKS; ++n) T.t[h][n] = (unsigned short)D3_END;
-  }
-  return T;
-}
-__device__ const D3TaskTable D3_TASKS = d3_make_tasks();
-
-// LDS read-modify-write on a flag word, as explicit DS instructions (a generic-pointer atomic compiles to flat_atomic_*)
-__device__ __forceinline__ void d3_or(volatile int* p, int v) {
-  const unsigned off = (unsigned)(uintptr_t)p;
-  asm volatile("ds_or_b32 %0, %1" : : "v"(off), "v"(v) : "memory");
-}
-__device__ __forceinline__ void d3_add(volatile int* p, int v) {
-  const unsigned off = (unsigned)(uintptr_t)p;
-  asm volatile("ds_add_u32 %0, %1" : : "v"(off), "v"(v) : "memory");
-}
-
-#define D3_IMG(bi, bj) (S + blk_off(bi, bj))     /* the block's home: register image [r][lane] while it accumulates, [16][17] once it is L */
-
-__device__ __forceinline__ int d3_simd_id() {
-  return (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3;     // HW_REG_HW_ID (4), SIMD_ID = bits 5:4
+  inv_merge_level<1>(S, wave, lane, Dinv);   // (4 work items per level: waves 4..7 only keep the barriers)
+  inv_merge_level<2>(S, wave, lane, Dinv);
+  inv_merge_level<4>(S, wave, lane, Dinv);
 }
 
 // element (r, cc) of the symmetric block (bi, bj) of A as the factor sees it: lower triangle of A, identity beyond nb
-__device__ __forceinline__ double d3_elem(const double* __restrict__ A, int lda, int nb, int r, int cc) {
+__device__ __forceinline__ double sym_elem(const double* __restrict__ A, int lda, int nb, int r, int cc) {
   const int hi = max(r, cc), lo = min(r, cc);
   if (hi >= nb) return (r == cc) ? 1.0 : 0.0;
   return A[(size_t)hi * lda + lo];
 }
-
-// stores acc = L[i][s]^T (lane (g, c), register r = L[i][s][c][g + 4r]) into the block's LDS home as L[i][s] and into A
-__device__ __forceinline__ void d3_store_LT(double* home, double* __restrict__ A, int lda, int nb, int i, int s, const d4_t& acc, int g, int c) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) home[c * BLD + g + 4 * r] = acc[r];
-  const int gr = i * 16 + c;
-  if (gr < nb) {
-    double* dst = A + (size_t)gr * lda + s * 16 + g;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) dst[4 * r] = acc[r];
-  }
-}
-
-// the transposed register image of block (i, k) of A straight from global memory: lane (g, c), register r = S[c][g + 4r]
-__device__ __forceinline__ void d3_load_image(double (&x)[4], const double* __restrict__ A, int lda, int nb, int i, int k, int g, int c) {
-  const int rr = i * 16 + c;
-  if (i == k) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) x[r] = d3_elem(A, lda, nb, rr, k * 16 + g + 4 * r);      // mirrored from the lower triangle
-  } else {
-    const double* src = A + (size_t)min(rr, nb - 1) * lda + k * 16 + g;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) x[r] = (rr < nb) ? src[4 * r] : 0.0;
-  }
-}
-
-// row block s of the inverse, columns hidx and hidx + 6, from registers into the LDS homes of row s of L and into the Dinv store
-__device__ __forceinline__ void d3_store_inverse_rows(double* S, double* __restrict__ Dinv, const double (&Xn)[2][4], int s, int hidx, int g, int c) {
-#pragma unroll
-  for (int q2 = 0; q2 < 2; ++q2) {
-    const int j = hidx + q2 * D3_NH;
-    if (j >= s) continue;
-    double* dst = S + blk_off(s, j);
-    double* gd = Dinv + (size_t)(s * 16 + g) * NB + j * 16 + c;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      dst[(g + 4 * r) * BLD + c] = Xn[q2][r];
-      gd[(size_t)4 * r * NB] = Xn[q2][r];
-    }
-  }
-}
-
-__device__ int ffgp_d3_dbg[32];     // state of the flags when a hand-off timed out (development aid)
 
 // members of a ragged launch (blocks of different sizes sharing one chain, ffgp_potrf_ragged): each workgroup's own diagonal block
 struct DiagRag {
@@ -639,352 +180,21 @@ struct DiagRag {
   unsigned pub_val;            // enqueued before it on its stream is complete then (la_record_deferred); nullptr = none
 };
 
-template <bool RAG>
-__global__ __launch_bounds__(512, 4) void ffgp_potrf_diag128_v3(double* __restrict__ A, int lda, int nb, double* __restrict__ Dinv,
-                                                                int* info, int row_base, int prio, long sA, long sD, int sInfo,
-                                                                DiagRag rag) {
-  if constexpr (RAG) {
-    // (ragged batch: workgroup b factors member b's block -- own matrix, leading dimension, block size, Dinv slot, status word)
-    A = rag.A[blockIdx.x];
-    Dinv = rag.Dinv[blockIdx.x];
-    lda = rag.lda[blockIdx.x];
-    nb = rag.nb[blockIdx.x];
-    info += rag.info[blockIdx.x];
-  } else {
-    // (batched factorisation: workgroup b factors block b -- its own matrix, Dinv store and status word)
-    A += (size_t)blockIdx.x * sA;
-    Dinv += (size_t)blockIdx.x * sD;
-    info += blockIdx.x * sInfo;
-  }
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* S = lds;
-  volatile D3Flags* fl = reinterpret_cast<volatile D3Flags*>(lds + NBLK_LOWER * BLKSZ);
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (uniform: scalar control flow)
-  const int g = lane >> 4, c = lane & 15;
-  // the previous panel is complete the moment this kernel runs (stream order): publish that to the update stream's waiting gate
-  if (rag.pub && blockIdx.x == 0 && tid == 64) __hip_atomic_store(rag.pub, rag.pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (wave == 0) D2_TRACE(0);
-  // wave 0's first operands need no update: it fetches them itself, straight into the registers of F(0) and G(0), and the loads fly
-  // while the roles are handed out
-  double v[4], sb[4], sb2[4];
-  d4_t D;
-  if (wave == 0) {
-    double x[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = d3_elem(A, lda, nb, g + 4 * r, c);
-    d3_load_image(sb, A, lda, nb, 1, 0, g, c);
-    d3_load_image(sb2, A, lda, nb, 2, 0, g, c);
-    d3_load_image(x, A, lda, nb, 1, 1, g, c);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) D[r] = x[r];
-  }
-  // ---- roles: every wave publishes its SIMD; one barrier; the wave that shares wave 0's SIMD steps aside
-  // d2_st is inline asm: the compiler's wait-count pass does not see the LDS store inside it and puts NO s_waitcnt in front of the
-  // barrier -- a wave could pass the barrier with its store still in flight.  Under load that happened: a wave read simd[w] before
-  // wave w's store had landed (0, which matched wave 0's SIMD 0), the waves disagreed about who the partner is, one helper role stayed
-  // empty and the others waited for it until the watchdog fired (found by the co-running test leg; only ever seen beside two
-  // eigensolvers).  Every flag store that a barrier is meant to publish is therefore drained explicitly.
-  if (tid < (int)(sizeof(D3Flags) / sizeof(int))) d2_st(reinterpret_cast<volatile int*>(fl) + tid, 0);
-  D2_LDS_FENCE();
-  __syncthreads();
-  if (lane == 0) d2_st(&fl->simd[wave], d3_simd_id());
-  D2_LDS_FENCE();
-  __syncthreads();
-  int partner = 4;
-  {
-    int mine;      // lane l < 8 looks at wave l's SIMD: one LDS read for the whole search
-    const unsigned off = (unsigned)(uintptr_t)&fl->simd[lane & 7];
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(mine) : "v"(off) : "memory");
-    const int s0 = __builtin_amdgcn_readfirstlane(mine);
-    const unsigned long long same = __ballot(mine == s0 && lane >= 1 && lane < 8);
-    if (same) partner = __ffsll((long long)same) - 1;
-  }
-  volatile int* ab = &fl->abort;
-  if (wave != 0 && wave == partner) return;      // (its SIMD now belongs to the pivot chain alone)
-  const int hidx = (wave < partner) ? wave - 1 : wave - 2;
-
-  if (wave == 0) {
-    // ================================ the serial chain ================================
-    if (prio) __builtin_amdgcn_s_setprio(3);
-    double w[4];
-    D2_TRACE(1);
-    for (int jj = 0; jj < 8; ++jj) {
-      // ---- F(jj)
-      int cc = c, gg = g;
-      asm volatile("" : "+v"(cc), "+v"(gg));      // (opaque per iteration: see v2)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) w[r] = (gg + 4 * r == cc) ? 1.0 : 0.0;
-      double rowA = bperm_d(v[0], cc);
-      double rowW = (cc == 0) ? 1.0 : 0.0;
-      {
-        double hA = bperm_d(v[0], 16 + cc), hW = (cc == 1) ? 1.0 : 0.0;
-        double pRow = 0.0, pt = 0.0, ptw = 0.0;
-        double dcur = row_bcast64<0>(rowA), ycur = __builtin_amdgcn_rcp(dcur);
-#define F16_S(JJ) f16_step_dpp<JJ>(v, w, rowA, rowW, hA, hW, pRow, pt, ptw, dcur, ycur, cc, gg);
-        F16_S(0) F16_S(1) F16_S(2) F16_S(3) F16_S(4) F16_S(5) F16_S(6) F16_S(7) F16_S(8) F16_S(9) F16_S(10) F16_S(11) F16_S(12) F16_S(13)
-        F16_S(14) F16_S(15)
-#undef F16_S
-      }
-      D2_TRACE(64 + jj);     // the 16 pivots are done
-      if (lane == 0) d2_st(&fl->prog[0], 16 * jj + 1);
-      // operands of G(jj), register images left by their owners: requested now, under the post-processing below
-      if (jj >= 1 && jj < 7) {
-        if (!d2_wait_ge(&fl->hs, jj + 1, ab, info, 1) || !d2_wait_ge(&fl->hd, jj + 1, ab, info, 2)) break;
-        if (jj < 6 && !d2_wait_ge(&fl->h2, jj + 1, ab, info, 3)) break;
-        const double* Sb = D3_IMG(jj + 1, jj);
-        const double* Sd = D3_IMG(jj + 1, jj + 1);
-        const double* Sb2 = D3_IMG(min(jj + 2, 7), jj);
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq) sb[kq] = Sb[kq * 64 + lane];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) D[r] = Sd[r * 64 + lane];
-        if (jj < 6) {
-#pragma unroll
-          for (int kq = 0; kq < 4; ++kq) sb2[kq] = Sb2[kq * 64 + lane];
-        }
-      }
-      D2_TRACE(3 + 3 * jj);
-      const int q = c >> 2;
-      const double dsel = (q == 0) ? v[0] : (q == 1) ? v[1] : (q == 2) ? v[2] : v[3];
-      const double dcol = bperm_d(dsel, 16 * (c & 3) + c);
-      const double rs = rsqrt_nr(dcol);          // 1 / sqrt(pivot of column c)
-      const unsigned long long nonpos = __ballot(!(dcol > 0.0)) & 0xffffull;
-      const int bad = nonpos ? __ffsll((long long)nonpos) : 0;
-      double* Dj = S + blk_off(jj, jj);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = g + 4 * r;
-        const double rsi = bperm_d(rs, i);       // 1 / sqrt(pivot of column i): the row scaling of the inverse
-        const double x = (i >= c) ? w[r] * rsi : 0.0;
-        Dj[i * BLD + c] = x;                                              // inv(L_jj) for the helpers and for G
-        const int gr = jj * 16 + i, gc = jj * 16 + c;
-        if (i >= c) {
-          Dinv[(size_t)gr * NB + gc] = x;
-          if (gr < nb) A[(size_t)gr * lda + gc] = v[r] * rs;              // L_jj
-        }
-      }
-      if (bad && lane == 0 && (jj * 16 + bad) <= nb) atomicCAS(info, 0, row_base + jj * 16 + bad);
-      D2_LDS_FENCE();
-      if (lane == 0) d2_st(&fl->seqF, jj + 1);
-      D2_TRACE(2 + 3 * jj);
-      if (jj == 7) break;
-      // ---- G(jj): the solves of block rows jj + 1 and jj + 2 (both feed the blocks wave 0 needs next, one flag hop away), then
-      // the next diagonal block
-      d4_t Y = {0.0, 0.0, 0.0, 0.0}, Y2 = {0.0, 0.0, 0.0, 0.0};
-      double wa[4];
-      D2_TRACE(72 + jj);
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) wa[kq] = Dj[c * BLD + kq * 4 + g];
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) Y = __builtin_amdgcn_mfma_f64_16x16x4f64(wa[kq], sb[kq], Y, 0, 0, 0);
-      if (jj < 6) {
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq) Y2 = __builtin_amdgcn_mfma_f64_16x16x4f64(wa[kq], sb2[kq], Y2, 0, 0, 0);
-      }
-      {   // L[jj+1][jj] = Y^T (its image sits in sb), L[jj+2][jj] = Y2^T: to LDS and announced first -- the helpers' next hop
-        double* h1 = S + blk_off(jj + 1, jj);
-        double* h2 = S + blk_off(min(jj + 2, 7), jj);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h1[c * BLD + g + 4 * r] = Y[r];
-        if (jj < 6) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) h2[c * BLD + g + 4 * r] = Y2[r];
-        }
-      }
-      D2_LDS_FENCE();
-      if (lane == 0) d3_or(&fl->rows[jj], (jj < 6) ? (3 << (jj + 1)) : (1 << (jj + 1)));
-      D2_TRACE(80 + jj);     // rows jj + 1, jj + 2 of column jj announced
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) D = __builtin_amdgcn_mfma_f64_16x16x4f64(Y[kq], Y[kq], D, 0, 0, 1);   // D -= Y^T Y
-      {   // ... and to global memory while those products run
-        const int gr = (jj + 1) * 16 + c;
-        if (gr < nb) {
-          double* dst = A + (size_t)gr * lda + jj * 16 + g;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dst[4 * r] = Y[r];
-        }
-        if (jj < 6 && gr + 16 < nb) {
-          double* dst = A + (size_t)(gr + 16) * lda + jj * 16 + g;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dst[4 * r] = Y2[r];
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = D[r];
-      D2_TRACE(4 + 3 * jj);
-    }
-    return;
-  }
-
-  // ================================ helpers ================================
-  // ---- prologue: the owned blocks come from global memory as transposed register images, all loads in flight at once
-  // (one block after the other was one memory round trip each: 6.5 us before the first stage).  (1, 0), (1, 1), (2, 0) are wave 0's.
-  {
-    double x[6][4];
-#pragma unroll
-    for (int u = 0; u < 6; ++u) {
-      const int t = hidx + u * D3_NH;                  // enumeration index -> (i, k)
-      int k = 0, i = t + 1;
-#pragma unroll
-      for (int kk = 1; kk < 8; ++kk) {
-        const int t0 = 8 * kk - 1 - kk * (kk - 1) / 2;
-        if (t >= t0) { k = kk; i = kk + (t - t0); }
-      }
-      if (t > 34 || (k == 0 && i <= 2) || (k == 1 && i == 1)) continue;
-      d3_load_image(x[u], A, lda, nb, i, k, g, c);
-    }
-#pragma unroll
-    for (int u = 0; u < 6; ++u) {
-      const int t = hidx + u * D3_NH;
-      int k = 0, i = t + 1;
-#pragma unroll
-      for (int kk = 1; kk < 8; ++kk) {
-        const int t0 = 8 * kk - 1 - kk * (kk - 1) / 2;
-        if (t >= t0) { k = kk; i = kk + (t - t0); }
-      }
-      if (t > 34 || (k == 0 && i <= 2) || (k == 1 && i == 1)) continue;
-      double* img = D3_IMG(i, k);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) img[r * 64 + lane] = x[u][r];
-    }
-    D2_LDS_FENCE();
-  }
-  if (hidx == 0) D2_TRACE(31);
-  const int my_desc = D3_TASKS.t[hidx][lane];  // lane t holds descriptor t of this helper's list
-  double Xn[2][4];                             // the row block of the inverse computed in a stage, stored once row s of L is dead
-  const double* Ws = S;                        // inv(L_s)
-  volatile int* rows = &fl->rows[0];           // rows[s], bit i: L[i][s] is final and in LDS
-  int seen = 0;                                // lane p: the bits of rows[p] this wave has seen set (one poll serves every later task)
-#pragma unroll 1
-  for (int t = 0; t < D3_MAXTASKS; ++t) {
-    const int desc = __builtin_amdgcn_readlane(my_desc, t);
-    if (lane == 0) d2_st(&fl->prog[1 + hidx], 1 + t);      // (post-mortem of a timed-out hand-off: where every helper stood)
-    if (desc == D3_END) break;
-    const int type = desc & 3, i = (desc >> 2) & 7, k = (desc >> 5) & 7, flag = (desc >> 8) & 3, s = (desc >> 10) & 7;
-    if (type == D3_STAGE) {
-      if (hidx == 0 && s >= 1) D2_TRACE(31 + 4 * s);          // (slot 35 + 4 (s - 1): the previous stage is complete)
-      if (!d2_wait_ge(&fl->seqF, s + 1, ab, info, 4)) return;
-      if (hidx == 0) D2_TRACE(32 + 4 * s);
-      Ws = S + blk_off(s, s);
-      rows = &fl->rows[s];
-    } else if (type == D3_TRSM) {
-      // ---- triangular solve of an owned block of column s (its updates were completed in the earlier stages)
-      double* home = D3_IMG(i, s);
-      double b[4];
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) b[kq] = home[kq * 64 + lane];
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * BLD + kq * 4 + g], b[kq], acc, 0, 0, 0);
-      d3_store_LT(home, A, lda, nb, i, s, acc, g, c);
-      D2_LDS_FENCE();
-      if (lane == 0) d3_or(rows, 1 << i);
-    } else if (type == D3_UPDATE) {
-      // ---- columns p0 .. s of L update a later block this wave owns:  image -= L[k][p] L[i][p]^T  (the transposed update)
-      const int p0 = (desc >> 13) & 7;
-      const int need = (1 << i) | (1 << k);
-      double* img = D3_IMG(i, k);
-      d4_t acc;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[r] = img[r * 64 + lane];
-#pragma unroll 1
-      for (int p = p0; p <= s; ++p) {
-        // rows i and k of column p must be final: lane p of `seen` remembers what this wave saw of rows[p] (bits only ever get set)
-        int have = __builtin_amdgcn_readlane(seen, p);
-        if ((have & need) != need) {
-          int spins = 0;
-          while (((have = d2_ld(&fl->rows[p])) & need) != need) {
-            __builtin_amdgcn_s_sleep(1);
-            if ((++spins & 63) == 0 && (spins > (1 << 21) || d2_ld(ab))) {
-              if (!d2_ld(ab)) {
-                atomicExch(info, FFGP_DIAG_WATCHDOG + 5);
-                if (lane == 0) {     // post-mortem: which hand-off never came (printed by ffgp_map_info)
-                  ffgp_d3_dbg[0] = hidx; ffgp_d3_dbg[1] = s; ffgp_d3_dbg[2] = p; ffgp_d3_dbg[3] = i; ffgp_d3_dbg[4] = k; ffgp_d3_dbg[5] = have;
-                  ffgp_d3_dbg[6] = d2_ld(&fl->seqF); ffgp_d3_dbg[7] = d2_ld(&fl->hs); ffgp_d3_dbg[8] = d2_ld(&fl->hd); ffgp_d3_dbg[9] = d2_ld(&fl->h2);
-                  for (int z = 0; z < 8; ++z) ffgp_d3_dbg[10 + z] = d2_ld(&fl->rows[z]);
-                  for (int z = 0; z < 8; ++z) ffgp_d3_dbg[18 + z] = d2_ld(&fl->cntA[z]);
-                  ffgp_d3_dbg[26] = t;
-                  for (int z = 0; z < 5; ++z) ffgp_d3_dbg[27 + z] = d2_ld(&fl->prog[z]) | (d2_ld(&fl->prog[z + (z < 3 ? 5 : 0)]) << 16);
-                }
-              }
-              d2_st(ab, 1);
-              return;
-            }
-          }
-          D2_COMPILER_FENCE();
-          seen = (lane == p) ? have : seen;
-        }
-        const double* Lk = S + blk_off(k, p);
-        const double* Li = S + blk_off(i, p);
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Lk[c * BLD + kq * 4 + g], Li[c * BLD + kq * 4 + g], acc, 0, 0, 1);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) img[r * 64 + lane] = acc[r];
-      if (flag) {                              // complete as far as its owner is concerned: an operand of G(s + 1)
-        D2_LDS_FENCE();
-        if (lane == 0) d2_st((flag == 1) ? &fl->hs : (flag == 2) ? &fl->hd : &fl->h2, s + 2);
-      }
-    } else {
-      // ---- row block s of the inverse, columns j = hidx and hidx + 6:  X[s][j] = -inv(L_s) T_j,  T_j = sum_{k=j}^{s-1} L[s][k] X[k][j].
-      // It overwrites row s of L in place, so it may only be stored once all six helpers have finished reading that row (cntA[s]):
-      // the values stay in registers for one stage and are stored at the START of the next stage's inverse task -- a helper that
-      // waited here for the slowest one was late for the next column's urgent updates.
-      if (hidx == 0) D2_TRACE(34 + 4 * s);
-      if (s >= 2) {
-        if (!d2_wait_ge(&fl->cntA[s - 1], D3_NH, ab, info, 6)) return;
-        d3_store_inverse_rows(S, Dinv, Xn, s - 1, hidx, g, c);
-        D2_LDS_FENCE();
-      }
-#pragma unroll
-      for (int q2 = 0; q2 < 2; ++q2) {
-        const int j = hidx + q2 * D3_NH;
-        if (j >= s) continue;
-        d4_t T = {0.0, 0.0, 0.0, 0.0};
-        for (int kk = j; kk < s; ++kk) mma16<false>(T, S + blk_off(s, kk), BLD, S + blk_off(kk, j), BLD, lane);
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * BLD + kq * 4 + g], T[kq], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Xn[q2][r] = -acc[r];
-      }
-      // every read of row s of L by this wave is behind it (the updates of column s's blocks ran in earlier stages)
-      D2_LDS_FENCE();
-      if (lane == 0) d3_add(&fl->cntA[s], 1);
-      if (s == 7) {                            // the last row block: nothing follows, store it now
-        if (!d2_wait_ge(&fl->cntA[7], D3_NH, ab, info, 7)) return;
-        d3_store_inverse_rows(S, Dinv, Xn, 7, hidx, g, c);
-      }
-    }
-  }
-  if (hidx == 0) D2_TRACE(63);
-}
-
 // ------------------------------------------------------------------------------------------------------------
-// potrf_diag128_v4 (round 6): the stage loop of the one-launch trainer (train.hip) as the diagonal-block kernel.
-//
-// v3 is a flag-driven pipeline: wave 0 carries the pivot chain AND the solves of the next two block rows AND the next diagonal
-// block's update (G: 12 dependent MFMAs and two LDS round trips per stage) while six helpers follow task lists behind LDS flags -- 3.5 us
-// per 16 columns, co-limited between wave 0 and the helpers.  Here every stage has TWO workgroup barriers and nothing else to wait for:
-//   [A] wave 0 applies column jj - 1 to its diagonal block on the way into the registers and factors + inverts it (the same DP-ALU DPP
-//       pivot step); in its shadow the helper waves (those that do not share wave 0's SIMD) apply column jj - 1 to every other block and
-//       compute row block jj - 1 of the inverse into registers;
+// potrf_diag128_v4 (round 6): factor one diagonal block (nb <= 128 valid rows/cols, identity-padded) and invert it, on the stage loop
+// of the one-launch trainer (train.hip).  Every stage has TWO workgroup barriers and nothing else to wait for:
+//   [A] wave 0 applies column jj - 1 to its diagonal block on the way into the registers and factors + inverts it (diag16_factor); in
+//       its shadow the helper waves (those that do not share wave 0's SIMD) apply column jj - 1 to every other block and compute row
+//       block jj - 1 of the inverse into registers;
 //   [B] the inverse's row is stored (LDS + Dinv store), all eight waves solve column jj with inv(L_jj) (one block each) and write L.
-// Only ceil(nb / 16) stages run.  25.2 us per 128-block alone against v3's 28.6 (rocprofv3 kernel trace, profiles/r06g_*).  A variant with
-// ONE workgroup barrier per stage -- wave 0 solving block row jj itself in v3's way (Y = inv(L) S^T, D -= Y^T Y in registers) and the
-// helpers meeting at an LDS counter that wave 0 only arrives at -- was built and measured equal (docs/experiments.md, round 6).  The factor differs from v3's in the last bits (the updates reach a
-// block in a different order); both are held to LAPACK (1e-11) by the same tests.
+// Only ceil(nb / 16) stages run.  25.2 us per 128-block alone against 28.6 for round 4's flag-driven pipeline (v3: wave 0 carried the
+// pivot chain, the solves of the next two block rows and the next diagonal block's update while six helpers followed task lists behind
+// LDS flags; rocprofv3 kernel trace, profiles/r06g_*; v3 was retired later, commit afe272f is the last tree that has it).  A variant
+// with ONE workgroup barrier per stage -- wave 0 solving block row jj itself in v3's way (Y = inv(L) S^T, D -= Y^T Y in registers) and
+// the helpers meeting at an LDS counter that wave 0 only arrives at -- was built and measured equal (docs/experiments.md, round 6).
 // ------------------------------------------------------------------------------------------------------------
 #define DIAG4_LDS_DOUBLES (NBLK_LOWER * BLKSZ + 128 + 16)
-#ifndef FFGP_D4_DBG
-#define FFGP_D4_DBG 0      // timing-only ablations of v4 (results wrong when non-zero): 1 = helpers idle in [A], 2 = wave 0 skips its pivots
-#endif
 #define DIAG4_LDS_BYTES (DIAG4_LDS_DOUBLES * 8)
-
-// (workgroup barrier that publishes LDS only: the kernel's global stores -- L, the Dinv store -- are read by nobody inside it, and
-//  __syncthreads() would expose their round trip to L2 at every one of the 2 x 8 barriers)
-#define D4_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 template <bool RAG>
 __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restrict__ A, int lda, int nb, double* __restrict__ Dinv,
@@ -1006,29 +216,19 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
   int* flags = reinterpret_cast<int*>(lds + NBLK_LOWER * BLKSZ + 128);      // [0..7] SIMD of wave w
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, c = lane & 15;
+  // the previous panel is complete the moment this kernel runs (stream order): publish that to the update stream's waiting gate
   if (rag.pub && blockIdx.x == 0 && tid == 64) __hip_atomic_store(rag.pub, rag.pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (prio) __builtin_amdgcn_s_setprio(3);
   const int nst = (nb + 15) >> 4;
-  if (lane == 0) flags[wave] = d3_simd_id();
-  D4_BARRIER();
-  int hidx = -1, nh = 0;      // helpers: the waves that do not share wave 0's SIMD (fp64 MFMAs and the pivot loop's DP-ALU work share a pipe)
-  {
-    const int s0 = flags[0];
-    for (int w_ = 1; w_ < 8; ++w_) {
-      const bool is_h = flags[w_] != s0;
-      if (is_h && w_ == wave) hidx = nh;
-      nh += is_h ? 1 : 0;
-    }
-    if (nh == 0) { nh = 7; hidx = wave - 1; }
-    hidx = __builtin_amdgcn_readfirstlane(hidx);
-    nh = __builtin_amdgcn_readfirstlane(nh);
-  }
+  if (lane == 0) flags[wave] = simd_id();
+  LDS_BARRIER();
+  HELPER_ROLES(flags, wave, hidx, nh);
   // ---- loads: wave 0 takes block (0, 0) straight into the factor's registers; the other waves bring every other lower block of the
   //      first nst block rows into LDS ([16][17] images; diagonal blocks mirrored to full), all loads of a wave in flight at once
   double v0[4];
   if (wave == 0) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v0[r] = d3_elem(A, lda, nb, g + 4 * r, c);
+    for (int r = 0; r < 4; ++r) v0[r] = sym_elem(A, lda, nb, g + 4 * r, c);
   } else {
     const int nblk = nst * (nst + 1) / 2;
     double x[6][4];
@@ -1036,18 +236,19 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
     for (int u = 0; u < 6; ++u) {
       const int t = wave + 7 * u;      // blocks 1 .. nblk - 1 of the row-major enumeration over seven waves
       if (t >= nblk) continue;
-      int bi = 0;
+      // (blk_unrank spelled out here and below: as calls, the same code compiles to a different instruction schedule of this kernel)
+int bi = 0;
 #pragma unroll
       for (int q = 1; q < 8; ++q) bi += (t >= q * (q + 1) / 2) ? 1 : 0;
       const int bj = t - bi * (bi + 1) / 2;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) x[u][r] = d3_elem(A, lda, nb, bi * 16 + g + 4 * r, bj * 16 + c);
+      for (int r = 0; r < 4; ++r) x[u][r] = sym_elem(A, lda, nb, bi * 16 + g + 4 * r, bj * 16 + c);
     }
 #pragma unroll
     for (int u = 0; u < 6; ++u) {
       const int t = wave + 7 * u;
       if (t >= nblk) continue;
-      int bi = 0;
+int bi = 0;
 #pragma unroll
       for (int q = 1; q < 8; ++q) bi += (t >= q * (q + 1) / 2) ? 1 : 0;
       const int bj = t - bi * (bi + 1) / 2;
@@ -1057,7 +258,7 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
     }
     // rows beyond the stages that run: identity in the Dinv store (a previous, larger block may have left its inverse there)
     for (int t = nst * (nst + 1) / 2 + (wave - 1); t < NBLK_LOWER; t += 7) {
-      int bi = 0;
+int bi = 0;
 #pragma unroll
       for (int q = 1; q < 8; ++q) bi += (t >= q * (q + 1) / 2) ? 1 : 0;
       const int bj = t - bi * (bi + 1) / 2;
@@ -1076,7 +277,7 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
       d4_t upd = {0.0, 0.0, 0.0, 0.0};
       if (jj > 0) mma16<true>(upd, S + blk_off(jj, jj - 1), BLD, S + blk_off(jj, jj - 1), BLD, lane);
       int cc = c, gg = g;
-      asm volatile("" : "+v"(cc), "+v"(gg));      // (opaque per iteration: see v2)
+      asm volatile("" : "+v"(cc), "+v"(gg));      // (opaque per iteration: the stage loop must not be specialised per jj)
       double v[4], w[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1090,10 +291,8 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
         double pRow = 0.0, pt = 0.0, ptw = 0.0;
         double dcur = row_bcast64<0>(rowA), ycur = __builtin_amdgcn_rcp(dcur);
 #define F16_S(JJ) f16_step_dpp<JJ>(v, w, rowA, rowW, hA, hW, pRow, pt, ptw, dcur, ycur, cc, gg);
-        if (!(FFGP_D4_DBG & 2)) {
         F16_S(0) F16_S(1) F16_S(2) F16_S(3) F16_S(4) F16_S(5) F16_S(6) F16_S(7) F16_S(8) F16_S(9) F16_S(10) F16_S(11) F16_S(12) F16_S(13)
         F16_S(14) F16_S(15)
-        }
 #undef F16_S
       }
       const int q = c >> 2;
@@ -1115,13 +314,14 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
         }
       }
       if (bad && lane == 0 && (jj * 16 + bad) <= nb) atomicCAS(info, 0, row_base + jj * 16 + bad);
-    } else if (hidx >= 0 && jj > 0 && !(FFGP_D4_DBG & 1)) {
+    } else if (hidx >= 0 && jj > 0) {
       // column jj - 1 reaches every block (i, k), jj <= k <= i, but (jj, jj).  (Two tasks at a time -- both tasks' operands requested before
-      // either product, the two MFMA chains alternating -- was measured SLOWER: 25.9 against 25.2 us per block.  By ablation
-      // (-DFFGP_D4_DBG) the kernel is co-limited: without wave 0's pivots it takes the same time, with idle helpers 2.9 us less.)
+      // either product, the two MFMA chains alternating -- was measured SLOWER: 25.9 against 25.2 us per block.  By ablation -- timing-only
+      // builds without the helpers' or wave 0's work, last in commit afe272f -- the kernel is co-limited: without wave 0's pivots it takes
+      // the same time, with idle helpers 2.9 us less.)
       const int m = nst - jj;
       for (int t = 1 + hidx; t < m * (m + 1) / 2; t += nh) {
-        int a = 0;
+int a = 0;
 #pragma unroll
         for (int q = 1; q < 8; ++q) a += (t >= q * (q + 1) / 2) ? 1 : 0;
         const int b = t - a * (a + 1) / 2;
@@ -1156,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
         }
       }
     }
-    D4_BARRIER();
+    LDS_BARRIER();
     if (hidx >= 0 && jj > 0) {      // row jj - 1 of L is dead now: the inverse's row takes its place (and goes to the Dinv store)
 #pragma unroll
       for (int q2 = 0; q2 < 2; ++q2) {
@@ -1182,7 +382,7 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
         if (gr < nb) A[(size_t)gr * lda + jj * 16 + c] = acc[r];
       }
     }
-    D4_BARRIER();
+    LDS_BARRIER();
   }
   if (nst > 1 && hidx >= 0) {      // the last row block of the inverse: the helpers' columns, one product left per column
     const int s_ = nst - 1;
@@ -1421,72 +621,49 @@ static int launch_trsm128_set(ffgp_handle* h, const TrsmSet& set, int cnt, int m
 // ------------------------------------------------------------------------------------------------------------
 static inline void la_take_deferred(ffgp_handle* h, DiagRag& dr);
 static int launch_diag(ffgp_handle* h, double* Ablk, int lda, int nb, double* Dinv_blk, int row_base, int do_factor) {
-  if (h->bt_F > 1 && !(do_factor && h->diag_v2 == 4)) return FFGP_ERR_ARG;   // only the round-4 kernel is batched
-  if (!(h->diag_attr_set & 1)) {   // per handle = per device (the attribute lives in the device's context)
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
-    h->diag_attr_set |= 1;
-  }
-  if (do_factor && h->diag_v2 == 4) {   // round 4: owner-computes helpers, wave 0's SIMD partner steps aside (the barrier version keeps
-                                       // the inverse-only entry)
-    if (!(h->diag_attr_set & 4)) {
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   DIAG_LDS_BYTES));
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   DIAG_LDS_BYTES));
-      h->diag_attr_set |= 4;
+  if (h->bt_F > 1 && !do_factor) return FFGP_ERR_ARG;   // only the factor kernel is batched
+  if (!do_factor) {   // the inverse of a factor produced elsewhere
+    if (!(h->diag_attr_set & 1)) {   // per handle = per device (the attribute lives in the device's context)
+      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, DIAG_LDS_BYTES));
+      h->diag_attr_set |= 1;
     }
-    // (diag_excl: the panel's FIRST diagonal block of a chain-bound carry iteration asks for a whole CU's LDS, so the S_bz workgroups that
-    //  start the moment it publishes cannot land beside it -- see ffgp_potrf_impl.  Only where a workgroup may have that much: the
-    //  limit is asked for once, and a device or runtime that says less simply keeps the ordinary launch)
-    if (!h->lds_cap_known) {
-      int cap = 0;
-      if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess) {
-        (void)hipGetLastError();
-        cap = 64 * 1024;
-      }
-      h->lds_cap = cap;
-      h->lds_cap_known = 1;
-    }
-    const bool excl = h->diag_excl_now && h->bt_F <= 1 && h->lds_cap >= 160 * 1024;
-    const int lds_bytes = excl ? 160 * 1024 : DIAG_LDS_BYTES;
-    if (excl && !h->diag_v4 && !(h->diag_attr_set & 8)) {
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   160 * 1024));
-      h->diag_attr_set |= 8;
-    }
-    if (h->diag_v4 && !(h->diag_attr_set & 16)) {
-      const int want = h->lds_cap >= 160 * 1024 ? 160 * 1024 : DIAG4_LDS_BYTES;
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-      FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
-      h->diag_attr_set |= 16;
-    }
-    // the pending "panel complete" publication is taken only now, when nothing can fail between here and the launch that carries it
-    DiagRag dr = DiagRag();
-    la_take_deferred(h, dr);
-    if (h->diag_v4) {      // round 6: two barriers per stage (ffgp_potrf_diag128_v4)
-      const int lds4 = excl ? lds_bytes : DIAG4_LDS_BYTES;
-      auto kern = ffgp_potrf_diag128_v4<false>;
-      if (h->bt_F > 1)
-        hipLaunchKernelGGL(kern, dim3(h->bt_F), dim3(512), DIAG4_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
-                           h->bt_info, row_base, h->aux_prio, h->bt_sA, h->bt_sD, 1, dr);
-      else
-        hipLaunchKernelGGL(kern, dim3(1), dim3(512), lds4, h->stream, Ablk, lda, nb, Dinv_blk, h->d_info,
-                           row_base, h->aux_prio, 0L, 0L, 0, dr);
-    } else if (h->bt_F > 1)
-      hipLaunchKernelGGL(ffgp_potrf_diag128_v3<false>, dim3(h->bt_F), dim3(512), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
-                         h->bt_info, row_base, h->aux_prio, h->bt_sA, h->bt_sD, 1, dr);
-    else
-      hipLaunchKernelGGL(ffgp_potrf_diag128_v3<false>, dim3(1), dim3(512), lds_bytes, h->stream, Ablk, lda, nb, Dinv_blk, h->d_info,
-                         row_base, h->aux_prio, 0L, 0L, 0, dr);
-    if (hipGetLastError() != hipSuccess) {      // the launch that carried the publication did not happen: write it plainly, report
-      if (dr.pub) (void)hipStreamWriteValue32(h->stream, dr.pub, dr.pub_val, 0);
-      return FFGP_ERR_HIP;
-    }
+    hipLaunchKernelGGL(ffgp_potrf_diag128, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk, h->aux_prio);
     return FFGP_OK;
   }
-  hipLaunchKernelGGL(ffgp_potrf_diag128, dim3(1), dim3(DIAG_THREADS), DIAG_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
-                     h->d_info, row_base, do_factor, /*dbg=*/0, h->aux_prio);
+  // (diag_excl: the panel's FIRST diagonal block of a chain-bound carry iteration asks for a whole CU's LDS, so the S_bz workgroups that
+  //  start the moment it publishes cannot land beside it -- see ffgp_potrf_impl.  Only where a workgroup may have that much: the
+  //  limit is asked for once, and a device or runtime that says less simply keeps the ordinary launch)
+  if (!h->lds_cap_known) {
+    int cap = 0;
+    if (hipDeviceGetAttribute(&cap, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess) {
+      (void)hipGetLastError();
+      cap = 64 * 1024;
+    }
+    h->lds_cap = cap;
+    h->lds_cap_known = 1;
+  }
+  const bool excl = h->diag_excl_now && h->bt_F <= 1 && h->lds_cap >= 160 * 1024;
+  if (!(h->diag_attr_set & 2)) {
+    const int want = h->lds_cap >= 160 * 1024 ? 160 * 1024 : DIAG4_LDS_BYTES;
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, want));
+    h->diag_attr_set |= 2;
+  }
+  // the pending "panel complete" publication is taken only now, when nothing can fail between here and the launch that carries it
+  DiagRag dr = DiagRag();
+  la_take_deferred(h, dr);
+  auto kern = ffgp_potrf_diag128_v4<false>;
+  if (h->bt_F > 1)
+    hipLaunchKernelGGL(kern, dim3(h->bt_F), dim3(512), DIAG4_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk,
+                       h->bt_info, row_base, h->aux_prio, h->bt_sA, h->bt_sD, 1, dr);
+  else
+    hipLaunchKernelGGL(kern, dim3(1), dim3(512), excl ? 160 * 1024 : DIAG4_LDS_BYTES, h->stream, Ablk, lda, nb, Dinv_blk, h->d_info,
+                       row_base, h->aux_prio, 0L, 0L, 0, dr);
+  if (hipGetLastError() != hipSuccess) {      // the launch that carried the publication did not happen: write it plainly, report
+    if (dr.pub) (void)hipStreamWriteValue32(h->stream, dr.pub, dr.pub_val, 0);
+    return FFGP_ERR_HIP;
+  }
   return FFGP_OK;
 }
 
@@ -1566,6 +743,7 @@ static inline int la_slot(const ffgp_handle* h, hipEvent_t ev) {
 // runtime's 2.9-4.7, tools/native/handoff_probe.hip `kgate` / `vgate`), but watches the 100 MHz wall clock: after `ticks` without the
 // value it writes FFGP_HANDOFF_WATCHDOG into the status word and LEAVES -- the kernels behind it then run on incomplete data and the
 // call returns FFGP_ERR_HANDOFF instead of never returning; the handle goes back to event pairs (ffgp_map_info).
+#define FFGP_HANDOFF_WATCHDOG 0x7fffffe0
 __global__ void ffgp_handoff_gate(const unsigned* __restrict__ word, unsigned need, int* info, long ticks) {
   if (threadIdx.x != 0) return;
   const long t0 = wall_clock64();
@@ -1675,9 +853,9 @@ static int la_record_on_next_gemm(ffgp_handle* h, hipEvent_t ev, hipStream_t s) 
 }
 static int la_record_deferred(ffgp_handle* h, hipEvent_t ev, hipStream_t s) {
   const int slot = la_slot(h, ev);
-  // (only ffgp_potrf_diag128_v3 publishes: with another diagonal-block kernel selected -- option diag_v2 -- nobody would pick the word up, and
-  //  the plain write at the end of the factorisation would sit behind kernels that wait for it; found by the suite's barrier-kernel case)
-  if (slot < 0 || !h->ho_defer || h->diag_v2 != 4 || h->use_naive) return la_record(h, ev, s);
+  // (only the factor kernel, ffgp_potrf_diag128_v4, publishes: with the naive kernels nobody would pick the word up, and the plain write at
+  //  the end of the factorisation would sit behind kernels that wait for it)
+  if (slot < 0 || !h->ho_defer || h->use_naive) return la_record(h, ev, s);
   FFGP_CHECK(la_flush(h));
   h->ho_seq[slot] += 1;
   h->ho_defer_slot = slot;
@@ -1975,7 +1153,7 @@ int ffgp_potrf_impl(ffgp_handle* h, double* A, int n, int mtot, int lda, int syn
 // ------------------------------------------------------------------------------------------------------------
 int ffgp_potrf_ragged(ffgp_handle* h, int R, const ffgp_rag_block* mem) {
   if (R <= 0) return FFGP_OK;
-  if (!mem || h->use_naive || h->diag_v2 != 4) return FFGP_ERR_ARG;
+  if (!mem || h->use_naive) return FFGP_ERR_ARG;
   const int NB1 = h->nb_outer;
   std::vector<int> form(R);
   bool any_la = false;
@@ -1989,19 +1167,12 @@ int ffgp_potrf_ragged(ffgp_handle* h, int R, const ffgp_rag_block* mem) {
     any_la = any_la || form[f] == 1;
     nmax = max(nmax, b.n);
   }
-  if (!(h->diag_attr_set & 4)) {
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 DIAG_LDS_BYTES));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v3<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 DIAG_LDS_BYTES));
-    h->diag_attr_set |= 4;
-  }
-  if (h->diag_v4 && !(h->diag_attr_set & 32)) {      // (the ragged launches never ask for more than the kernel's own image)
-    if (!(h->diag_attr_set & 16)) {
+  if (!(h->diag_attr_set & 4)) {      // (the ragged launches never ask for more than the kernel's own image)
+    if (!(h->diag_attr_set & 2)) {
       FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<true>), hipFuncAttributeMaxDynamicSharedMemorySize, DIAG4_LDS_BYTES));
       FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_potrf_diag128_v4<false>), hipFuncAttributeMaxDynamicSharedMemorySize, DIAG4_LDS_BYTES));
     }
-    h->diag_attr_set |= 32;
+    h->diag_attr_set |= 4;
   }
   FFGP_CHECK(la_begin(h));
   h->ho_info = h->bt_info + mem[0].info_index;      // (a gate that gives up reports through the first member's status word)
@@ -2042,12 +1213,8 @@ int ffgp_potrf_ragged(ffgp_handle* h, int R, const ffgp_rag_block* mem) {
         if (!cnt) continue;
         la_take_deferred(h, dr);
         for (int c = cnt; c < FFGP_RAG_MAX; ++c) { dr.A[c] = dr.A[0]; dr.Dinv[c] = dr.Dinv[0]; dr.lda[c] = dr.lda[0]; dr.nb[c] = dr.nb[0]; dr.info[c] = dr.info[0]; }
-        if (h->diag_v4) {
-          hipLaunchKernelGGL(ffgp_potrf_diag128_v4<true>, dim3(cnt), dim3(512), DIAG4_LDS_BYTES,
-                             h->stream, (double*)nullptr, 0, 0, (double*)nullptr, h->bt_info, j0, h->aux_prio, 0L, 0L, 0, dr);
-        } else
-        hipLaunchKernelGGL(ffgp_potrf_diag128_v3<true>, dim3(cnt), dim3(512), DIAG_LDS_BYTES, h->stream, (double*)nullptr, 0, 0, (double*)nullptr,
-                           h->bt_info, j0, h->aux_prio, 0L, 0L, 0, dr);
+        hipLaunchKernelGGL(ffgp_potrf_diag128_v4<true>, dim3(cnt), dim3(512), DIAG4_LDS_BYTES,
+                           h->stream, (double*)nullptr, 0, 0, (double*)nullptr, h->bt_info, j0, h->aux_prio, 0L, 0L, 0, dr);
       }
       // TRSM of every row below: A21 <- A21 * Dj^T, in place
       in.clear();
@@ -2159,27 +1326,12 @@ int ffgp_potrf_ragged(ffgp_handle* h, int R, const ffgp_rag_block* mem) {
   return rc;
 }
 
-// status word -> return code: a pivot index passes through; the diagonal-block kernel's watchdog is a library error
+// status word -> return code: a pivot index passes through; a look-ahead gate that gave up is a library error
 int ffgp_map_info(int v) {
   if (v == FFGP_HANDOFF_WATCHDOG) {
     fprintf(stderr, "[ffgp] look-ahead: a gate waited for a cross-stream hand-off that never came and gave up (a tool that runs this "
                     "process's kernels one at a time?); the call's results are invalid -- FFGP_HANDOFF=events keeps the event pairs\n");
     return FFGP_ERR_HANDOFF;
-  }
-  if (v >= FFGP_DIAG_WATCHDOG) {
-    fprintf(stderr, "[ffgp] potrf_diag128: a wave waited ~1 s for a hand-off inside the kernel and gave up (internal error; hand-off %d)\n",
-            v - FFGP_DIAG_WATCHDOG);
-    int dbg[32];
-    if (hipMemcpyFromSymbol(dbg, HIP_SYMBOL(ffgp_d3_dbg), sizeof(dbg)) == hipSuccess) {
-      fprintf(stderr, "[ffgp]   helper %d stage %d column %d block (%d, %d) have 0x%x task %d | seqF %d hs %d hd %d h2 %d | rows", dbg[0], dbg[1], dbg[2],
-              dbg[3], dbg[4], dbg[5], dbg[26], dbg[6], dbg[7], dbg[8], dbg[9]);
-      for (int z = 0; z < 8; ++z) fprintf(stderr, " %x", dbg[10 + z]);
-      fprintf(stderr, " | cntA");
-      for (int z = 0; z < 8; ++z) fprintf(stderr, " %d", dbg[18 + z]);
-      fprintf(stderr, " | prog w0 %d h0..5 %d %d %d %d %d %d\n", dbg[27] & 0xffff, dbg[28] & 0xffff, dbg[29] & 0xffff, dbg[30] & 0xffff, dbg[31] & 0xffff,
-              dbg[27] >> 16, dbg[28] >> 16);
-    }
-    return FFGP_ERR_HIP;
   }
   return v;
 }

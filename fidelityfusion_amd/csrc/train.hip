@@ -10,7 +10,7 @@
 //   ->  blocked Cholesky AND inverse, two workgroup barriers per 16-column stage: wave 0 factors + inverts the diagonal block in
 //       registers on the DP-ALU DPP pivot step of f16_steps.h while the helper waves apply the previous column and form the previous row
 //       of the inverse; then all eight waves solve the column.  Only ceil(n / 16) stages run: n = 32 costs a quarter of n = 128.
-//       (This loop became the factorisation's diagonal-block kernel, ffgp_potrf_diag128_v4 in potrf.hip.)
+//       (This loop became the factorisation's diagonal-block kernel, ffgp_potrf_diag128_v4 in potrf.hip; the two share diag_block.h.)
 //   ->  Gamma = L^-1 Y, A = L^-T Gamma as MFMA block chains on zero-padded [128][16] images, the value
 //   ->  Sigma^-1 = L^-T L^-1 block by block on the matrix cores, each 16 x 16 block consumed in its accumulators: G = d/2 Sigma^-1 - 1/2 A A^T,
 //       the gradient sums of grad.hip (amplitude, length scales, trace) -- Sigma^-1 is never stored
@@ -23,18 +23,13 @@
 // Covers: n <= 128, D <= 16, d <= 16, one radial-profile kernel, V1 likelihood, diag_add and diag_vec (no matrix / all-entries /
 // mean(K) extras, no learnable profile parameter): what cigp_v10 produces.  Everything else keeps the paths it had.
 #include "ffgp_internal.h"
-#include "f16_steps.h"
+#include "diag_block.h"
 
 #define TR_T 512
-#define TR_BLD 17
-#define TR_BLK (16 * TR_BLD)
-#define TR_NBLK 36
 #define TR_N 128
 #define TR_D 16
 #define TR_Y 16
 #define TR_NRED 20        // values of the step's one workgroup reduction: ss, s_amp, tr G, log-det, tot[16]
-
-typedef double tr_d4 __attribute__((ext_vector_type(4)));
 
 struct TrainModel {
   int n, D, d, nw;                       // nw: raw length scales (1 = one value broadcast over the D dimensions)
@@ -63,10 +58,6 @@ struct TrainCommon {
   int info_max;
   long* prof;                            // development (FFGP_TRAIN_TRACE=1): [12] wall_clock64 ticks per phase, summed over model 0's steps
 };
-// workgroup barrier that publishes LDS only: __syncthreads() also drains the wave's GLOBAL stores (the kernel values parked for the
-// gradient pass, the trace), whose round trip to L2 would be exposed at every barrier behind them.  Nothing inside the step loop is
-// handed from thread to thread through global memory.
-#define TR_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #define TR_PROF(k)                                                   \
   do {                                                               \
     if (cm.prof && tid == 0 && blockIdx.x == 0) {                    \
@@ -125,40 +116,15 @@ __device__ __forceinline__ double tr_wsum(double x) {
   return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
 }
 
-__device__ __forceinline__ int tr_blk(int bi, int bj) { return (bi * (bi + 1) / 2 + bj) * TR_BLK; }
-// t-th block of the row-major enumeration of the lower block triangle -> (bi, bj)
-__device__ __forceinline__ void tr_unblk(int t, int& bi, int& bj) {
-  bi = 0;
-#pragma unroll
-  for (int q = 1; q < 8; ++q) bi += (t >= q * (q + 1) / 2) ? 1 : 0;
-  bj = t - bi * (bi + 1) / 2;
-}
 // block dealt to `wave` in round q of the assembly / the Sigma^-1 pass: the row-major enumeration has the expensive blocks of the Sigma^-1
 // pass first (block (bi, bj) costs nst - bi products), so the rounds run forwards and backwards in turn -- 16 products for the busiest
 // wave at n = 128 instead of 19.  Both passes MUST deal alike: the kernel values travel from one to the other by (block, lane) slot.
 __device__ __forceinline__ int tr_deal(int q, int wave) { return 8 * q + ((q & 1) ? 7 - wave : wave); }
-__device__ __forceinline__ double tr_rsqrt(double d) {
-  double y = __builtin_amdgcn_rsq(d);
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const double e = __builtin_fma(-d * y, y, 1.0);
-    y = __builtin_fma(0.5 * y, e, y);
-  }
-  return y;
-}
-// acc += P * Q^T on 16 x 16 blocks of the LDS image: P[m][k] at pa[m * 17 + k], Q[n][k] at pb[n * 17 + k]
-__device__ __forceinline__ void tr_mma_nt(tr_d4& acc, const double* pa, const double* pb, int lane) {
-#pragma unroll
-  for (int kq = 0; kq < 4; ++kq) {
-    const int k = kq * 4 + (lane >> 4);
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[(lane & 15) * TR_BLD + k], pb[(lane & 15) * TR_BLD + k], acc, 0, 0, 0);
-  }
-}
 // acc += sum_{kb = k0}^{k1 - 1} op(P_kb) * Q_kb over 16 x 16 blocks, the NEXT block's operands requested before this block's four MFMAs
 // (a runtime loop of load-then-multiply rounds waits one LDS round trip per block).  P_kb at baseA + offA(kb): element (m, k) at
 // [m * lda + k], or (TA) the transposed block: (m, k) at [k * lda + m]; Q_kb at baseB + offB(kb): element (k, n) at [k * ldb + n].
 template <bool TA, class OA, class OB>
-__device__ __forceinline__ void tr_chain(tr_d4& acc, int k0, int k1, const double* baseA, OA offA, int lda, const double* baseB, OB offB,
+__device__ __forceinline__ void tr_chain(d4_t& acc, int k0, int k1, const double* baseA, OA offA, int lda, const double* baseB, OB offB,
                                          int ldb, int lane) {
   if (k0 >= k1) return;
   const int m = lane & 15, g = lane >> 4;
@@ -194,13 +160,13 @@ __device__ __forceinline__ void tr_chain(tr_d4& acc, int k0, int k1, const doubl
   }
 }
 // accumulator (lane (g, c), register r = entry (g + 4 r, c)) -> the block's [16][17] home
-__device__ __forceinline__ void tr_store(double* dst, const tr_d4& acc, int g, int c, double sign) {
+__device__ __forceinline__ void tr_store(double* dst, const d4_t& acc, int g, int c, double sign) {
 #pragma unroll
-  for (int r = 0; r < 4; ++r) dst[(g + 4 * r) * TR_BLD + c] = sign * acc[r];
+  for (int r = 0; r < 4; ++r) dst[(g + 4 * r) * BLD + c] = sign * acc[r];
 }
 
 // LDS (doubles): S 36 * 272 | Xs [128][17] | Ym, Gam, Am [128][16] each | piv [128] | dvec [128] | small
-#define TR_OFF_XS (TR_NBLK * TR_BLK)
+#define TR_OFF_XS (NBLK_LOWER * BLKSZ)
 #define TR_OFF_YM (TR_OFF_XS + TR_N * (TR_D + 1))
 #define TR_OFF_GAM (TR_OFF_YM + TR_N * TR_Y)
 #define TR_OFF_AM (TR_OFF_GAM + TR_N * TR_Y)
@@ -256,32 +222,17 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       mo2[tid] = M.state[npar + tid];
     }
   }
-  for (int t = wave; t < TR_NBLK; t += 8) {
+  for (int t = wave; t < NBLK_LOWER; t += 8) {
     int bi, bj;
-    tr_unblk(t, bi, bj);
+    blk_unrank(t, bi, bj);
     if (bi < nst) continue;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) S[tr_blk(bi, bj) + (g + 4 * r) * TR_BLD + c] = (bi == bj && g + 4 * r == c) ? 1.0 : 0.0;
+    for (int r = 0; r < 4; ++r) S[blk_off(bi, bj) + (g + 4 * r) * BLD + c] = (bi == bj && g + 4 * r == c) ? 1.0 : 0.0;
   }
   if (tid == 0) flags[0] = 0;
-  if (lane == 0) flags[8 + wave] = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3;      // HW_REG_HW_ID, SIMD_ID (bits 5:4)
+  if (lane == 0) flags[8 + wave] = simd_id();
   __syncthreads();
-  // helpers of the factorisation's stage [A]: the waves that do NOT share wave 0's SIMD (six, with two waves per SIMD)
-  int hidx = -1, nh = 0;
-  {
-    const int s0 = flags[8];
-    for (int w_ = 1; w_ < 8; ++w_) {
-      const bool is_h = flags[8 + w_] != s0;
-      if (is_h && w_ == wave) hidx = nh;
-      nh += is_h ? 1 : 0;
-    }
-    if (nh == 0) {      // (every wave on one SIMD cannot happen with 8 waves on 4 SIMDs; keep the kernel correct anyway)
-      nh = 7;
-      hidx = wave - 1;
-    }
-    hidx = __builtin_amdgcn_readfirstlane(hidx);
-    nh = __builtin_amdgcn_readfirstlane(nh);
-  }
+  HELPER_ROLES(flags + 8, wave, hidx, nh);      // helpers of the factorisation's stage [A]
   if (tid < D) wv[tid] = tr_link_val(M.l.w_link, raw[M.l.w_broadcast ? 0 : tid], M.l.w_c);
   if (tid == 64) sc[0] = tr_link_val(M.l.amp_link, raw[nw], M.l.amp_c);
   if (tid == 65) sc[1] = M.dadd ? tr_link_val(M.l.dadd_link, raw[nw + 1], M.l.dadd_c) : 0.0;
@@ -302,7 +253,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       const int i = idx / D, k = idx - i * D;
       Xs[i * (TR_D + 1) + k] = (M.X[idx] - M.X[k]) * wv[k];
     }
-    TR_BARRIER();
+    LDS_BARRIER();
     const double amp = sc[0], dadd = sc[1];
     TR_PROF(0);
 
@@ -312,8 +263,8 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       const int t = tr_deal(q_, wave);
       if (t >= nblk) continue;
       int bi, bj;
-      tr_unblk(t, bi, bj);
-      double* dst = S + tr_blk(bi, bj);
+    blk_unrank(t, bi, bj);
+      double* dst = S + blk_off(bi, bj);
       const int j = bj * 16 + c;
       double xj[DM], sq[4];
 #pragma unroll
@@ -337,10 +288,10 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         double kv = amp * ev;
         if (i == j) kv += dadd + dvec[i];
         if (i >= n || j >= n) kv = (i == j) ? 1.0 : 0.0;
-        dst[(g + 4 * r) * TR_BLD + c] = kv;
+        dst[(g + 4 * r) * BLD + c] = kv;
       }
     }
-    TR_BARRIER();
+    LDS_BARRIER();
     TR_PROF(1);
 
     // ---- P2: blocked Cholesky over 16-column stages AND the inverse, two barriers per stage.
@@ -350,17 +301,17 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     //       compute row block jj - 1 of the inverse, X[s][j] = -inv(L_s) sum_{k=j}^{s-1} L[s][k] X[k][j], into registers;
     //   [B] the inverse's row is stored over row jj - 1 of L (nobody reads it any more) and column jj is solved by all waves.
     for (int jj = 0; jj < nst; ++jj) {
-      tr_d4 Xn[2];
+      d4_t Xn[2];
       if (wave == 0) {
-        double* Dj = S + tr_blk(jj, jj);
-        tr_d4 upd = {0.0, 0.0, 0.0, 0.0};      // the one update still missing from this block: applied on the way into the registers
-        if (jj > 0) tr_mma_nt(upd, S + tr_blk(jj, jj - 1), S + tr_blk(jj, jj - 1), lane);
+        double* Dj = S + blk_off(jj, jj);
+        d4_t upd = {0.0, 0.0, 0.0, 0.0};      // the one update still missing from this block: applied on the way into the registers
+        if (jj > 0) mma16<true>(upd, S + blk_off(jj, jj - 1), BLD, S + blk_off(jj, jj - 1), BLD, lane);
         int cc = c, gg = g;
         asm volatile("" : "+v"(cc), "+v"(gg));      // (opaque per iteration: the stage loop must not be specialised per jj)
         double v[4], w[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          v[r] = Dj[(gg + 4 * r) * TR_BLD + cc] - upd[r];
+          v[r] = Dj[(gg + 4 * r) * BLD + cc] - upd[r];
           w[r] = (gg + 4 * r == cc) ? 1.0 : 0.0;
         }
         double rowA = bperm_d(v[0], cc);
@@ -377,7 +328,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         const int q = c >> 2;
         const double dsel = (q == 0) ? v[0] : (q == 1) ? v[1] : (q == 2) ? v[2] : v[3];
         const double dcol = bperm_d(dsel, 16 * (c & 3) + c);      // pivot of column c
-        const double rs = tr_rsqrt(dcol);
+        const double rs = rsqrt_nr(dcol);
         const unsigned long long nonpos = __ballot(!(dcol > 0.0)) & 0xffffull;
         const int bad = nonpos ? __ffsll((long long)nonpos) : 0;
         if (g == 0) piv[jj * 16 + c] = dcol;
@@ -385,7 +336,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         for (int r = 0; r < 4; ++r) {
           const int i = g + 4 * r;
           const double rsi = bperm_d(rs, i);
-          Dj[i * TR_BLD + c] = (i >= c) ? w[r] * rsi : 0.0;       // inv(L_jj)
+          Dj[i * BLD + c] = (i >= c) ? w[r] * rsi : 0.0;       // inv(L_jj)
         }
         if (bad && lane == 0 && jj * 16 + bad <= n && flags[0] == 0) flags[0] = jj * 16 + bad;
       } else if (hidx >= 0 && jj > 0) {
@@ -393,13 +344,13 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         const int m = nst - jj;
         for (int t = 1 + hidx; t < m * (m + 1) / 2; t += nh) {
           int a, b;
-          tr_unblk(t, a, b);
+          blk_unrank(t, a, b);
           const int i = jj + a, k = jj + b;
-          tr_d4 acc = {0.0, 0.0, 0.0, 0.0};
-          tr_mma_nt(acc, S + tr_blk(i, jj - 1), S + tr_blk(k, jj - 1), lane);
-          double* dst = S + tr_blk(i, k);
+          d4_t acc = {0.0, 0.0, 0.0, 0.0};
+          mma16<true>(acc, S + blk_off(i, jj - 1), BLD, S + blk_off(k, jj - 1), BLD, lane);
+          double* dst = S + blk_off(i, k);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) dst[(g + 4 * r) * TR_BLD + c] -= acc[r];
+          for (int r = 0; r < 4; ++r) dst[(g + 4 * r) * BLD + c] -= acc[r];
         }
         // row block s = jj - 1 of the inverse, columns hidx and hidx + nh, kept in registers until row s of L is dead
         const int s_ = jj - 1;
@@ -407,31 +358,31 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         for (int q2 = 0; q2 < 2; ++q2) {
           const int j = hidx + q2 * nh;
           if (j >= s_) continue;
-          tr_d4 T = {0.0, 0.0, 0.0, 0.0};
-          tr_chain<false>(T, j, s_, S + tr_blk(s_, 0), [](int k) { return k * TR_BLK; }, TR_BLD, S, [j](int k) { return tr_blk(k, j); }, TR_BLD, lane);
-          tr_d4 acc = {0.0, 0.0, 0.0, 0.0};
-          const double* Ws = S + tr_blk(s_, s_);
+          d4_t T = {0.0, 0.0, 0.0, 0.0};
+          tr_chain<false>(T, j, s_, S + blk_off(s_, 0), [](int k) { return k * BLKSZ; }, BLD, S, [j](int k) { return blk_off(k, j); }, BLD, lane);
+          d4_t acc = {0.0, 0.0, 0.0, 0.0};
+          const double* Ws = S + blk_off(s_, s_);
 #pragma unroll
-          for (int kq = 0; kq < 4; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * TR_BLD + kq * 4 + g], T[kq], acc, 0, 0, 0);
+          for (int kq = 0; kq < 4; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * BLD + kq * 4 + g], T[kq], acc, 0, 0, 0);
           Xn[q2] = acc;
         }
       }
-      TR_BARRIER();
+      LDS_BARRIER();
       TR_PROF(2);
       if (hidx >= 0 && jj > 0) {
 #pragma unroll
         for (int q2 = 0; q2 < 2; ++q2) {
           const int j = hidx + q2 * nh;
-          if (j < jj - 1) tr_store(S + tr_blk(jj - 1, j), Xn[q2], g, c, -1.0);
+          if (j < jj - 1) tr_store(S + blk_off(jj - 1, j), Xn[q2], g, c, -1.0);
         }
       }
       // solve: L[i][jj] = S[i][jj] inv(L_jj)^T for the block rows below
       for (int i = jj + 1 + wave; i < nst; i += 8) {
-        tr_d4 acc = {0.0, 0.0, 0.0, 0.0};
-        tr_mma_nt(acc, S + tr_blk(i, jj), S + tr_blk(jj, jj), lane);
-        tr_store(S + tr_blk(i, jj), acc, g, c, 1.0);
+        d4_t acc = {0.0, 0.0, 0.0, 0.0};
+        mma16<true>(acc, S + blk_off(i, jj), BLD, S + blk_off(jj, jj), BLD, lane);
+        tr_store(S + blk_off(i, jj), acc, g, c, 1.0);
       }
-      TR_BARRIER();
+      LDS_BARRIER();
       TR_PROF(3);
     }
     if (flags[0] != 0) {       // (uniform: every thread reads the same word behind the barrier)
@@ -452,17 +403,17 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     // ---- the last row block of the inverse (s = nst - 1), one column per wave
     if (nst > 1) {
       const int s_ = nst - 1, j = wave;
-      tr_d4 X = {0.0, 0.0, 0.0, 0.0};
+      d4_t X = {0.0, 0.0, 0.0, 0.0};
       if (j < s_) {
-        tr_d4 T = {0.0, 0.0, 0.0, 0.0};
-        tr_chain<false>(T, j, s_, S + tr_blk(s_, 0), [](int k) { return k * TR_BLK; }, TR_BLD, S, [j](int k) { return tr_blk(k, j); }, TR_BLD, lane);
-        const double* Ws = S + tr_blk(s_, s_);
+        d4_t T = {0.0, 0.0, 0.0, 0.0};
+        tr_chain<false>(T, j, s_, S + blk_off(s_, 0), [](int k) { return k * BLKSZ; }, BLD, S, [j](int k) { return blk_off(k, j); }, BLD, lane);
+        const double* Ws = S + blk_off(s_, s_);
 #pragma unroll
-        for (int kq = 0; kq < 4; ++kq) X = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * TR_BLD + kq * 4 + g], T[kq], X, 0, 0, 0);
+        for (int kq = 0; kq < 4; ++kq) X = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * BLD + kq * 4 + g], T[kq], X, 0, 0, 0);
       }
-      TR_BARRIER();
-      if (j < s_) tr_store(S + tr_blk(s_, j), X, g, c, -1.0);
-      TR_BARRIER();
+      LDS_BARRIER();
+      if (j < s_) tr_store(S + blk_off(s_, j), X, g, c, -1.0);
+      LDS_BARRIER();
     }
     TR_PROF(5);
 
@@ -471,21 +422,21 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     {
       if (wave < nst) {
         const int bi = wave;
-        tr_d4 acc = {0.0, 0.0, 0.0, 0.0};
-        tr_chain<false>(acc, 0, bi + 1, S + tr_blk(bi, 0), [](int kb) { return kb * TR_BLK; }, TR_BLD, Ym, [](int kb) { return kb * 16 * TR_Y; },
+        d4_t acc = {0.0, 0.0, 0.0, 0.0};
+        tr_chain<false>(acc, 0, bi + 1, S + blk_off(bi, 0), [](int kb) { return kb * BLKSZ; }, BLD, Ym, [](int kb) { return kb * 16 * TR_Y; },
                         TR_Y, lane);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Gam[(bi * 16 + g + 4 * r) * TR_Y + c] = acc[r];
       }
-      TR_BARRIER();
+      LDS_BARRIER();
       if (7 - wave < nst) {
         const int bi = 7 - wave;
-        tr_d4 acc = {0.0, 0.0, 0.0, 0.0};
-        tr_chain<true>(acc, bi, nst, S, [bi](int kb) { return tr_blk(kb, bi); }, TR_BLD, Gam, [](int kb) { return kb * 16 * TR_Y; }, TR_Y, lane);
+        d4_t acc = {0.0, 0.0, 0.0, 0.0};
+        tr_chain<true>(acc, bi, nst, S, [bi](int kb) { return blk_off(kb, bi); }, BLD, Gam, [](int kb) { return kb * 16 * TR_Y; }, TR_Y, lane);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Am[(bi * 16 + g + 4 * r) * TR_Y + c] = acc[r];
       }
-      TR_BARRIER();
+      LDS_BARRIER();
     }
     TR_PROF(6);
 
@@ -505,12 +456,12 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       const int t = tr_deal(q_, wave);
       if (t >= nblk) continue;
       int bi, bj;
-      tr_unblk(t, bi, bj);
+    blk_unrank(t, bi, bj);
       double evs[4];      // (requested before the block's products: the loads fly under the MFMA chain; written by this very lane)
 #pragma unroll
       for (int r = 0; r < 4; ++r) evs[r] = M.kbuf[(t * 4 + r) * 64 + lane];
-      tr_d4 acc = {0.0, 0.0, 0.0, 0.0};
-      tr_chain<true>(acc, bi, nst, S, [bi](int kb) { return tr_blk(kb, bi); }, TR_BLD, S, [bj](int kb) { return tr_blk(kb, bj); }, TR_BLD, lane);
+      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+      tr_chain<true>(acc, bi, nst, S, [bi](int kb) { return blk_off(kb, bi); }, BLD, S, [bj](int kb) { return blk_off(kb, bj); }, BLD, lane);
       const int j = bj * 16 + c;
       double xj[DM];
 #pragma unroll
@@ -562,14 +513,14 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
 #pragma unroll
         for (int q = 0; q < NV; ++q) red[wave * TR_NRED + q] = vals[q];
       }
-      TR_BARRIER();
+      LDS_BARRIER();
       if (tid < NV) {
         double x = 0.0;
 #pragma unroll
         for (int wv_ = 0; wv_ < 8; ++wv_) x += red[wv_ * TR_NRED + tid];
         tot[tid] = x;
       }
-      TR_BARRIER();
+      LDS_BARRIER();
     }
     TR_PROF(8);
     // ---- P6: the loss of this step (before the update), the raw gradients through the links, Adam
@@ -639,7 +590,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         sc[1] = tr_link_val(M.l.dadd_link, pnew, M.l.dadd_c);
       }
     }
-    TR_BARRIER();
+    LDS_BARRIER();
     TR_PROF(9);
   }
   // ---- parameters and moments back to the caller's tensors (a failed step left them as they were when it began)
@@ -699,7 +650,7 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
   const size_t info_off = bc_off + ((size_t)2 * steps * sizeof(double) + 255) / 256 * 256;
   const size_t head = info_off + (size_t)2 * F * sizeof(int);
   const size_t k_off = (head + 255) / 256 * 256;
-  const size_t need = k_off + (size_t)F * TR_NBLK * 256 * sizeof(double);
+  const size_t need = k_off + (size_t)F * NBLK_LOWER * 256 * sizeof(double);
   if (need > h->train_tab_bytes) {
     FFGP_HIP(hipStreamSynchronize(h->stream));
     if (h->train_tab) hipFree(h->train_tab);
@@ -731,7 +682,7 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     m.clamp = q.clamp_min; m.rinv = (q.kparam != 0.0) ? 1.0 / q.kparam : 1.0; m.pi_const = q.pi_const; m.kfun = q.kfun;
     m.state = state_dev + (size_t)f * state_stride;
     m.trace = trace_dev + (size_t)f * trace_stride;
-    m.kbuf = reinterpret_cast<double*>(dev + k_off) + (size_t)f * TR_NBLK * 256;
+    m.kbuf = reinterpret_cast<double*>(dev + k_off) + (size_t)f * NBLK_LOWER * 256;
     m.want_grad = 1;
   }
   double* bc = reinterpret_cast<double*>(host + bc_off);
@@ -808,7 +759,7 @@ int ffgp_small_mfma_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const 
                                  TR_LDS_DOUBLES * (int)sizeof(double)));
     attr_set[h->device] = true;
   }
-  if (!h->small_kbuf) FFGP_HIP(hipMalloc(&h->small_kbuf, (size_t)TR_EVAL_BATCH * TR_NBLK * 256 * sizeof(double)));
+  if (!h->small_kbuf) FFGP_HIP(hipMalloc(&h->small_kbuf, (size_t)TR_EVAL_BATCH * NBLK_LOWER * 256 * sizeof(double)));
   TrainCommon cm;
   memset(&cm, 0, sizeof(cm));
   cm.steps = 1;
@@ -840,7 +791,7 @@ int ffgp_small_mfma_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const 
         m.g_w = gg->g_w_dev; m.g_amp = gg->g_amp_dev; m.g_dadd = gg->g_diag_add_dev; m.g_Y = gg->g_Y_dev; m.g_dvec = gg->g_diag_vec_dev;
       }
       m.want_grad = (m.g_w || m.g_amp || m.g_dadd || m.g_Y || m.g_dvec) ? 1 : 0;
-      m.kbuf = h->small_kbuf + (size_t)z * TR_NBLK * 256;
+      m.kbuf = h->small_kbuf + (size_t)z * NBLK_LOWER * 256;
       Dmax = std::max(Dmax, q.D);
     }
     if (Dmax <= 8)

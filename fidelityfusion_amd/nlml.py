@@ -418,7 +418,7 @@ CHAIN_BATCH_MAX_F = 256      # ffgp_nlml_fused_batch's limit on the members of o
 
 def _chain_batches(items, metas, tensors, rec, lo, hi):
     """members [lo, hi) of a shared-chain batch -> tensor [hi - lo].  include/ffgp.h leaves the fallback to the caller: the library
-    refuses the batch (FFGP_ERR_ARG) in states it otherwise allows -- option `naive` = 1, `diag_v2` = 0, more than 256 members -- and
+    refuses the batch (FFGP_ERR_ARG) in states it otherwise allows -- option `naive` = 1, more than 256 members -- and
     reports FFGP_ERR_ALLOC when the F-fold workspace does not fit.  Here: chunks of at most 256 members; a chunk that does not fit is
     halved until it does; a chunk the library refuses (or a single leftover member) goes through the individual calls, which work in
     all of those states and need one block of memory.  Values and gradients are the individual calls' either way."""

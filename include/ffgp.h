@@ -223,9 +223,6 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
                         transpose); results agree with the full form to rounding.  n = 8192: update 21.8 -> 12.3 ms, A * Y and its
                         sums 16.1 -> 20.6 ms, eigh 234.3 -> 229.7 ms; below ~6000 rows the full form is as fast.  "sb_sym_wg"
                         (default 2048): workgroups the lower-triangle A * Y launch aims for,
-            "diag_v2" (default 4: the round-4 diagonal-block kernel ffgp_potrf_diag128_v3 -- owner-computes helper waves, no
-                        barrier; 0 = the barrier version (ffgp_nlml_fused_batch then returns FFGP_ERR_ARG: only the default kernel
-                        is batched).  Any other value is refused),
             "chase_pack" (placement of the bulge chase's 256 working wavefronts: every pack-th workgroup works.  Default 1 = one per
                         compute unit over the whole chip (N = 8192: 64.6 ms; 2 = on every other XCD: 69.4, 4: 92, 8: 166); beside
                         other blocks' kernels 1 and 2 measure the same (config 5's eight blocks: 1.43-1.47 s per step either way),
@@ -253,10 +250,6 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
                         behaviour, not a contract: every XCD-local launch is followed by a chip-wide launch that chases whatever sweeps
                         the first did not hand out -- none on a full MI355X; all of them when no wave landed on the chosen XCD, as in a
                         partition mode or on a CU-masked stream),
-            "diag_v4" (default 1: the factorisation's 128 x 128 diagonal blocks on ffgp_potrf_diag128_v4 -- two workgroup barriers per
-                        16-column stage, the inverse's rows formed in the shadow of the next block's pivots: 25.2 us per block against
-                        28.6 for the flag-driven pipeline of round 4 (v3, = 0), forward N = 1024 / 4096 / 8192 -6.9 / -5.7 / -2.0 %;
-                        the factors differ in the last bits (the updates reach a block in another order)),
             "ho_gate" / "ho_timeout_ms" (default 1 / 2000: the look-ahead's cross-stream waits are the library's own one-wave gate kernel,
                         which gives up after ho_timeout_ms without its value -- the call then returns FFGP_ERR_HANDOFF instead of hanging the
                         GPU, e.g. under a tool that runs this process's kernels one at a time and is not recognised at create time;
@@ -274,7 +267,10 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
    Retired keys, refused with FFGP_ERR_ARG like any unknown key: "raw_graph_max_n", "diag_dbg", "la_split", "nb_big", "nb_big_until",
    "sb_lookahead", "sb_av_gemm", "sb_qr4", "q2_wave4", "eig_overlap", "band_log2", "polite_pad_kb", "pass_split_min", "tail_mask_m",
    "tail_mask_cus", "syrk_h64", "syrk_direct" (switches of experiments that were measured and lost, docs/experiments.md; the library
-   runs with the values they had by default), and the values 1 and 3 of "diag_v2".    */
+   runs with the values they had by default), "diag_v2" and "diag_v4" (they chose among the diagonal-block kernels: the factorisation
+   runs on ffgp_potrf_diag128_v4 -- two workgroup barriers per 16-column stage, 25.2 us per 128 x 128 block against 28.6 for round 4's
+   flag-driven pipeline v3, forward N = 1024 / 4096 / 8192 -6.9 / -5.7 / -2.0 % -- and a factor produced elsewhere is inverted by
+   ffgp_potrf_diag128; commit afe272f is the last tree with v3 and the barrier kernel's factor path).    */
 int ffgp_set_option(ffgp_handle* h, const char* key, double value);
 /* Create the handle's side streams now and use each once, so that they bind their hardware queues before streams the process creates
    later (ROCm binds at first use; a late stream shares a queue with an earlier one and runs in line with it).  For the main handle of
@@ -501,7 +497,7 @@ int ffgp_nlml_fused_small_batch(ffgp_handle* h, int F, const ffgp_problem* p, co
    per-member sizes, and a member leaves the chain's launches when its columns are used up: the chain runs max(n) / 128 steps.
    p, g (may be NULL), links (NULL = effective parameters): arrays of F; nll_dev[f] receives block f's value; status[f] (host, may
    be NULL) its own factorisation status (0, or the 1-based index of the first non-positive pivot of THAT block).  Returns the first
-   non-zero status; FFGP_ERR_ARG when the blocks do not meet the conditions -- also with options "naive" = 1 or "diag_v2" = 0, F > 256,
+   non-zero status; FFGP_ERR_ARG when the blocks do not meet the conditions -- also with option "naive" = 1, F > 256,
    a ragged member above 12288 rows -- and FFGP_ERR_ALLOC when the F-fold workspace does not fit: evaluate the blocks one by one
    (or in smaller batches) then, as fidelityfusion_amd/nlml.py::_chain_batches does.  Synchronous.                               */
 int ffgp_nlml_fused_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, double* nll_dev,

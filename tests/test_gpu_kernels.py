@@ -261,53 +261,44 @@ def test_potrf_matches_lapack(ff, tile, n):
 
 
 # switches of experiments that were measured and lost (docs/experiments.md), each with the value the library runs with (one the old
-# option accepted): ffgp_set_option refuses them like any unknown key
+# option accepted), and the two options that chose a retired diagonal-block kernel, with every value they accepted: ffgp_set_option
+# refuses them like any unknown key
 RETIRED_OPTIONS = {"raw_graph_max_n": 0, "diag_dbg": 0, "la_split": 1, "nb_big": 0, "nb_big_until": 0, "sb_lookahead": 0, "sb_av_gemm": 0,
                    "sb_qr4": 0, "q2_wave4": 1, "eig_overlap": 0, "band_log2": 3, "polite_pad_kb": 40, "pass_split_min": 0, "tail_mask_m": 0,
-                   "tail_mask_cus": 8, "syrk_h64": 0, "syrk_direct": 0}
+                   "tail_mask_cus": 8, "syrk_h64": 0, "syrk_direct": 0, "diag_v2": (0, 1, 3, 4), "diag_v4": (0, 1)}
 
 
 @pytest.mark.noisy
-@pytest.mark.parametrize("mode", [0, 4, 40])
-def test_potrf_diag_kernel_variants(ff, mode):
-    """the diagonal-block kernel in its forms -- 0: barrier version, 4: the default, round 6's ffgp_potrf_diag128_v4 (two barriers per
-    16-column stage, the inverse's rows in the shadow of the next block's pivots), 40: round 4's flag-driven pipeline v3 (option
-    diag_v4 = 0) -- against LAPACK at sizes with full, partial and single blocks; the factor and the cached block inverses must be
-    bit-stable over repeated calls while a background load shares the GPU (LDS flag protocols, no barrier after the role hand-out).
-    The retired option keys and diag_v2 = 1 / 3 (the round-3 pipelines) are refused."""
+def test_potrf_diag_kernel_variants(ff):
+    """the diagonal-block kernel, ffgp_potrf_diag128_v4 (two barriers per 16-column stage, the inverse's rows in the shadow of the next
+    block's pivots), against LAPACK at sizes with full, partial and single blocks; the factor and the cached block inverses must be
+    bit-stable over repeated calls while a background load shares the GPU.  The retired option keys are refused."""
     import ctypes as C
     from fidelityfusion_amd import _lib
     h = _lib.handle(0)
-    for key, val in RETIRED_OPTIONS.items():
-        assert _lib.lib.ffgp_set_option(h, key.encode(), C.c_double(val)) == _lib.FFGP_ERR_ARG, key
-    for v in (1, 3):
-        assert _lib.lib.ffgp_set_option(h, b"diag_v2", C.c_double(v)) == _lib.FFGP_ERR_ARG, v
-    assert _lib.lib.ffgp_set_option(h, b"diag_v2", C.c_double(4 if mode == 40 else mode)) == 0
-    assert _lib.lib.ffgp_set_option(h, b"diag_v4", C.c_double(0 if mode == 40 else 1)) == 0
-    try:
-        for n in (128, 100, 16, 129, 640, 1000, 1537, 4300):      # (1537, 4300: with the look-ahead's side stream and its hand-offs)
-            rng = np.random.default_rng(10 * n + mode)
-            S = spd(n, rng)
-            ref = np.linalg.cholesky(S)
-            first = None
-            for rep in range(3):
-                rc, out, _, _ = potrf(ff, S)
-                assert rc == 0
-                got = np.tril(out[:n, :n])
-                assert relerr(got, ref) < 1e-11, (mode, n)
-                assert (out[:n, :n][np.triu_indices(n, 1)] == 777.0).all(), "strictly-upper triangle was written"
-                if first is None:
-                    first = got
-                else:
-                    assert (got == first).all(), "factor changed between identical calls (mode %d, n %d)" % (mode, n)
-        # a non-positive pivot inside a diagonal block is reported with its 1-based index by every variant
-        S = spd(300, np.random.default_rng(7))
-        S[200, 200] = -5.0
-        rc, _, _, _ = potrf(ff, S)
-        assert rc == 201, (mode, rc)
-    finally:
-        assert _lib.lib.ffgp_set_option(h, b"diag_v2", C.c_double(4)) == 0
-        assert _lib.lib.ffgp_set_option(h, b"diag_v4", C.c_double(1)) == 0
+    for key, vals in RETIRED_OPTIONS.items():
+        for val in np.atleast_1d(vals):
+            assert _lib.lib.ffgp_set_option(h, key.encode(), C.c_double(val)) == _lib.FFGP_ERR_ARG, (key, val)
+    for n in (128, 100, 16, 129, 640, 1000, 1537, 4300):      # (1537, 4300: with the look-ahead's side stream and its hand-offs)
+        rng = np.random.default_rng(10 * n + 4)
+        S = spd(n, rng)
+        ref = np.linalg.cholesky(S)
+        first = None
+        for rep in range(3):
+            rc, out, _, _ = potrf(ff, S)
+            assert rc == 0
+            got = np.tril(out[:n, :n])
+            assert relerr(got, ref) < 1e-11, n
+            assert (out[:n, :n][np.triu_indices(n, 1)] == 777.0).all(), "strictly-upper triangle was written"
+            if first is None:
+                first = got
+            else:
+                assert (got == first).all(), "factor changed between identical calls (n %d)" % n
+    # a non-positive pivot inside a diagonal block is reported with its 1-based index
+    S = spd(300, np.random.default_rng(7))
+    S[200, 200] = -5.0
+    rc, _, _, _ = potrf(ff, S)
+    assert rc == 201, rc
 
 
 @pytest.mark.parametrize("n", [4000, 6200])

@@ -980,9 +980,9 @@ def test_ragged_blocks_share_one_chain(shapes):
 
 
 def test_shared_chain_falls_back_when_the_library_refuses_the_batch():
-    """include/ffgp.h leaves the fallback to the caller: with option naive = 1 or diag_v2 = 0 ffgp_nlml_fused_batch returns
-    FFGP_ERR_ARG, and more than 256 members do not fit one call -- negative_log_likelihood_many must still return the individual
-    calls' values (and gradients) instead of raising"""
+    """include/ffgp.h leaves the fallback to the caller: with option naive = 1, or with members the ragged chain does not take under the
+    handle's options, ffgp_nlml_fused_batch returns FFGP_ERR_ARG, and more than 256 members do not fit one call --
+    negative_log_likelihood_many must still return the individual calls' values (and gradients) instead of raising"""
     from fidelityfusion_amd import _lib
     from fidelityfusion_amd import kernel
     from fidelityfusion_amd import nlml as NL
@@ -992,7 +992,7 @@ def test_shared_chain_falls_back_when_the_library_refuses_the_batch():
     models = [cigp(kernel.ARDKernel(3), 0.6 + 0.1 * f).double().to(DEV) for f in range(F_)]
     xs = [T(rng.uniform(0, 1, (n, 3))) for _ in range(F_)]
     ys = [T(rng.standard_normal((n, 2)), grad=True) for _ in range(F_)]
-    for key, val, back in (("naive", 1, 0), ("diag_v2", 0, 4)):
+    for key, val, back in (("naive", 1, 0),):
         _lib.set_option(key, val, 0)
         try:
             ref = torch.stack([m.negative_log_likelihood(x, y).reshape(()) for m, x, y in zip(models, xs, ys)])
@@ -1002,6 +1002,30 @@ def test_shared_chain_falls_back_when_the_library_refuses_the_batch():
             assert all(y.grad is not None and torch.isfinite(y.grad).all() for y in ys)
         finally:
             _lib.set_option(key, back, 0)
+    # a refusal on the library's own factorisation path: members of different sizes above 512 rows with la_min_n = 0 and
+    # la_carry_n = 512 would need the look-ahead's carry form only in some iterations, which the ragged chain does not run
+    rx = [T(rng.uniform(0, 1, (m, 3))) for m in (600, 640, 700)]
+    ry = [T(rng.standard_normal((m, 2)), grad=True) for m in (600, 640, 700)]
+    real, seen = _lib.lib.ffgp_nlml_fused_batch, []
+
+    def spy(*args):
+        rc = real(*args)
+        seen.append(rc)
+        return rc
+    _lib.lib.ffgp_nlml_fused_batch = spy
+    _lib.set_option("la_min_n", 0, 0)
+    _lib.set_option("la_carry_n", 512, 0)
+    try:
+        ref = torch.stack([m.negative_log_likelihood(x, y).reshape(()) for m, x, y in zip(models, rx, ry)])
+        vals = negative_log_likelihood_many(models, rx, ry)
+        assert seen and all(rc == _lib.FFGP_ERR_ARG for rc in seen), seen
+        assert torch.equal(vals.detach(), ref.detach())
+        vals.sum().backward()
+        assert all(y.grad is not None and torch.isfinite(y.grad).all() for y in ry)
+    finally:
+        _lib.lib.ffgp_nlml_fused_batch = real
+        _lib.set_option("la_min_n", 1024, 0)
+        _lib.set_option("la_carry_n", 12288, 0)
     # chunking: a limit of two members per chain call -> chunks of two plus a single leftover, same values
     old = NL.CHAIN_BATCH_MAX_F
     NL.CHAIN_BATCH_MAX_F = 2

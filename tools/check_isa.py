@@ -79,13 +79,19 @@ def _check_chase_publish_one(asm, name):
 
 
 def check_diag_barriers(asm=None):
-    """In `ffgp_potrf_diag128_v3` the role hand-out publishes flag words with inline-asm LDS stores and then meets a workgroup barrier:
-    the compiler's wait-count pass does not see inside inline asm, so every `s_barrier` must be preceded by an explicit
-    `s_waitcnt lgkmcnt(0)` (round 4: without it a wave passed the barrier with its store in flight, the waves disagreed about their
-    roles under load and a hand-off timed out)."""
-    body = function_body(asm or device_asm("potrf.hip"), "ffgp_potrf_diag128_v3")
+    """`ffgp_potrf_diag128_v4` meets its workgroup barriers through LDS_BARRIER (diag_block.h): an explicit `s_waitcnt lgkmcnt(0)` and
+    `s_barrier` in one inline-asm statement, which publishes the waves' LDS stores (the SIMD words of the role hand-out, the blocks of
+    every stage) without draining the global ones.  Every `s_barrier` must follow an `s_waitcnt lgkmcnt(0)` with no LDS instruction in
+    between (round 4: a wave that passed the barrier with its store in flight made the waves disagree about their roles).  Both
+    instantiations; three barriers each: the role hand-out and the two of a stage."""
+    asm = asm or device_asm("potrf.hip")
+    return [_check_diag_barriers_one(asm, "ffgp_potrf_diag128_v4ILb0E"), _check_diag_barriers_one(asm, "ffgp_potrf_diag128_v4ILb1E")]
+
+
+def _check_diag_barriers_one(asm, name):
+    body = function_body(asm, name)
     bars = [i for i, l in enumerate(body) if l.strip() == "s_barrier"]
-    assert len(bars) == 2, "expected the two barriers of the role hand-out, found %d" % len(bars)
+    assert len(bars) == 3, "expected the barriers of the role hand-out and of the stage loop (3), found %d" % len(bars)
     for b in bars:
         prev = [l.strip() for l in body[max(0, b - 16):b] if l.strip() and not l.strip().startswith(";")]
         drains = [j for j, l in enumerate(prev) if re.match(r"s_waitcnt .*lgkmcnt\(0\)", l)]
@@ -96,5 +102,5 @@ def check_diag_barriers(asm=None):
 
 
 if __name__ == "__main__":
-    print("ffgp_potrf_diag128_v3: barriers behind an LDS drain:", check_diag_barriers())
+    print("ffgp_potrf_diag128_v4: barriers behind an LDS drain:", check_diag_barriers())
     print("sb2st_chase: counter stores behind an explicit vmcnt(0):", check_chase_publish())
