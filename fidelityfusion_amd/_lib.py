@@ -74,6 +74,12 @@ class Adam(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
 
 
+class Residual(C.Structure):
+    """ffgp_residual: a residual member of ffgp_train_residual_raw (rho_dev NULL = a plain model)"""
+    _fields_ = [("rho_dev", _dp), ("y_low_dev", _dp), ("y_high_dev", _dp), ("v_low_dev", _dp), ("v_low_stride", C.c_long),
+                ("v_high_dev", _dp), ("v_high_stride", C.c_long), ("rho_last_dev", _dp)]
+
+
 LINK_ID, LINK_INV_ABS_EPS, LINK_EXP_NEG, LINK_INV, LINK_ABS, LINK_EXP_SQ, LINK_SQUARE = range(7)
 
 
@@ -139,6 +145,8 @@ EXPORTS = {
     "ffgp_nlml_fused_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), _dp, C.POINTER(Grads), C.POINTER(C.c_int)]),
     "ffgp_train_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.c_int, C.POINTER(Adam), _dp, C.c_long, C.c_long,
                                  _dp, C.c_long]),
+    "ffgp_train_residual_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(Residual), C.c_int,
+                                          C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),

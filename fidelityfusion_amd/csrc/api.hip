@@ -1231,13 +1231,16 @@ __global__ void ffgp_adam_kernel(int F, ffgp_train_slot sl, const double* __rest
     }
   }
   const int nw = sl.nw[f];
+  const int npar = nw + 2 + (sl.rho[f] ? 1 : 0);      // (a residual member's rho is the last parameter; its gradient is in gbuf)
   if (threadIdx.x == 0) trace[(size_t)f * trace_stride + step] = bad ? __builtin_nan("") : loss[f];
   if (bad) return;
   const int i = threadIdx.x;
-  if (i >= nw + 2) return;
-  double* par = (i < nw) ? sl.w[f] + i : (i == nw ? sl.amp[f] : sl.dadd[f]);
+  if (i >= npar) return;
+  double* par = (i < nw) ? sl.w[f] + i : (i == nw ? sl.amp[f] : (i == nw + 1 ? sl.dadd[f] : sl.rho[f]));
   double g;
-  if (geff) {
+  if (i == nw + 2) {
+    g = gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + i];
+  } else if (geff) {
     // (one model, blocked path: the gradients arrive with respect to the EFFECTIVE parameters [w (D) | amp | diag_add]; the links'
     //  chain rule -- ffgp_link_bwd's arithmetic -- is applied here instead of in a launch of its own)
     if (i < nw) {
@@ -1257,7 +1260,7 @@ __global__ void ffgp_adam_kernel(int F, ffgp_train_slot sl, const double* __rest
     g = gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + i];
   }
   double* m = state + (size_t)f * state_stride + i;
-  double* v = m + (nw + 2);
+  double* v = m + npar;
   const double m1 = m[0] + (g - m[0]) * (1.0 - b1);        // exp_avg.lerp_(grad, 1 - beta1)
   const double v1 = v[0] * b2 + (1.0 - b2) * g * g;        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
   m[0] = m1;
@@ -1266,27 +1269,84 @@ __global__ void ffgp_adam_kernel(int F, ffgp_train_slot sl, const double* __rest
   par[0] = par[0] + (-(lr / bc1)) * (m1 / denom);          // param.addcdiv_(exp_avg, denom, value = -step_size)
 }
 
-int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
-                   long state_stride, long step0, double* trace_dev, long trace_stride) {
+// residual members of the launch-per-stage loop (ffgp_train_residual_raw): per step their targets and diagonal extra are formed from rho
+// before the likelihood call, and dloss/drho is reduced from its dloss/dY and dloss/ddiag_vec after it
+struct ffgp_resid_slot {
+  const double* rho[FFGP_TRAIN_MAXF];
+  const double* yl[FFGP_TRAIN_MAXF];
+  const double* yh[FFGP_TRAIN_MAXF];
+  const double* vl[FFGP_TRAIN_MAXF];
+  const double* vh[FFGP_TRAIN_MAXF];
+  long vls[FFGP_TRAIN_MAXF], vhs[FFGP_TRAIN_MAXF];
+  double* r[FFGP_TRAIN_MAXF];            // [n, d] targets
+  double* dv[FFGP_TRAIN_MAXF];           // [n] |s|
+  const double* gY[FFGP_TRAIN_MAXF];     // [n, d] dloss/dr
+  const double* gdv[FFGP_TRAIN_MAXF];    // [n] dloss/ddvec
+  double* rho_last[FFGP_TRAIN_MAXF];
+  long nd[FFGP_TRAIN_MAXF];
+  int n[FFGP_TRAIN_MAXF], nw[FFGP_TRAIN_MAXF];
+};
+// r = y_high - rho y_low, dvec = |v_high - rho v_low| (a product, then a difference: torch's rounding); rho_last = rho
+__global__ void ffgp_resid_form(ffgp_resid_slot rs) {
+  const int f = blockIdx.y;
+  if (!rs.rho[f]) return;
+  const double rho = rs.rho[f][0];
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t < rs.nd[f]) rs.r[f][t] = __dsub_rn(rs.yh[f][t], __dmul_rn(rho, rs.yl[f][t]));
+  if (rs.vl[f] && t < rs.n[f]) rs.dv[f][t] = fabs(__dsub_rn(rs.vh[f][t * rs.vhs[f]], __dmul_rn(rho, rs.vl[f][t * rs.vls[f]])));
+  if (t == 0 && rs.rho_last[f]) rs.rho_last[f][0] = rho;
+}
+// gbuf slot nw + 2 <- dloss/drho = -sum gY .* y_low - sum_i gdv_i sgn(s_i) v_low,ii (one workgroup per member, fixed order)
+__global__ void ffgp_resid_grad(ffgp_resid_slot rs, double* __restrict__ gbuf) {
+  const int f = blockIdx.x;
+  if (!rs.rho[f]) return;
+  __shared__ double part[256];
+  const double rho = rs.rho[f][0];
+  double x = 0.0;
+  for (long t = threadIdx.x; t < rs.nd[f]; t += 256) x = __builtin_fma(rs.gY[f][t], rs.yl[f][t], x);
+  if (rs.vl[f]) {
+    for (int i = threadIdx.x; i < rs.n[f]; i += 256) {
+      const double vl = rs.vl[f][(long)i * rs.vls[f]];
+      const double s = __dsub_rn(rs.vh[f][(long)i * rs.vhs[f]], __dmul_rn(rho, vl));
+      x = __builtin_fma(rs.gdv[f][i], (s > 0.0) ? vl : ((s < 0.0) ? -vl : 0.0), x);      // (sgn(0) = 0: torch's abs backward)
+    }
+  }
+  part[threadIdx.x] = x;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + rs.nw[f] + 2] = -part[0];
+}
+
+static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, int steps,
+                      const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
   if (!h || !p || !l || !opt || !state_dev || !trace_dev || F <= 0 || F > FFGP_TRAIN_MAXF || steps <= 0 || step0 < 0 || trace_stride < steps)
     return FFGP_ERR_ARG;
-  FFGP_HIP(hipSetDevice(h->device));
   ffgp_train_slot sl;
-  bool all_small = true;
+  bool all_small = true, any_res = false;
   for (int f = 0; f < F; ++f) {
     const ffgp_problem& q = p[f];
     if (!q.w_dev || !q.amp_dev || !q.diag_add_dev || q.cov_dev || q.pair || q.tree || q.D <= 0 || q.D > 128 || q.n <= 0 || q.d <= 0) return FFGP_ERR_ARG;
+    const bool res = r && r[f].rho_dev;
+    if (res && (!r[f].y_low_dev || !r[f].y_high_dev || !q.X_dev || (!r[f].v_low_dev) != (!r[f].v_high_dev) ||
+                (r[f].v_low_dev && (r[f].v_low_stride < 0 || r[f].v_high_stride < 0))))
+      return FFGP_ERR_ARG;
     const int nw = l[f].w_broadcast ? 1 : q.D;
-    if (state_stride < 2 * (nw + 2)) return FFGP_ERR_ARG;
+    if (state_stride < 2 * (nw + 2 + (res ? 1 : 0))) return FFGP_ERR_ARG;
     sl.w[f] = const_cast<double*>(q.w_dev);
     sl.amp[f] = const_cast<double*>(q.amp_dev);
     sl.dadd[f] = const_cast<double*>(q.diag_add_dev);
+    sl.rho[f] = res ? r[f].rho_dev : nullptr;
     sl.nw[f] = nw;
+    any_res = any_res || res;
   }
+  FFGP_HIP(hipSetDevice(h->device));
   {   // every model small enough for one workgroup: the whole loop is ONE launch (train.hip)
     bool persist = true;
-    for (int f = 0; f < F && persist; ++f) persist = ffgp_train_persist_ok(h, p + f, l + f);
-    if (persist) return ffgp_train_persist(h, F, p, l, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
+    for (int f = 0; f < F && persist; ++f) persist = ffgp_train_persist_ok(h, p + f, l + f, r ? r + f : nullptr);
+    if (persist) return ffgp_train_persist(h, F, p, l, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, r);
   }
   if (!h->train_g) {
     FFGP_HIP(hipMalloc(&h->train_g, (size_t)FFGP_TRAIN_MAXF * (FFGP_TRAIN_GSTRIDE + 1) * sizeof(double)));
@@ -1295,21 +1355,58 @@ int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_link
   double* loss = h->train_g + (size_t)FFGP_TRAIN_MAXF * FFGP_TRAIN_GSTRIDE;
   std::vector<ffgp_grads> g(F);
   std::vector<ffgp_links> lk(l, l + F);
+  std::vector<ffgp_problem> pq(p, p + F);      // (residual members: targets and diagonal extra in the call's own buffers)
+  ffgp_resid_slot rs;
+  memset(&rs, 0, sizeof(rs));
+  double* rbuf = nullptr;
+  long rmax = 0;
+  if (any_res) {      // per residual member [r (n d) | dvec (n) | dloss/dr (n d) | dloss/ddvec (n)], freed when the call returns
+    size_t tot = 0;
+    for (int f = 0; f < F; ++f)
+      if (sl.rho[f]) tot += 2 * ((size_t)p[f].n * p[f].d + p[f].n);
+    FFGP_HIP(hipMalloc(&rbuf, tot * sizeof(double)));
+    size_t off = 0;
+    for (int f = 0; f < F; ++f) {
+      if (!sl.rho[f]) continue;
+      const long n = p[f].n, nd = n * p[f].d;
+      rs.rho[f] = sl.rho[f];
+      rs.yl[f] = r[f].y_low_dev; rs.yh[f] = r[f].y_high_dev;
+      rs.vl[f] = r[f].v_low_dev; rs.vh[f] = r[f].v_high_dev; rs.vls[f] = r[f].v_low_stride; rs.vhs[f] = r[f].v_high_stride;
+      rs.r[f] = rbuf + off; rs.dv[f] = rs.r[f] + nd;
+      rs.gY[f] = rs.dv[f] + n; rs.gdv[f] = rs.gY[f] + nd;
+      rs.rho_last[f] = r[f].rho_last_dev;
+      rs.nd[f] = nd; rs.n[f] = (int)n; rs.nw[f] = sl.nw[f];
+      off += 2 * (nd + n);
+      rmax = std::max(rmax, std::max(nd, n));
+      pq[f].Y_dev = rs.r[f];
+      pq[f].diag_vec_dev = rs.vl[f] ? rs.dv[f] : nullptr;
+      pq[f].diag_stride = 1;
+    }
+  }
   for (int f = 0; f < F; ++f) {
     memset(&g[f], 0, sizeof(ffgp_grads));
     g[f].g_w_dev = gbuf + (size_t)f * FFGP_TRAIN_GSTRIDE;
     g[f].g_amp_dev = g[f].g_w_dev + sl.nw[f];
     g[f].g_diag_add_dev = g[f].g_amp_dev + 1;
-    all_small = all_small && ffgp_small_batch_ok(p + f, &g[f]);
+    if (sl.rho[f]) {
+      g[f].g_Y_dev = const_cast<double*>(rs.gY[f]);
+      if (rs.vl[f]) g[f].g_diag_vec_dev = const_cast<double*>(rs.gdv[f]);
+    }
+    all_small = all_small && ffgp_small_batch_ok(&pq[f], &g[f]);
   }
+  p = pq.data();
   // the sticky status word starts clean: a failure of an EARLIER call on this handle is that call's to report
-  FFGP_CHECK(ffgp_zero_async(h, h->d_info, 2 * sizeof(int)));
+  if (const int zrc = ffgp_zero_async(h, h->d_info, 2 * sizeof(int))) {
+    if (rbuf) hipFree(rbuf);
+    return zrc;
+  }
   // (the one-kernel paths -- n <= 40, or option small_finish -- apply the links inside their kernel and write raw gradients)
   const bool one_kernel = ffgp_small_ok(h, p, &g[0]) || ffgp_small2_ok(h, p, &g[0]);
   h->defer_info_copy = 1;      // (the per-call read-back of the status word: once, after the loop)
   h->fold_info = (F == 1) ? 1 : 0;   // one model: the Adam kernel clears / accumulates the status words (see ffgp_adam_kernel)
   int lrc = FFGP_OK;
   for (int k = 0; k < steps && lrc == FFGP_OK; ++k) {
+    if (any_res) hipLaunchKernelGGL(ffgp_resid_form, dim3((unsigned)((rmax + 255) / 256), F), dim3(256), 0, h->stream, rs);
     if (all_small && F > 1) {
       if ((lrc = ffgp_zero_async(h, h->d_info, sizeof(int))) != FFGP_OK) break;
       if ((lrc = ffgp_small_batch_enqueue(h, F, p, lk.data(), loss, g.data())) != FFGP_OK) break;
@@ -1318,6 +1415,7 @@ int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_link
       for (int f = 0; f < F && lrc == FFGP_OK; ++f) lrc = nlml_fused_raw_enqueue(h, p + f, &lk[f], loss + f, &g[f]);
       if (lrc != FFGP_OK) break;
     }
+    if (any_res) hipLaunchKernelGGL(ffgp_resid_grad, dim3(F), dim3(256), 0, h->stream, rs, gbuf);
     const double t = (double)(step0 + k + 1);
     const double bc1 = 1.0 - std::pow(opt->beta1, t), bc2 = 1.0 - std::pow(opt->beta2, t);
     hipLaunchKernelGGL(ffgp_adam_kernel, dim3(F), dim3(192), 0, h->stream, F, sl, gbuf, state_dev, state_stride, opt->lr, opt->beta1,
@@ -1329,12 +1427,30 @@ int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_link
   h->fold_info = 0;
   if (lrc != FFGP_OK) {
     hipStreamSynchronize(h->stream);
+    if (rbuf) hipFree(rbuf);
     return lrc;
   }
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
+  if (hipGetLastError() != hipSuccess) {
+    hipStreamSynchronize(h->stream);
+    if (rbuf) hipFree(rbuf);
+    return FFGP_ERR_HIP;
+  }
   FFGP_HIP(hipMemcpyAsync(h->h_info, h->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   ffgp_invalidate(h);
-  return ffgp_wait(h);
+  const int rc = ffgp_wait(h);
+  if (rbuf) hipFree(rbuf);
+  return rc;
+}
+
+int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
+                   long state_stride, long step0, double* trace_dev, long trace_stride) {
+  return train_impl(h, F, p, l, nullptr, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
+}
+
+int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, int steps,
+                            const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+  if (!r) return FFGP_ERR_ARG;
+  return train_impl(h, F, p, l, r, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
 }
 
 // copies a captured graph's staged outputs (value, then an optional gradient block) into the caller's buffers (the forward graph

@@ -42,6 +42,9 @@ int main() {
     int st[2] = {0, 0};
     EXPECT(ffgp_nlml_fused_batch(nullptr, 2, &p, &lk, &x, nullptr, st) < 0);
     EXPECT(ffgp_train_raw(nullptr, 1, &p, &lk, 3, &ad, &x, 8, 0, &x, 3) < 0);
+    ffgp_residual rs;
+    std::memset(&rs, 0, sizeof rs);
+    EXPECT(ffgp_train_residual_raw(nullptr, 1, &p, &lk, &rs, 3, &ad, &x, 8, 0, &x, 3) < 0);
     ffgp_kdesc kd[2];
     ffgp_kdesc_grads kg[2];
     std::memset(kd, 0, sizeof kd);

@@ -339,6 +339,7 @@ struct ffgp_train_slot {
   double* w[FFGP_TRAIN_MAXF];
   double* amp[FFGP_TRAIN_MAXF];
   double* dadd[FFGP_TRAIN_MAXF];
+  double* rho[FFGP_TRAIN_MAXF];        // residual members (ffgp_train_residual_raw): raw rho, the (nw + 3)-th parameter; else null
   int nw[FFGP_TRAIN_MAXF];
 };
 
@@ -372,11 +373,11 @@ int ffgp_small_enqueue(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* 
 bool ffgp_small2_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_grads* g);
 bool ffgp_small_batch_ok(const ffgp_problem* p, const ffgp_grads* g);
 // train.hip: K Adam steps of F small models in ONE launch (one persistent workgroup per model)
-bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l);
+bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r = nullptr);
 bool ffgp_small_mfma_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_grads* g);      // one likelihood (+ gradients), n <= 128: same kernel, no Adam
 int ffgp_small_mfma_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g, int info_max);
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
-                       long state_stride, long step0, double* trace_dev, long trace_stride);
+                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r = nullptr);
 int ffgp_small_batch_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g);
 // ---- workspace
 int ffgp_ensure_ws(ffgp_handle* h, size_t bytes);

@@ -20,6 +20,11 @@
 // they were when the step began); the other models of the launch train on.
 // EVALUATE mode (tr_body<DM, false>, ffgp_small_mfma_kernel): the same pass once, without Adam -- value, raw-parameter gradients, dL/dY and
 // diag G written out -- for ffgp_nlml_fused_small_batch and ffgp_nlml_fused_raw at n <= 128.
+// RESIDUAL members (tr_body<DM, true, true>, ffgp_train_resid_kernel; train_AR's fidelities above 0, AR_autoRegression.py:123-137):
+// the targets are r = y_high - rho y_low and the diagonal extra |v_high,ii - rho v_low,ii|, re-formed at every step from a learnable rho
+// that lives in LDS beside the other raw parameters; dloss/drho = -sum A .* y_low - sum_i G_ii sgn(s_i) v_low,ii is one more total of
+// the step's reduction and rho is a fourth Adam parameter.  y_low / y_high are read from global memory (no room for two more [128][16]
+// images), the two diagonals sit in LDS.  Plain members may share the launch: the residual code is skipped for them.
 // Covers: n <= 128, D <= 16, d <= 16, one radial-profile kernel, V1 likelihood, diag_add and diag_vec (no matrix / all-entries /
 // mean(K) extras, no learnable profile parameter): what cigp_v10 produces.  Everything else keeps the paths it had.
 #include "ffgp_internal.h"
@@ -47,6 +52,14 @@ struct TrainModel {
   int want_grad;
   double* kbuf;                          // [36][4][64] this model's kernel values K / amp, written by the assembly and read back by the
                                          // gradient pass of the same step (same lane, same slot: the exp is evaluated once per entry and step)
+};
+// a residual member's link (ffgp_residual): rho == nullptr is a plain model
+struct TrainResid {
+  double* rho;                           // [1] RAW rho, updated in place when the kernel ends
+  const double* yl; const double* yh;    // [n, d]
+  const double* vl; const double* vh;    // optional diagonals: entry i at vl[i * vl_stride], vh[i * vh_stride] (both or neither)
+  long vl_stride, vh_stride;
+  double* rho_last;                      // optional [1]: rho at the start of the last step taken
 };
 struct TrainCommon {
   int steps;
@@ -175,11 +188,28 @@ __device__ __forceinline__ void tr_store(double* dst, const d4_t& acc, int g, in
 #define TR_OFF_SMALL (TR_OFF_DVEC + TR_N)
 #define TR_SMALL_DOUBLES (16 + 3 * 20 + 8 + 8 * TR_NRED + TR_NRED + 16)
 #define TR_LDS_DOUBLES (TR_OFF_SMALL + TR_SMALL_DOUBLES)
+// residual launches: the reduction has one more total (dloss/drho), then vl | vh | sgv = sgn(s) vl | diag G [128] each, rsum [8] (per-wave
+// sums of A .* y_low), rho at the start of the step [1]
+#define TR_NRED_RES (TR_NRED + 1)
+#define TR_OFF_RES (TR_OFF_SMALL + TR_SMALL_DOUBLES + 9 * (TR_NRED_RES - TR_NRED))
+#define TR_LDS_DOUBLES_RES (TR_OFF_RES + 4 * TR_N + 16)
+static_assert(TR_LDS_DOUBLES_RES * sizeof(double) <= 160 * 1024, "the residual launch's LDS exceeds a CU's 160 KiB");
+
+// a uniform word / pointer parked in LDS, read where it is used: loop-invariant values hoisted out of the step loop stay in scalar
+// registers for the whole kernel, and the scalar file is full (its spills take vector registers the step's phases need)
+__device__ __forceinline__ int tr_lds_int(const int* p) { return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile int*>(p)); }
+__device__ __forceinline__ double* tr_lds_ptr(const int* p) {
+  const unsigned lo = (unsigned)tr_lds_int(p), hi = (unsigned)tr_lds_int(p + 1);
+  return reinterpret_cast<double*>(((unsigned long long)hi << 32) | lo);
+}
 
 // DM: the input dimensions the per-entry loops are unrolled for (8 or 16: every model of the launch has D <= DM)
 // TRAIN: every step of the loop with Adam inside; !TRAIN ("evaluate"): ONE pass that writes the value and the gradients out
-template <int DM, bool TRAIN>
-__device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& cm) {
+// RESID (with TRAIN only): members with R.rho set are residual models (see the head of this file)
+template <int DM, bool TRAIN, bool RESID = false>
+__device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& cm, const TrainResid* Rp = nullptr) {
+  static_assert(TRAIN || !RESID, "residual members train");
+  constexpr int NRED = RESID ? TR_NRED_RES : TR_NRED;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* S = lds;
   double* Xs = lds + TR_OFF_XS;
@@ -193,14 +223,24 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   double* mom = raw + 20;                  // [20] exp_avg
   double* mo2 = mom + 20;                  // [20] exp_avg_sq
   double* sc = mo2 + 20;                   // [8]  amp, dadd, logdet
-  double* red = sc + 8;                    // [8][TR_NRED] per-wave partial sums
-  double* tot = red + 8 * TR_NRED;         // [TR_NRED] the step's totals
-  int* flags = reinterpret_cast<int*>(tot + TR_NRED);     // [0] bad pivot of the current step
+  double* red = sc + 8;                    // [8][NRED] per-wave partial sums
+  double* tot = red + 8 * NRED;            // [NRED] the step's totals
+  int* flags = reinterpret_cast<int*>(tot + NRED);        // [0] bad pivot of the current step
+  double* rvl = lds + TR_OFF_RES;          // residual members: [128] v_low diagonal
+  double* rvh = rvl + TR_N;                // [128] v_high diagonal
+  double* sgv = rvh + TR_N;                // [128] sgn(s_i) v_low,ii of the current step
+  double* gdg = sgv + TR_N;                // [128] G_ii of the current step
+  double* rsum = gdg + TR_N;               // [8]   per-wave sums of A .* y_low
+  double* rho0 = rsum + 8;                 // [1]   rho at the start of the current step
+  int* rmode = reinterpret_cast<int*>(rho0 + 1);      // [0] 0 plain member, 1 residual, 2 residual with diagonals; [2..9] y_low, y_high,
+                                                      // rho, rho_last (read through tr_lds_int / tr_lds_ptr)
+  bool isres = RESID && Rp->rho != nullptr;           // (for the set-up only: the step loop reads rmode)
+  bool hasv = isres && Rp->vl != nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, c = lane & 15;
   const int n = M.n, D = M.D, d = M.d, nw = M.nw;
   const int nst = (n + 15) >> 4, nblk = nst * (nst + 1) / 2;
-  const int npar = nw + 2;
+  const int npar = nw + 2 + (isres ? 1 : 0);      // (a residual member's rho is raw[nw + 2])
   const double oscale = (M.l.out_scale != 0.0) ? M.l.out_scale : 1.0;
   ExpCoef ec;
   ffgp_exp_load(ec);
@@ -209,14 +249,25 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   // targets, Gamma and A live as [128][16] images, zero beyond (n, d): the matrix-core products read them without guards
   for (int idx = tid; idx < TR_N * TR_Y; idx += TR_T) {
     const int i = idx >> 4, q = idx & 15;
-    Ym[idx] = (i < n && q < d) ? M.Y[i * d + q] : 0.0;
+    Ym[idx] = (!isres && i < n && q < d) ? M.Y[i * d + q] : 0.0;      // (a residual member's are formed at every step)
     Gam[idx] = 0.0;
     Am[idx] = 0.0;
   }
   for (int idx = tid; idx < TR_N * (TR_D + 1); idx += TR_T) Xs[idx] = 0.0;      // (columns >= D and rows >= n stay zero: the unrolled loops read them)
-  for (int i = tid; i < TR_N; i += TR_T) dvec[i] = (M.diag_vec && i < n) ? M.diag_vec[(size_t)i * M.diag_stride] : 0.0;
+  if (!isres) {
+    for (int i = tid; i < TR_N; i += TR_T) dvec[i] = (M.diag_vec && i < n) ? M.diag_vec[(size_t)i * M.diag_stride] : 0.0;
+  } else {      // (formed at every step from rho; zero beyond n and without diagonals)
+    for (int i = tid; i < TR_N; i += TR_T) {
+      dvec[i] = 0.0;
+      sgv[i] = 0.0;
+      gdg[i] = 0.0;
+      rvl[i] = (hasv && i < n) ? Rp->vl[(size_t)i * Rp->vl_stride] : 0.0;
+      rvh[i] = (hasv && i < n) ? Rp->vh[(size_t)i * Rp->vh_stride] : 0.0;
+    }
+  }
   if (tid < npar) {
-    raw[tid] = (tid < nw) ? M.w[tid] : (tid == nw ? M.amp[0] : (M.dadd ? M.dadd[0] : 0.0));
+    if (isres && tid == nw + 2) raw[tid] = Rp->rho[0];
+    else raw[tid] = (tid < nw) ? M.w[tid] : (tid == nw ? M.amp[0] : (M.dadd ? M.dadd[0] : 0.0));
     if (TRAIN) {
       mom[tid] = M.state[tid];
       mo2[tid] = M.state[npar + tid];
@@ -231,6 +282,16 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   }
   if (tid == 0) flags[0] = 0;
   if (lane == 0) flags[8 + wave] = simd_id();
+  if (RESID && tid == 0) {
+    rmode[0] = hasv ? 2 : (isres ? 1 : 0);
+    const double* pv[4] = {isres ? Rp->yl : nullptr, isres ? Rp->yh : nullptr, Rp->rho, Rp->rho_last};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned long long u = reinterpret_cast<unsigned long long>(pv[k]);
+      rmode[2 + 2 * k] = (int)(unsigned)u;
+      rmode[3 + 2 * k] = (int)(unsigned)(u >> 32);
+    }
+  }
   __syncthreads();
   HELPER_ROLES(flags + 8, wave, hidx, nh);      // helpers of the factorisation's stage [A]
   if (tid < D) wv[tid] = tr_link_val(M.l.w_link, raw[M.l.w_broadcast ? 0 : tid], M.l.w_c);
@@ -252,6 +313,26 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     for (int idx = tid; idx < n * D; idx += TR_T) {      // (shifted by the first point: only differences enter the kernel)
       const int i = idx / D, k = idx - i * D;
       Xs[i * (TR_D + 1) + k] = (M.X[idx] - M.X[k]) * wv[k];
+    }
+    isres = RESID && tr_lds_int(rmode) != 0;
+    if (isres) {      // this step's targets r = y_high - rho y_low and diagonal extra |s|, s = v_high - rho v_low, rounded as torch's
+                      // `y_high - rho * y_low` (a product, then a difference: never contracted)
+      hasv = tr_lds_int(rmode) == 2;
+      const double* yl = tr_lds_ptr(rmode + 2);
+      const double* yh = tr_lds_ptr(rmode + 4);
+      const double rho = raw[nw + 2];
+      for (int idx = tid; idx < n * TR_Y; idx += TR_T) {      // (over the image: no division by d)
+        const int i = idx >> 4, q = idx & 15;
+        if (q < d) Ym[idx] = __dsub_rn(yh[i * d + q], __dmul_rn(rho, yl[i * d + q]));
+      }
+      if (hasv) {
+        for (int i = tid; i < n; i += TR_T) {
+          const double s = __dsub_rn(rvh[i], __dmul_rn(rho, rvl[i]));
+          dvec[i] = fabs(s);
+          sgv[i] = (s > 0.0) ? rvl[i] : ((s < 0.0) ? -rvl[i] : 0.0);      // (torch's abs backward: sgn(0) = 0)
+        }
+      }
+      if (tid == 0) rho0[0] = rho;
     }
     LDS_BARRIER();
     const double amp = sc[0], dadd = sc[1];
@@ -429,12 +510,27 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         for (int r = 0; r < 4; ++r) Gam[(bi * 16 + g + 4 * r) * TR_Y + c] = acc[r];
       }
       LDS_BARRIER();
+      double ay = 0.0;      // residual members: this lane's part of sum A .* y_low
+      isres = RESID && tr_lds_int(rmode) != 0;
       if (7 - wave < nst) {
         const int bi = 7 - wave;
         d4_t acc = {0.0, 0.0, 0.0, 0.0};
         tr_chain<true>(acc, bi, nst, S, [bi](int kb) { return blk_off(kb, bi); }, BLD, Gam, [](int kb) { return kb * 16 * TR_Y; }, TR_Y, lane);
 #pragma unroll
         for (int r = 0; r < 4; ++r) Am[(bi * 16 + g + 4 * r) * TR_Y + c] = acc[r];
+        if (isres) {      // (y_low requested after the chain, not under it: four more live values there cost the <8> instantiation its
+                          //  spill-free allocation)
+          const double* yl = tr_lds_ptr(rmode + 2);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int i = bi * 16 + g + 4 * r;
+            ay = __builtin_fma(acc[r], (i < n && c < d) ? yl[i * d + c] : 0.0, ay);
+          }
+        }
+      }
+      if (isres) {
+        ay = tr_wsum(ay);
+        if (lane == 0) rsum[wave] = ay;
       }
       LDS_BARRIER();
     }
@@ -490,6 +586,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         if (i == j) {
           trg += gv;
           if (!TRAIN && live) dvec[i] = gv;      // (evaluate mode: diag G for g_diag_vec; the diagonal extra was consumed by the assembly)
+          if (RESID) gdg[i] = gv;                 // (residual members: the diagonal term of dloss/drho, summed behind the reduction's barrier)
         }
         const double wl = (sq >= M.clamp) ? sym * gv * amp * m2 : 0.0;
 #pragma unroll
@@ -511,14 +608,28 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       }
       if (lane == 0) {
 #pragma unroll
-        for (int q = 0; q < NV; ++q) red[wave * TR_NRED + q] = vals[q];
+        for (int q = 0; q < NV; ++q) red[wave * NRED + q] = vals[q];
       }
       LDS_BARRIER();
       if (tid < NV) {
         double x = 0.0;
 #pragma unroll
-        for (int wv_ = 0; wv_ < 8; ++wv_) x += red[wv_ * TR_NRED + tid];
+        for (int wv_ = 0; wv_ < 8; ++wv_) x += red[wv_ * NRED + tid];
         tot[tid] = x;
+      }
+      isres = RESID && tr_lds_int(rmode) != 0;
+      hasv = RESID && tr_lds_int(rmode) == 2;
+      if (isres && wave == 1) {      // dloss/drho (before the output scale) = -sum A .* y_low - sum_i G_ii sgn(s_i) v_low,ii, beside wave 0's totals
+        double x = 0.0;
+        if (hasv)
+          for (int i = lane; i < n; i += 64) x = __builtin_fma(gdg[i], sgv[i], x);
+        x = tr_wsum(x);
+        if (lane == 0) {
+          double a = 0.0;
+#pragma unroll
+          for (int wv_ = 0; wv_ < 8; ++wv_) a += rsum[wv_];
+          tot[NRED - 1] = -a - x;
+        }
       }
       LDS_BARRIER();
     }
@@ -553,7 +664,8 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       break;
     }
     if (tid == 0) M.trace[step] = value;
-    if (tid < npar) {
+    isres = RESID && tr_lds_int(rmode) != 0;
+    if (tid < nw + 2 + (isres ? 1 : 0)) {
       double gr;
       if (tid < nw) {
         if (!M.l.w_broadcast) {
@@ -565,8 +677,10 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         }
       } else if (tid == nw) {
         gr = oscale * tot[1] * tr_link_der(M.l.amp_link, raw[nw], M.l.amp_c);
-      } else {
+      } else if (!isres || tid == nw + 1) {
         gr = oscale * tot[2] * tr_link_der(M.l.dadd_link, raw[nw + 1], M.l.dadd_c);
+      } else {
+        gr = oscale * tot[NRED - 1];      // rho (raw = effective)
       }
       const double bc1 = cm.bc[2 * step], bc2s = cm.bc[2 * step + 1];
       const double m1 = mom[tid] + (gr - mom[tid]) * (1.0 - cm.b1);          // exp_avg.lerp_(grad, 1 - beta1)
@@ -586,7 +700,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         }
       } else if (tid == nw) {
         sc[0] = tr_link_val(M.l.amp_link, pnew, M.l.amp_c);
-      } else {
+      } else if (!isres || tid == nw + 1) {
         sc[1] = tr_link_val(M.l.dadd_link, pnew, M.l.dadd_c);
       }
     }
@@ -594,12 +708,19 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     TR_PROF(9);
   }
   // ---- parameters and moments back to the caller's tensors (a failed step left them as they were when it began)
-  if (TRAIN && tid < npar) {
+  if (RESID) isres = tr_lds_int(rmode) != 0;
+  const int npe = nw + 2 + (isres ? 1 : 0);
+  if (TRAIN && tid < npe) {
     if (tid < nw) M.w[tid] = raw[tid];
     else if (tid == nw) M.amp[0] = raw[tid];
-    else M.dadd[0] = raw[tid];
+    else if (!isres || tid == nw + 1) M.dadd[0] = raw[tid];
+    else {
+      tr_lds_ptr(rmode + 6)[0] = raw[tid];
+      double* rl = tr_lds_ptr(rmode + 8);
+      if (rl) rl[0] = rho0[0];
+    }
     M.state[tid] = mom[tid];
-    M.state[npar + tid] = mo2[tid];
+    M.state[npe + tid] = mo2[tid];
   }
   (void)failed;
 }
@@ -608,6 +729,13 @@ template <int DM>
 __global__ __launch_bounds__(TR_T) void ffgp_train_persist_kernel(const TrainModel* __restrict__ tab, TrainCommon cm) {
   const TrainModel M = tab[blockIdx.x];
   tr_body<DM, true>(M, cm);
+}
+// a launch with at least one residual member (rtab[f].rho == nullptr: a plain member)
+template <int DM>
+__global__ __launch_bounds__(TR_T) void ffgp_train_resid_kernel(const TrainModel* __restrict__ tab, const TrainResid* __restrict__ rtab,
+                                                                TrainCommon cm) {
+  const TrainModel M = tab[blockIdx.x];
+  tr_body<DM, true, true>(M, cm, rtab + blockIdx.x);
 }
 // evaluate mode: up to eight models per launch, their descriptions by value (the enqueue-only entry points must not stage anything in
 // host memory that a later call could overwrite)
@@ -621,11 +749,12 @@ __global__ __launch_bounds__(TR_T) void ffgp_small_mfma_kernel(TrainEvalBatch b,
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l) {
+bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r) {
   if (h->train_persist_off || h->use_naive || h->timing) return false;
   if (p->n <= 0 || p->n > TR_N || p->D <= 0 || p->D > TR_D || p->d <= 0 || p->d > TR_Y) return false;
   if (p->cov_dev || p->pair || p->tree || p->add_mat_dev || p->add_all != 0.0 || p->mean_jitter != 0.0) return false;
-  if (!p->X_dev || !p->Y_dev || !p->w_dev || !p->amp_dev || !p->diag_add_dev) return false;
+  const bool res = r && r->rho_dev;      // (a residual member's targets come from r: its Y_dev is ignored)
+  if (!p->X_dev || (!res && !p->Y_dev) || !p->w_dev || !p->amp_dev || !p->diag_add_dev) return false;
   if (p->kfun < FFGP_KFUN_SE || p->kfun > FFGP_KFUN_RQ || p->ll_variant != FFGP_LL_V1) return false;
   (void)l;
   return true;
@@ -634,19 +763,27 @@ bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ff
 // steps of F models (each must pass ffgp_train_persist_ok), one launch; synchronous.  Returns 0 or the pivot status of the first
 // model (in the caller's order) whose Sigma was not positive definite at some step.
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
-                       long state_stride, long step0, double* trace_dev, long trace_stride) {
+                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r) {
   static bool attr_set[64] = {false};
   if (h->device >= 0 && h->device < 64 && !attr_set[h->device]) {
     FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_persist_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  TR_LDS_DOUBLES * (int)sizeof(double)));
     FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_persist_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  TR_LDS_DOUBLES * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_resid_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES_RES * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_resid_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES_RES * (int)sizeof(double)));
     attr_set[h->device] = true;
   }
-  // one device block: [F models | 2 steps bias corrections | 2 F status ints | F x 36 x 256 kernel values]; its first three parts are
-  // staged in pinned host memory owned by the handle (an asynchronous copy from a temporary would have to be waited for)
+  bool any_res = false;
+  for (int f = 0; f < F && r; ++f) any_res = any_res || r[f].rho_dev != nullptr;
+  // one device block: [F models | F residual links (residual launches) | 2 steps bias corrections | 2 F status ints | F x 36 x 256 kernel
+  // values]; its first four parts are staged in pinned host memory owned by the handle (an asynchronous copy from a temporary would have
+  // to be waited for)
   const size_t tab_bytes = (size_t)F * sizeof(TrainModel);
-  const size_t bc_off = (tab_bytes + 255) / 256 * 256;
+  const size_t res_off = (tab_bytes + 255) / 256 * 256;
+  const size_t bc_off = any_res ? res_off + ((size_t)F * sizeof(TrainResid) + 255) / 256 * 256 : res_off;
   const size_t info_off = bc_off + ((size_t)2 * steps * sizeof(double) + 255) / 256 * 256;
   const size_t head = info_off + (size_t)2 * F * sizeof(int);
   const size_t k_off = (head + 255) / 256 * 256;
@@ -685,6 +822,17 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     m.kbuf = reinterpret_cast<double*>(dev + k_off) + (size_t)f * NBLK_LOWER * 256;
     m.want_grad = 1;
   }
+  if (any_res) {
+    TrainResid* tr = reinterpret_cast<TrainResid*>(host + res_off);
+    for (int f = 0; f < F; ++f) {
+      const ffgp_residual& q = r[f];
+      tr[f].rho = q.rho_dev;
+      if (!q.rho_dev) continue;
+      tr[f].yl = q.y_low_dev; tr[f].yh = q.y_high_dev;
+      tr[f].vl = q.v_low_dev; tr[f].vh = q.v_high_dev; tr[f].vl_stride = q.v_low_stride; tr[f].vh_stride = q.v_high_stride;
+      tr[f].rho_last = q.rho_last_dev;
+    }
+  }
   double* bc = reinterpret_cast<double*>(host + bc_off);
   for (int k = 0; k < steps; ++k) {
     const double t = (double)(step0 + k + 1);
@@ -707,7 +855,14 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
   }
   int Dmax = 0;
   for (int f = 0; f < F; ++f) Dmax = std::max(Dmax, p[f].D);
-  if (Dmax <= 8)
+  const TrainResid* rtab = reinterpret_cast<const TrainResid*>(dev + res_off);
+  if (any_res && Dmax <= 8)
+    hipLaunchKernelGGL(ffgp_train_resid_kernel<8>, dim3(F), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
+                       reinterpret_cast<const TrainModel*>(dev), rtab, cm);
+  else if (any_res)
+    hipLaunchKernelGGL(ffgp_train_resid_kernel<16>, dim3(F), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
+                       reinterpret_cast<const TrainModel*>(dev), rtab, cm);
+  else if (Dmax <= 8)
     hipLaunchKernelGGL(ffgp_train_persist_kernel<8>, dim3(F), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream,
                        reinterpret_cast<const TrainModel*>(dev), cm);
   else

@@ -19,7 +19,8 @@ TRAIN_THREADS = 4          # host threads (handle + stream each) that train the 
 
 class AdamState:
     """torch.optim.Adam's per-parameter state of the models of one `train_many` chunk, kept on the device between calls:
-    buf[f] = [exp_avg (nw + 2) | exp_avg_sq (nw + 2)] in the order length scales, signal variance, log_beta; `step` = updates taken."""
+    buf[f] = [exp_avg (nw + 2) | exp_avg_sq (nw + 2)] in the order length scales, signal variance, log_beta (a residual model:
+    [exp_avg (nw + 3) | exp_avg_sq (nw + 3)], rho last); `step` = updates taken."""
 
     def __init__(self, buf, stride, step=0):
         self.buf, self.stride, self.step = buf, stride, step
@@ -53,14 +54,35 @@ def _eligible(model, x, y):
     return lk, y, y_var
 
 
-def _reference_loop(models, xs, ys, steps, lr, betas, eps, opts):
-    """the reference's loop itself (one torch.optim.Adam per model): models that the fused call cannot train"""
+def _split_residual(res):
+    """(rho, y_low, y_high) in train_AR's forms -> rho, y_low mean, y_high mean, v_low, v_high (the variances None in the subset form)"""
+    rho, yl, yh = res
+    if isinstance(yl, (list, tuple)):
+        return rho, yl[0], yh[0], yl[1], yh[1]
+    return rho, yl, yh, None, None
+
+
+def _residual_targets(res, rho):
+    """train_AR's residual at this rho (AR_autoRegression.py:125-126,131-132): [y_high - rho * y_low, |v_high - rho * v_low| or None]"""
+    _, yl, yh, vl, vh = _split_residual(res)
+    with torch.no_grad():
+        return [yh - rho * yl, None if vl is None else (vh - rho * vl).abs()]
+
+
+def _reference_loop(models, xs, ys, steps, lr, betas, eps, opts, residual=None, targets=None):
+    """the reference's loop itself (one torch.optim.Adam per model, rho in a residual model's): models that the fused call cannot train"""
     trace = torch.empty((len(models), steps), dtype=torch.float64)
     for f, (m, x, y) in enumerate(zip(models, xs, ys)):
+        res = residual[f] if residual is not None else None
         if opts[f] is None:
-            opts[f] = torch.optim.Adam(m.parameters(), lr=lr, betas=betas, eps=eps)
+            opts[f] = torch.optim.Adam(list(m.parameters()) + ([res[0]] if res is not None else []), lr=lr, betas=betas, eps=eps)
         for k in range(steps):
             opts[f].zero_grad()
+            if res is not None:      # the residual at the current rho, with its graph (AR_autoRegression.py:123-137)
+                rho, yl, yh, vl, vh = _split_residual(res)
+                y = [yh - rho * yl, (vh - rho * vl).abs()] if vl is not None else yh - rho * yl
+                if k == steps - 1:
+                    targets[f] = [y[0].detach(), y[1].detach()] if vl is not None else [y.detach(), None]
             loss = -m.negative_log_likelihood(x, y)
             loss.backward()
             opts[f].step()
@@ -68,7 +90,29 @@ def _reference_loop(models, xs, ys, steps, lr, betas, eps, opts):
     return trace
 
 
-def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None):
+def _residual_ok(res, x):
+    """a residual link the fused call can train: a one-element fp64 rho that requires grad, fp64 targets [n, d] (and [n, n] variances)
+    on x's device that carry no gradient"""
+    from . import functional as F
+    rho, yl, yh, vl, vh = _split_residual(res)
+    if not (isinstance(rho, torch.Tensor) and rho.numel() == 1 and rho.dtype == torch.float64 and rho.device == x.device and rho.requires_grad
+            and rho.is_leaf):
+        return False
+    n = x.shape[0]
+    for t in (yl, yh):
+        if not (isinstance(t, torch.Tensor) and t.dim() == 2 and t.shape[0] == n and t.shape == yh.shape and t.dtype == torch.float64
+                and t.device == x.device and t.is_contiguous() and not t.requires_grad):
+            return False
+    if (vl is None) != (vh is None):
+        return False
+    for v in (vl, vh):
+        if v is not None and not (isinstance(v, torch.Tensor) and v.dim() == 2 and tuple(v.shape) == (n, n) and v.device == x.device
+                                  and not v.requires_grad and F.raw_ok(v)):
+            return False
+    return True
+
+
+def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None):
     """`steps` Adam iterations on every model of `models` (independent `cigp` models, `xs[f]`, `ys[f]` their training data; y may be
     `[y, y_var]`), each exactly the reference's iteration (FidelityFusion_Models/ResGP.py:82-88): loss = -negative_log_likelihood,
     gradients of the three raw parameters, torch.optim.Adam(lr, betas, eps) update.  Returns `(trace, state)`:
@@ -82,25 +126,48 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     optimiser state of a failed call is not advanced).
     Two differences from running the loop yourself: the parameters are updated in place on the device and are left WITHOUT `.grad`
     (there is no autograd pass), and the Adam moments live in the returned `state`, not in a `torch.optim.Adam` -- there is no
-    `optimizer.state_dict()` to checkpoint; keep `state` (and the step count inside it) instead."""
+    `optimizer.state_dict()` to checkpoint; keep `state` (and the step count inside it) instead.
+    `residual[f]` = (rho, y_low, y_high) makes model f one of train_AR's residual fidelities (AR_autoRegression.py:123-137; `ys[f]` is then
+    None): every step trains it on y_high - rho * y_low -- y_low, y_high tensors [n, d] (subset form) or [mean, var] lists with var [n, n]
+    (then |v_high - rho * v_low| is the y_var whose diagonal enters Sigma) -- and rho (a one-element fp64 parameter) is a fourth Adam
+    parameter, updated in place like the others.  state["residual_targets"][f] = [res_mean, res_var] (res_var None in the subset form)
+    is that residual at the rho of the start of the last step, computed with torch: what train_AR hands to add_data."""
     models, xs, ys = list(models), list(xs), list(ys)
     nF = len(models)
     if not (nF == len(xs) == len(ys)) or steps <= 0:
         raise ValueError("train_many: models, xs, ys must have one length and steps must be positive")
-    elig = [_eligible(m, x, y) for m, x, y in zip(models, xs, ys)]
+    if residual is not None:
+        residual = list(residual)
+        if len(residual) != nF:
+            raise ValueError("train_many: residual must have one entry per model")
+        for f, res in enumerate(residual):
+            if res is not None and (ys[f] is not None or len(res) != 3):
+                raise ValueError("train_many: a residual model takes (rho, y_low, y_high) and ys[f] = None")
+            if res is None and ys[f] is None:
+                raise ValueError("train_many: model %d has neither targets nor a residual link" % f)
+    res_of = (lambda f: residual[f]) if residual is not None else (lambda f: None)
+    # a residual model's eligibility is judged on its y_high (same shape as its targets) and its link
+    ys_e = [ys[f] if res_of(f) is None else _split_residual(res_of(f))[2] for f in range(nF)]
+    elig = [_eligible(m, x, y) for m, x, y in zip(models, xs, ys_e)]
+    for f in range(nF):
+        if res_of(f) is not None and elig[f] is not None and not _residual_ok(res_of(f), xs[f]):
+            elig[f] = None
     fused = all(e is not None for e in elig) and len({x.device for x in xs}) == 1
     if state is None:
         state = {"fused": fused, "chunks": {}, "opts": [None] * nF}
+    state["residual_targets"] = [None] * nF
     if not fused or not state["fused"]:
         if state["fused"]:
             raise ValueError("train_many: this state belongs to fused training; the models no longer qualify for it")
-        return _reference_loop(models, xs, ys, steps, lr, betas, eps, state["opts"]), state
+        trace = _reference_loop(models, xs, ys, steps, lr, betas, eps, state["opts"], residual, state["residual_targets"])
+        return trace, state
     JITTER, PI = _jitter_and_pi()
     from . import functional as F
     from .blocks import threaded_blocks
     dev = xs[0].device
     trace = torch.empty((nF, steps), dtype=torch.float64, device=dev)
     opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
+    rho_last = {f: torch.empty_like(res_of(f)[0].detach()) for f in range(nF) if res_of(f) is not None}
 
     def describe(f):
         lk, y, y_var = elig[f]
@@ -122,7 +189,16 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         ll.amp_link, ll.amp_c = lk["amp_link"], 0.0
         ll.dadd_link, ll.dadd_c = _lib.LINK_EXP_NEG, JITTER
         ll.out_scale = 1.0          # the value is the loss the reference minimises: -negative_log_likelihood = +nll
-        return p, ll, lk["w"].numel()
+        rs = _lib.Residual()
+        if res_of(f) is not None:
+            rho, yl, yh, vl, vh = _split_residual(res_of(f))
+            p.diag_vec_dev, p.diag_stride = None, 0
+            rs.rho_dev, rs.y_low_dev, rs.y_high_dev = rho.data_ptr(), yl.data_ptr(), yh.data_ptr()
+            if vl is not None:
+                rs.v_low_dev, rs.v_low_stride = vl.data_ptr(), vl.stride(0) + vl.stride(1)
+                rs.v_high_dev, rs.v_high_stride = vh.data_ptr(), vh.stride(0) + vh.stride(1)
+            rs.rho_last_dev = rho_last[f].data_ptr()
+        return p, ll, rs, lk["w"].numel() + (1 if res_of(f) is not None else 0)
 
     def run(idx):
         """one ffgp_train_raw call for the models `idx` (<= 16) on the calling thread's handle and stream; returns the status"""
@@ -130,10 +206,12 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         _lib.bind_stream(h, dev.index)
         P = (Problem * len(idx))()
         L = (_lib.Links * len(idx))()
+        R = (_lib.Residual * len(idx))()
         nws = []
         for j, f in enumerate(idx):
-            P[j], L[j], nw = describe(f)
+            P[j], L[j], R[j], nw = describe(f)
             nws.append(nw)
+        anyres = any(res_of(f) is not None for f in idx)
         stride = 2 * (max(nws) + 2)
         key = tuple(idx)
         st = state["chunks"].get(key)
@@ -143,8 +221,12 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         # the chunk's rows of the trace: contiguous when the models are consecutive, else through a staging block
         contiguous = list(idx) == list(range(idx[0], idx[0] + len(idx)))
         tr = trace[idx[0]:idx[0] + len(idx)] if contiguous else torch.empty((len(idx), steps), dtype=torch.float64, device=dev)
-        rc = check(lib.ffgp_train_raw(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
-                                      tr.data_ptr(), tr.stride(0)), "ffgp_train_raw")
+        if anyres:
+            rc = check(lib.ffgp_train_residual_raw(h, len(idx), P, L, R, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
+                                                   tr.data_ptr(), tr.stride(0)), "ffgp_train_residual_raw")
+        else:
+            rc = check(lib.ffgp_train_raw(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
+                                          tr.data_ptr(), tr.stride(0)), "ffgp_train_raw")
         if rc == 0:      # (a call that failed leaves its optimisers where they were: the caller sees LinAlgError)
             st.step += steps
         if not contiguous:
@@ -172,8 +254,8 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     # the library wrote the parameters behind autograd's back: bump their version counters (cached posteriors key on them)
     bump = getattr(torch.autograd.graph, "increment_version", None)      # (torch >= 2.1: no kernel; else an in-place no-op add)
     with torch.no_grad():
-        for m in models:
-            for q in m.parameters():
+        for f, m in enumerate(models):
+            for q in list(m.parameters()) + ([res_of(f)[0]] if res_of(f) is not None else []):
                 if bump is not None:
                     bump(q)
                 else:
@@ -181,4 +263,6 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     for idx, rc in rcs:
         if rc > 0:
             _raise_not_pd(rc, "linalg.cholesky (train_many, model%s %s)" % ("s" if len(idx) > 1 else "", ", ".join(map(str, idx))))
+    for f, rl in rho_last.items():      # train_AR's data for the fidelity: the residual at the rho of the start of the last step
+        state["residual_targets"][f] = _residual_targets(res_of(f), rl.reshape(res_of(f)[0].shape))
     return trace, state

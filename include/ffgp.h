@@ -529,6 +529,29 @@ typedef struct ffgp_adam {
 } ffgp_adam;
 int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, int steps, const ffgp_adam* opt,
                    double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
+
+/* ffgp_train_raw with RESIDUAL members -- train_AR's fidelities above 0 (FidelityFusion_Models/AR_autoRegression.py:123-137): model f
+   trains on the targets r = y_high - rho * y_low and, in the non-subset form, the diagonal extra dvec_i = |v_high,ii - rho * v_low,ii|
+   (Sigma = K + diag_add + diag(dvec)), both re-formed from the current rho at every step and rounded as torch rounds
+   `y_high - rho * y_low` (a product, then a difference).  rho is a fourth Adam parameter (same lr, betas, eps):
+   dloss/drho = -sum_{i,q} A_iq y_low,iq - sum_i G_ii sgn(s_i) v_low,ii, with A = Sigma^-1 r, G = 1/2 (d Sigma^-1 - A A^T),
+   s_i = v_high,ii - rho v_low,ii and sgn(0) = 0 (torch's abs backward).  r[f].rho_dev = NULL (or r = NULL) is a plain model, exactly as
+   ffgp_train_raw trains it; plain and residual members may share a call.  For a residual member p[f].Y_dev and p[f].diag_vec_dev are
+   ignored, and its Adam state is [exp_avg (nw + 3) | exp_avg_sq (nw + 3)] in the order w, amp, diag_add, rho.  rho_last_dev, when set,
+   receives the rho at the start of the last step taken (what train_AR keeps as the fidelity's training data).  Everything else --
+   routing (one launch for n <= 128, option "train_persist"), trace, status and failure semantics -- is ffgp_train_raw's.         */
+typedef struct {
+  double* rho_dev;            /* [1] raw rho, updated in place; NULL = a plain model */
+  const double* y_low_dev;    /* [n, d] */
+  const double* y_high_dev;   /* [n, d] */
+  const double* v_low_dev;    /* optional: entry i at v_low_dev[i * v_low_stride] (pass an n x n var with stride n + 1) */
+  long v_low_stride;
+  const double* v_high_dev;   /* optional, set exactly when v_low_dev is */
+  long v_high_stride;
+  double* rho_last_dev;       /* optional [1] */
+} ffgp_residual;
+int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, const ffgp_residual* r, int steps,
+                            const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 int ffgp_nlml_fused_small_batch_async(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, double* nll_dev,
                                       const ffgp_grads* g);
 
