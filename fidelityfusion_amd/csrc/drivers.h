@@ -1,0 +1,67 @@
+// What the host-driver translation units (handle.hip, nlml.hip, nlml_batch.hip, train_loop.hip, api.hip) need from each other.
+#pragma once
+#include "ffgp_internal.h"
+
+// ---- handle.hip
+void stage_mark(ffgp_handle* h, int idx);      // records stage timer idx on the handle's stream (option "timing")
+void stage_collect(ffgp_handle* h);
+struct RawGraph {          // the captured forward call (option "fwd_graph", ffgp_nlml_fused_async in nlml.hip)
+  ffgp_problem p;
+  unsigned long epoch;
+  int seen;               // 1 = this signature was enqueued plainly last time (buffers are warm): capture next
+  hipGraph_t graph;
+  hipGraphExec_t exec;
+  bool valid;
+  double* stage;          // the value the graph writes
+};
+void ffgp_rawg_drop(RawGraph* r);      // forgets the captured call (null: nothing to do); the struct and its staging slot stay
+
+// ---- raw parameters: elementwise links around the fused call (kernels in nlml.hip / nlml_batch.hip, the Adam kernel of train_loop.hip)
+__device__ __forceinline__ double ffgp_link_val(int kind, double p, double c) {
+  switch (kind) {
+    case FFGP_LINK_INV_ABS_EPS: return 1.0 / (fabs(p) + c);
+    case FFGP_LINK_EXP_NEG: return exp(-p) + c;
+    case FFGP_LINK_INV: return 1.0 / p + c;
+    case FFGP_LINK_ABS: return fabs(p);
+    case FFGP_LINK_EXP_SQ: { const double e = exp(p); return e * e; }
+    case FFGP_LINK_SQUARE: return p * p + c;
+    default: return p;
+  }
+}
+__device__ __forceinline__ double ffgp_link_der(int kind, double p, double c) {
+  switch (kind) {
+    case FFGP_LINK_INV_ABS_EPS: { const double a = fabs(p) + c; return ((p > 0.0) ? -1.0 : ((p < 0.0) ? 1.0 : 0.0)) / (a * a); }
+    case FFGP_LINK_EXP_NEG: return -exp(-p);
+    case FFGP_LINK_INV: return -1.0 / (p * p);
+    case FFGP_LINK_ABS: return (p > 0.0) ? 1.0 : ((p < 0.0) ? -1.0 : 0.0);
+    case FFGP_LINK_EXP_SQ: { const double e = exp(p); return 2.0 * e * e; }
+    case FFGP_LINK_SQUARE: return 2.0 * p;
+    default: return 1.0;
+  }
+}
+
+// ---- nlml.hip: the pieces every likelihood driver shares
+// the six gradients every driver knows (g_cov_dev / g_pair: the drivers that accept them test them next to this)
+static inline bool ffgp_wants_grad(const ffgp_grads* g) {
+  return g && (g->g_w_dev || g->g_amp_dev || g->g_diag_add_dev || g->g_Y_dev || g->g_diag_vec_dev || g->g_kparam_dev);
+}
+// status epilogue of an enqueued likelihood: sticky first failure, read-back (ffgp_train_raw's loop switches either off: fold_info / defer_info_copy)
+int ffgp_finish_info(ffgp_handle* h);
+// Links scaffold.  eff / geff = [w (D) | amp | diag_add]: the effective parameters ffgp_link_fwd writes and the gradients with respect
+// to them.  *q = *p, and with links its w / amp / diag_add point into eff; *gq = *g (when g is given), and with links the three
+// parameter gradients that were asked for point into geff.  Returns whether ffgp_link_bwd has anything to carry back.
+bool ffgp_links_redirect(const ffgp_problem* p, const ffgp_links* l, const ffgp_grads* g, double* eff, double* geff, ffgp_problem* q,
+                         ffgp_grads* gq);
+// ... and after the likelihood: the chain rule geff -> raw gradients (when chain), then the output scale.  p, g: the caller's own; g may be null
+void ffgp_links_finish(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_grads* g, const double* geff, bool chain,
+                       double* nll_dev);
+// scratch of the gradient stages, in doubles: L^-1, Sigma^-1 -> G, TRTRI scratch + the top level's L21 X11 when the inverse is split,
+// A^T = (Sigma^-1 Y)^T, partial sums of the parameter gradients; V2 only: (L^-1 A)^T and B^T = (Sigma^-1 A)^T
+struct ffgp_grad_scratch {
+  size_t X, S, T, At, P, Ct, Bt;
+};
+ffgp_grad_scratch ffgp_grad_scratch_sizes(int n, int d, int D, int ll_variant, int pair_leaves);      // pair_leaves 0: one radial profile
+// V1 gradient stages once X = L^-1 and S = Sigma^-1 are there: A^T = Gamma^T L^-1 (d x n), G = d/2 Sigma^-1 - 1/2 A A^T (lower, in
+// place of Sigma^-1), the parameter gradients from G.  d nll / dY = A is left in At for the caller to transpose.
+int ffgp_grad_v1_stages(ffgp_handle* h, const ffgp_problem* q, const ffgp_grads* gq, int D, double mean_jitter, const double* Gt,
+                        const double* X, double* S, double* At, double* P, int ld);

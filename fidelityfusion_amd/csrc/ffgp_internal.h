@@ -30,7 +30,7 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
     if (s_ != 0) return s_;         \
   } while (0)
 
-#define FFGP_GRAD_LANES 4      // gradient lanes of ffgp_nlml_fused_batch (api.hip)
+#define FFGP_GRAD_LANES 4      // size of the handle's per-lane arrays; ffgp_nlml_fused_batch (nlml_batch.hip) runs at most 3 lanes
 static inline int ffgp_round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // radial profiles (include/ffgp.h FFGP_KFUN_*): value phi(s) and  -2 * dphi/ds  (the factor that turns G o K' into the
@@ -145,7 +145,7 @@ struct GemmRagIn {
   int m, n, k;
 };
 
-int ffgp_live_handles();      // handles alive in this process (api.hip)
+int ffgp_live_handles();      // handles alive in this process (handle.hip)
 
 struct ffgp_handle {
   int device;
@@ -219,7 +219,7 @@ struct ffgp_handle {
   int chase_xcc;        // the XCD this handle's XCD-local chases run on
   int chase_xl;         // bulge chase with every working wave on one XCD, hand-overs through that XCD's L2 (sb2st.hip)
   hipStream_t aux3;     // fourth stream: gradient lane 2 of ffgp_nlml_fused_batch (created with aux2)
-  hipStream_t aux2;     // third stream: the head of the triangular inverse under the factorisation's tail (nlml_fused_enqueue)
+  hipStream_t aux2;     // third stream: the head of the triangular inverse under the factorisation's tail (nlml_fused_plain, nlml.hip)
   hipEvent_t tri_ev[2]; // [0] factor columns < tri_hook_col are final (recorded by ffgp_potrf_impl on the side stream); [1] head done
   int tri_hook_col, tri_hook_fired;
   // batched factorisation (ffgp_nlml_fused_batch): F identical-shape blocks at fixed strides share ONE chain of launches -- every
@@ -238,7 +238,7 @@ struct ffgp_handle {
   int defer_info_copy;  // ffgp_train_raw's loop: the enqueue paths skip their per-call read-back of the status word
   double* train_g;      // ffgp_train_raw: gradients of the raw parameters [MAXF x GSTRIDE] + the step's losses [MAXF]
   // gradient lanes of ffgp_nlml_fused_batch: members of different sizes run their inverse / gradient stages side by side
-  int grad_lanes;       // option "grad_lanes" (default 4; 1 = member after member)
+  int grad_lanes;       // option "grad_lanes" (default 3, at most 3; 1 = member after member)
   hipStream_t lane_st[FFGP_GRAD_LANES];   // [0] unused (lane 0 is the call's stream)
   hipEvent_t lane_ev[FFGP_GRAD_LANES];    // [0] fork, [z] lane z done
   double* lane_skw[FFGP_GRAD_LANES];      // per-lane split-K workspaces (swapped into h->skw while a member is enqueued on the lane)
@@ -271,7 +271,7 @@ struct ffgp_handle {
   int small2_off;              // option "small_finish" (default 0 = off): 1 = 40 < n <= 128 runs assembly + the blocked diagonal-block
                                // factorisation + ONE finishing kernel (7 launches instead of 21); measured +-5-10 % per training step
   unsigned long alloc_epoch;   // bumped whenever one of the handle's device buffers is re-allocated (captured pointers go stale)
-  int fwd_graph;               // option "fwd_graph" (default 0): forward-only calls replay a captured hipGraph (api.hip)
+  int fwd_graph;               // option "fwd_graph" (default 0): forward-only calls replay a captured hipGraph (nlml.hip)
   struct RawGraph* fwdg;
   long graph_replays;
   double* d_asm;     // assembly on the matrix cores: shifted + scaled inputs and their squared norms (n (D + 1) doubles)
@@ -379,7 +379,43 @@ int ffgp_small_mfma_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const 
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
                        long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r = nullptr);
 int ffgp_small_batch_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g);
-// ---- workspace
+// ---- assemble.hip, solve.hip, grad.hip, pair.hip, join.hip, eig.hip: the stages the host drivers string together
+int ffgp_assemble_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const double* w,
+                       const double* amp, double clamp_min, const double* diag_add, const double* diag_vec,
+                       long diag_stride, const double* add_mat, int ld_add, double add_all, double mean_jitter, double* K,
+                       int ldk, int lower_only, int kfun, double kparam);
+int ffgp_transpose(ffgp_handle* h, const double* src, int rows, int cols, int ld_src, double* dst, int ld_dst, double scale);
+int ffgp_trtri_impl(ffgp_handle* h, const double* L, int n, int ldl, double* X, int ldx, double* T);
+int ffgp_lauum_impl(ffgp_handle* h, const double* X, int n, int ldx, double* S, int lds_);
+int ffgp_trtri_lauum_ob(ffgp_handle* h, int F, const double* L0, long sL, int n, int ldl, double* X0, long sX, int ldx, double* T0, long sT,
+                        double* S0, long sS, int lds_, const double* dinv0, long sD);
+int ffgp_nll_reduce_impl(ffgp_handle* h, int variant, const double* L, int n, int ldl, const double* M, int rows, int cols,
+                         int ldm, int d, double pi_const, double* out_dev);
+int ffgp_grad_impl(ffgp_handle* h, const double* X, int n, int D, const double* w, const double* amp, double clamp,
+                   const double* G, int ldg, double mean_jitter, double* g_w, double* g_amp, double* g_diag_add,
+                   double* g_diag_vec, double* partial_ws, int kfun, double kparam, double* g_kparam);
+size_t ffgp_grad_partial_doubles(int n, int D);
+int ffgp_kernel_grad_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const double* w,
+                          const double* amp, double clamp, int kfun, double kparam, const double* dK, int ldk, double* g_w,
+                          double* g_amp, double* g_kparam);
+int ffgp_kernel_wt_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const double* w,
+                        const double* amp, double clamp, int kfun, double kparam, const double* dK, int ldk, double* Wt,
+                        int ldw);
+
+int ffgp_assemble_pair_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const ffgp_ktree* t,
+                            const double* diag_add, const double* diag_vec, long diag_stride, const double* add_mat, int ld_add,
+                            double add_all, double mean_jitter, double* K, int ldk, int lower_only);
+size_t ffgp_grad_pair_partial_doubles(int n1, int n2, int D, int rect, int nl);
+int ffgp_grad_pair_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const ffgp_ktree* t,
+                        const double* G, int ldg, int rect, const double* trG_dev, double mj_coef, double* partial_ws,
+                        const ffgp_kdesc_grads* g);
+int ffgp_pair_wt_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const ffgp_ktree* t, const double* dK,
+                      int ldk, double* Wt, int ldw, long leaf_stride);
+int ffgp_rows_in_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, unsigned char* found);
+
+int ffgp_syevj_small_impl(ffgp_handle* h, const double* M, int n, int ldm, int batch, long strideM, double* Q, int ldq,
+                          long strideQ, double* evals, long strideE, int descending);
+// ---- workspace (handle.hip)
 int ffgp_ensure_ws(ffgp_handle* h, size_t bytes);
 // zero `bytes` (a multiple of 4) on the handle's stream with a kernel: small fills on the captured (graph) path go through this
 // instead of hipMemsetAsync, whose graph nodes replayed wrong values on this ROCm build; large ones keep the runtime's fill

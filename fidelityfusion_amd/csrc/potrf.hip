@@ -738,7 +738,7 @@ static inline int la_slot(const ffgp_handle* h, hipEvent_t ev) {
   return -1;
 }
 // The wait is the library's OWN one-wave kernel (round 6): hipStreamWaitValue32 is a polling kernel of the runtime with no timeout -- in a
-// process whose dispatches are serialised by a tool that is not on default_ho_values()'s list (api.hip) it would spin for a producer
+// process whose dispatches are serialised by a tool that is not on default_ho_values()'s list (handle.hip) it would spin for a producer
 // that can never start, and the GPU hangs.  This gate polls the same word (measured at the same cost per hop: 3.5-4.0 us against the
 // runtime's 2.9-4.7, tools/native/handoff_probe.hip `kgate` / `vgate`), but watches the 100 MHz wall clock: after `ticks` without the
 // value it writes FFGP_HANDOFF_WATCHDOG into the status word and LEAVES -- the kernels behind it then run on incomplete data and the
@@ -756,7 +756,7 @@ __global__ void ffgp_handoff_gate(const unsigned* __restrict__ word, unsigned ne
   }
   // (no fence of its own: the kernels behind the gate acquire at their dispatch, as after any kernel boundary)
 }
-// Create-time self-test across two streams (api.hip, create_resources): the gate is enqueued on the side stream FIRST, the write that
+// Create-time self-test across two streams (handle.hip, create_resources): the gate is enqueued on the side stream FIRST, the write that
 // satisfies it on the handle's own stream afterwards.  Where kernels of different queues can run side by side the gate sees the value
 // within microseconds; in a process whose dispatches are serialised it gives up after 50 ms -- the handle then keeps the event pairs for
 // its whole life (ho_selftest_failed: option "ho_values" = 1 is refused).  This is the DETECTION; the list of environment variables in

@@ -1,6 +1,6 @@
 // One-kernel NLML (+ closed-form gradients) for the sizes the reference's own demos and experiments run (N = 16 ... 128;
 // GaussianProcess/cigp_v10.py:76-79, FidelityFusion_Models/ResGP.py:115-164, Experiments/GAR_Aligned/exp_aligned.py:58-126): the
-// blocked path of api.hip needs ~18 launches for work that one workgroup holds in LDS, and at these sizes a step IS its launches.
+// blocked path of nlml.hip needs ~18 launches for work that one workgroup holds in LDS, and at these sizes a step IS its launches.
 //
 // One workgroup of 256 threads, everything in LDS (<= 136 KB): Sigma as a packed lower triangle that becomes L, L^-1, Sigma^-1 and G in
 // place.  assemble (any radial profile, all Sigma extras incl. the mean(K) jitter) -> right-looking Cholesky (2-D thread tiling of the
@@ -18,7 +18,7 @@
 #define SM_T 256    // threads (1024 were measured: the 16-wave barriers cost more than the extra waves hide)
 #define SM_T2 1024  // threads of the finishing launch (FROM_FACTOR)
 #define SM_TG 16    // the trailing update's thread grid is SM_TG x SM_TG
-#define SM_MAX_FAST_N 40   // above this the blocked path of api.hip (whole chip, MFMA kernels) is faster: tools/small_kernel_bench.py
+#define SM_MAX_FAST_N 40   // above this the blocked path of nlml.hip (whole chip, MFMA kernels) is faster: tools/small_kernel_bench.py
 
 struct SmallArgs {
   int n, D, d;

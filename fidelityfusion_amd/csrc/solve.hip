@@ -303,7 +303,7 @@ int ffgp_trtri_lauum_ob(ffgp_handle* h, int F, const double* L0, long sL, int n,
 // The same inverse in two parts, split at column n1 (a power-of-two multiple of 128, n1 < n <= 2 n1 -- the top level's own split):
 //   head: everything that only needs the factor's first n1 columns -- X11 = L11^-1 and Ttop = L21 X11 (3/4 of the flops when
 //         n = 2 n1).  Those columns are final long before the factorisation ends, so the head runs on a third stream UNDER the
-//         factorisation's chain-bound tail (nlml_fused_enqueue);
+//         factorisation's chain-bound tail (nlml_fused_plain, nlml.hip);
 //   tail: X22 = L22^-1 and X21 = -X22 Ttop, after the factorisation.
 // The head reads the store of inverted diagonal blocks while the factorisation is still appending to it: blocks < n1 / 128 only.
 int ffgp_trtri_head(ffgp_handle* h, const double* L, int n, int ldl, double* X, int ldx, double* T, double* Ttop, int n1) {

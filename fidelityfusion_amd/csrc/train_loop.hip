@@ -1,0 +1,253 @@
+// K training steps in one call, launch per stage: the loop around the likelihood drivers with Adam on the device, and the residual
+// members' kernels.  (train.hip is the one-launch trainer this falls through to when every model is small.)  See include/ffgp.h.
+#include <cmath>
+#include <memory>
+
+#include "drivers.h"
+
+// ---- K training steps in ONE call -------------------------------------------------------------------------------------------
+// The reference's hot loop (FidelityFusion_Models/ResGP.py:78-112: per fidelity 100-1000 iterations of zero_grad / loss =
+// -negative_log_likelihood / backward / Adam step at N = 16 ... 500) costs one Python round trip, one autograd graph and one status
+// read-back per iteration through the drop-in modules -- 0.28-0.32 ms at N <= 128, of which 0.125 ms is GPU work.  Here the whole
+// loop is enqueued by one call: per step the likelihood + closed-form gradients on the raw parameters (the same launches as
+// ffgp_nlml_fused_raw, or ONE launch for all models when they are small: ffgp_nlml_fused_small_batch's kernel) and one Adam
+// kernel that updates the raw parameters IN PLACE on the device (torch.optim.Adam's arithmetic, operation for operation: lerp,
+// mul + addcmul, bias corrections computed on the host with the C library's pow as Python does, sqrt / div / add eps, addcdiv) and
+// stores the step's loss in the trace.  No host synchronisation inside the loop; the factorisation status is sticky and read once
+// at the end (the first step whose Sigma was not positive definite; the parameters stop moving from that step on).
+extern "C" __global__ void ffgp_adam_kernel(int F, ffgp_train_slot sl, const double* __restrict__ gbuf, double* __restrict__ state, long state_stride,
+                                 double lr, double b1, double b2, double eps, double bc1, double bc2_sqrt, const double* __restrict__ loss,
+                                 double* __restrict__ trace, long trace_stride, int step, int* __restrict__ info, int fold,
+                                 const double* __restrict__ geff, ffgp_links lk, int lD, double lsc) {
+  const int f = blockIdx.x;
+  if (f >= F) return;
+  const int i0 = info[0], i1 = info[1];
+  const int bad = i0 | i1;
+  if (fold) {      // (one model per call: this kernel also keeps the status words -- sticky first failure, current word cleared for the
+    __syncthreads();   //  next step's factorisation -- two single-thread launches per step otherwise)
+    if (threadIdx.x == 0) {
+      if (i1 == 0 && i0 != 0) info[1] = i0;
+      info[0] = 0;
+    }
+  }
+  const int nw = sl.nw[f];
+  const int npar = nw + 2 + (sl.rho[f] ? 1 : 0);      // (a residual member's rho is the last parameter; its gradient is in gbuf)
+  if (threadIdx.x == 0) trace[(size_t)f * trace_stride + step] = bad ? __builtin_nan("") : loss[f];
+  if (bad) return;
+  const int i = threadIdx.x;
+  if (i >= npar) return;
+  double* par = (i < nw) ? sl.w[f] + i : (i == nw ? sl.amp[f] : (i == nw + 1 ? sl.dadd[f] : sl.rho[f]));
+  double g;
+  if (i == nw + 2) {
+    g = gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + i];
+  } else if (geff) {
+    // (one model, blocked path: the gradients arrive with respect to the EFFECTIVE parameters [w (D) | amp | diag_add]; the links'
+    //  chain rule -- ffgp_link_bwd's arithmetic -- is applied here instead of in a launch of its own)
+    if (i < nw) {
+      if (!lk.w_broadcast) {
+        g = lsc * geff[i] * ffgp_link_der(lk.w_link, par[0], lk.w_c);
+      } else {
+        double sg = 0.0;
+        for (int k = 0; k < lD; ++k) sg += geff[k];
+        g = lsc * sg * ffgp_link_der(lk.w_link, par[0], lk.w_c);
+      }
+    } else if (i == nw) {
+      g = lsc * geff[lD] * ffgp_link_der(lk.amp_link, par[0], lk.amp_c);
+    } else {
+      g = lsc * geff[lD + 1] * ffgp_link_der(lk.dadd_link, par[0], lk.dadd_c);
+    }
+  } else {
+    g = gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + i];
+  }
+  double* m = state + (size_t)f * state_stride + i;
+  double* v = m + npar;
+  const double m1 = m[0] + (g - m[0]) * (1.0 - b1);        // exp_avg.lerp_(grad, 1 - beta1)
+  const double v1 = v[0] * b2 + (1.0 - b2) * g * g;        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+  m[0] = m1;
+  v[0] = v1;
+  const double denom = sqrt(v1) / bc2_sqrt + eps;
+  par[0] = par[0] + (-(lr / bc1)) * (m1 / denom);          // param.addcdiv_(exp_avg, denom, value = -step_size)
+}
+
+// residual members of the launch-per-stage loop (ffgp_train_residual_raw): per step their targets and diagonal extra are formed from rho
+// before the likelihood call, and dloss/drho is reduced from its dloss/dY and dloss/ddiag_vec after it
+struct ffgp_resid_slot {
+  const double* rho[FFGP_TRAIN_MAXF];
+  const double* yl[FFGP_TRAIN_MAXF];
+  const double* yh[FFGP_TRAIN_MAXF];
+  const double* vl[FFGP_TRAIN_MAXF];
+  const double* vh[FFGP_TRAIN_MAXF];
+  long vls[FFGP_TRAIN_MAXF], vhs[FFGP_TRAIN_MAXF];
+  double* r[FFGP_TRAIN_MAXF];            // [n, d] targets
+  double* dv[FFGP_TRAIN_MAXF];           // [n] |s|
+  const double* gY[FFGP_TRAIN_MAXF];     // [n, d] dloss/dr
+  const double* gdv[FFGP_TRAIN_MAXF];    // [n] dloss/ddvec
+  double* rho_last[FFGP_TRAIN_MAXF];
+  long nd[FFGP_TRAIN_MAXF];
+  int n[FFGP_TRAIN_MAXF], nw[FFGP_TRAIN_MAXF];
+};
+// r = y_high - rho y_low, dvec = |v_high - rho v_low| (a product, then a difference: torch's rounding); rho_last = rho
+extern "C" __global__ void ffgp_resid_form(ffgp_resid_slot rs) {
+  const int f = blockIdx.y;
+  if (!rs.rho[f]) return;
+  const double rho = rs.rho[f][0];
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t < rs.nd[f]) rs.r[f][t] = __dsub_rn(rs.yh[f][t], __dmul_rn(rho, rs.yl[f][t]));
+  if (rs.vl[f] && t < rs.n[f]) rs.dv[f][t] = fabs(__dsub_rn(rs.vh[f][t * rs.vhs[f]], __dmul_rn(rho, rs.vl[f][t * rs.vls[f]])));
+  if (t == 0 && rs.rho_last[f]) rs.rho_last[f][0] = rho;
+}
+// gbuf slot nw + 2 <- dloss/drho = -sum gY .* y_low - sum_i gdv_i sgn(s_i) v_low,ii (one workgroup per member, fixed order)
+extern "C" __global__ void ffgp_resid_grad(ffgp_resid_slot rs, double* __restrict__ gbuf) {
+  const int f = blockIdx.x;
+  if (!rs.rho[f]) return;
+  __shared__ double part[256];
+  const double rho = rs.rho[f][0];
+  double x = 0.0;
+  for (long t = threadIdx.x; t < rs.nd[f]; t += 256) x = __builtin_fma(rs.gY[f][t], rs.yl[f][t], x);
+  if (rs.vl[f]) {
+    for (int i = threadIdx.x; i < rs.n[f]; i += 256) {
+      const double vl = rs.vl[f][(long)i * rs.vls[f]];
+      const double s = __dsub_rn(rs.vh[f][(long)i * rs.vhs[f]], __dmul_rn(rho, vl));
+      x = __builtin_fma(rs.gdv[f][i], (s > 0.0) ? vl : ((s < 0.0) ? -vl : 0.0), x);      // (sgn(0) = 0: torch's abs backward)
+    }
+  }
+  part[threadIdx.x] = x;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + rs.nw[f] + 2] = -part[0];
+}
+
+static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, int steps,
+                      const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+  if (!h || !p || !l || !opt || !state_dev || !trace_dev || F <= 0 || F > FFGP_TRAIN_MAXF || steps <= 0 || step0 < 0 || trace_stride < steps)
+    return FFGP_ERR_ARG;
+  ffgp_train_slot sl;
+  bool all_small = true, any_res = false;
+  for (int f = 0; f < F; ++f) {
+    const ffgp_problem& q = p[f];
+    if (!q.w_dev || !q.amp_dev || !q.diag_add_dev || q.cov_dev || q.pair || q.tree || q.D <= 0 || q.D > 128 || q.n <= 0 || q.d <= 0) return FFGP_ERR_ARG;
+    const bool res = r && r[f].rho_dev;
+    if (res && (!r[f].y_low_dev || !r[f].y_high_dev || !q.X_dev || (!r[f].v_low_dev) != (!r[f].v_high_dev) ||
+                (r[f].v_low_dev && (r[f].v_low_stride < 0 || r[f].v_high_stride < 0))))
+      return FFGP_ERR_ARG;
+    const int nw = l[f].w_broadcast ? 1 : q.D;
+    if (state_stride < 2 * (nw + 2 + (res ? 1 : 0))) return FFGP_ERR_ARG;
+    sl.w[f] = const_cast<double*>(q.w_dev);
+    sl.amp[f] = const_cast<double*>(q.amp_dev);
+    sl.dadd[f] = const_cast<double*>(q.diag_add_dev);
+    sl.rho[f] = res ? r[f].rho_dev : nullptr;
+    sl.nw[f] = nw;
+    any_res = any_res || res;
+  }
+  FFGP_HIP(hipSetDevice(h->device));
+  {   // every model small enough for one workgroup: the whole loop is ONE launch (train.hip)
+    bool persist = true;
+    for (int f = 0; f < F && persist; ++f) persist = ffgp_train_persist_ok(h, p + f, l + f, r ? r + f : nullptr);
+    if (persist) return ffgp_train_persist(h, F, p, l, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, r);
+  }
+  if (!h->train_g) {
+    FFGP_HIP(hipMalloc(&h->train_g, (size_t)FFGP_TRAIN_MAXF * (FFGP_TRAIN_GSTRIDE + 1) * sizeof(double)));
+  }
+  double* gbuf = h->train_g;
+  double* loss = h->train_g + (size_t)FFGP_TRAIN_MAXF * FFGP_TRAIN_GSTRIDE;
+  std::vector<ffgp_grads> g(F);
+  std::vector<ffgp_links> lk(l, l + F);
+  std::vector<ffgp_problem> pq(p, p + F);      // (residual members: targets and diagonal extra in the call's own buffers)
+  ffgp_resid_slot rs;
+  memset(&rs, 0, sizeof(rs));
+  double* rbuf = nullptr;
+  std::unique_ptr<double, hipError_t (*)(void*)> rbuf_owner(nullptr, hipFree);      // frees rbuf on every way out, after its synchronisation
+  long rmax = 0;
+  if (any_res) {      // per residual member [r (n d) | dvec (n) | dloss/dr (n d) | dloss/ddvec (n)], freed when the call returns
+    size_t tot = 0;
+    for (int f = 0; f < F; ++f)
+      if (sl.rho[f]) tot += 2 * ((size_t)p[f].n * p[f].d + p[f].n);
+    FFGP_HIP(hipMalloc(&rbuf, tot * sizeof(double)));
+    rbuf_owner.reset(rbuf);
+    size_t off = 0;
+    for (int f = 0; f < F; ++f) {
+      if (!sl.rho[f]) continue;
+      const long n = p[f].n, nd = n * p[f].d;
+      rs.rho[f] = sl.rho[f];
+      rs.yl[f] = r[f].y_low_dev; rs.yh[f] = r[f].y_high_dev;
+      rs.vl[f] = r[f].v_low_dev; rs.vh[f] = r[f].v_high_dev; rs.vls[f] = r[f].v_low_stride; rs.vhs[f] = r[f].v_high_stride;
+      rs.r[f] = rbuf + off; rs.dv[f] = rs.r[f] + nd;
+      rs.gY[f] = rs.dv[f] + n; rs.gdv[f] = rs.gY[f] + nd;
+      rs.rho_last[f] = r[f].rho_last_dev;
+      rs.nd[f] = nd; rs.n[f] = (int)n; rs.nw[f] = sl.nw[f];
+      off += 2 * (nd + n);
+      rmax = std::max(rmax, std::max(nd, n));
+      pq[f].Y_dev = rs.r[f];
+      pq[f].diag_vec_dev = rs.vl[f] ? rs.dv[f] : nullptr;
+      pq[f].diag_stride = 1;
+    }
+  }
+  for (int f = 0; f < F; ++f) {
+    memset(&g[f], 0, sizeof(ffgp_grads));
+    g[f].g_w_dev = gbuf + (size_t)f * FFGP_TRAIN_GSTRIDE;
+    g[f].g_amp_dev = g[f].g_w_dev + sl.nw[f];
+    g[f].g_diag_add_dev = g[f].g_amp_dev + 1;
+    if (sl.rho[f]) {
+      g[f].g_Y_dev = const_cast<double*>(rs.gY[f]);
+      if (rs.vl[f]) g[f].g_diag_vec_dev = const_cast<double*>(rs.gdv[f]);
+    }
+    all_small = all_small && ffgp_small_batch_ok(&pq[f], &g[f]);
+  }
+  p = pq.data();
+  // the sticky status word starts clean: a failure of an EARLIER call on this handle is that call's to report
+  FFGP_CHECK(ffgp_zero_async(h, h->d_info, 2 * sizeof(int)));
+  // (the one-kernel paths -- n <= 40, or option small_finish -- apply the links inside their kernel and write raw gradients)
+  const bool one_kernel = ffgp_small_ok(h, p, &g[0]) || ffgp_small2_ok(h, p, &g[0]);
+  h->defer_info_copy = 1;      // (the per-call read-back of the status word: once, after the loop)
+  h->fold_info = (F == 1) ? 1 : 0;   // one model: the Adam kernel clears / accumulates the status words (see ffgp_adam_kernel)
+  int lrc = FFGP_OK;
+  for (int k = 0; k < steps && lrc == FFGP_OK; ++k) {
+    if (any_res) hipLaunchKernelGGL(ffgp_resid_form, dim3((unsigned)((rmax + 255) / 256), F), dim3(256), 0, h->stream, rs);
+    if (all_small && F > 1) {
+      if ((lrc = ffgp_zero_async(h, h->d_info, sizeof(int))) != FFGP_OK) break;
+      if ((lrc = ffgp_small_batch_enqueue(h, F, p, lk.data(), loss, g.data())) != FFGP_OK) break;
+      if ((lrc = ffgp_finish_info(h)) != FFGP_OK) break;      // (several models: fold_info is off, the read-back deferred -- the sticky word's launch alone)
+    } else {
+      for (int f = 0; f < F && lrc == FFGP_OK; ++f) lrc = ffgp_nlml_fused_raw_async(h, p + f, &lk[f], loss + f, &g[f]);
+      if (lrc != FFGP_OK) break;
+    }
+    if (any_res) hipLaunchKernelGGL(ffgp_resid_grad, dim3(F), dim3(256), 0, h->stream, rs, gbuf);
+    const double t = (double)(step0 + k + 1);
+    const double bc1 = 1.0 - std::pow(opt->beta1, t), bc2 = 1.0 - std::pow(opt->beta2, t);
+    hipLaunchKernelGGL(ffgp_adam_kernel, dim3(F), dim3(192), 0, h->stream, F, sl, gbuf, state_dev, state_stride, opt->lr, opt->beta1,
+                       opt->beta2, opt->eps, bc1, std::sqrt(bc2), loss, trace_dev, trace_stride, k, h->d_info, h->fold_info,
+                       (h->fold_info && !one_kernel) ? h->d_link + 256 : (const double*)nullptr, lk[0], p[0].D,
+                       (lk[0].out_scale == 0.0) ? 1.0 : lk[0].out_scale);
+  }
+  h->defer_info_copy = 0;
+  h->fold_info = 0;
+  if (lrc != FFGP_OK) {
+    hipStreamSynchronize(h->stream);
+    return lrc;
+  }
+  if (hipGetLastError() != hipSuccess) {
+    hipStreamSynchronize(h->stream);
+    return FFGP_ERR_HIP;
+  }
+  FFGP_HIP(hipMemcpyAsync(h->h_info, h->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  ffgp_invalidate(h);
+  return ffgp_wait(h);
+}
+
+extern "C" {
+
+int ffgp_train_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
+                   long state_stride, long step0, double* trace_dev, long trace_stride) {
+  return train_impl(h, F, p, l, nullptr, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
+}
+
+int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, int steps,
+                            const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+  if (!r) return FFGP_ERR_ARG;
+  return train_impl(h, F, p, l, r, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
+}
+
+}  // extern "C"

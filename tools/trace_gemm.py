@@ -16,7 +16,8 @@ SO = os.path.join(ROOT, "fidelityfusion_amd", "libffgp_trace.so")
 
 
 def build():
-    srcs = ["gemm.hip", "potrf.hip", "assemble.hip", "solve.hip", "grad.hip", "join.hip", "eig.hip", "api.hip"]
+    with open(os.path.join(CSRC, "Makefile")) as f:      # the library's translation units: the Makefile's own list
+        srcs = next(line for line in f if line.startswith("SRCS =")).split("=", 1)[1].split()
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-DFFGP_GEMM_TRACE", "-shared",
            "-Wno-unused-value", "-Wno-unused-result", "-I" + os.path.join(ROOT, "include"), "-o", SO] + [os.path.join(CSRC, f) for f in srcs]
     subprocess.check_call(cmd)
