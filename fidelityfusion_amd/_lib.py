@@ -69,6 +69,17 @@ class Links(C.Structure):
                 ("dadd_link", C.c_int), ("dadd_c", C.c_double), ("out_scale", C.c_double)]
 
 
+class LeafLinks(C.Structure):
+    """ffgp_leaf_links: the maps of one leaf of a composed kernel (ffgp_train_tree_raw)"""
+    _fields_ = [("w_link", C.c_int), ("w_c", C.c_double), ("w_broadcast", C.c_int), ("amp_link", C.c_int), ("amp_c", C.c_double),
+                ("center_train", C.c_int)]
+
+
+class TreeLinks(C.Structure):
+    """ffgp_tree_links: the leaves' maps in the tree's canonical leaf order, the noise parameter's map, the output scale"""
+    _fields_ = [("leaf", LeafLinks * 4), ("dadd_link", C.c_int), ("dadd_c", C.c_double), ("out_scale", C.c_double)]
+
+
 class Adam(C.Structure):
     """ffgp_adam: torch.optim.Adam's hyper-parameters for ffgp_train_raw"""
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double)]
@@ -147,6 +158,8 @@ EXPORTS = {
                                  _dp, C.c_long]),
     "ffgp_train_residual_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(Residual), C.c_int,
                                           C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
+    "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
+                                      C.c_long, _dp, C.c_long]),
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),

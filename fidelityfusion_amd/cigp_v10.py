@@ -11,7 +11,8 @@ import torch
 import torch.nn as nn
 
 from . import functional as F
-from .train import train_many  # noqa: F401  (K Adam steps of independent models per library call: the reference's train loops)
+from .train import train_many  # noqa: F401  (K Adam steps of independent models per library call: the reference's train loops --
+#                                              single library kernels and SumKernel / ProductKernel trees alike, see train.train_many)
 
 
 def _kfun(k):

@@ -40,6 +40,19 @@ __device__ __forceinline__ double ffgp_link_der(int kind, double p, double c) {
   }
 }
 
+// ---- torch.optim.Adam's update of ONE parameter with gradient g (no weight decay, no amsgrad), operation for operation; bc1 and
+// bc2_sqrt = 1 - beta1^t and sqrt(1 - beta2^t), computed on the host.  The one copy: ffgp_adam_kernel (train_loop.hip) and
+// ffgp_tree_adam_kernel (train_tree.hip) both call it.
+__device__ __forceinline__ void ffgp_adam_update(double* par, double* m, double* v, double g, double lr, double b1, double b2, double eps,
+                                                 double bc1, double bc2_sqrt) {
+  const double m1 = m[0] + (g - m[0]) * (1.0 - b1);        // exp_avg.lerp_(grad, 1 - beta1)
+  const double v1 = v[0] * b2 + (1.0 - b2) * g * g;        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+  m[0] = m1;
+  v[0] = v1;
+  const double denom = sqrt(v1) / bc2_sqrt + eps;
+  par[0] = par[0] + (-(lr / bc1)) * (m1 / denom);          // param.addcdiv_(exp_avg, denom, value = -step_size)
+}
+
 // ---- nlml.hip: the pieces every likelihood driver shares
 // the six gradients every driver knows (g_cov_dev / g_pair: the drivers that accept them test them next to this)
 static inline bool ffgp_wants_grad(const ffgp_grads* g) {

@@ -237,6 +237,8 @@ struct ffgp_handle {
   int fold_info;        // ffgp_train_raw with one model: status-word upkeep lives in the Adam kernel
   int defer_info_copy;  // ffgp_train_raw's loop: the enqueue paths skip their per-call read-back of the status word
   double* train_g;      // ffgp_train_raw: gradients of the raw parameters [MAXF x GSTRIDE] + the step's losses [MAXF]
+  double* train_tree;   // ffgp_train_tree_raw: [member table | losses | effective parameters | their gradients], sized from the call's members
+  size_t train_tree_bytes;
   // gradient lanes of ffgp_nlml_fused_batch: members of different sizes run their inverse / gradient stages side by side
   int grad_lanes;       // option "grad_lanes" (default 3, at most 3; 1 = member after member)
   hipStream_t lane_st[FFGP_GRAD_LANES];   // [0] unused (lane 0 is the call's stream)

@@ -273,6 +273,7 @@ int ffgp_destroy(ffgp_handle* h) {
   if (h->ho_mem) hipFree(h->ho_mem);
   if (h->bt_info) hipFree(h->bt_info);
   if (h->train_g) hipFree(h->train_g);
+  if (h->train_tree) hipFree(h->train_tree);
   for (int z = 0; z < FFGP_GRAD_LANES; ++z) {
     if (h->lane_ev[z]) hipEventDestroy(h->lane_ev[z]);
     if (z > 0 && h->lane_skw[z]) hipFree(h->lane_skw[z]);

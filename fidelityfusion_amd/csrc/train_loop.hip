@@ -61,12 +61,7 @@ extern "C" __global__ void ffgp_adam_kernel(int F, ffgp_train_slot sl, const dou
   }
   double* m = state + (size_t)f * state_stride + i;
   double* v = m + npar;
-  const double m1 = m[0] + (g - m[0]) * (1.0 - b1);        // exp_avg.lerp_(grad, 1 - beta1)
-  const double v1 = v[0] * b2 + (1.0 - b2) * g * g;        // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-  m[0] = m1;
-  v[0] = v1;
-  const double denom = sqrt(v1) / bc2_sqrt + eps;
-  par[0] = par[0] + (-(lr / bc1)) * (m1 / denom);          // param.addcdiv_(exp_avg, denom, value = -step_size)
+  ffgp_adam_update(par, m, v, g, lr, b1, b2, eps, bc1, bc2_sqrt);
 }
 
 // residual members of the launch-per-stage loop (ffgp_train_residual_raw): per step their targets and diagonal extra are formed from rho

@@ -1,0 +1,223 @@
+// K training steps in one call for models whose kernel is a composition (ffgp_ktree: SumKernel / ProductKernel trees of 2-4 leaves),
+// launch per stage at every size: ffgp_train_tree_raw.  Per step: ONE launch maps every member's raw leaf parameters to the effective
+// w / amp / diag_add the tile pass reads, the likelihood and its gradients are ffgp_nlml_fused_async's own launches on a shadow
+// problem that points at those values, and ONE launch carries the gradients back through the links and takes Adam's step (the
+// update function of ffgp_adam_kernel, drivers.h).  See include/ffgp.h.
+#include <cmath>
+#include <vector>
+
+#include "drivers.h"
+
+#define FFGP_TREE_MAXL 4
+// one member, as both kernels read it from device memory (F <= 16 of them: too large for a kernel argument)
+struct ffgp_tree_member {
+  double* w[FFGP_TREE_MAXL];       // raw parameter storages, leaf by leaf
+  double* amp[FFGP_TREE_MAXL];
+  double* cen[FFGP_TREE_MAXL];     // a trained centre (linear leaf), else null
+  double* dadd;
+  double w_c[FFGP_TREE_MAXL], amp_c[FFGP_TREE_MAXL];
+  double dadd_c, sc;
+  long eff, geff;                  // where this member's effective parameters / their gradients start in the scratch (doubles)
+  int w_link[FFGP_TREE_MAXL], amp_link[FFGP_TREE_MAXL], nw[FFGP_TREE_MAXL];
+  int dadd_link, D, nl, P;
+};
+// effective parameters of a member: leaf e at e (D + 1) as [w (D) | amp], then diag_add at nl (D + 1);
+// their gradients: leaf e at e (2 D + 1) as [g_w (D) | g_amp | g_center (D)], then g_diag_add at nl (2 D + 1)
+
+// raw -> effective, one workgroup per member (ffgp_link_fwd's arithmetic for every leaf)
+extern "C" __global__ void ffgp_tree_link_fwd(const ffgp_tree_member* __restrict__ tab, double* __restrict__ scratch) {
+  const ffgp_tree_member* M = tab + blockIdx.x;
+  const int D = M->D, per = D + 1, tot = M->nl * per + 1;
+  double* eff = scratch + M->eff;
+  for (int i = threadIdx.x; i < tot; i += blockDim.x) {
+    double val;
+    if (i == tot - 1) {
+      val = ffgp_link_val(M->dadd_link, M->dadd[0], M->dadd_c);
+    } else {
+      const int e = i / per, k = i - e * per;
+      if (k < D) val = ffgp_link_val(M->w_link[e], M->w[e][(M->nw[e] == D) ? k : 0], M->w_c[e]);
+      else val = ffgp_link_val(M->amp_link[e], M->amp[e][0], M->amp_c[e]);
+    }
+    eff[i] = val;
+  }
+}
+
+// the links' chain rule (ffgp_link_bwd's arithmetic; a broadcast length scale: the D effective gradients summed in index order
+// first), the step's losses into the trace, Adam's step on every raw parameter of every member, and the upkeep of the status words
+// as ffgp_adam_kernel does it with `fold` -- ONE workgroup, so that the words are read by every thread before thread 0 rewrites
+// them; the threads run over (member, raw parameter) pairs, pmax = the largest P of the call.
+extern "C" __global__ void ffgp_tree_adam_kernel(int F, int pmax, const ffgp_tree_member* __restrict__ tab, const double* __restrict__ scratch,
+                                                 double* __restrict__ state, long state_stride, double lr, double b1, double b2, double eps,
+                                                 double bc1, double bc2_sqrt, const double* __restrict__ loss, double* __restrict__ trace,
+                                                 long trace_stride, int step, int* __restrict__ info) {
+  const int i0 = info[0], i1 = info[1];
+  const int bad = i0 | i1;
+  __syncthreads();
+  if (threadIdx.x == 0) {      // sticky first failure, current word cleared for the next step's factorisations
+    if (i1 == 0 && i0 != 0) info[1] = i0;
+    info[0] = 0;
+  }
+  for (int f = threadIdx.x; f < F; f += blockDim.x)
+    trace[(size_t)f * trace_stride + step] = bad ? __builtin_nan("") : tab[f].sc * loss[f];
+  if (bad) return;
+  const int items = F * pmax;
+  for (int j = threadIdx.x; j < items; j += blockDim.x) {
+    const int f = j / pmax, i = j - f * pmax;
+    const ffgp_tree_member* M = tab + f;
+    const int P = M->P;
+    if (i >= P) continue;
+    const int D = M->D, gper = 2 * D + 1;
+    const double sc = M->sc;
+    const double* ge = scratch + M->geff;
+    double* par;
+    double g;
+    if (i == P - 1) {
+      par = M->dadd;
+      g = sc * ge[M->nl * gper] * ffgp_link_der(M->dadd_link, par[0], M->dadd_c);
+    } else {
+      int e = 0, k = i;
+      for (; e < M->nl - 1; ++e) {
+        const int cnt = M->nw[e] + 1 + (M->cen[e] ? D : 0);
+        if (k < cnt) break;
+        k -= cnt;
+      }
+      const double* gl = ge + e * gper;
+      const int nw = M->nw[e];
+      if (k < nw) {
+        par = M->w[e] + k;
+        if (nw == D) {
+          g = sc * gl[k] * ffgp_link_der(M->w_link[e], par[0], M->w_c[e]);
+        } else {
+          double sg = 0.0;
+          for (int q = 0; q < D; ++q) sg += gl[q];
+          g = sc * sg * ffgp_link_der(M->w_link[e], par[0], M->w_c[e]);
+        }
+      } else if (k == nw) {
+        par = M->amp[e];
+        g = sc * gl[D] * ffgp_link_der(M->amp_link[e], par[0], M->amp_c[e]);
+      } else {
+        par = M->cen[e] + (k - nw - 1);
+        g = sc * gl[D + 1 + (k - nw - 1)];      // (identity link)
+      }
+    }
+    double* m = state + (size_t)f * state_stride + i;
+    ffgp_adam_update(par, m, m + P, g, lr, b1, b2, eps, bc1, bc2_sqrt);
+  }
+}
+
+extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* l, int steps, const ffgp_adam* opt,
+                                   double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+  if (!h || !p || !l || !opt || !state_dev || !trace_dev || F <= 0 || F > FFGP_TRAIN_MAXF || steps <= 0 || step0 < 0 || trace_stride < steps)
+    return FFGP_ERR_ARG;
+  std::vector<ffgp_tree_member> tab(F);
+  std::vector<ffgp_problem> pq(p, p + F);                        // the shadow problems: trees whose leaves read the effective parameters
+  std::vector<ffgp_ktree> tq(F);
+  std::vector<ffgp_kdesc> kq((size_t)F * FFGP_TREE_MAXL);
+  std::vector<ffgp_kdesc_grads> gk((size_t)F * FFGP_TREE_MAXL);
+  std::vector<ffgp_grads> g(F);
+  const size_t tab_doubles = ((size_t)F * sizeof(ffgp_tree_member) + sizeof(double) - 1) / sizeof(double);
+  size_t off = tab_doubles + FFGP_TRAIN_MAXF;                    // [table | losses | per member: effective parameters, gradients]
+  int pmax = 0;
+  for (int f = 0; f < F; ++f) {
+    const ffgp_problem& q = p[f];
+    const ffgp_ktree* t = q.tree;
+    if (!t || q.pair || q.cov_dev || !t->leaf || t->n_leaves < 2 || t->n_leaves > FFGP_TREE_MAXL || q.D <= 0 || q.D > 128 || q.n <= 0 ||
+        q.d <= 0 || !q.X_dev || !q.Y_dev || !q.diag_add_dev || (q.ll_variant != FFGP_LL_V1 && q.ll_variant != FFGP_LL_V2))
+      return FFGP_ERR_ARG;
+    const int D = q.D, nl = t->n_leaves;
+    ffgp_tree_member& M = tab[f];
+    memset(&M, 0, sizeof(M));
+    int P = 1;
+    for (int e = 0; e < nl; ++e) {
+      const ffgp_kdesc& k = t->leaf[e];
+      const ffgp_leaf_links& ll = l[f].leaf[e];
+      const bool linear = (k.kfun == FFGP_KFUN_LINEAR);
+      if (!k.w_dev || !k.amp_dev || !(linear || (k.kfun >= FFGP_KFUN_SE && k.kfun <= FFGP_KFUN_MATERN52))) return FFGP_ERR_ARG;
+      if (ll.center_train && !(linear && k.center_dev)) return FFGP_ERR_ARG;
+      M.w[e] = const_cast<double*>(k.w_dev);
+      M.amp[e] = const_cast<double*>(k.amp_dev);
+      M.cen[e] = ll.center_train ? const_cast<double*>(k.center_dev) : nullptr;
+      M.w_link[e] = ll.w_link; M.w_c[e] = ll.w_c;
+      M.amp_link[e] = ll.amp_link; M.amp_c[e] = ll.amp_c;
+      M.nw[e] = ll.w_broadcast ? 1 : D;
+      P += M.nw[e] + 1 + (ll.center_train ? D : 0);
+    }
+    if (state_stride < 2 * (long)P) return FFGP_ERR_ARG;
+    M.dadd = const_cast<double*>(q.diag_add_dev);
+    M.dadd_link = l[f].dadd_link; M.dadd_c = l[f].dadd_c;
+    M.sc = (l[f].out_scale == 0.0) ? 1.0 : l[f].out_scale;
+    M.D = D; M.nl = nl; M.P = P;
+    M.eff = (long)off; off += (size_t)nl * (D + 1) + 1;
+    M.geff = (long)off; off += (size_t)nl * (2 * D + 1) + 1;
+    pmax = std::max(pmax, P);
+  }
+  FFGP_HIP(hipSetDevice(h->device));
+  if (h->train_tree_bytes < off * sizeof(double)) {      // (every earlier call on this handle has returned: nothing reads the old buffer)
+    if (h->train_tree) FFGP_HIP(hipFree(h->train_tree));
+    h->train_tree = nullptr;
+    h->train_tree_bytes = 0;
+    if (hipMalloc(&h->train_tree, off * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();
+      return FFGP_ERR_ALLOC;
+    }
+    h->train_tree_bytes = off * sizeof(double);
+  }
+  double* scratch = h->train_tree;
+  const ffgp_tree_member* tab_dev = reinterpret_cast<const ffgp_tree_member*>(scratch);
+  double* loss = scratch + tab_doubles;
+  for (int f = 0; f < F; ++f) {
+    const ffgp_tree_member& M = tab[f];
+    const int D = M.D;
+    double* eff = scratch + M.eff;
+    double* ge = scratch + M.geff;
+    tq[f] = *p[f].tree;
+    tq[f].leaf = &kq[(size_t)f * FFGP_TREE_MAXL];
+    for (int e = 0; e < M.nl; ++e) {
+      ffgp_kdesc& k = kq[(size_t)f * FFGP_TREE_MAXL + e];
+      k = p[f].tree->leaf[e];
+      k.w_dev = eff + (size_t)e * (D + 1);
+      k.amp_dev = k.w_dev + D;
+      ffgp_kdesc_grads& ke = gk[(size_t)f * FFGP_TREE_MAXL + e];
+      memset(&ke, 0, sizeof(ke));
+      ke.g_w_dev = ge + (size_t)e * (2 * D + 1);
+      ke.g_amp_dev = ke.g_w_dev + D;
+      if (M.cen[e]) ke.g_center_dev = ke.g_amp_dev + 1;
+    }
+    pq[f].tree = &tq[f];
+    pq[f].diag_add_dev = eff + (size_t)M.nl * (D + 1);
+    memset(&g[f], 0, sizeof(ffgp_grads));
+    g[f].g_diag_add_dev = ge + (size_t)M.nl * (2 * D + 1);
+    g[f].g_pair = &gk[(size_t)f * FFGP_TREE_MAXL];
+  }
+  // (the table's host copy lives until the call's synchronisation below, on every way out)
+  if (hipMemcpyAsync(scratch, tab.data(), (size_t)F * sizeof(ffgp_tree_member), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+    hipStreamSynchronize(h->stream);
+    return FFGP_ERR_HIP;
+  }
+  // the sticky status word starts clean: a failure of an EARLIER call on this handle is that call's to report
+  int lrc = ffgp_zero_async(h, h->d_info, 2 * sizeof(int));
+  h->defer_info_copy = 1;      // (the per-call read-back of the status word: once, after the loop)
+  h->fold_info = 1;            // the Adam kernel clears / accumulates the status words; the factorisations of a step share info[0]
+  for (int k = 0; k < steps && lrc == FFGP_OK; ++k) {
+    hipLaunchKernelGGL(ffgp_tree_link_fwd, dim3(F), dim3(256), 0, h->stream, tab_dev, scratch);
+    for (int f = 0; f < F && lrc == FFGP_OK; ++f) lrc = ffgp_nlml_fused_async(h, &pq[f], loss + f, &g[f]);
+    if (lrc != FFGP_OK) break;
+    const double t = (double)(step0 + k + 1);
+    const double bc1 = 1.0 - std::pow(opt->beta1, t), bc2 = 1.0 - std::pow(opt->beta2, t);
+    hipLaunchKernelGGL(ffgp_tree_adam_kernel, dim3(1), dim3(256), 0, h->stream, F, pmax, tab_dev, scratch, state_dev, state_stride, opt->lr,
+                       opt->beta1, opt->beta2, opt->eps, bc1, std::sqrt(bc2), loss, trace_dev, trace_stride, k, h->d_info);
+  }
+  h->defer_info_copy = 0;
+  h->fold_info = 0;
+  if (lrc != FFGP_OK) {
+    hipStreamSynchronize(h->stream);
+    return lrc;
+  }
+  if (hipGetLastError() != hipSuccess) {
+    hipStreamSynchronize(h->stream);
+    return FFGP_ERR_HIP;
+  }
+  FFGP_HIP(hipMemcpyAsync(h->h_info, h->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  ffgp_invalidate(h);
+  return ffgp_wait(h);
+}

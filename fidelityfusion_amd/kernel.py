@@ -145,6 +145,13 @@ class LinearKernel(nn.Module):
         return {"kfun": F.FFGP_KFUN_LINEAR, "w": 1.0 / self.length_scales, "amp": self.signal_variance.abs(), "clamp": F.NEG_INF,
                 "kparam": 1.0, "center": self.center}
 
+    def links(self):
+        """the raw parameters and their maps as a LEAF of a composition (`_Pair.tree_links`, ffgp_train_tree_raw): w = 1 / length_scales,
+        amp = |signal_variance|, the centre trained as it stands.  (On its own a linear kernel has no raw-parameter likelihood call:
+        `functional.raw_path` returns None for it.)"""
+        return {"w": self.length_scales, "w_link": _lib.LINK_INV, "w_c": 0.0, "amp": self.signal_variance, "amp_link": _lib.LINK_ABS,
+                "clamp": F.NEG_INF, "kfun": F.FFGP_KFUN_LINEAR, "kparam": 1.0, "center": self.center}
+
     def forward(self, x1, x2):
         c, ls = self.center.to(x1.device), self.length_scales.to(x1.device)
         z1, z2 = (x1 - c) / ls, (x2 - c) / ls
@@ -185,6 +192,23 @@ class _Pair(nn.Module):
     def fusable(self):
         """`pair()` would return descriptors (checked on the module structure alone: no tensor is touched)"""
         return FUSE_PAIRS and _flatten(self) is not None
+
+    def tree_links(self):
+        """(leaf modules in canonical order, (shape, ops), the leaves' `links()` dicts) when ffgp_train_tree_raw can train this
+        composition on its raw parameters (`train_many`), else None: not `fusable()` (more than four leaves, a user module,
+        FUSE_PAIRS = False), a leaf without links (MaternKernel with another nu, a user module with a descriptor), a leaf with a
+        learnable profile parameter (RationalQuadraticKernel's alpha), or one module or parameter used in two leaves (torch would
+        sum those gradients into ONE parameter; the library would take two Adam steps on it)."""
+        if not self.fusable():
+            return None
+        leaves, form = _flatten(self)
+        lks = [k.links() if hasattr(k, "links") else None for k in leaves]
+        if any(lk is None or isinstance(lk.get("kparam"), torch.Tensor) for lk in lks):
+            return None
+        pars = [id(t) for lk in lks for t in (lk["w"], lk["amp"], lk.get("center")) if t is not None]
+        if len(set(map(id, leaves))) != len(leaves) or len(set(pars)) != len(pars):
+            return None
+        return leaves, form, lks
 
     def forward(self, x1, x2):
         pr = self.pair()

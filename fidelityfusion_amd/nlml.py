@@ -529,7 +529,7 @@ def nlml_raw(X, Y, lk, rdadd, dadd_link, dadd_c, diag_vec=None, add_mat=None, ad
 def raw_path(kernel, x_train, y_train, *others):
     """the kernel's `links()` when the raw-parameter fast path applies to this call, else None"""
     lk = kernel.links() if hasattr(kernel, "links") else None
-    if lk is None:
+    if lk is None or lk["kfun"] == FFGP_KFUN_LINEAR:      # (a linear part has links only as a leaf of a composition: kernel._Pair.tree_links)
         return None
     kp = lk.get("kparam")
     if not raw_ok(x_train, y_train, lk["w"], lk["amp"], kp if isinstance(kp, torch.Tensor) else None, *others):

@@ -4,6 +4,8 @@
 as ONE call of ffgp_train_raw: likelihood, closed-form gradients and torch.optim.Adam's update of the raw parameters on the device,
 the loss trace returned, the factorisation status read once.  Through the drop-in modules a step costs 0.28-0.32 ms at N <= 128 (one
 Python round trip, one autograd graph, one status read-back); here it costs its GPU work.
+Models whose kernel is a SumKernel / ProductKernel tree of up to four library kernels -- SumKernel(LinearKernel, MaternKernel) is the
+kernel of the reference's demos and two-fidelity models -- take the same route through ffgp_train_tree_raw (launch per stage, every size).
 """
 import ctypes as C
 
@@ -20,7 +22,10 @@ TRAIN_THREADS = 4          # host threads (handle + stream each) that train the 
 class AdamState:
     """torch.optim.Adam's per-parameter state of the models of one `train_many` chunk, kept on the device between calls:
     buf[f] = [exp_avg (nw + 2) | exp_avg_sq (nw + 2)] in the order length scales, signal variance, log_beta (a residual model:
-    [exp_avg (nw + 3) | exp_avg_sq (nw + 3)], rho last); `step` = updates taken."""
+    [exp_avg (nw + 3) | exp_avg_sq (nw + 3)], rho last); `step` = updates taken.
+    A chunk of composed-kernel models (ffgp_train_tree_raw): buf[f] = [exp_avg (P) | exp_avg_sq (P)], P = sum over the leaves of
+    (length scales + 1 + the centre's D for a LinearKernel) + 1, in the order leaf by leaf in the tree's canonical leaf order
+    (`kernel._Pair.tree_links`: length scales, signal variance, centre), then log_beta."""
 
     def __init__(self, buf, stride, step=0):
         self.buf, self.stride, self.step = buf, stride, step
@@ -43,6 +48,8 @@ def _eligible(model, x, y):
         return None
     if y_var is not None and not F.raw_ok(y_var):
         return None
+    if hasattr(model.kernel, "tree_links"):      # SumKernel / ProductKernel: ffgp_train_tree_raw, or the reference's loop
+        return _eligible_tree(model, x, y, y_var)
     with torch.enable_grad():
         lk = F.raw_path(model.kernel, x, y, model.log_beta)
     if lk is None or isinstance(lk.get("kparam"), torch.Tensor) or y.requires_grad:
@@ -52,6 +59,34 @@ def _eligible(model, x, y):
     if {id(q) for q in model.parameters()} != {id(lk["w"]), id(lk["amp"]), id(model.log_beta)}:
         return None      # a kernel with further learnable parameters (MaternKernel's rho is a constant; RQ's alpha is not)
     return lk, y, y_var
+
+
+def _eligible_tree(model, x, y, y_var):
+    """`_eligible` for a composed kernel: ({"tree": (leaf modules, (shape, ops), leaf links)}, y, y_var) when ffgp_train_tree_raw can
+    train the model -- `kernel.tree_links()` applies, everything fp64, contiguous and on one GPU, every leaf parameter (length scales,
+    signal variance, a linear leaf's centre) and log_beta trainable and together exactly the model's parameters, data without gradients"""
+    from . import functional as F
+    tl = model.kernel.tree_links()
+    if tl is None or not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor)):
+        return None
+    pars = [t for lk in tl[2] for t in (lk["w"], lk["amp"], lk.get("center")) if t is not None] + [model.log_beta]
+    if not F.raw_ok(x, y, y_var, *pars):
+        return None
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0] or x.shape[1] > 128 or model.log_beta.numel() != 1:
+        return None
+    D = x.shape[1]
+    for lk in tl[2]:
+        if lk["w"].numel() not in (1, D) or lk["amp"].numel() != 1 or (lk.get("center") is not None and lk["center"].numel() != D):
+            return None
+    if x.requires_grad or y.requires_grad or (y_var is not None and y_var.requires_grad) or not all(t.requires_grad for t in pars):
+        return None
+    if len({id(t) for t in pars}) != len(pars) or {id(q) for q in model.parameters()} != {id(t) for t in pars}:
+        return None
+    return {"tree": tl}, y, y_var
+
+
+def _is_tree(e):
+    return e is not None and "tree" in e[0]
 
 
 def _split_residual(res):
@@ -121,6 +156,13 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     Models on one GPU in fp64 with a library kernel are trained by ffgp_train_raw, up to 16 per call (small models -- N <= 128, D,
     d <= 16 -- take ONE kernel launch for ALL their steps: csrc/train.hip, a persistent workgroup per model); anything else runs the
     reference's loop through the drop-in modules.
+    Models whose kernel is a SumKernel / ProductKernel composition with `tree_links()` (2-4 library kernels, LinearKernel with its
+    trained centre included; every leaf parameter and log_beta trainable, and nothing else) are trained by ffgp_train_tree_raw, launch
+    per stage: those of at most 128 points up to 16 per call -- calls of their own, beside the plain and residual models' -- and every
+    larger one in a call of its own, side by side with the other large models.  A not-PD Sigma in one model of such a call stops all
+    of that call's models at that step.  A composed-kernel model given a `residual=` link is NOT fused: it (and with it the whole
+    `train_many` call, state["fused"] = False) keeps the reference's loop, as do compositions with a RationalQuadraticKernel leaf, a
+    module used as two leaves, or kernel.FUSE_PAIRS = False.
     A Sigma that is not positive definite raises torch.linalg.LinAlgError as the reference's loop would; the failing model's parameters
     then hold the values they had when that step began (the other small models of the same call have completed their steps; the
     optimiser state of a failed call is not advanced).
@@ -150,8 +192,8 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     ys_e = [ys[f] if res_of(f) is None else _split_residual(res_of(f))[2] for f in range(nF)]
     elig = [_eligible(m, x, y) for m, x, y in zip(models, xs, ys_e)]
     for f in range(nF):
-        if res_of(f) is not None and elig[f] is not None and not _residual_ok(res_of(f), xs[f]):
-            elig[f] = None
+        if res_of(f) is not None and elig[f] is not None and (_is_tree(elig[f]) or not _residual_ok(res_of(f), xs[f])):
+            elig[f] = None      # (a composed kernel with a residual link: the reference's loop -- ffgp_train_tree_raw has no residual members)
     fused = all(e is not None for e in elig) and len({x.device for x in xs}) == 1
     if state is None:
         state = {"fused": fused, "chunks": {}, "opts": [None] * nF}
@@ -200,8 +242,75 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
             rs.rho_last_dev = rho_last[f].data_ptr()
         return p, ll, rs, lk["w"].numel() + (1 if res_of(f) is not None else 0)
 
+    def describe_tree(f, keep):
+        """model f with a composed kernel: its problem (the tree's leaves on their RAW parameters) and ffgp_tree_links; P = its number
+        of raw parameters.  The ctypes arrays the problem points to are appended to `keep`."""
+        (tl, y, y_var), x, m = elig[f], xs[f], models[f]
+        _, form, lks = tl["tree"]
+        n, D = x.shape
+        shape, ops = form
+        p = Problem()
+        p.n, p.D, p.d = n, D, y.shape[1]
+        p.X_dev, p.Y_dev, p.diag_add_dev = x.data_ptr(), y.data_ptr(), m.log_beta.data_ptr()
+        if y_var is not None:
+            p.diag_stride = y_var.shape[1] + 1 if y_var.dim() == 2 else 1
+            p.diag_vec_dev = y_var.data_ptr()
+        p.ll_variant, p.pi_const = FFGP_LL_V1, PI
+        arr = (_lib.KDesc * len(lks))()
+        tree, tk = _lib.KTree(), _lib.TreeLinks()
+        P = 1
+        for e, lk in enumerate(lks):
+            arr[e].kfun, arr[e].clamp_min, arr[e].kparam = lk["kfun"], lk["clamp"], float(lk.get("kparam", 1.0))
+            arr[e].w_dev, arr[e].amp_dev = lk["w"].data_ptr(), lk["amp"].data_ptr()
+            le = tk.leaf[e]
+            le.w_link, le.w_c, le.w_broadcast = lk["w_link"], lk["w_c"], 1 if lk["w"].numel() == 1 and D > 1 else 0
+            le.amp_link, le.amp_c = lk["amp_link"], 0.0
+            if lk.get("center") is not None:
+                arr[e].center_dev, le.center_train = lk["center"].data_ptr(), 1
+            P += lk["w"].numel() + 1 + (D if lk.get("center") is not None else 0)
+        tree.n_leaves, tree.shape, tree.leaf = len(lks), shape, arr
+        for i, o in enumerate(ops):
+            tree.op[i] = o
+        p.tree = C.pointer(tree)
+        tk.dadd_link, tk.dadd_c, tk.out_scale = _lib.LINK_EXP_NEG, JITTER, 1.0
+        keep += [arr, tree]
+        return p, tk, P
+
+    def run_tree(idx):
+        """one ffgp_train_tree_raw call for the composed-kernel models `idx` (<= 16); Adam state [exp_avg (P) | exp_avg_sq (P)] per model"""
+        h = _lib.handle(dev.index)
+        _lib.bind_stream(h, dev.index)
+        P = (Problem * len(idx))()
+        L = (_lib.TreeLinks * len(idx))()
+        keep, npar = [], []
+        for j, f in enumerate(idx):
+            P[j], L[j], n_ = describe_tree(f, keep)
+            npar.append(n_)
+        return launch(idx, 2 * max(npar), lambda st, tr: check(
+            lib.ffgp_train_tree_raw(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), st.stride, int(st.step), tr.data_ptr(),
+                                    tr.stride(0)), "ffgp_train_tree_raw"))
+
+    def launch(idx, stride, call):
+        """the chunk's Adam state and trace rows around one library call `call(state, trace rows)`; returns the status"""
+        key = tuple(idx)
+        st = state["chunks"].get(key)
+        if st is None or st.stride != stride or st.buf.device != dev:
+            st = AdamState(torch.zeros((len(idx), stride), dtype=torch.float64, device=dev), stride)
+            state["chunks"][key] = st
+        # the chunk's rows of the trace: contiguous when the models are consecutive, else through a staging block
+        contiguous = list(idx) == list(range(idx[0], idx[0] + len(idx)))
+        tr = trace[idx[0]:idx[0] + len(idx)] if contiguous else torch.empty((len(idx), steps), dtype=torch.float64, device=dev)
+        rc = call(st, tr)
+        if rc == 0:      # (a call that failed leaves its optimisers where they were: the caller sees LinAlgError)
+            st.step += steps
+        if not contiguous:
+            trace[list(idx)] = tr
+        return rc
+
     def run(idx):
         """one ffgp_train_raw call for the models `idx` (<= 16) on the calling thread's handle and stream; returns the status"""
+        if _is_tree(elig[idx[0]]):
+            return run_tree(idx)
         h = _lib.handle(dev.index)
         _lib.bind_stream(h, dev.index)
         P = (Problem * len(idx))()
@@ -213,39 +322,32 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
             nws.append(nw)
         anyres = any(res_of(f) is not None for f in idx)
         stride = 2 * (max(nws) + 2)
-        key = tuple(idx)
-        st = state["chunks"].get(key)
-        if st is None or st.stride != stride or st.buf.device != dev:
-            st = AdamState(torch.zeros((len(idx), stride), dtype=torch.float64, device=dev), stride)
-            state["chunks"][key] = st
-        # the chunk's rows of the trace: contiguous when the models are consecutive, else through a staging block
-        contiguous = list(idx) == list(range(idx[0], idx[0] + len(idx)))
-        tr = trace[idx[0]:idx[0] + len(idx)] if contiguous else torch.empty((len(idx), steps), dtype=torch.float64, device=dev)
         if anyres:
-            rc = check(lib.ffgp_train_residual_raw(h, len(idx), P, L, R, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
-                                                   tr.data_ptr(), tr.stride(0)), "ffgp_train_residual_raw")
-        else:
-            rc = check(lib.ffgp_train_raw(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
-                                          tr.data_ptr(), tr.stride(0)), "ffgp_train_raw")
-        if rc == 0:      # (a call that failed leaves its optimisers where they were: the caller sees LinAlgError)
-            st.step += steps
-        if not contiguous:
-            trace[list(idx)] = tr
-        return rc
+            return launch(idx, stride, lambda st, tr: check(
+                lib.ffgp_train_residual_raw(h, len(idx), P, L, R, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
+                                            tr.data_ptr(), tr.stride(0)), "ffgp_train_residual_raw"))
+        return launch(idx, stride, lambda st, tr: check(
+            lib.ffgp_train_raw(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step), tr.data_ptr(),
+                               tr.stride(0)), "ffgp_train_raw"))
 
     # small models (one workgroup each: ONE launch per step for up to 16 of them) go together; every larger model is a call of its
     # own -- and, when there are several, they train SIDE BY SIDE from host threads with a handle and a stream each
     # (blocks.threaded_blocks: the calls only enqueue and wait once, ctypes drops the GIL inside them), so that one model's
     # latency-bound chain of small kernels runs in the gaps of the others'
+    # Models with a composed kernel (ffgp_train_tree_raw) form calls of their own: up to 16 of at most 128 points per call, the larger
+    # ones one call each beside the other large models.
     shapes = [(xs[f].shape[0], xs[f].shape[1], elig[f][1].shape[1]) for f in range(nF)]
-    small = [f for f in range(nF) if shapes[f][0] <= F.SMALL_BATCH_MAX_N and shapes[f][1] <= F.SMALL_BATCH_MAX_D
+    trees = {f for f in range(nF) if _is_tree(elig[f])}
+    small = [f for f in range(nF) if f not in trees and shapes[f][0] <= F.SMALL_BATCH_MAX_N and shapes[f][1] <= F.SMALL_BATCH_MAX_D
              and shapes[f][2] <= F.SMALL_BATCH_MAX_d]
-    large = [f for f in range(nF) if f not in set(small)]
+    small_trees = [f for f in sorted(trees) if shapes[f][0] <= F.SMALL_BATCH_MAX_N]
+    large = [f for f in range(nF) if f not in set(small) and f not in set(small_trees)]
     if len(small) == 1:      # (a lone small model gains nothing from the batch kernel: its own call folds the tail launches)
         large, small = sorted(large + small), []
     rcs = []
-    for c0 in range(0, len(small), TRAIN_MAX_MODELS):
-        rcs.append((small[c0:c0 + TRAIN_MAX_MODELS], run(small[c0:c0 + TRAIN_MAX_MODELS])))
+    for group in (small, small_trees):
+        for c0 in range(0, len(group), TRAIN_MAX_MODELS):
+            rcs.append((group[c0:c0 + TRAIN_MAX_MODELS], run(group[c0:c0 + TRAIN_MAX_MODELS])))
     if len(large) >= 2 and _lib.current_slot() == 0:
         outs = threaded_blocks([(lambda f=f: run([f])) for f in large], nslots=min(TRAIN_THREADS, len(large)), device_index=dev.index)
         rcs += [([f], rc) for f, rc in zip(large, outs)]

@@ -555,6 +555,39 @@ int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const 
 int ffgp_nlml_fused_small_batch_async(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, double* nll_dev,
                                       const ffgp_grads* g);
 
+/* ffgp_train_raw for models whose kernel is a COMPOSITION -- SumKernel / ProductKernel trees of 2-4 leaves (ffgp_ktree), the kernel of
+   the reference's own demos and of every two-fidelity model (SumKernel(LinearKernel, MaternKernel): GaussianProcess/cigp_v10.py:81,111,
+   147; two_fidelity_models/ResGP.py:25,28) -- at every size, launch per stage.  p[f].tree describes model f (p[f].pair is not accepted
+   here); the leaves' w_dev / amp_dev / center_dev and p[f].diag_add_dev hold the modules' RAW parameters, and links[f] names every
+   leaf's maps as ffgp_links does for a single kernel (leaf[e] belongs to tree->leaf[e]; a FFGP_KFUN_LINEAR leaf with center_train has
+   its centre trained as it stands, identity link).  Per step and without any host synchronisation: ONE launch maps all members' raw
+   parameters to effective w [D], amp and diag_add in handle-owned scratch (ffgp_link_val's arithmetic: a leaf's values are those
+   ffgp_nlml_fused_raw forms for a single kernel, bit for bit), the likelihood and its gradients run as ffgp_nlml_fused_async's own
+   launches model after model on that scratch, and ONE launch applies the links' chain rule (a broadcast scalar length scale: its D
+   effective gradients summed in index order, then one derivative), stores the losses in the trace and takes torch.optim.Adam's step
+   on every raw parameter in place -- the update function of ffgp_train_raw's kernel.
+   Adam state per model: [exp_avg (P) | exp_avg_sq (P)] at stride state_stride >= 2 P doubles, with
+       P = sum over the leaves of (nw + 1 + (center_train ? D : 0)) + 1        (nw = 1 for a broadcast scalar length scale, else D)
+   in the order leaf 0 (w, amp, centre), leaf 1, ..., then diag_add -- the tree's canonical leaf order.  Trace, state, step0, the
+   return value and the failure semantics are ffgp_train_raw's launch-per-stage form: the status is shared by the call's members, and
+   from the first step whose Sigma was not positive definite in ANY member on no parameter of the call moves and the trace holds NaN.
+   Every Sigma extra and both likelihood variants of ffgp_nlml_fused's tree path are accepted.  FFGP_ERR_ARG, before anything is
+   enqueued: F outside 1..16, a member without .tree or with n_leaves outside 2..4, a FFGP_KFUN_RQ leaf (its learnable alpha travels
+   as a host double), cov_dev, D > 128, a leaf without w_dev / amp_dev, center_train on a leaf that is not linear or has no
+   center_dev, state_stride < 2 P.  Synchronous.                                                                               */
+typedef struct {
+  int w_link; double w_c; int w_broadcast;   /* the leaf's raw w_dev holds 1 value (broadcast to all D) or D */
+  int amp_link; double amp_c;
+  int center_train;                          /* FFGP_KFUN_LINEAR: center_dev is a trained raw parameter [D] */
+} ffgp_leaf_links;
+typedef struct {
+  ffgp_leaf_links leaf[4];
+  int dadd_link; double dadd_c;
+  double out_scale;                          /* as ffgp_links.out_scale (0 is read as 1) */
+} ffgp_tree_links;
+int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, int steps, const ffgp_adam* opt,
+                        double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another

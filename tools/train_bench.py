@@ -1,5 +1,10 @@
 """K Adam steps per call (cigp_v10.train_many -> ffgp_train_raw) against the per-step loop through the drop-in modules
-(gate: 200 steps at N = 128 in <= 20 ms).  python tools/train_bench.py [steps]"""
+(gate: 200 steps at N = 128 in <= 20 ms).  python tools/train_bench.py [steps]
+
+python tools/train_bench.py tree [steps]: the same for the reference's demo kernel SumKernel(LinearKernel, MaternKernel) -- train_many
+(ffgp_train_tree_raw) against the per-step loop these models ran on before, both in this process, alternating, three rounds each
+after a warm-up of either; and, for information, the single-kernel Matern model of the same size through the launch-per-stage trainer
+(option train_persist = 0): what the tree pass costs per step."""
 import os
 import sys
 import time
@@ -11,7 +16,9 @@ from bench import synthetic_xy
 from fidelityfusion_amd import kernel
 from fidelityfusion_amd.cigp_v10 import cigp, train_many
 
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+mode = "tree" if len(sys.argv) > 1 and sys.argv[1] == "tree" else "plain"
+args = sys.argv[2:] if mode == "tree" else sys.argv[1:]
+steps = int(args[0]) if args else 200
 for kv in os.environ.get("FFGP_OPTS", "").split(","):      # library options for A/B runs: FFGP_OPTS=small_finish=1
     if kv:
         from fidelityfusion_amd import _lib
@@ -21,11 +28,13 @@ dev = torch.device("cuda", 0)
 torch.set_default_dtype(torch.float64)
 
 
-def make(n, D, d, F=1):
+def make(n, D, d, F=1, kind="ard"):
     ms, xs, ys = [], [], []
     for f in range(F):
         X, Y = synthetic_xy(n, D, d, seed=f)
-        ms.append(cigp(kernel.ARDKernel(D), 1.0).to(dev))
+        k = {"ard": lambda: kernel.ARDKernel(D), "matern": lambda: kernel.MaternKernel(D),
+             "tree": lambda: kernel.SumKernel(kernel.LinearKernel(D), kernel.MaternKernel(D))}[kind]()
+        ms.append(cigp(k, 1.0).to(dev))
         xs.append(torch.tensor(X, device=dev))
         ys.append(torch.tensor(Y, device=dev))
     return ms, xs, ys
@@ -40,6 +49,45 @@ def loop(ms, xs, ys, k):
             loss.backward()
             opt.step()
 
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def tree_mode():
+    from fidelityfusion_amd import _lib
+    print("SumKernel(LinearKernel(2), MaternKernel(2, nu = 2.5)), d = 1, %d Adam steps; ms per call: median [min .. max] of 3 alternating rounds" % steps)
+    for n, F in ((16, 1), (32, 1), (128, 1), (300, 1), (1024, 1), (64, 16)):
+        fused, looped = make(n, 2, 1, F, "tree"), make(n, 2, 1, F, "tree")
+        _, st = train_many(*fused, 5)
+        assert st["fused"] is True, "the tree model was not trained by the library call"
+        loop(*looped, 5)
+        t_many, t_loop = [], []
+        for _ in range(3):
+            t_many.append(timed(lambda: train_many(*fused, steps)))
+            t_loop.append(timed(lambda: loop(*looped, steps)))
+        _lib.set_option("train_persist", 0, 0)
+        try:
+            single = make(n, 2, 1, F, "matern")
+            train_many(*single, 5)
+            t_single = sorted(timed(lambda: train_many(*single, steps)) for _ in range(3))
+        finally:
+            _lib.set_option("train_persist", 1, 0)
+        t_many.sort(), t_loop.sort()
+        print("N=%5d F=%2d  train_many %8.2f [%8.2f .. %8.2f] (%.3f ms/step/model)   per-step loop %8.2f [%8.2f .. %8.2f] (%.3f)   x%.1f"
+              "   | single Matern, launch per stage: %8.2f (%.3f ms/step/model)"
+              % (n, F, t_many[1], t_many[0], t_many[2], t_many[1] / steps / F, t_loop[1], t_loop[0], t_loop[2], t_loop[1] / steps / F,
+                 t_loop[1] / t_many[1], t_single[1], t_single[1] / steps / F), flush=True)
+        assert t_many[2] < t_loop[0], "train_many is not ahead of the per-step loop at N = %d, F = %d" % (n, F)
+
+
+if mode == "tree":
+    tree_mode()
+    sys.exit(0)
 
 for n, D, d, F in ((32, 5, 1, 1), (128, 5, 1, 1), (256, 5, 1, 1), (512, 5, 1, 1), (1024, 8, 1, 1), (128, 5, 1, 8), (64, 5, 1, 16), (300, 5, 1, 3), (512, 5, 1, 4), (1024, 8, 1, 4)):
     ms, xs, ys = make(n, D, d, F)
