@@ -91,6 +91,17 @@ class Residual(C.Structure):
                 ("v_high_dev", _dp), ("v_high_stride", C.c_long), ("rho_last_dev", _dp)]
 
 
+class AcqProblem(C.Structure):
+    """ffgp_acq_problem: a frozen posterior and the acquisition on it (ffgp_acq_optimize)"""
+    _fields_ = [("n", C.c_int), ("D", C.c_int), ("d", C.c_int), ("X_dev", _dp), ("L_dev", _dp), ("ldl", C.c_int), ("alpha_dev", _dp),
+                ("w_dev", _dp), ("amp_dev", _dp), ("clamp_min", C.c_double), ("kfun", C.c_int), ("kparam", C.c_double),
+                ("var_add_all", C.c_double), ("var_floor", C.c_double), ("acq", C.c_int), ("kappa", C.c_double), ("xi", C.c_double),
+                ("f_best", C.c_double)]
+
+
+FFGP_ACQ_UCB, FFGP_ACQ_EI = 0, 1
+FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D, FFGP_ACQ_MAX_STEPS = 256, 16, 4096      # include/ffgp.h
+
 LINK_ID, LINK_INV_ABS_EPS, LINK_EXP_NEG, LINK_INV, LINK_ABS, LINK_EXP_SQ, LINK_SQUARE = range(7)
 
 
@@ -160,6 +171,7 @@ EXPORTS = {
                                           C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                       C.c_long, _dp, C.c_long]),
+    "ffgp_acq_optimize": (C.c_int, [C.c_void_p, C.POINTER(AcqProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),

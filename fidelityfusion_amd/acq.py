@@ -1,0 +1,104 @@
+"""The acquisition optimiser of the Bayesian-optimisation drivers (reference: Bayesian_optimization/acq.py:10-181).
+
+`UCB` and `EI` are the reference's classes on any `mean_func` / `variance_func` callables, as differentiable torch code.
+`optimize_acqf` is its Adam loop with its selection rule (acq.py:48-68).  For a frozen `cigp` (or a `functional.Posterior`) the
+whole loop is ONE kernel launch (`Posterior.optimize_acquisition`, csrc/acq.hip) whenever the posterior is a single radial library
+kernel of the kernel's sizes; otherwise -- and for acquisition objects on arbitrary callables -- it runs step by step.  The start
+points are the caller's: the reference draws them inside the function, in fp32.  PI, KG and PF are not provided: the reference gives
+them no gradient or a random one."""
+import inspect
+import math
+
+import torch
+
+from .posterior import Posterior
+
+
+def _norm_cdf(z):
+    return 0.5 * torch.erfc(-z / math.sqrt(2.0))
+
+
+def _norm_pdf(z):
+    return torch.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi)
+
+
+class UCB:
+    """mean + kappa * sqrt(variance)  (acq.py:118-144)"""
+
+    def __init__(self, mean_func, variance_func, kappa=2.0):
+        self.mean_func = mean_func
+        self.variance_func = variance_func
+        self.kappa = kappa
+
+    def forward(self, X):
+        return self.mean_func(X) + self.kappa * torch.sqrt(self.variance_func(X))
+
+
+class EI:
+    """(mean - f_best - xi) Phi(Z) + std phi(Z), Z = (mean - f_best - xi) / std, std clamped at 1e-9 (acq.py:147-181).  Phi and phi
+    are taken on detached values, as the reference takes them from scipy -- which leaves d/dmean = Phi and d/dstd = phi, the exact
+    derivative -- but stay in the dtype and on the device of the inputs."""
+
+    def __init__(self, mean_func, variance_func, xi=0.01):
+        self.mean_func = mean_func
+        self.variance_func = variance_func
+        self.xi = xi
+
+    def forward(self, X, f_best):
+        mean = self.mean_func(X)
+        std = torch.clamp(torch.sqrt(self.variance_func(X)), min=1e-9)
+        u = mean - f_best - self.xi
+        Z = (u / std).detach()
+        return u * _norm_cdf(Z) + std * _norm_pdf(Z)
+
+
+def select_best(X0, trace, hist):
+    """the reference's selection (acq.py:52-66): best = X0 with the loss at X0; after step k, if that step's loss (evaluated before
+    its update: -trace[k].sum()) is below the best so far, best_x becomes X after that update (hist[k + 1])"""
+    losses = (-trace.sum(1)).tolist()
+    best_x, best_value = X0, losses[0]      # (the loss at X0 is step 0's own loss)
+    for k, loss in enumerate(losses):
+        if loss < best_value:
+            best_value = loss
+            best_x = hist[k + 1]
+    return best_x.detach().clone()
+
+
+def _generic_loop(acq, X0, f_best, steps, lr):
+    """acq.py:48-62 on an acquisition object with forward(X) or forward(X, f_best): plain torch, wherever X0 lives"""
+    two = len(inspect.signature(acq.forward).parameters) == 2
+    X = X0.detach().clone().requires_grad_(True)
+    opt = torch.optim.Adam([X], lr=lr)
+    trace, hist = [], []
+    for _ in range(steps):
+        opt.zero_grad()
+        a = acq.forward(X, f_best) if two else acq.forward(X)
+        (-a.sum()).backward()
+        hist.append(X.detach().clone())
+        trace.append(a.detach().reshape(X.shape[0], -1).sum(1))
+        opt.step()
+    hist.append(X.detach().clone())
+    return X.detach(), torch.stack(trace), torch.stack(hist)
+
+
+def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0,
+                  var_floor=1e-12, return_best_only=True):
+    """The reference's `optimize_acqf` from the start points X0 [Q, D] (untouched): `steps` (its `num_restarts`) Adam iterations at
+    `lr` on loss = -acq(X).sum(), then its selection rule (`select_best`); `return_best_only=False` returns the final points.
+      * model = a `cigp`: the posterior of (x_train, y_train) the model caches, with the noise `cigp.forward` adds to the variance
+        (1 / beta); model = a `functional.Posterior`: as it stands (no noise added).  acq = "ucb" (kappa, var_floor) or "ei" (f_best, xi);
+      * model = an acquisition object (`UCB`, `EI`, anything with forward(X) or forward(X, f_best)): the step-by-step torch loop."""
+    if X0 is None:
+        raise ValueError("optimize_acqf needs the start points X0 [Q, D]")
+    if isinstance(model, Posterior) or hasattr(model, "_cached_posterior"):
+        if isinstance(model, Posterior):
+            post, noise = model, 0.0
+        else:
+            y = y_train[0] if isinstance(y_train, list) else y_train
+            post = model._cached_posterior(x_train, y)[0]
+            noise = float(model.log_beta.detach().exp().pow(-1))
+        X, trace, hist, _ = post.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
+                                                      var_add_all=noise, var_floor=var_floor)
+    else:
+        X, trace, hist = _generic_loop(model, X0, f_best, steps, lr)
+    return select_best(X0, trace, hist) if return_best_only else X

@@ -181,7 +181,11 @@ class Posterior:
     def predict_diff(self, Xs, full_cov=True, var_add_all=0.0):
         """`predict` with autograd w.r.t. the query points: K_s and K_ss come from the differentiable kernel call, the
         solves run on the cached factor (`_PosteriorQuery`).  The hyper-parameters, X and Y are constants here -- use
-        the model's own forward under autograd when their gradients are wanted as well."""
+        the model's own forward under autograd when their gradients are wanted as well.
+        Rounding note: the triangular solves use the handle's inverted diagonal blocks of the factor.  A fused
+        `optimize_acquisition` call rebuilds those blocks from the finished factor, where the factorisation had left its own;
+        the two differ in the last bits, so `predict` / `predict_diff` results after such a call can differ at rounding level
+        from the ones before it (both are solves on the same factor to working precision)."""
         dev, n = self.dev, self.n
         Xsd = Xs.to(device=dev, dtype=torch.float64)
         _check_same_D(self.X, Xsd)
@@ -194,6 +198,88 @@ class Posterior:
             Kss = self.amp.expand(Xsd.shape[0])                  # phi(0) = 1 for every radial profile
         mean, var = _PosteriorQuery.apply(self, Ks, Kss, full_cov)
         return mean, var + var_add_all
+
+    def acq_fusable(self, X0):
+        """whether `optimize_acquisition` from X0 takes the one-launch call (ffgp_acq_optimize): ONE radial library kernel, one output,
+        n and D within the kernel's LDS-tile limits, the start points fp64 on this posterior's GPU"""
+        return (self.tree is None and 0 <= int(self.kfun[0]) < FFGP_KFUN_LINEAR and self.d == 1 and 1 <= self.n <= _lib.FFGP_ACQ_MAX_N
+                and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D and isinstance(X0, torch.Tensor) and X0.is_cuda and X0.device == self.dev
+                and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1 and X0.shape[1] == self.D)
+
+    def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_add_all=0.0, var_floor=1e-12,
+                             betas=(0.9, 0.999), eps=1e-8, state=None):
+        """`steps` Adam iterations of the reference's acquisition optimiser on this frozen posterior
+        (Bayesian_optimization/acq.py:48-68: zero_grad(); loss = -acq(X).sum(); loss.backward(); Adam.step()), from the start points
+        X0 [Q, D] (left untouched).  acq = "ucb": mean + kappa sqrt(max(var, var_floor)); "ei": acq.py:161-181 with f_best, xi.
+        Returns (X [Q, D], trace [steps, Q] = the acquisition values BEFORE each step's update, hist [steps + 1, Q, D] = the points
+        before each step and the final ones, state).  `state` carries Adam's moments and step count into a following call and reports
+        the path as state["fused"]: ONE kernel launch for the whole loop when `acq_fusable(X0)` and steps <= 4096 (csrc/acq.hip),
+        otherwise the per-step loop -- `predict_diff` and torch.optim.Adam -- which covers composed kernels, LinearKernel, several
+        outputs (the values of a point's outputs are summed, as the reference's `.sum()` does) and larger n.
+        The fused call rebuilds the handle's inverted diagonal blocks from the factor (one extra launch per call), so its result
+        depends on the factor alone; later `predict` / `predict_diff` calls then solve with those blocks (see `predict_diff`)."""
+        acq = str(acq).lower()
+        if acq not in ("ucb", "ei"):
+            raise ValueError("acq must be 'ucb' or 'ei', got %r" % (acq,))
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be at least 1")
+        if not isinstance(X0, torch.Tensor) or X0.dim() != 2 or X0.shape[1] != self.D:
+            raise ValueError("X0 must be [Q, %d] like the training inputs" % self.D)
+        step0 = int(state["step"]) if state is not None else 0
+        if self.acq_fusable(X0) and steps <= _lib.FFGP_ACQ_MAX_STEPS:
+            return self._optimize_acq_fused(X0, steps, lr, acq, kappa, xi, f_best, var_add_all, var_floor, betas, eps, state, step0)
+        dev = self.dev
+        X = X0.detach().to(device=dev, dtype=torch.float64).clone().requires_grad_(True)
+        opt = torch.optim.Adam([X], lr=lr, betas=betas, eps=eps)
+        if state is not None:
+            opt.state[X] = {"step": torch.tensor(float(step0)), "exp_avg": _dev(state["exp_avg"], dev).clone(),
+                            "exp_avg_sq": _dev(state["exp_avg_sq"], dev).clone()}
+        Q = X.shape[0]
+        trace = torch.empty((steps, Q), dtype=torch.float64, device=dev)
+        hist = torch.empty((steps + 1, Q, self.D), dtype=torch.float64, device=dev)
+        for k in range(steps):
+            opt.zero_grad()
+            mean, var = self.predict_diff(X, full_cov=False, var_add_all=var_add_all)
+            var = var.reshape(-1, 1)
+            if acq == "ucb":
+                a = mean + kappa * torch.sqrt(torch.clamp_min(var, var_floor))
+            else:
+                s = torch.clamp(torch.sqrt(var), min=1e-9)
+                u = mean - f_best - xi
+                Z = (u / s).detach()      # the reference takes Phi and phi from scipy on detached values
+                a = u * (0.5 * torch.erfc(-Z / math.sqrt(2.0))) + s * (torch.exp(-0.5 * Z * Z) / math.sqrt(2.0 * math.pi))
+            (-a.sum()).backward()
+            hist[k] = X.detach()
+            trace[k] = a.detach().sum(1)
+            opt.step()
+        hist[steps] = X.detach()
+        st = opt.state[X]
+        out = {"fused": False, "step": step0 + steps, "exp_avg": st["exp_avg"].detach(), "exp_avg_sq": st["exp_avg_sq"].detach()}
+        return (X.detach().to(device=X0.device, dtype=X0.dtype), trace.to(X0.device), hist.to(X0.device), out)
+
+    @torch.no_grad()
+    def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_add_all, var_floor, betas, eps, state, step0):
+        dev, n, Q, D = self.dev, self.n, X0.shape[0], self.D
+        if self.alpha is None:
+            self._solve_alpha()
+        alpha = self.alpha.reshape(-1).contiguous()
+        X = X0.detach().clone().contiguous()
+        buf = torch.zeros((2, Q, D), dtype=torch.float64, device=dev)
+        if state is not None:
+            buf[0] = _dev(state["exp_avg"], dev)
+            buf[1] = _dev(state["exp_avg_sq"], dev)
+        trace = torch.empty((steps, Q), dtype=torch.float64, device=dev)
+        hist = torch.empty((steps + 1, Q, D), dtype=torch.float64, device=dev)
+        p = _lib.AcqProblem(n=n, D=D, d=1, X_dev=self.X.data_ptr(), L_dev=self.W.data_ptr(), ldl=self.ld, alpha_dev=alpha.data_ptr(),
+                            w_dev=self.w.data_ptr(), amp_dev=self.amp.data_ptr(), clamp_min=float(self.clamp), kfun=int(self.kfun[0]),
+                            kparam=float(self.kfun[1]), var_add_all=float(var_add_all), var_floor=float(var_floor),
+                            acq=_lib.FFGP_ACQ_UCB if acq == "ucb" else _lib.FFGP_ACQ_EI, kappa=float(kappa), xi=float(xi),
+                            f_best=float(f_best))
+        opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
+        check(lib.ffgp_acq_optimize(self._h(), C.byref(p), _ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace), _ptr(hist),
+                                    None), "ffgp_acq_optimize")
+        return X, trace, hist, {"fused": True, "step": step0 + steps, "exp_avg": buf[0], "exp_avg_sq": buf[1]}
 
     @torch.no_grad()
     def append(self, X_new, Y_new):

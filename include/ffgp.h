@@ -588,6 +588,51 @@ typedef struct {
 int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, int steps, const ffgp_adam* opt,
                         double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 
+/* K Adam steps of an ACQUISITION optimiser on a frozen posterior in ONE launch -- the reference's second hot loop
+   (Bayesian_optimization/acq.py:48-68: `raw_samples` <= 500 query points, `num_restarts` = 30 iterations of zero_grad();
+   loss = -acq(X).sum(); loss.backward(); Adam.step(), the model untouched).  The loss is a sum of per-point terms and Adam is
+   element-wise: a workgroup owns 16 query points and runs all `steps` iterations on them without any cross-workgroup traffic
+   (csrc/acq.hip), and a point's trajectory does not depend on which other points share the call.
+   The posterior: training inputs X_dev [n, D], the Cholesky factor L_dev (ldl) of Sigma, alpha_dev [n] = Sigma^-1 y (d must be 1: an
+   acquisition value is a scalar per point), ONE radial library kernel in its effective form (w_dev [D], amp_dev, clamp_min, kfun in
+   FFGP_KFUN_SE ... FFGP_KFUN_RQ, kparam), var_add_all as in ffgp_predict.  L^-1 is formed once per call in handle workspace by the
+   library's triangular inverse; the handle's inverted diagonal blocks are rebuilt from L_dev on every call (the result depends on the
+   factor alone, not on what the handle served before) and are left keyed on L_dev, as after ffgp_trtri_diag.
+   Per query point x: k = k(X, x), mean = k^T alpha, V = L^-1 k, var = amp - |V|^2 + var_add_all (phi(0) = 1), and
+       FFGP_ACQ_UCB  a = mean + kappa sqrt(max(var, var_floor))        (no gradient through a variance below the floor: torch's clamp_min)
+       FFGP_ACQ_EI   s = max(sqrt(var), 1e-9), u = mean - f_best - xi, Z = u / s, a = u Phi(Z) + s phi(Z)      (acq.py:161-181; Phi and
+                     phi are constants of the reference's backward pass, which leaves da/dmean = Phi, da/ds = phi: the exact derivative)
+   The loss is -sum a; its input gradient is ffgp_kernel_input_weights' formula with the upstream c_i = -(da/dmean alpha_i - 2 da/dvar B_i),
+   B = L^-T V.  Adam is torch.optim.Adam's update as in ffgp_train_raw (bias corrections per step from step0, the steps already taken);
+   state_dev [2, Q, D] = exp_avg | exp_avg_sq, zero for a fresh optimiser, carried between calls together with step0.
+   Xq_dev [Q, D] is updated in place.  trace_dev [max(steps, 1), Q]: trace[k, j] = a_j at step k, BEFORE that step's update.  Optional:
+   hist_dev [steps + 1, Q, D]: hist[k] = the points before step k, hist[steps] = the final points; grad_dev [Q, D] = the gradient of
+   -sum a at the last evaluation.  steps = 0 is EVALUATE mode: trace[0] and grad_dev at Xq, nothing moves (opt / state_dev may be NULL).
+   FFGP_ERR_ARG, before anything is enqueued (Xq, state and trace untouched): a null pointer, n outside 1..FFGP_ACQ_MAX_N, D outside
+   1..FFGP_ACQ_MAX_D, steps outside 0..FFGP_ACQ_MAX_STEPS, d != 1, ldl < n, kfun = FFGP_KFUN_LINEAR or unknown, unknown acq, Q <= 0,
+   step0 < 0.  Synchronous; returns 0 -- no factorisation runs inside, nothing in it can fail numerically.                         */
+#define FFGP_ACQ_MAX_N 256        /* K_s, V and B of a 16-point tile stay in LDS as [n][16] images */
+#define FFGP_ACQ_MAX_D 16
+#define FFGP_ACQ_MAX_STEPS 4096
+enum { FFGP_ACQ_UCB = 0, FFGP_ACQ_EI = 1 };
+typedef struct {
+  int n, D, d;
+  const double* X_dev;
+  const double* L_dev;
+  int ldl;
+  const double* alpha_dev;
+  const double* w_dev;
+  const double* amp_dev;
+  double clamp_min;
+  int kfun;
+  double kparam;
+  double var_add_all, var_floor;
+  int acq;
+  double kappa, xi, f_best;
+} ffgp_acq_problem;
+int ffgp_acq_optimize(ffgp_handle* h, const ffgp_acq_problem* p, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                      double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another
