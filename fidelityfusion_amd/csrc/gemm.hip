@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "ffgp_internal.h"
+#include "diag_block.h"   // LDS_BARRIER
 
 #define BK 16
 #ifndef FFGP_PD_SMALL
@@ -319,6 +320,138 @@ __device__ __forceinline__ void gemm_tile_fast(const char* __restrict__ baseA, c
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// The 128 x 128 fast tile (PD = 1): the same k loop as gemm_tile_fast<.., 1>, rotated so that its one barrier sits between the MFMAs of
+// kq = 2 and kq = 3 of a k-tile instead of behind the 64th.  In gemm_tile_fast nothing of k-tile t+1 is in registers when the barrier
+// of k-tile t opens, so every wave drains the matrix pipe once per 64 MFMAs (LDS write completion, barrier skew of four waves, the
+// load-issue burst, an LDS read round trip); two waves per SIMD hide each other's drain only while they are out of phase, and a
+// workgroup alone on its CU hides nothing.  Here, per k-tile t reading LDS stage s = t & 1 (operand registers: two sets X, Y):
+//     top          global loads of k-tile t+1                       (buffer loads: SGPR resource + loop-invariant 32-bit lane offset)
+//     kq = 0       Y <- kq 1 of stage s ;  16 MFMAs on X
+//     kq = 1       X <- kq 2 of stage s ;  16 MFMAs on Y ;  wait for the global loads, store k-tile t+1 into stage s^1
+//     kq = 2       Y <- kq 3 of stage s ;  16 MFMAs on X ;  s_waitcnt lgkmcnt(0) + s_barrier   (LDS_BARRIER: global traffic not drained)
+//     kq = 3       X <- kq 0 of stage s^1 ; 16 MFMAs on Y   -- they cover that round trip; the loop closes with X ready
+// The prologue preloads X with kq 0 of k-tile 0 behind its barrier; the last k-tile is peeled and has no loads, stores, barrier or
+// next-stage reads.  Invariants:
+//   I1  a wave reaches the barrier of k-tile t only after all its reads of stage s have returned (the last ones, kq 3, are issued
+//       before the kq 2 MFMAs) and its writes into stage s^1 have completed: the barrier's own lgkmcnt(0) covers both.
+//   I2  behind that barrier a wave reads stage s^1 only; its next write into stage s comes after the kq 1 MFMAs of k-tile t+1, behind
+//       barrier t in program order, and every wave finished reading stage s before barrier t (I1).  Its next write into stage s^1
+//       comes behind barrier t+1, which every wave reaches with its reads of s^1 returned.
+//   I3  per accumulator the MFMAs keep gemm_tile_fast's order (kt ascending, kq ascending inside it, the same negate-A modifier, C
+//       loaded into the accumulators first): the values are the unrotated loop's bit for bit.
+// The compiler's scheduler would undo the rotation (it sinks the next-stage reads below the 64th MFMA, which puts a full LDS round trip
+// in front of the loop's first MFMA again), so the phase order is pinned with sched_barrier.
+// ------------------------------------------------------------------------------------------------------------
+typedef unsigned gemm_v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t gemm_rsrc(const char* base) {   // raw buffer over [base, base + 4 GiB): no stride, no swizzle
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, 0xffffffff, 0x00020000);
+}
+template <int TS>
+__device__ __forceinline__ void gload_buf(__amdgpu_buffer_rsrc_t r, const unsigned (&voff)[Geo<TS>::NLD], d2_t (&v)[Geo<TS>::NLD]) {
+#pragma unroll
+  for (int i = 0; i < Geo<TS>::NLD; ++i) v[i] = __builtin_bit_cast(d2_t, (gemm_v4u)__builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[i], 0, 0));
+}
+
+template <int OPA, int OPB, bool NEG>
+__device__ __forceinline__ void gemm_tile_fast128(const char* __restrict__ baseA, const char* __restrict__ baseB, size_t stepA, size_t stepB,
+                                                  char* __restrict__ baseC, size_t row4_bytes, unsigned voffC, bool load_c, double* smem,
+                                                  int nkt, int tid, const unsigned (&voffA)[4], const unsigned (&voffB)[4],
+                                                  const int (&offA)[4], const int (&offB)[4], int trace_bid) {
+  constexpr int TS = 128, W = 4;
+  constexpr int BUFA = opbuf<OPA, TS>(), BUFB = opbuf<OPB, TS>(), STAGE = BUFA + BUFB;
+  constexpr int subA = (OPA == OP_KMAJOR) ? 256 : 16;
+  constexpr int subB = (OPB == OP_KMAJOR) ? 256 : 16;
+#define GEMM_PIN() __builtin_amdgcn_sched_barrier(0)
+#define GEMM_READ(st, kq, a, b)                                         \
+  do {                                                                  \
+    _Pragma("unroll") for (int i = 0; i < W; ++i) a[i] = (st)[offA[kq] + i * subA];        \
+    _Pragma("unroll") for (int j = 0; j < W; ++j) b[j] = (st)[BUFA + offB[kq] + j * subB]; \
+    GEMM_PIN();                                                         \
+  } while (0)
+#define GEMM_MFMA(a, b)                                                 \
+  do {                                                                  \
+    _Pragma("unroll") for (int i = 0; i < W; ++i)                       \
+      _Pragma("unroll") for (int j = 0; j < W; ++j)                     \
+        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, NEG ? 1 : 0); /* blgp bit 0: -A */ \
+    GEMM_PIN();                                                         \
+  } while (0)
+  d2_t ra[4], rb[4];
+  gload_buf<TS>(gemm_rsrc(baseA), voffA, ra);
+  gload_buf<TS>(gemm_rsrc(baseB), voffB, rb);
+  d4_t acc[W][W];
+  if (load_c) {
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const char* rowb = baseC + (size_t)(i * 4 + r) * row4_bytes;
+#pragma unroll
+        for (int j = 0; j < W; ++j) acc[i][j][r] = *reinterpret_cast<const double*>(rowb + voffC + j * 128);
+      }
+  } else {
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+#pragma unroll
+      for (int j = 0; j < W; ++j) acc[i][j] = (d4_t){0.0, 0.0, 0.0, 0.0};
+  }
+  sstore<OPA, TS>(smem, tid, ra);
+  sstore<OPB, TS>(smem + BUFA, tid, rb);
+  LDS_BARRIER();      // (the C loads stay in flight: the first MFMA waits for them)
+#ifdef FFGP_GEMM_TRACE
+  if (tid == 0 && ffgp_trace_buf) ffgp_trace_buf[(size_t)trace_bid * 8 + 1] = __builtin_readcyclecounter();
+#endif
+  double xa[W], xb[W], ya[W], yb[W];
+  GEMM_PIN();
+  GEMM_READ(smem, 0, xa, xb);
+  for (int kt = 0; kt + 1 < nkt; ++kt) {
+    const double* sS = smem + (kt & 1) * STAGE;          // stage s
+    double* sN = smem + ((kt & 1) ^ 1) * STAGE;          // stage s^1
+    baseA += stepA;
+    baseB += stepB;
+    gload_buf<TS>(gemm_rsrc(baseA), voffA, ra);
+    gload_buf<TS>(gemm_rsrc(baseB), voffB, rb);
+    GEMM_PIN();
+    GEMM_READ(sS, 1, ya, yb);
+    GEMM_MFMA(xa, xb);
+    GEMM_READ(sS, 2, xa, xb);
+    GEMM_MFMA(ya, yb);
+    sstore<OPA, TS>(sN, tid, ra);
+    sstore<OPB, TS>(sN + BUFA, tid, rb);
+    GEMM_PIN();
+    GEMM_READ(sS, 3, ya, yb);
+    GEMM_MFMA(xa, xb);
+    LDS_BARRIER();
+    GEMM_PIN();
+    GEMM_READ(sN, 0, xa, xb);
+    GEMM_MFMA(ya, yb);
+  }
+  {
+    const double* sS = smem + ((nkt - 1) & 1) * STAGE;
+    GEMM_READ(sS, 1, ya, yb);
+    GEMM_MFMA(xa, xb);
+    GEMM_READ(sS, 2, xa, xb);
+    GEMM_MFMA(ya, yb);
+    GEMM_READ(sS, 3, ya, yb);
+    GEMM_MFMA(xa, xb);
+    GEMM_MFMA(ya, yb);
+  }
+#undef GEMM_PIN
+#undef GEMM_READ
+#undef GEMM_MFMA
+#ifdef FFGP_GEMM_TRACE
+  if (tid == 0 && ffgp_trace_buf) ffgp_trace_buf[(size_t)trace_bid * 8 + 2] = __builtin_readcyclecounter();
+#endif
+#pragma unroll
+  for (int i = 0; i < W; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      char* rowb = baseC + (size_t)(i * 4 + r) * row4_bytes;
+#pragma unroll
+      for (int j = 0; j < W; ++j) *reinterpret_cast<double*>(rowb + voffC + j * 128) = acc[i][j][r];
+    }
+}
+
 template <int OPA, int OPB, int TM, int TN, bool GUARD>
 __device__ __forceinline__ void gemm_mainloop(const GemmArgs& p, const double* __restrict__ Ag, const double* __restrict__ Bg,
                                               double* smem, int m0, int n0, int kt0, int kt1, int tid,
@@ -407,7 +540,12 @@ __device__ __forceinline__ void gemm_one_tile(const GemmArgs& p, const double* _
     lane_byte_offsets<OPA, TM>(p.lda, tid, voffA);
     lane_byte_offsets<OPB, TN>(p.ldb, tid, voffB);
     const unsigned voffC = (unsigned)((wm * (TM / 2) + (lane >> 4)) * p.ldc + wn * (TN / 2) + (lane & 15)) * 8u;
-    if (p.alpha < 0.0)
+    if constexpr (TM == 128 && TN == 128) {   // the rotated k loop
+      if (p.alpha < 0.0)
+        gemm_tile_fast128<OPA, OPB, true>(bA, bB, stepA, stepB, bC, row4, voffC, p.beta != 0.0, smem, kt1 - kt0, tid, voffA, voffB, offA, offB, bid);
+      else
+        gemm_tile_fast128<OPA, OPB, false>(bA, bB, stepA, stepB, bC, row4, voffC, p.beta != 0.0, smem, kt1 - kt0, tid, voffA, voffB, offA, offB, bid);
+    } else if (p.alpha < 0.0)
       gemm_tile_fast<OPA, OPB, TM, TN, true, PD>(bA, bB, stepA, stepB, bC, row4, voffC, p.beta != 0.0, smem, kt1 - kt0, tid, voffA,
                                              voffB, offA, offB, bid);
     else
