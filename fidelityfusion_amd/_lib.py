@@ -99,7 +99,22 @@ class AcqProblem(C.Structure):
                 ("f_best", C.c_double)]
 
 
+class AcqMember(C.Structure):
+    """ffgp_acq_member: one frozen posterior of a stack and its weights in the stack's mean and variance (ffgp_acq_optimize_stack)"""
+    _fields_ = [("n", C.c_int), ("D", C.c_int), ("d", C.c_int), ("X_dev", _dp), ("L_dev", _dp), ("ldl", C.c_long), ("alpha_dev", _dp),
+                ("w_dev", _dp), ("amp_dev", _dp), ("clamp_min", C.c_double), ("kfun", C.c_int), ("kparam", C.c_double),
+                ("var_add_all", C.c_double), ("mean_coef", C.c_double), ("var_coef", C.c_double)]
+
+
+class AcqStack(C.Structure):
+    """ffgp_acq_stack: the members (a host array), the per-point levels and the acquisition on the combined posterior"""
+    _fields_ = [("F", C.c_int), ("members", C.POINTER(AcqMember)), ("level_dev", _dp), ("var_floor", C.c_double), ("acq", C.c_int),
+                ("kappa", C.c_double), ("xi", C.c_double), ("f_best", C.c_double), ("accumulate_grad", C.c_int)]
+
+
 FFGP_ACQ_UCB, FFGP_ACQ_EI = 0, 1
+FFGP_ACQ_UCB_VAR = 2             # ffgp_acq_optimize_stack only
+FFGP_ACQ_MAX_MEMBERS = 8
 FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D, FFGP_ACQ_MAX_STEPS = 256, 16, 4096      # include/ffgp.h
 
 LINK_ID, LINK_INV_ABS_EPS, LINK_EXP_NEG, LINK_INV, LINK_ABS, LINK_EXP_SQ, LINK_SQUARE = range(7)
@@ -172,6 +187,7 @@ EXPORTS = {
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                       C.c_long, _dp, C.c_long]),
     "ffgp_acq_optimize": (C.c_int, [C.c_void_p, C.POINTER(AcqProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
+    "ffgp_acq_optimize_stack": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),

@@ -5,13 +5,15 @@
 whole loop is ONE kernel launch (`Posterior.optimize_acquisition`, csrc/acq.hip) whenever the posterior is a single radial library
 kernel of the kernel's sizes; otherwise -- and for acquisition objects on arbitrary callables -- it runs step by step.  The start
 points are the caller's: the reference draws them inside the function, in fp32.  PI, KG and PF are not provided: the reference gives
-them no gradient or a random one."""
+them no gradient or a random one.
+`optimize_acqf_mf` is the same loop on the posterior of a multi-fidelity stack (AR, ResGP: a list of per-fidelity `cigp`), the
+drivers' MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 -- every fidelity level in one launch (`PosteriorStack`, csrc/acq_stack.hip)."""
 import inspect
 import math
 
 import torch
 
-from .posterior import Posterior
+from .posterior import Posterior, PosteriorStack
 
 
 def _norm_cdf(z):
@@ -101,4 +103,33 @@ def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, 
                                                       var_add_all=noise, var_floor=var_floor)
     else:
         X, trace, hist = _generic_loop(model, X0, f_best, steps, lr)
+    return select_best(X0, trace, hist) if return_best_only else X
+
+
+def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12,
+                     accumulate_grad=False, return_best_only=True):
+    """The multi-fidelity drivers' acquisition optimiser (DMF_acq.py:226-262) on the posterior of AR / ResGP
+    (FidelityFusion_Models/AR_autoRegression.py:56-89): `models` is the trainers' `gpr_list` (frozen `cigp`), data[f] = (x_f, y_f) the
+    data model f was trained on (for f > 0 the residuals), rho = (rho_0, ...) AR's scale factors -- None: all ones, ResGP.  Member f
+    is model f's cached posterior with that model's 1 / beta added to its variance, weighted by (1, rho_0, rho_1, ...) in the mean
+    and by the squares in the variance.  `level` (int or [Q]) is each start point's `to_fidelity` (None: the top level), so the
+    drivers' loop over the fidelities is ONE call; acq = "ucb", "ei" or "ucb_var" (mean + kappa var, the drivers' UCB_MF with
+    kappa = 0.2 D); `accumulate_grad=True` omits zero_grad as the drivers' loop does.  Returns `select_best` on the trace, or the
+    final points with `return_best_only=False`."""
+    if X0 is None:
+        raise ValueError("optimize_acqf_mf needs the start points X0 [Q, D]")
+    models = list(models)
+    if len(data) != len(models):
+        raise ValueError("data holds one (x, y) pair per model")
+    coefs = [1.0] + ([1.0] * (len(models) - 1) if rho is None else [float(r) for r in rho])
+    if len(coefs) != len(models):
+        raise ValueError("rho holds one factor per model above the first")
+    members, noise = [], []
+    for m, (x, y) in zip(models, data):
+        y = y[0] if isinstance(y, list) else y
+        members.append(m._cached_posterior(x, y)[0])
+        noise.append(float(m.log_beta.detach().exp().pow(-1)))
+    stack = PosteriorStack(members, coefs)
+    X, trace, hist, _ = stack.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
+                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad)
     return select_best(X0, trace, hist) if return_best_only else X

@@ -17,10 +17,7 @@
 #include <cmath>
 #include <vector>
 
-#include "drivers.h"
-
-#define ACQ_T 256
-#define ACQ_TILE 16
+#include "acq_tile.h"
 
 struct AcqArgs {
   const double* X;       // [n, D]
@@ -37,47 +34,6 @@ struct AcqArgs {
   int n, np, D, ldx, Q, steps, kfun, acq;
   double clamp, rinv, var_add, var_floor, kappa, xi, f_best, lr, b1, b2, eps;
 };
-
-// acc += sum_{kb = k0}^{k1 - 1} op(A block) * Bm block kb.  A = L^-1 in global memory: block (bi, kb) as it stands, or (TA) block (kb, bi)
-// transposed.  Bm: an [np][16] LDS image.  The next block's operands are requested before this block's four MFMAs (tr_chain's pattern,
-// train.hip).
-template <bool TA>
-__device__ __forceinline__ void acq_chain(d4_t& acc, int k0, int k1, const double* __restrict__ A, int bi, int lda, const double* Bm, int lane) {
-  if (k0 >= k1) return;
-  const int m = lane & 15, g = lane >> 4;
-  double a[4], b[4];
-  {
-    const double* pa = TA ? A + (size_t)(16 * k0) * lda + 16 * bi : A + (size_t)(16 * bi) * lda + 16 * k0;
-    const double* pb = Bm + k0 * 256;
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) {
-      const int k = kq * 4 + g;
-      a[kq] = TA ? pa[k * lda + m] : pa[m * lda + k];
-      b[kq] = pb[k * 16 + m];
-    }
-  }
-  for (int kb = k0; kb < k1; ++kb) {
-    double an[4], bn[4];
-    const int kn = min(kb + 1, k1 - 1);      // (the last round re-reads its own block)
-    const double* pa = TA ? A + (size_t)(16 * kn) * lda + 16 * bi : A + (size_t)(16 * bi) * lda + 16 * kn;
-    const double* pb = Bm + kn * 256;
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) {
-      const int k = kq * 4 + g;
-      an[kq] = TA ? pa[k * lda + m] : pa[m * lda + k];
-      bn[kq] = pb[k * 16 + m];
-    }
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kq], b[kq], acc, 0, 0, 0);
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) {
-      a[kq] = an[kq];
-      b[kq] = bn[kq];
-    }
-  }
-}
-// block dealt to `wave` in round q: forwards and backwards in turn, so that the chains' lengths (bi + 1, nb - bi) even out
-__device__ __forceinline__ int acq_deal(int q, int wave) { return 4 * q + ((q & 1) ? 3 - wave : wave); }
 
 // LDS, in doubles: three [np][16] images (the second at least 256 DM: it also carries the gradient partials), X [np][DM], alpha [np],
 // the tile's points [16][DM], w^2 [DM], two [16][16] reduction pads

@@ -51,6 +51,46 @@ int main() {
     std::memset(kg, 0, sizeof kg);
     EXPECT(ffgp_assemble_pair(nullptr, &x, 1, &x, 1, 1, kd, FFGP_KOP_SUM, nullptr, nullptr, 0, nullptr, 0, 0.0, 0.0, &x, 2, 0) < 0);
     EXPECT(ffgp_kernel_grad_pair(nullptr, &x, 1, &x, 1, 1, kd, FFGP_KOP_PRODUCT, &x, 2, kg) < 0);
+    // the acquisition optimiser on a stack of posteriors: every refusal comes before the handle or a member is dereferenced
+    ffgp_acq_member mem[2];
+    std::memset(mem, 0, sizeof mem);
+    for (ffgp_acq_member& m : mem) {
+      m.n = 4; m.D = 1; m.d = 1; m.ldl = 4; m.kfun = FFGP_KFUN_SE; m.kparam = 1.0; m.mean_coef = 1.0; m.var_coef = 1.0;
+      m.X_dev = m.L_dev = m.alpha_dev = m.w_dev = m.amp_dev = &x;
+    }
+    ffgp_acq_stack stk;
+    std::memset(&stk, 0, sizeof stk);
+    stk.F = 2; stk.members = mem; stk.acq = FFGP_ACQ_UCB_VAR;
+    ffgp_handle* fake = reinterpret_cast<ffgp_handle*>(0x1);      // never dereferenced by a refused call
+    EXPECT(ffgp_acq_optimize_stack(nullptr, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, nullptr, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, nullptr, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, FFGP_ACQ_MAX_STEPS + 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, nullptr, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, nullptr, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, -1, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, nullptr, nullptr, nullptr) == FFGP_ERR_ARG);
+    stk.F = 0;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    stk.F = FFGP_ACQ_MAX_MEMBERS + 1;      // (the table holds two members: the count is refused before any is read)
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    stk.F = 2; stk.members = nullptr;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    stk.members = mem; stk.acq = 3;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    stk.acq = FFGP_ACQ_EI; mem[1].D = 2;      // members whose D differ
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].D = 1; mem[1].n = FFGP_ACQ_MAX_N + 1; mem[1].ldl = 512;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].n = 4; mem[1].ldl = 3;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].ldl = 4; mem[1].kfun = FFGP_KFUN_LINEAR;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].kfun = FFGP_KFUN_SE; mem[1].d = 2;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].d = 1; mem[0].alpha_dev = nullptr;
+    EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     std::printf("asan_host_check: no device -- argument / no-device paths clean\n");
     return 0;
   }

@@ -323,6 +323,162 @@ class Posterior:
         self.alpha = None
 
 
+class PosteriorStack:
+    """A stack of frozen per-fidelity posteriors queried as ONE model: the posterior of the reference's AR / ResGP / CAR
+    (FidelityFusion_Models/AR_autoRegression.py:56-89)
+        mean = sum_f mean_coef_f mean_f,   var = sum_f var_coef_f var_f      over the members 0..level (`to_fidelity`)
+    with mean_coefs = (1, rho_0, rho_1, ...) for AR and all ones for ResGP; `var_coefs` defaults to mean_coefs^2.  Every member is a
+    `Posterior` on the same GPU with the same input dimension; the members' n and kernels are their own."""
+
+    def __init__(self, members, mean_coefs, var_coefs=None):
+        members = list(members)
+        if not members or not all(isinstance(m, Posterior) for m in members):
+            raise ValueError("members must be a non-empty list of Posterior")
+        if any(m.dev != members[0].dev or m.D != members[0].D for m in members):
+            raise ValueError("the members of a PosteriorStack share one device and one input dimension")
+        self.members = members
+        self.mean_coefs = [float(c) for c in mean_coefs]
+        self.var_coefs = [c * c for c in self.mean_coefs] if var_coefs is None else [float(c) for c in var_coefs]
+        if len(self.mean_coefs) != len(members) or len(self.var_coefs) != len(members):
+            raise ValueError("one mean coefficient and one variance coefficient per member")
+        self.dev, self.D, self.F = members[0].dev, members[0].D, len(members)
+
+    def _var_adds(self, var_adds):
+        va = [0.0] * self.F if var_adds is None else [float(v) for v in var_adds]
+        if len(va) != self.F:
+            raise ValueError("var_adds holds one value per member")
+        return va
+
+    def _level(self, level, Q):
+        """None, or an int32 tensor [Q] on the stack's device with values in 0..F-1 (an int applies to every point)"""
+        if level is None:
+            return None
+        if isinstance(level, torch.Tensor):
+            lv = level.to(device=self.dev, dtype=torch.int32).reshape(-1).contiguous()
+        else:
+            lv = torch.full((Q,), int(level), dtype=torch.int32, device=self.dev)
+        if lv.shape[0] != Q or int(lv.min()) < 0 or int(lv.max()) >= self.F:
+            raise ValueError("level must hold %d values in 0..%d" % (Q, self.F - 1))
+        return lv
+
+    def predict_diff(self, Xs, level=None, var_adds=None):
+        """The combined mean [nt, d] and diagonal variance [nt] at Xs, differentiable w.r.t. Xs (the members' `predict_diff`);
+        `level` (int or [nt]) cuts the sums after member level[q]; `var_adds[f]` is member f's noise (its 1 / beta)."""
+        va = self._var_adds(var_adds)
+        lv = self._level(level, Xs.shape[0])
+        top = self.F - 1 if lv is None else int(lv.max())
+        mean = var = None
+        for f in range(top + 1):
+            m, v = self.members[f].predict_diff(Xs, full_cov=False, var_add_all=va[f])
+            cm, cv = self.mean_coefs[f], self.var_coefs[f]
+            if lv is not None:
+                on = (lv >= f).to(torch.float64)
+                m, v = m * on.unsqueeze(1), v * on
+            mean = cm * m if mean is None else mean + cm * m
+            var = cv * v if var is None else var + cv * v
+        return mean, var
+
+    def acq_fusable(self, X0):
+        """whether `optimize_acquisition` from X0 takes the one-launch call (ffgp_acq_optimize_stack)"""
+        return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_fusable(X0) for m in self.members)
+
+    def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12, betas=(0.9, 0.999),
+                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None):
+        """`Posterior.optimize_acquisition` on the stack's posterior, with the same return tuple (X, trace, hist, state).
+        acq = "ucb" / "ei" as there, or "ucb_var": mean + kappa var, the multi-fidelity drivers' form
+        (MF_BayesianOptimization/Discrete/DMF_acq.py:49-63).  `level` (int or [Q]) gives every point its own `to_fidelity`, so one
+        call optimises the acquisition at every fidelity; `accumulate_grad=True` runs the drivers' loop as it stands
+        (DMF_acq.py:246-255: no zero_grad, Adam sees the running sum of the gradients; the sum travels as state["grad_sum"]).
+        ONE kernel launch (csrc/acq_stack.hip) when every member is `acq_fusable` and there are at most 8 of them, otherwise the
+        per-step loop on `predict_diff` and torch.optim.Adam; state["fused"] says which."""
+        acq = str(acq).lower()
+        if acq not in ("ucb", "ei", "ucb_var"):
+            raise ValueError("acq must be 'ucb', 'ei' or 'ucb_var', got %r" % (acq,))
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError("steps must be at least 1")
+        if not isinstance(X0, torch.Tensor) or X0.dim() != 2 or X0.shape[1] != self.D:
+            raise ValueError("X0 must be [Q, %d] like the training inputs" % self.D)
+        va = self._var_adds(var_adds)
+        lv = self._level(level, X0.shape[0])
+        step0 = int(state["step"]) if state is not None else 0
+        if self.acq_fusable(X0) and steps <= _lib.FFGP_ACQ_MAX_STEPS:
+            return self._optimize_acq_fused(X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0)
+        dev = self.dev
+        X = X0.detach().to(device=dev, dtype=torch.float64).clone().requires_grad_(True)
+        opt = torch.optim.Adam([X], lr=lr, betas=betas, eps=eps)
+        if state is not None:
+            opt.state[X] = {"step": torch.tensor(float(step0)), "exp_avg": _dev(state["exp_avg"], dev).clone(),
+                            "exp_avg_sq": _dev(state["exp_avg_sq"], dev).clone()}
+            if accumulate_grad and state.get("grad_sum") is not None:
+                X.grad = _dev(state["grad_sum"], dev).clone()
+        Q = X.shape[0]
+        trace = torch.empty((steps, Q), dtype=torch.float64, device=dev)
+        hist = torch.empty((steps + 1, Q, self.D), dtype=torch.float64, device=dev)
+        for k in range(steps):
+            if not accumulate_grad:
+                opt.zero_grad()
+            mean, var = self.predict_diff(X, level=lv, var_adds=va)
+            var = var.reshape(-1, 1)
+            if acq == "ucb":
+                a = mean + kappa * torch.sqrt(torch.clamp_min(var, var_floor))
+            elif acq == "ucb_var":
+                a = mean + kappa * var
+            else:
+                s = torch.clamp(torch.sqrt(var), min=1e-9)
+                u = mean - f_best - xi
+                Z = (u / s).detach()      # the reference takes Phi and phi from scipy on detached values
+                a = u * (0.5 * torch.erfc(-Z / math.sqrt(2.0))) + s * (torch.exp(-0.5 * Z * Z) / math.sqrt(2.0 * math.pi))
+            (-a.sum()).backward()
+            hist[k] = X.detach()
+            trace[k] = a.detach().sum(1)
+            opt.step()
+        hist[steps] = X.detach()
+        st = opt.state[X]
+        out = {"fused": False, "step": step0 + steps, "exp_avg": st["exp_avg"].detach(), "exp_avg_sq": st["exp_avg_sq"].detach()}
+        if accumulate_grad:
+            out["grad_sum"] = X.grad.detach().clone()
+        return (X.detach().to(device=X0.device, dtype=X0.dtype), trace.to(X0.device), hist.to(X0.device), out)
+
+    def _member_table(self, va, keep):
+        """the ctypes array of ffgp_acq_member; `keep` collects the tensors its pointers refer to"""
+        tab = (_lib.AcqMember * self.F)()
+        for f, m in enumerate(self.members):
+            if m.alpha is None:
+                m._solve_alpha()
+            alpha = m.alpha.reshape(-1).contiguous()
+            keep.append(alpha)
+            tab[f] = _lib.AcqMember(n=m.n, D=m.D, d=1, X_dev=m.X.data_ptr(), L_dev=m.W.data_ptr(), ldl=m.ld, alpha_dev=alpha.data_ptr(),
+                                    w_dev=m.w.data_ptr(), amp_dev=m.amp.data_ptr(), clamp_min=float(m.clamp), kfun=int(m.kfun[0]),
+                                    kparam=float(m.kfun[1]), var_add_all=va[f], mean_coef=self.mean_coefs[f], var_coef=self.var_coefs[f])
+        return tab
+
+    @torch.no_grad()
+    def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0):
+        dev, Q, D = self.dev, X0.shape[0], self.D
+        keep = []
+        tab = self._member_table(va, keep)
+        X = X0.detach().clone().contiguous()
+        buf = torch.zeros((3 if accumulate_grad else 2, Q, D), dtype=torch.float64, device=dev)
+        if state is not None:
+            buf[0] = _dev(state["exp_avg"], dev)
+            buf[1] = _dev(state["exp_avg_sq"], dev)
+            if accumulate_grad and state.get("grad_sum") is not None:
+                buf[2] = _dev(state["grad_sum"], dev)
+        trace = torch.empty((steps, Q), dtype=torch.float64, device=dev)
+        hist = torch.empty((steps + 1, Q, D), dtype=torch.float64, device=dev)
+        code = {"ucb": _lib.FFGP_ACQ_UCB, "ei": _lib.FFGP_ACQ_EI, "ucb_var": _lib.FFGP_ACQ_UCB_VAR}[acq]
+        s = _lib.AcqStack(F=self.F, members=tab, level_dev=lv.data_ptr() if lv is not None else None, var_floor=float(var_floor), acq=code,
+                          kappa=float(kappa), xi=float(xi), f_best=float(f_best), accumulate_grad=1 if accumulate_grad else 0)
+        opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
+        check(lib.ffgp_acq_optimize_stack(self.members[0]._h(), C.byref(s), _ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace),
+                                          _ptr(hist), None), "ffgp_acq_optimize_stack")
+        out = {"fused": True, "step": step0 + steps, "exp_avg": buf[0], "exp_avg_sq": buf[1]}
+        if accumulate_grad:
+            out["grad_sum"] = buf[2]
+        return X, trace, hist, out
+
+
 class PosteriorCache:
     """Keeps the `Posterior` of a model while the SAME tensor objects (training inputs, targets, every parameter) come
     back with unchanged in-place version counters: in-place updates bump `_version`, `p.data = ...` moves the pointer,

@@ -633,6 +633,44 @@ typedef struct {
 int ffgp_acq_optimize(ffgp_handle* h, const ffgp_acq_problem* p, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
                       double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* The same loop on a STACK of frozen posteriors -- the multi-fidelity drivers' acquisition optimiser
+   (MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 on AR / ResGP / CAR: FidelityFusion_Models/AR_autoRegression.py:56-89) -- in
+   ONE launch (csrc/acq_stack.hip).  Every member is a posterior as in ffgp_acq_problem, within that entry's limits, all of the same D;
+   per query point q
+       mean = sum_f on_f mean_coef_f (k_f^T alpha_f),   var = sum_f on_f var_coef_f (amp_f - |L_f^-1 k_f|^2 + var_add_all_f),
+       on_f = (f <= level[q])      (level_dev NULL: every member; AR's `to_fidelity`, per point)
+   and the acquisition value on (mean, var): FFGP_ACQ_UCB and FFGP_ACQ_EI exactly as ffgp_acq_optimize defines them, or
+       FFGP_ACQ_UCB_VAR  a = mean + kappa var      (DMF_acq.py:49-63; this entry only)
+   `level` enters as an exact 0 / 1 factor on a member's coefficients: a point's trajectory does not depend on its tile, its
+   neighbours or their levels, and level = k everywhere is the stack cut after member k, bit for bit.  L_f^-1 of every member is
+   formed once per call in handle workspace; the handle's inverted diagonal blocks are rebuilt before each and are left keyed on the
+   LAST member's factor.  Xq, trace, hist, grad, step0, opt and evaluate mode (steps = 0) keep ffgp_acq_optimize's contract.
+   state_dev is [2, Q, D] = exp_avg | exp_avg_sq, or with accumulate_grad [3, Q, D]: the third plane is the gradient accumulator --
+   the driver's loop never calls zero_grad (DMF_acq.py:246-255), so the gradient Adam sees at step k is the sum of the gradients of
+   steps 0..k; zero for a fresh optimiser, carried between calls like the moments.  grad_dev is the last evaluation's own gradient.
+   FFGP_ERR_ARG, before anything is enqueued (Xq, state and trace untouched): a null pointer (level_dev, hist_dev and grad_dev may be
+   NULL), F outside 1..FFGP_ACQ_MAX_MEMBERS, a member outside ffgp_acq_optimize's limits (n, D, d != 1, ldl < n or beyond int, kfun),
+   members whose D differ, an unknown acq, Q <= 0, steps outside 0..FFGP_ACQ_MAX_STEPS, step0 < 0.  level values are read as
+   min(level, F - 1); a negative level switches every member off.  Synchronous; returns 0.                                        */
+#define FFGP_ACQ_MAX_MEMBERS 8
+#define FFGP_ACQ_UCB_VAR 2   /* a = mean + kappa * var  (DMF_acq.py:49-63); stack entry only */
+typedef struct {             /* one frozen member: the posterior fields of ffgp_acq_problem */
+  int n, D, d;
+  const double *X_dev, *L_dev; long ldl;
+  const double *alpha_dev, *w_dev, *amp_dev;
+  double clamp_min; int kfun; double kparam;
+  double var_add_all;        /* this member's 1/beta */
+  double mean_coef, var_coef;/* its weight in the stack's mean and variance (AR: rho, rho^2) */
+} ffgp_acq_member;
+typedef struct {
+  int F; const ffgp_acq_member* members;   /* host array */
+  const int* level_dev;      /* [Q] or NULL: point q sees members 0..level[q] (to_fidelity); NULL = all */
+  double var_floor; int acq; double kappa, xi, f_best;
+  int accumulate_grad;       /* 1: no zero_grad between steps, as DMF_acq.py:246-255 runs */
+} ffgp_acq_stack;
+int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                            double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another
