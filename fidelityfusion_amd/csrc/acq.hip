@@ -14,9 +14,6 @@
 //   5. torch.optim.Adam's update (ffgp_adam_update) by the thread that owns (j, dim): x, exp_avg and exp_avg_sq live in its registers
 //      for the whole call
 // Nothing of a point's arithmetic depends on its column or tile: a point run alone follows the same trajectory bit for bit.
-#include <cmath>
-#include <vector>
-
 #include "acq_tile.h"
 
 struct AcqArgs {
@@ -34,13 +31,6 @@ struct AcqArgs {
   int n, np, D, ldx, Q, steps, kfun, acq;
   double clamp, rinv, var_add, var_floor, kappa, xi, f_best, lr, b1, b2, eps;
 };
-
-// LDS, in doubles: three [np][16] images (the second at least 256 DM: it also carries the gradient partials), X [np][DM], alpha [np],
-// the tile's points [16][DM], w^2 [DM], two [16][16] reduction pads
-static constexpr size_t acq_lds_doubles(int np, int DM) {
-  const size_t img = (size_t)np * 16, img1 = img > (size_t)256 * DM ? img : (size_t)256 * DM;
-  return 2 * img + img1 + (size_t)np * DM + np + 16 * DM + DM + 512;
-}
 
 template <int DM>
 __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
@@ -207,7 +197,6 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
 template <int DM>
 static int acq_launch(ffgp_handle* h, const AcqArgs& a, int grid) {
   const size_t lds = acq_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
-  static_assert(acq_lds_doubles(FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D) * sizeof(double) <= 160 * 1024, "the acquisition kernel's LDS exceeds a CU's 160 KiB");
   // set on every call: the attribute belongs to the current device, and a host-side "already set" table would be shared state between
   // the threads of different handles (a host-side call, nothing is enqueued)
   FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_acq_kernel<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -216,47 +205,31 @@ static int acq_launch(ffgp_handle* h, const AcqArgs& a, int grid) {
   return FFGP_OK;
 }
 
+static int acq_single_launch(ffgp_handle* h, const AcqStackArgs& s, int grid) {
+  const AcqStackMember& m = s.m[0];
+  AcqArgs a;
+  a.X = m.X; a.Linv = m.Linv; a.alpha = m.alpha; a.w = m.w; a.amp = m.amp; a.bc = s.bc;
+  a.Xq = s.Xq; a.state = s.state; a.trace = s.trace; a.hist = s.hist; a.grad = s.grad;
+  a.n = m.n; a.np = m.np; a.D = s.D; a.ldx = m.np; a.Q = s.Q; a.steps = s.steps; a.kfun = m.kfun; a.acq = s.acq;
+  a.clamp = m.clamp; a.rinv = m.rinv; a.var_add = m.var_add; a.var_floor = s.var_floor; a.kappa = s.kappa; a.xi = s.xi; a.f_best = s.f_best;
+  a.lr = s.lr; a.b1 = s.b1; a.b2 = s.b2; a.eps = s.eps;
+  if (s.D <= 2) return acq_launch<2>(h, a, grid);
+  if (s.D <= 8) return acq_launch<8>(h, a, grid);
+  return acq_launch<16>(h, a, grid);
+}
+
+// One posterior is the stack of one member with both coefficients 1, no levels and no accumulation: the checks, the workspace, the
+// triangular inverse and the bias corrections are the stack entry's (acq_run, acq_stack.hip); only the kernel and its launch are this file's.
 int ffgp_acq_optimize(ffgp_handle* h, const ffgp_acq_problem* p, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
                       long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
-  if (!h || !p || !Xq_dev || !trace_dev || Q <= 0 || steps < 0 || steps > FFGP_ACQ_MAX_STEPS || step0 < 0) return FFGP_ERR_ARG;
-  if (steps > 0 && (!opt || !state_dev)) return FFGP_ERR_ARG;
-  if (!p->X_dev || !p->L_dev || !p->alpha_dev || !p->w_dev || !p->amp_dev) return FFGP_ERR_ARG;
-  if (p->n < 1 || p->n > FFGP_ACQ_MAX_N || p->D < 1 || p->D > FFGP_ACQ_MAX_D || p->d != 1 || p->ldl < p->n) return FFGP_ERR_ARG;
-  if (p->kfun < FFGP_KFUN_SE || p->kfun > FFGP_KFUN_RQ) return FFGP_ERR_ARG;      // (the linear kernel's k(x, x) depends on x)
-  if (p->acq != FFGP_ACQ_UCB && p->acq != FFGP_ACQ_EI) return FFGP_ERR_ARG;
-  FFGP_HIP(hipSetDevice(h->device));
-  const int n = p->n, np = ffgp_round_up(n, 16), iters = steps > 0 ? steps : 1;
-  // workspace: [L^-1 (np x np, zero-padded) | TRTRI scratch | bias corrections]
-  const size_t xd = (size_t)np * np, td = (size_t)n * n / 4 + (size_t)n * FFGP_NB + 16;
-  FFGP_CHECK(ffgp_ensure_ws(h, (xd + td + 2 * (size_t)iters) * sizeof(double)));
-  double* X = h->ws;
-  double* T = X + xd;
-  double* bc_dev = T + td;
-  FFGP_CHECK(ffgp_zero_async(h, X, xd * sizeof(double)));
-  // The handle's inverted diagonal blocks are rebuilt from the factor on every call: the blocks a factorisation leaves behind and the ones
-  // ffgp_refresh_dinv forms from the finished factor differ by rounding, and which of the two the store holds depends on what else the
-  // handle served in between -- a trajectory must depend on the factor alone (12 + 18 steps = 30 steps bit for bit).  It also makes
-  // the call independent of the cached-inverse contract: the store is left keyed on L_dev with content that matches it.
-  ffgp_invalidate(h);
-  FFGP_CHECK(ffgp_trtri_impl(h, p->L_dev, n, p->ldl, X, np, T));
-  std::vector<double> bc(2 * (size_t)iters, 1.0);
-  for (int k = 0; k < steps; ++k) {
-    const double t = (double)(step0 + k + 1);
-    bc[2 * k] = 1.0 - std::pow(opt->beta1, t);
-    bc[2 * k + 1] = std::sqrt(1.0 - std::pow(opt->beta2, t));
-  }
-  FFGP_HIP(hipMemcpyAsync(bc_dev, bc.data(), bc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  AcqArgs a;
-  a.X = p->X_dev; a.Linv = X; a.alpha = p->alpha_dev; a.w = p->w_dev; a.amp = p->amp_dev; a.bc = bc_dev;
-  a.Xq = Xq_dev; a.state = state_dev; a.trace = trace_dev; a.hist = hist_dev; a.grad = grad_dev;
-  a.n = n; a.np = np; a.D = p->D; a.ldx = np; a.Q = Q; a.steps = steps; a.kfun = p->kfun; a.acq = p->acq;
-  a.clamp = p->clamp_min; a.rinv = (p->kparam != 0.0) ? 1.0 / p->kparam : 1.0;
-  a.var_add = p->var_add_all; a.var_floor = p->var_floor; a.kappa = p->kappa; a.xi = p->xi; a.f_best = p->f_best;
-  a.lr = opt ? opt->lr : 0.0; a.b1 = opt ? opt->beta1 : 0.0; a.b2 = opt ? opt->beta2 : 0.0; a.eps = opt ? opt->eps : 0.0;
-  const int grid = (Q + ACQ_TILE - 1) / ACQ_TILE;
-  if (p->D <= 2) FFGP_CHECK(acq_launch<2>(h, a, grid));
-  else if (p->D <= 8) FFGP_CHECK(acq_launch<8>(h, a, grid));
-  else FFGP_CHECK(acq_launch<16>(h, a, grid));
-  FFGP_HIP(hipStreamSynchronize(h->stream));
-  return FFGP_OK;
+  if (!p || (p->acq != FFGP_ACQ_UCB && p->acq != FFGP_ACQ_EI)) return FFGP_ERR_ARG;      // FFGP_ACQ_UCB_VAR: the stack entry only
+  ffgp_acq_member m = {};
+  m.n = p->n; m.D = p->D; m.d = p->d;
+  m.X_dev = p->X_dev; m.L_dev = p->L_dev; m.ldl = p->ldl; m.alpha_dev = p->alpha_dev; m.w_dev = p->w_dev; m.amp_dev = p->amp_dev;
+  m.clamp_min = p->clamp_min; m.kfun = p->kfun; m.kparam = p->kparam; m.var_add_all = p->var_add_all;
+  m.mean_coef = 1.0; m.var_coef = 1.0;
+  ffgp_acq_stack s = {};
+  s.F = 1; s.members = &m; s.level_dev = nullptr;
+  s.var_floor = p->var_floor; s.acq = p->acq; s.kappa = p->kappa; s.xi = p->xi; s.f_best = p->f_best; s.accumulate_grad = 0;
+  return acq_run(h, &s, acq_single_launch, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev);
 }

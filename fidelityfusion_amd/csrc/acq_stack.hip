@@ -22,35 +22,6 @@
 
 #include "acq_tile.h"
 
-struct AcqStackMember {
-  const double* X;       // [n, D]
-  const double* Linv;    // [np, np], zero above the diagonal and in the padding
-  const double* alpha;   // [n]
-  const double* w;       // [D]
-  const double* amp;
-  double clamp, rinv, var_add, mean_coef, var_coef;
-  int n, np, kfun, pad;
-};
-
-struct AcqStackArgs {
-  AcqStackMember m[FFGP_ACQ_MAX_MEMBERS];
-  const int* level;      // [Q] or null
-  const double* bc;      // [2 steps] bias corrections
-  double* Xq;            // [Q, D]
-  double* state;         // [2 or 3, Q, D] or null (evaluate mode)
-  double* trace;         // [max(steps, 1), Q]
-  double* hist;          // [steps + 1, Q, D] or null
-  double* grad;          // [Q, D] or null
-  int F, npmax, D, Q, steps, acq, accumulate;
-  double var_floor, kappa, xi, f_best, lr, b1, b2, eps;
-};
-
-// LDS, in doubles, sized by the largest member (np = the largest np_f): acq.hip's layout
-static constexpr size_t acq_stack_lds_doubles(int np, int DM) {
-  const size_t img = (size_t)np * 16, img1 = img > (size_t)256 * DM ? img : (size_t)256 * DM;
-  return 2 * img + img1 + (size_t)np * DM + np + 16 * DM + DM + 512;
-}
-
 // A workgroup-uniform value kept in a vector register: the member table's fields on top of acq.hip's arguments are more uniform
 // values than the scalar file holds, and the vector file has the room (a scalar spill would cost the kernel a private segment).
 template <class T>
@@ -272,17 +243,22 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_stack_acq_kernel(AcqStackArgs a) {
 
 template <int DM>
 static int acq_stack_launch(ffgp_handle* h, const AcqStackArgs& a, int grid) {
-  const size_t lds = acq_stack_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
-  static_assert(acq_stack_lds_doubles(FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D) * sizeof(double) <= 160 * 1024, "the stack kernel's LDS exceeds a CU's 160 KiB");
+  const size_t lds = acq_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
   // set on every call, as acq.hip does: the attribute belongs to the current device
   FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_stack_acq_kernel<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(ffgp_stack_acq_kernel<DM>, dim3(grid), dim3(ACQ_T), acq_stack_lds_doubles(a.npmax, DM) * sizeof(double), h->stream, a);
+  hipLaunchKernelGGL(ffgp_stack_acq_kernel<DM>, dim3(grid), dim3(ACQ_T), acq_lds_doubles(a.npmax, DM) * sizeof(double), h->stream, a);
   if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
   return FFGP_OK;
 }
 
-int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
-                            long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid) {
+  if (a.D <= 2) return acq_stack_launch<2>(h, a, grid);
+  if (a.D <= 8) return acq_stack_launch<8>(h, a, grid);
+  return acq_stack_launch<16>(h, a, grid);
+}
+
+int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
   if (!h || !s || !Xq_dev || !trace_dev || Q <= 0 || steps < 0 || steps > FFGP_ACQ_MAX_STEPS || step0 < 0) return FFGP_ERR_ARG;
   if (steps > 0 && (!opt || !state_dev)) return FFGP_ERR_ARG;
   if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members) return FFGP_ERR_ARG;
@@ -319,7 +295,10 @@ int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_
     m.X = p.X_dev; m.Linv = X; m.alpha = p.alpha_dev; m.w = p.w_dev; m.amp = p.amp_dev;
     m.clamp = p.clamp_min; m.rinv = (p.kparam != 0.0) ? 1.0 / p.kparam : 1.0; m.var_add = p.var_add_all;
     m.mean_coef = p.mean_coef; m.var_coef = p.var_coef; m.n = n; m.np = np; m.kfun = p.kfun; m.pad = 0;
-    // the handle's inverted diagonal blocks are rebuilt from each factor (see ffgp_acq_optimize): a trajectory depends on the factors alone
+    // The handle's inverted diagonal blocks are rebuilt from each factor on every call: the blocks a factorisation leaves behind and the
+    // ones ffgp_refresh_dinv forms from the finished factor differ by rounding, and which of the two the store holds depends on what else
+    // the handle served in between -- a trajectory must depend on the factors alone (12 + 18 steps = 30 steps bit for bit).  It also
+    // makes the call independent of the cached-inverse contract: the store is left keyed on the last L_dev with content that matches it.
     ffgp_invalidate(h);
     FFGP_CHECK(ffgp_trtri_impl(h, p.L_dev, n, (int)p.ldl, X, np, T));
     X += (size_t)np * np;
@@ -339,9 +318,12 @@ int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_
   a.var_floor = s->var_floor; a.kappa = s->kappa; a.xi = s->xi; a.f_best = s->f_best;
   a.lr = opt ? opt->lr : 0.0; a.b1 = opt ? opt->beta1 : 0.0; a.b2 = opt ? opt->beta2 : 0.0; a.eps = opt ? opt->eps : 0.0;
   const int grid = (Q + ACQ_TILE - 1) / ACQ_TILE;
-  if (D <= 2) FFGP_CHECK(acq_stack_launch<2>(h, a, grid));
-  else if (D <= 8) FFGP_CHECK(acq_stack_launch<8>(h, a, grid));
-  else FFGP_CHECK(acq_stack_launch<16>(h, a, grid));
+  FFGP_CHECK(launch(h, a, grid));
   FFGP_HIP(hipStreamSynchronize(h->stream));
   return FFGP_OK;
+}
+
+int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
+                            long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+  return acq_run(h, s, acq_stack_launch_by_d, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev);
 }

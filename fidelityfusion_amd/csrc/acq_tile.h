@@ -1,6 +1,7 @@
-// The tile arithmetic shared by the acquisition optimisers' kernels (acq.hip: one frozen posterior; acq_stack.hip: a stack of them):
-// a 256-thread workgroup owns 16 query points, K_s / V / B live in LDS as [np][16] images, and V = L^-1 K_s, B = L^-T V are
-// v_mfma_f64_16x16x4_f64 block chains whose A operand, L^-1, is read from global memory / L2 with one block of prefetch.
+// What the acquisition optimisers' two kernels share (acq.hip: one frozen posterior; acq_stack.hip: a stack of them): a 256-thread
+// workgroup owns 16 query points, K_s / V / B live in LDS as [np][16] images, and V = L^-1 K_s, B = L^-T V are v_mfma_f64_16x16x4_f64
+// block chains whose A operand, L^-1, is read from global memory / L2 with one block of prefetch.  The host side exists once: acq_run
+// (acq_stack.hip) serves both entries, a single posterior as the stack of one member.
 #pragma once
 #include "drivers.h"
 
@@ -47,3 +48,38 @@ __device__ __forceinline__ void acq_chain(d4_t& acc, int k0, int k1, const doubl
 }
 // block dealt to `wave` in round q: forwards and backwards in turn, so that the chains' lengths (bi + 1, nb - bi) even out
 __device__ __forceinline__ int acq_deal(int q, int wave) { return 4 * q + ((q & 1) ? 3 - wave : wave); }
+
+// LDS of either kernel, in doubles, sized by the largest posterior of the call: three [np][16] images (the second at least 256 DM: it
+// also carries the gradient partials), X [np][DM], alpha [np], the tile's points [16][DM], w^2 [DM], two [16][16] reduction pads
+static constexpr size_t acq_lds_doubles(int np, int DM) {
+  const size_t img = (size_t)np * 16, img1 = img > (size_t)256 * DM ? img : (size_t)256 * DM;
+  return 2 * img + img1 + (size_t)np * DM + np + 16 * DM + DM + 512;
+}
+static_assert(acq_lds_doubles(FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D) * sizeof(double) <= 160 * 1024, "the acquisition kernels' LDS exceeds a CU's 160 KiB");
+
+// ---- the host side: one driver (acq_run, acq_stack.hip) for both entries; the stack kernel takes AcqStackArgs as it stands
+struct AcqStackMember {
+  const double* X;       // [n, D]
+  const double* Linv;    // [np, np], zero above the diagonal and in the padding
+  const double* alpha;   // [n]
+  const double* w;       // [D]
+  const double* amp;
+  double clamp, rinv, var_add, mean_coef, var_coef;
+  int n, np, kfun, pad;
+};
+struct AcqStackArgs {
+  AcqStackMember m[FFGP_ACQ_MAX_MEMBERS];
+  const int* level;      // [Q] or null
+  const double* bc;      // [2 steps] bias corrections
+  double* Xq;            // [Q, D]
+  double* state;         // [2 or 3, Q, D] or null (evaluate mode)
+  double* trace;         // [max(steps, 1), Q]
+  double* hist;          // [steps + 1, Q, D] or null
+  double* grad;          // [Q, D] or null
+  int F, npmax, D, Q, steps, acq, accumulate;
+  double var_floor, kappa, xi, f_best, lr, b1, b2, eps;
+};
+// Checks the call, forms every member's L^-1 and the bias-correction table in handle workspace, launches through `launch` and waits.
+typedef int (*acq_launch_fn)(ffgp_handle* h, const AcqStackArgs& a, int grid);
+int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev);

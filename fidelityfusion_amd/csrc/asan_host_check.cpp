@@ -91,6 +91,27 @@ int main() {
     EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     mem[1].d = 1; mem[0].alpha_dev = nullptr;
     EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    // the single-posterior entry builds its one-member stack on the host and forwards: its refusals, next to the stack entry's
+    ffgp_acq_problem ap;
+    std::memset(&ap, 0, sizeof ap);
+    ap.n = 4; ap.D = 1; ap.d = 1; ap.ldl = 4; ap.kfun = FFGP_KFUN_SE; ap.kparam = 1.0; ap.acq = FFGP_ACQ_UCB;
+    ap.X_dev = ap.L_dev = ap.alpha_dev = ap.w_dev = ap.amp_dev = &x;
+    EXPECT(ffgp_acq_optimize(nullptr, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize(fake, nullptr, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize(fake, &ap, nullptr, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, nullptr, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, -1, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    ap.n = 0;
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    ap.n = 4; ap.D = FFGP_ACQ_MAX_D + 1;
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    ap.D = 1; ap.d = 2;
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    ap.d = 1; ap.kfun = FFGP_KFUN_LINEAR;
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    ap.kfun = FFGP_KFUN_SE; ap.acq = FFGP_ACQ_UCB_VAR;      // the stack entry only
+    EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     std::printf("asan_host_check: no device -- argument / no-device paths clean\n");
     return 0;
   }

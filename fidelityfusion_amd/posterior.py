@@ -221,65 +221,10 @@ class Posterior:
         acq = str(acq).lower()
         if acq not in ("ucb", "ei"):
             raise ValueError("acq must be 'ucb' or 'ei', got %r" % (acq,))
-        steps = int(steps)
-        if steps < 1:
-            raise ValueError("steps must be at least 1")
-        if not isinstance(X0, torch.Tensor) or X0.dim() != 2 or X0.shape[1] != self.D:
-            raise ValueError("X0 must be [Q, %d] like the training inputs" % self.D)
-        step0 = int(state["step"]) if state is not None else 0
-        if self.acq_fusable(X0) and steps <= _lib.FFGP_ACQ_MAX_STEPS:
-            return self._optimize_acq_fused(X0, steps, lr, acq, kappa, xi, f_best, var_add_all, var_floor, betas, eps, state, step0)
-        dev = self.dev
-        X = X0.detach().to(device=dev, dtype=torch.float64).clone().requires_grad_(True)
-        opt = torch.optim.Adam([X], lr=lr, betas=betas, eps=eps)
-        if state is not None:
-            opt.state[X] = {"step": torch.tensor(float(step0)), "exp_avg": _dev(state["exp_avg"], dev).clone(),
-                            "exp_avg_sq": _dev(state["exp_avg_sq"], dev).clone()}
-        Q = X.shape[0]
-        trace = torch.empty((steps, Q), dtype=torch.float64, device=dev)
-        hist = torch.empty((steps + 1, Q, self.D), dtype=torch.float64, device=dev)
-        for k in range(steps):
-            opt.zero_grad()
-            mean, var = self.predict_diff(X, full_cov=False, var_add_all=var_add_all)
-            var = var.reshape(-1, 1)
-            if acq == "ucb":
-                a = mean + kappa * torch.sqrt(torch.clamp_min(var, var_floor))
-            else:
-                s = torch.clamp(torch.sqrt(var), min=1e-9)
-                u = mean - f_best - xi
-                Z = (u / s).detach()      # the reference takes Phi and phi from scipy on detached values
-                a = u * (0.5 * torch.erfc(-Z / math.sqrt(2.0))) + s * (torch.exp(-0.5 * Z * Z) / math.sqrt(2.0 * math.pi))
-            (-a.sum()).backward()
-            hist[k] = X.detach()
-            trace[k] = a.detach().sum(1)
-            opt.step()
-        hist[steps] = X.detach()
-        st = opt.state[X]
-        out = {"fused": False, "step": step0 + steps, "exp_avg": st["exp_avg"].detach(), "exp_avg_sq": st["exp_avg_sq"].detach()}
-        return (X.detach().to(device=X0.device, dtype=X0.dtype), trace.to(X0.device), hist.to(X0.device), out)
-
-    @torch.no_grad()
-    def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_add_all, var_floor, betas, eps, state, step0):
-        dev, n, Q, D = self.dev, self.n, X0.shape[0], self.D
-        if self.alpha is None:
-            self._solve_alpha()
-        alpha = self.alpha.reshape(-1).contiguous()
-        X = X0.detach().clone().contiguous()
-        buf = torch.zeros((2, Q, D), dtype=torch.float64, device=dev)
-        if state is not None:
-            buf[0] = _dev(state["exp_avg"], dev)
-            buf[1] = _dev(state["exp_avg_sq"], dev)
-        trace = torch.empty((steps, Q), dtype=torch.float64, device=dev)
-        hist = torch.empty((steps + 1, Q, D), dtype=torch.float64, device=dev)
-        p = _lib.AcqProblem(n=n, D=D, d=1, X_dev=self.X.data_ptr(), L_dev=self.W.data_ptr(), ldl=self.ld, alpha_dev=alpha.data_ptr(),
-                            w_dev=self.w.data_ptr(), amp_dev=self.amp.data_ptr(), clamp_min=float(self.clamp), kfun=int(self.kfun[0]),
-                            kparam=float(self.kfun[1]), var_add_all=float(var_add_all), var_floor=float(var_floor),
-                            acq=_lib.FFGP_ACQ_UCB if acq == "ucb" else _lib.FFGP_ACQ_EI, kappa=float(kappa), xi=float(xi),
-                            f_best=float(f_best))
-        opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
-        check(lib.ffgp_acq_optimize(self._h(), C.byref(p), _ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace), _ptr(hist),
-                                    None), "ffgp_acq_optimize")
-        return X, trace, hist, {"fused": True, "step": step0 + steps, "exp_avg": buf[0], "exp_avg_sq": buf[1]}
+        # one posterior is the stack of one member with coefficient 1: the checks, the per-step loop and the fused call live there
+        return _SinglePosterior([self], [1.0]).optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
+                                                                    var_floor=var_floor, betas=betas, eps=eps, var_adds=[var_add_all],
+                                                                    state=state)
 
     @torch.no_grad()
     def append(self, X_new, Y_new):
@@ -456,8 +401,6 @@ class PosteriorStack:
     @torch.no_grad()
     def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0):
         dev, Q, D = self.dev, X0.shape[0], self.D
-        keep = []
-        tab = self._member_table(va, keep)
         X = X0.detach().clone().contiguous()
         buf = torch.zeros((3 if accumulate_grad else 2, Q, D), dtype=torch.float64, device=dev)
         if state is not None:
@@ -468,15 +411,36 @@ class PosteriorStack:
         trace = torch.empty((steps, Q), dtype=torch.float64, device=dev)
         hist = torch.empty((steps + 1, Q, D), dtype=torch.float64, device=dev)
         code = {"ucb": _lib.FFGP_ACQ_UCB, "ei": _lib.FFGP_ACQ_EI, "ucb_var": _lib.FFGP_ACQ_UCB_VAR}[acq]
-        s = _lib.AcqStack(F=self.F, members=tab, level_dev=lv.data_ptr() if lv is not None else None, var_floor=float(var_floor), acq=code,
-                          kappa=float(kappa), xi=float(xi), f_best=float(f_best), accumulate_grad=1 if accumulate_grad else 0)
         opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
-        check(lib.ffgp_acq_optimize_stack(self.members[0]._h(), C.byref(s), _ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace),
-                                          _ptr(hist), None), "ffgp_acq_optimize_stack")
+        self._acq_call(va, lv, dict(var_floor=float(var_floor), acq=code, kappa=float(kappa), xi=float(xi), f_best=float(f_best)), accumulate_grad,
+                       (_ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace), _ptr(hist), None))
         out = {"fused": True, "step": step0 + steps, "exp_avg": buf[0], "exp_avg_sq": buf[1]}
         if accumulate_grad:
             out["grad_sum"] = buf[2]
         return X, trace, hist, out
+
+    def _acq_call(self, va, lv, acq_fields, accumulate_grad, call):
+        """the C entry of the fused call; `call`: its arguments after the problem description"""
+        keep = []
+        s = _lib.AcqStack(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
+                          accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
+        check(lib.ffgp_acq_optimize_stack(self.members[0]._h(), C.byref(s), *call), "ffgp_acq_optimize_stack")
+
+
+class _SinglePosterior(PosteriorStack):
+    """`Posterior.optimize_acquisition`: the stack of that one member with coefficient 1, whose fused call is the single-posterior
+    entry (ffgp_acq_optimize, its own kernel in csrc/acq.hip)"""
+
+    def _acq_call(self, va, lv, acq_fields, accumulate_grad, call):
+        assert self.F == 1 and lv is None and not accumulate_grad, "ffgp_acq_optimize serves one posterior, without levels or accumulation"
+        m = self.members[0]
+        if m.alpha is None:
+            m._solve_alpha()
+        alpha = m.alpha.reshape(-1).contiguous()
+        p = _lib.AcqProblem(n=m.n, D=m.D, d=1, X_dev=m.X.data_ptr(), L_dev=m.W.data_ptr(), ldl=m.ld, alpha_dev=alpha.data_ptr(),
+                            w_dev=m.w.data_ptr(), amp_dev=m.amp.data_ptr(), clamp_min=float(m.clamp), kfun=int(m.kfun[0]),
+                            kparam=float(m.kfun[1]), var_add_all=va[0], **acq_fields)
+        check(lib.ffgp_acq_optimize(m._h(), C.byref(p), *call), "ffgp_acq_optimize")
 
 
 class PosteriorCache:
