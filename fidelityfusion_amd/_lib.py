@@ -99,6 +99,13 @@ class AcqProblem(C.Structure):
                 ("f_best", C.c_double)]
 
 
+class AcqTreeProblem(C.Structure):
+    """ffgp_acq_tree_problem: a frozen posterior on a composed kernel and the acquisition on it (ffgp_acq_optimize_tree)"""
+    _fields_ = [("n", C.c_int), ("D", C.c_int), ("d", C.c_int), ("X_dev", _dp), ("L_dev", _dp), ("ldl", C.c_int), ("alpha_dev", _dp),
+                ("tree", C.POINTER(KTree)), ("var_add_all", C.c_double), ("var_floor", C.c_double), ("acq", C.c_int), ("kappa", C.c_double),
+                ("xi", C.c_double), ("f_best", C.c_double)]
+
+
 class AcqMember(C.Structure):
     """ffgp_acq_member: one frozen posterior of a stack and its weights in the stack's mean and variance (ffgp_acq_optimize_stack)"""
     _fields_ = [("n", C.c_int), ("D", C.c_int), ("d", C.c_int), ("X_dev", _dp), ("L_dev", _dp), ("ldl", C.c_long), ("alpha_dev", _dp),
@@ -187,6 +194,7 @@ EXPORTS = {
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                       C.c_long, _dp, C.c_long]),
     "ffgp_acq_optimize": (C.c_int, [C.c_void_p, C.POINTER(AcqProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
+    "ffgp_acq_optimize_tree": (C.c_int, [C.c_void_p, C.POINTER(AcqTreeProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_stack": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),

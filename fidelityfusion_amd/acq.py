@@ -84,11 +84,13 @@ def _generic_loop(acq, X0, f_best, steps, lr):
 
 
 def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0,
-                  var_floor=1e-12, return_best_only=True):
+                  var_floor=1e-12, return_best_only=True, fuse_composed=False):
     """The reference's `optimize_acqf` from the start points X0 [Q, D] (untouched): `steps` (its `num_restarts`) Adam iterations at
     `lr` on loss = -acq(X).sum(), then its selection rule (`select_best`); `return_best_only=False` returns the final points.
       * model = a `cigp`: the posterior of (x_train, y_train) the model caches, with the noise `cigp.forward` adds to the variance
         (1 / beta); model = a `functional.Posterior`: as it stands (no noise added).  acq = "ucb" (kappa, var_floor) or "ei" (f_best, xi);
+        `fuse_composed=True` runs a composed kernel's loop (SumKernel / ProductKernel trees, the reference's own
+        SumKernel(LinearKernel, MaternKernel)) in one launch as well (`Posterior.optimize_acquisition`, csrc/acq_tree.hip);
       * model = an acquisition object (`UCB`, `EI`, anything with forward(X) or forward(X, f_best)): the step-by-step torch loop."""
     if X0 is None:
         raise ValueError("optimize_acqf needs the start points X0 [Q, D]")
@@ -100,7 +102,7 @@ def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, 
             post = model._cached_posterior(x_train, y)[0]
             noise = float(model.log_beta.detach().exp().pow(-1))
         X, trace, hist, _ = post.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
-                                                      var_add_all=noise, var_floor=var_floor)
+                                                      var_add_all=noise, var_floor=var_floor, fuse_composed=fuse_composed)
     else:
         X, trace, hist = _generic_loop(model, X0, f_best, steps, lr)
     return select_best(X0, trace, hist) if return_best_only else X

@@ -205,7 +205,7 @@ static int acq_launch(ffgp_handle* h, const AcqArgs& a, int grid) {
   return FFGP_OK;
 }
 
-static int acq_single_launch(ffgp_handle* h, const AcqStackArgs& s, int grid) {
+static int acq_single_launch(ffgp_handle* h, const AcqStackArgs& s, int grid, const ffgp_ktree*) {
   const AcqStackMember& m = s.m[0];
   AcqArgs a;
   a.X = m.X; a.Linv = m.Linv; a.alpha = m.alpha; a.w = m.w; a.amp = m.amp; a.bc = s.bc;

@@ -251,25 +251,25 @@ static int acq_stack_launch(ffgp_handle* h, const AcqStackArgs& a, int grid) {
   return FFGP_OK;
 }
 
-static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid) {
+static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree*) {
   if (a.D <= 2) return acq_stack_launch<2>(h, a, grid);
   if (a.D <= 8) return acq_stack_launch<8>(h, a, grid);
   return acq_stack_launch<16>(h, a, grid);
 }
 
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
-            long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree) {
   if (!h || !s || !Xq_dev || !trace_dev || Q <= 0 || steps < 0 || steps > FFGP_ACQ_MAX_STEPS || step0 < 0) return FFGP_ERR_ARG;
   if (steps > 0 && (!opt || !state_dev)) return FFGP_ERR_ARG;
-  if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members) return FFGP_ERR_ARG;
+  if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members || (tree && s->F != 1)) return FFGP_ERR_ARG;
   if (s->acq != FFGP_ACQ_UCB && s->acq != FFGP_ACQ_EI && s->acq != FFGP_ACQ_UCB_VAR) return FFGP_ERR_ARG;
   const int F = s->F, D = s->members[0].D;
   for (int f = 0; f < F; ++f) {
     const ffgp_acq_member& p = s->members[f];
-    if (!p.X_dev || !p.L_dev || !p.alpha_dev || !p.w_dev || !p.amp_dev) return FFGP_ERR_ARG;
+    if (!p.X_dev || !p.L_dev || !p.alpha_dev || (!tree && (!p.w_dev || !p.amp_dev))) return FFGP_ERR_ARG;
     if (p.n < 1 || p.n > FFGP_ACQ_MAX_N || p.D < 1 || p.D > FFGP_ACQ_MAX_D || p.D != D || p.d != 1) return FFGP_ERR_ARG;
     if (p.ldl < p.n || p.ldl > INT_MAX) return FFGP_ERR_ARG;
-    if (p.kfun < FFGP_KFUN_SE || p.kfun > FFGP_KFUN_RQ) return FFGP_ERR_ARG;      // (the linear kernel's k(x, x) depends on x)
+    if (!tree && (p.kfun < FFGP_KFUN_SE || p.kfun > FFGP_KFUN_RQ)) return FFGP_ERR_ARG;      // (the linear kernel's k(x, x) depends on x)
   }
   FFGP_HIP(hipSetDevice(h->device));
   const int iters = steps > 0 ? steps : 1;
@@ -318,7 +318,7 @@ int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, doubl
   a.var_floor = s->var_floor; a.kappa = s->kappa; a.xi = s->xi; a.f_best = s->f_best;
   a.lr = opt ? opt->lr : 0.0; a.b1 = opt ? opt->beta1 : 0.0; a.b2 = opt ? opt->beta2 : 0.0; a.eps = opt ? opt->eps : 0.0;
   const int grid = (Q + ACQ_TILE - 1) / ACQ_TILE;
-  FFGP_CHECK(launch(h, a, grid));
+  FFGP_CHECK(launch(h, a, grid, tree));
   FFGP_HIP(hipStreamSynchronize(h->stream));
   return FFGP_OK;
 }

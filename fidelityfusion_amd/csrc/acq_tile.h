@@ -1,4 +1,5 @@
-// What the acquisition optimisers' two kernels share (acq.hip: one frozen posterior; acq_stack.hip: a stack of them): a 256-thread
+// What the acquisition optimisers' kernels share (acq.hip: one frozen posterior; acq_stack.hip: a stack of them; acq_tree.hip: one
+// posterior on a composed kernel): a 256-thread
 // workgroup owns 16 query points, K_s / V / B live in LDS as [np][16] images, and V = L^-1 K_s, B = L^-T V are v_mfma_f64_16x16x4_f64
 // block chains whose A operand, L^-1, is read from global memory / L2 with one block of prefetch.  The host side exists once: acq_run
 // (acq_stack.hip) serves both entries, a single posterior as the stack of one member.
@@ -80,6 +81,8 @@ struct AcqStackArgs {
   double var_floor, kappa, xi, f_best, lr, b1, b2, eps;
 };
 // Checks the call, forms every member's L^-1 and the bias-correction table in handle workspace, launches through `launch` and waits.
-typedef int (*acq_launch_fn)(ffgp_handle* h, const AcqStackArgs& a, int grid);
+// `tree` (ffgp_acq_optimize_tree only, checked by that entry): the one member's kernel is this composition, so the member carries no
+// w_dev / amp_dev / kfun of its own and those three checks are skipped; it is handed on to `launch`.
+typedef int (*acq_launch_fn)(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree* tree);
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
-            long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree = nullptr);

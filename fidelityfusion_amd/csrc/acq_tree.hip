@@ -1,0 +1,398 @@
+// The acquisition optimiser's Adam loop on a frozen posterior whose kernel is a COMPOSITION -- a SumKernel / ProductKernel tree of 2-4
+// leaves, radial profiles and LinearKernel alike -- in one launch (ffgp_acq_optimize_tree, include/ffgp.h).
+// Reference: Bayesian_optimization/cigp.py:119, GaussianProcess/cigp_v10.py:81 and the two-fidelity models run on
+// SumKernel(LinearKernel(1), MaternKernel(1)); the loop is Bayesian_optimization/acq.py:48-68.  The plan is ffgp_acq_kernel's (acq.hip):
+// a 256-thread workgroup owns 16 query points and runs all the steps, V = L^-1 K_s and B = L^-T V are acq_tile.h's block chains on
+// [np][16] LDS images.  What differs:
+//   * k(X_i, x_j) is the tree of the leaves' values, its nodes rounded one by one as pair.hip's tree_op rounds them;
+//   * there is no derivative image: up to four leaves' factors do not fit beside the three images, so the gradient pass re-evaluates the
+//     leaves from Xs (stage 1's arithmetic again, small beside the two chain passes) and runs the tree's reverse sweep per row.  Two
+//     images remain: K_s -> B, and V -> the gradient partials;
+//   * the leaves' length scales differ, so w_e^2 is folded into every term before the row sum; da/dmean and da/dvar are known before
+//     the gradient pass, so a thread still carries ONE partial of DM doubles;
+//   * k(x, x) depends on x through the linear leaves: var = k(x, x) - |V|^2 + var_add, and the owner of (j, dim) adds
+//     -(da/dvar) dk(x, x)/dx to the loss gradient.  A radial leaf's self value amp phi(max(0, clamp)) is a constant.
+// Per-row derivative of leaf e with respect to x_j (dk/dv_e from the reverse sweep in front):
+//     radial:  -amp_e (-2 phi_e'(s_e)) w_e^2 o (x_j - X_i), zero where s_e < clamp_e;      linear:  amp_e w_e^2 o (X_i - c_e)
+// Nothing of a point's arithmetic depends on its column or tile: a point run alone follows the same trajectory bit for bit.
+#include <climits>
+
+#include "acq_tile.h"
+
+#define ACQ_TREE_MAX 4
+
+struct AcqTreeLeaf {
+  const double* w;       // [D]
+  const double* amp;
+  const double* center;  // [D] or null (the origin); linear leaves only
+  double clamp, rinv;
+  int kfun, pad;
+};
+struct AcqTreeArgs {
+  const double* X;       // [n, D]
+  const double* Linv;    // [np, np], zero above the diagonal and in the padding
+  const double* alpha;   // [n]
+  const double* bc;      // [2 steps] bias corrections
+  double* Xq;            // [Q, D]
+  double* state;         // [2, Q, D] or null (evaluate mode)
+  double* trace;         // [max(steps, 1), Q]
+  double* hist;          // [steps + 1, Q, D] or null
+  double* grad;          // [Q, D] or null
+  AcqTreeLeaf k[ACQ_TREE_MAX];
+  int n, np, D, Q, steps, acq, nl, shape, op[3];
+  double var_add, var_floor, kappa, xi, f_best, lr, b1, b2, eps;
+};
+
+// LDS in doubles: two [np][16] images (the second at least 256 DM: it also carries the gradient partials), X [np][DM], alpha [np], the
+// tile's points [16][DM], per leaf w^2 [DM] and centre [DM], per leaf (amp, clamp, 1 / kparam, self value) [4], two [16][16] reduction pads
+static constexpr size_t acq_tree_lds_doubles(int np, int DM) {
+  const size_t img = (size_t)np * 16, img1 = img > (size_t)256 * DM ? img : (size_t)256 * DM;
+  return img + img1 + (size_t)np * DM + np + 16 * DM + 2 * ACQ_TREE_MAX * DM + 4 * ACQ_TREE_MAX + 512;
+}
+static_assert(acq_tree_lds_doubles(FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D) * sizeof(double) <= 160 * 1024,
+              "the tree acquisition kernel's LDS exceeds a CU's 160 KiB");
+
+// one node: separately rounded product / sum (pair.hip's tree_op)
+__device__ __forceinline__ double acq_tree_op(int op, double x, double y) {
+#pragma clang fp contract(off)
+  const double pr = x * y, sm = x + y;
+  return op == FFGP_KOP_PRODUCT ? pr : sm;
+}
+// the canonical trees of include/ffgp.h on the leaves' values (v[e] = 0 past the last leaf)
+__device__ __forceinline__ double acq_tree_eval(const AcqTreeArgs& a, const double (&v)[ACQ_TREE_MAX]) {
+  const double t0 = acq_tree_op(a.op[0], v[0], v[1]);
+  if (a.nl == 2) return t0;
+  if (a.nl == 3) return acq_tree_op(a.op[1], t0, v[2]);
+  if (a.shape == FFGP_TREE_BALANCED) return acq_tree_op(a.op[2], t0, acq_tree_op(a.op[1], v[2], v[3]));
+  return acq_tree_op(a.op[2], acq_tree_op(a.op[1], t0, v[2]), v[3]);
+}
+// d root / d leaf values (pair.hip's tree_back with upstream 1)
+__device__ __forceinline__ void acq_tree_back(const AcqTreeArgs& a, const double (&v)[ACQ_TREE_MAX], double (&gv)[ACQ_TREE_MAX]) {
+  const double t0 = acq_tree_op(a.op[0], v[0], v[1]);
+  double gt0 = 1.0;
+  gv[2] = 0.0;
+  gv[3] = 0.0;
+  if (a.nl == 3) {
+    const bool pr = a.op[1] == FFGP_KOP_PRODUCT;
+    gt0 = pr ? v[2] : 1.0;
+    gv[2] = pr ? t0 : 1.0;
+  }
+  if (a.nl == 4) {
+    const bool p1 = a.op[1] == FFGP_KOP_PRODUCT, p2 = a.op[2] == FFGP_KOP_PRODUCT;
+    if (a.shape == FFGP_TREE_BALANCED) {
+      const double t1 = acq_tree_op(a.op[1], v[2], v[3]);
+      gt0 = p2 ? t1 : 1.0;
+      const double gt1 = p2 ? t0 : 1.0;
+      gv[2] = p1 ? gt1 * v[3] : gt1;
+      gv[3] = p1 ? gt1 * v[2] : gt1;
+    } else {
+      const double t1 = acq_tree_op(a.op[1], t0, v[2]);
+      const double gt1 = p2 ? v[3] : 1.0;
+      gv[3] = p2 ? t1 : 1.0;
+      gt0 = p1 ? gt1 * v[2] : gt1;
+      gv[2] = p1 ? gt1 * t0 : gt1;
+    }
+  }
+  const bool p0 = a.op[0] == FFGP_KOP_PRODUCT;
+  gv[0] = p0 ? gt0 * v[1] : gt0;
+  gv[1] = p0 ? gt0 * v[0] : gt0;
+}
+
+// a leaf's bilinear form on (training row xr, query point xj): the squared scaled distance, or the scaled dot product about the centre
+template <int DM>
+__device__ __forceinline__ double acq_tree_form(bool lin, const double* xr, const double (&xj)[DM], const double* w2, const double* cen) {
+  double s = 0.0;
+  if (lin) {
+#pragma unroll
+    for (int dd = 0; dd < DM; ++dd) s = __builtin_fma(w2[dd] * (xj[dd] - cen[dd]), xr[dd] - cen[dd], s);
+  } else {
+#pragma unroll
+    for (int dd = 0; dd < DM; ++dd) {
+      const double df = xr[dd] - xj[dd];
+      s = __builtin_fma(w2[dd] * df, df, s);
+    }
+  }
+  return s;
+}
+
+template <int DM>
+__global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
+  extern __shared__ double acq_lds[];
+  const int np = a.np, nb = np >> 4, n = a.n, D = a.D, nl = a.nl;
+  const size_t img = (size_t)np * 16;
+  double* img0 = acq_lds;                                              // K_s, then B = Sigma^-1 K_s
+  double* img1 = img0 + img;                                           // V = L^-1 K_s, then the gradient partials
+  double* Xs = img1 + (img > (size_t)256 * DM ? img : (size_t)256 * DM);
+  double* al = Xs + (size_t)np * DM;
+  double* xq = al + np;
+  double* w2 = xq + 16 * DM;                                           // [leaf][DM]
+  double* cen = w2 + ACQ_TREE_MAX * DM;                                // [leaf][DM]
+  double* lp = cen + ACQ_TREE_MAX * DM;                                // [leaf][amp, clamp, 1 / kparam, radial self value]
+  double* redm = lp + 4 * ACQ_TREE_MAX;
+  double* redv = redm + 256;
+
+  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4, wave = tid >> 6, lane = tid & 63, g = lane >> 4;
+  const int q0 = blockIdx.x * ACQ_TILE;
+  bool lin[ACQ_TREE_MAX];
+#pragma unroll
+  for (int e = 0; e < ACQ_TREE_MAX; ++e) lin[e] = a.k[e].kfun == FFGP_KFUN_LINEAR;
+
+  for (int idx = tid; idx < np * DM; idx += ACQ_T) {
+    const int i = idx / DM, dd = idx % DM;
+    Xs[idx] = (i < n && dd < D) ? a.X[(size_t)i * D + dd] : 0.0;
+  }
+  for (int i = tid; i < np; i += ACQ_T) al[i] = (i < n) ? a.alpha[i] : 0.0;
+#pragma unroll
+  for (int e = 0; e < ACQ_TREE_MAX; ++e) {
+    if (e < nl && tid < DM) {
+      const double wv = (tid < D) ? a.k[e].w[tid] : 0.0;
+      w2[e * DM + tid] = wv * wv;
+      cen[e * DM + tid] = (tid < D && lin[e] && a.k[e].center) ? a.k[e].center[tid] : 0.0;
+    }
+    if (e < nl && tid == 0) {
+      const double amp = a.k[e].amp[0];
+      lp[4 * e] = amp;
+      lp[4 * e + 1] = a.k[e].clamp;
+      lp[4 * e + 2] = a.k[e].rinv;
+      lp[4 * e + 3] = lin[e] ? 0.0 : amp * ffgp_kfun_val(a.k[e].kfun, a.k[e].rinv, fmax(0.0, a.k[e].clamp));
+    }
+  }
+  // the owner of (point j, dimension rg) keeps that coordinate and its Adam moments in registers for the whole call; the columns of a
+  // ragged last tile repeat the last point and write nothing
+  const int qo = q0 + j;
+  const bool owner = rg < DM, live = owner && rg < D && qo < a.Q;
+  double xo = 0.0, mo = 0.0, vo = 0.0;
+  if (owner) {
+    const size_t e = (size_t)min(qo, a.Q - 1) * D + rg;
+    if (rg < D) {
+      xo = a.Xq[e];
+      if (a.steps > 0) {
+        mo = a.state[e];
+        vo = a.state[(size_t)a.Q * D + e];
+      }
+    }
+    xq[j * DM + rg] = xo;
+  }
+  __syncthreads();
+
+  const int iters = a.steps > 0 ? a.steps : 1;
+  for (int k = 0; k < iters; ++k) {
+    // ---- 1. K_s, mean; k(x, x) and its reverse sweep
+    double xj[DM];
+#pragma unroll
+    for (int dd = 0; dd < DM; ++dd) xj[dd] = xq[j * DM + dd];
+    double msum = 0.0;
+    for (int p = 0; p < nb; ++p) {
+      const int i = 16 * p + rg;
+      double v[ACQ_TREE_MAX];
+#pragma unroll
+      for (int e = 0; e < ACQ_TREE_MAX; ++e) {
+        v[e] = 0.0;
+        if (e < nl) {
+          const double s = acq_tree_form<DM>(lin[e], Xs + i * DM, xj, w2 + e * DM, cen + e * DM);
+          v[e] = lp[4 * e] * (lin[e] ? s : ffgp_kfun_val(a.k[e].kfun, lp[4 * e + 2], fmax(s, lp[4 * e + 1])));
+        }
+      }
+      const double kv = (i < n) ? acq_tree_eval(a, v) : 0.0;
+      img0[i * 16 + j] = kv;
+      msum = __builtin_fma(kv, al[i], msum);
+    }
+    redm[rg * 16 + j] = msum;
+    double sv[ACQ_TREE_MAX], gs[ACQ_TREE_MAX];
+#pragma unroll
+    for (int e = 0; e < ACQ_TREE_MAX; ++e) {
+      sv[e] = 0.0;
+      if (e < nl) {
+        sv[e] = lp[4 * e + 3];
+        if (lin[e]) {
+          double s = 0.0;
+#pragma unroll
+          for (int dd = 0; dd < DM; ++dd) {
+            const double df = xj[dd] - cen[e * DM + dd];
+            s = __builtin_fma(w2[e * DM + dd] * df, df, s);
+          }
+          sv[e] = lp[4 * e] * s;
+        }
+      }
+    }
+    const double kss = acq_tree_eval(a, sv);
+    acq_tree_back(a, sv, gs);
+    __syncthreads();
+    double mean = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mean += redm[r * 16 + j];
+
+    // ---- 2. V = L^-1 K_s, |V_j|^2
+    double vvp = 0.0;
+    for (int q = 0; q < 4; ++q) {
+      const int bi = acq_deal(q, wave);
+      if (bi >= nb) continue;
+      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+      acq_chain<false>(acc, 0, bi + 1, a.Linv, bi, np, img0, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        img1[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
+        vvp = __builtin_fma(acc[r], acc[r], vvp);
+      }
+    }
+    redv[rg * 16 + j] = vvp;
+    __syncthreads();
+    double vv = 0.0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) vv += redv[r * 16 + j];
+
+    // ---- 3. B = L^-T V (into the image of K_s)
+    for (int q = 0; q < 4; ++q) {
+      const int bi = acq_deal(q, wave);
+      if (bi >= nb) continue;
+      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+      acq_chain<true>(acc, bi, nb, a.Linv, bi, np, img1, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) img0[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
+    }
+
+    // ---- 4. the acquisition value and its derivatives with respect to mean and variance
+    const double var = kss - vv + a.var_add;
+    double av, gm, gv;
+    if (a.acq == FFGP_ACQ_UCB) {
+      const double sd = sqrt(fmax(var, a.var_floor));
+      av = mean + a.kappa * sd;
+      gm = 1.0;
+      gv = (var >= a.var_floor) ? a.kappa * 0.5 / sd : 0.0;      // torch's clamp_min: no gradient below the floor
+    } else {
+      const double sd = sqrt(var), s = fmax(sd, 1e-9), u = mean - a.f_best - a.xi, Z = u / s;
+      const double Phi = 0.5 * erfc(-Z * 0.70710678118654752440), phi = exp(-0.5 * Z * Z) * 0.39894228040143267794;
+      av = u * Phi + s * phi;
+      gm = Phi;                                   // Phi and phi are constants of the reference's backward pass: exact all the same
+      gv = (sd >= 1e-9) ? phi * 0.5 / sd : 0.0;
+    }
+    __syncthreads();
+
+    // ---- the input gradient: the leaves again from Xs, the reverse sweep per row; partial sums over this thread's rows, then over the
+    //      16 row groups in a fixed order
+    double ga[DM];
+#pragma unroll
+    for (int dd = 0; dd < DM; ++dd) ga[dd] = 0.0;
+    for (int p = 0; p < nb; ++p) {
+      const int i = 16 * p + rg;
+      const double c = (i < n) ? -(gm * al[i] - 2.0 * gv * img0[i * 16 + j]) : 0.0;
+      double v[ACQ_TREE_MAX], dv[ACQ_TREE_MAX], gl[ACQ_TREE_MAX];
+#pragma unroll
+      for (int e = 0; e < ACQ_TREE_MAX; ++e) {
+        v[e] = 0.0;
+        dv[e] = 0.0;
+        if (e < nl) {
+          const double s = acq_tree_form<DM>(lin[e], Xs + i * DM, xj, w2 + e * DM, cen + e * DM);
+          const double amp = lp[4 * e];
+          if (lin[e]) {
+            v[e] = amp * s;
+            dv[e] = amp;
+          } else {
+            const double cl = lp[4 * e + 1], sc = fmax(s, cl);
+            v[e] = amp * ffgp_kfun_val(a.k[e].kfun, lp[4 * e + 2], sc);
+            dv[e] = (i < n && s >= cl) ? -(amp * ffgp_kfun_m2d(a.k[e].kfun, lp[4 * e + 2], sc)) : 0.0;
+          }
+        }
+      }
+      acq_tree_back(a, v, gl);
+#pragma unroll
+      for (int e = 0; e < ACQ_TREE_MAX; ++e) {
+        if (e < nl) {
+          const double wt = c * gl[e] * dv[e];
+          if (lin[e]) {
+#pragma unroll
+            for (int dd = 0; dd < DM; ++dd) ga[dd] = __builtin_fma(wt, w2[e * DM + dd] * (Xs[i * DM + dd] - cen[e * DM + dd]), ga[dd]);
+          } else {
+#pragma unroll
+            for (int dd = 0; dd < DM; ++dd) ga[dd] = __builtin_fma(wt, w2[e * DM + dd] * (xj[dd] - Xs[i * DM + dd]), ga[dd]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int dd = 0; dd < DM; ++dd) img1[(rg * DM + dd) * 16 + j] = ga[dd];
+    __syncthreads();
+
+    // ---- 5. outputs and Adam, by the owner of (j, rg): the row sum, and the self term -(da/dvar) dk(x, x)/dx of the linear leaves
+    if (owner) {
+      double gx = 0.0;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) gx += img1[(r * DM + rg) * 16 + j];
+      double ds = 0.0;
+#pragma unroll
+      for (int e = 0; e < ACQ_TREE_MAX; ++e)
+        if (e < nl && lin[e]) ds = __builtin_fma(gs[e] * (2.0 * lp[4 * e]), w2[e * DM + rg] * (xo - cen[e * DM + rg]), ds);
+      gx -= gv * ds;
+      if (live) {
+        const size_t e = (size_t)qo * D + rg;
+        if (rg == 0) a.trace[(size_t)k * a.Q + qo] = av;
+        if (a.hist) a.hist[(size_t)k * a.Q * D + e] = xo;
+        if (a.grad && k == iters - 1) a.grad[e] = gx;
+      }
+      if (a.steps > 0 && rg < D)
+        ffgp_adam_update(&xo, &mo, &vo, gx, a.lr, a.b1, a.b2, a.eps, a.bc[2 * k], a.bc[2 * k + 1]);
+      xq[j * DM + rg] = xo;
+    }
+    __syncthreads();
+  }
+  if (live && a.steps > 0) {
+    const size_t e = (size_t)qo * D + rg;
+    a.Xq[e] = xo;
+    a.state[e] = mo;
+    a.state[(size_t)a.Q * D + e] = vo;
+    if (a.hist) a.hist[(size_t)a.steps * a.Q * D + e] = xo;
+  }
+}
+
+template <int DM>
+static int acq_tree_launch(ffgp_handle* h, const AcqTreeArgs& a, int grid) {
+  const size_t lds = acq_tree_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
+  // set on every call, as acq.hip does: the attribute belongs to the current device
+  FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_tree_acq_kernel<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(ffgp_tree_acq_kernel<DM>, dim3(grid), dim3(ACQ_T), acq_tree_lds_doubles(a.np, DM) * sizeof(double), h->stream, a);
+  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
+  return FFGP_OK;
+}
+
+// the leaf table travels by value in the kernel's arguments
+static int acq_tree_launch_by_d(ffgp_handle* h, const AcqStackArgs& s, int grid, const ffgp_ktree* t) {
+  const AcqStackMember& m = s.m[0];
+  AcqTreeArgs a = {};
+  a.X = m.X; a.Linv = m.Linv; a.alpha = m.alpha; a.bc = s.bc;
+  a.Xq = s.Xq; a.state = s.state; a.trace = s.trace; a.hist = s.hist; a.grad = s.grad;
+  for (int e = 0; e < ACQ_TREE_MAX; ++e) {
+    const ffgp_kdesc& k = t->leaf[e < t->n_leaves ? e : 0];      // (the entries past the last leaf are never read)
+    a.k[e].w = k.w_dev; a.k[e].amp = k.amp_dev; a.k[e].center = (k.kfun == FFGP_KFUN_LINEAR) ? k.center_dev : nullptr;
+    a.k[e].clamp = k.clamp_min; a.k[e].rinv = (k.kparam != 0.0) ? 1.0 / k.kparam : 1.0; a.k[e].kfun = k.kfun; a.k[e].pad = 0;
+  }
+  a.n = m.n; a.np = m.np; a.D = s.D; a.Q = s.Q; a.steps = s.steps; a.acq = s.acq;
+  a.nl = t->n_leaves; a.shape = (t->n_leaves == 4) ? t->shape : FFGP_TREE_CHAIN;
+  for (int i = 0; i < 3; ++i) a.op[i] = (i + 1 < t->n_leaves) ? t->op[i] : FFGP_KOP_SUM;
+  a.var_add = m.var_add; a.var_floor = s.var_floor; a.kappa = s.kappa; a.xi = s.xi; a.f_best = s.f_best;
+  a.lr = s.lr; a.b1 = s.b1; a.b2 = s.b2; a.eps = s.eps;
+  if (s.D <= 2) return acq_tree_launch<2>(h, a, grid);
+  if (s.D <= 8) return acq_tree_launch<8>(h, a, grid);
+  return acq_tree_launch<16>(h, a, grid);
+}
+
+// The tree is checked here; everything else -- the remaining checks, the workspace, the triangular inverse, the bias corrections,
+// launch and wait -- is the stack entry's driver on a stack of one member (acq_run, acq_stack.hip), told that the member's kernel is `tree`.
+int ffgp_acq_optimize_tree(ffgp_handle* h, const ffgp_acq_tree_problem* p, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                           double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+  if (!p || (p->acq != FFGP_ACQ_UCB && p->acq != FFGP_ACQ_EI)) return FFGP_ERR_ARG;      // FFGP_ACQ_UCB_VAR: the stack entry only
+  const ffgp_ktree* t = p->tree;
+  if (!t || !t->leaf || t->n_leaves < 2 || t->n_leaves > ACQ_TREE_MAX) return FFGP_ERR_ARG;
+  if (t->n_leaves == 4 && t->shape != FFGP_TREE_CHAIN && t->shape != FFGP_TREE_BALANCED) return FFGP_ERR_ARG;
+  for (int i = 0; i + 1 < t->n_leaves; ++i)
+    if (t->op[i] != FFGP_KOP_SUM && t->op[i] != FFGP_KOP_PRODUCT) return FFGP_ERR_ARG;
+  for (int e = 0; e < t->n_leaves; ++e)
+    if (t->leaf[e].kfun < FFGP_KFUN_SE || t->leaf[e].kfun > FFGP_KFUN_LINEAR || !t->leaf[e].w_dev || !t->leaf[e].amp_dev) return FFGP_ERR_ARG;
+  ffgp_acq_member m = {};
+  m.n = p->n; m.D = p->D; m.d = p->d;
+  m.X_dev = p->X_dev; m.L_dev = p->L_dev; m.ldl = p->ldl; m.alpha_dev = p->alpha_dev;
+  m.var_add_all = p->var_add_all; m.mean_coef = 1.0; m.var_coef = 1.0;
+  ffgp_acq_stack s = {};
+  s.F = 1; s.members = &m; s.level_dev = nullptr;
+  s.var_floor = p->var_floor; s.acq = p->acq; s.kappa = p->kappa; s.xi = p->xi; s.f_best = p->f_best; s.accumulate_grad = 0;
+  return acq_run(h, &s, acq_tree_launch_by_d, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev, t);
+}

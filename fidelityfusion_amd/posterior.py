@@ -206,8 +206,17 @@ class Posterior:
                 and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D and isinstance(X0, torch.Tensor) and X0.is_cuda and X0.device == self.dev
                 and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1 and X0.shape[1] == self.D)
 
+    def acq_tree_fusable(self, X0):
+        """whether `optimize_acquisition(..., fuse_composed=True)` from X0 takes the one-launch call for composed kernels
+        (ffgp_acq_optimize_tree): a descriptor tree of 2-4 library leaves (radial profiles and LinearKernel), one output, n and D
+        within the kernel's LDS-tile limits, the start points fp64 on this posterior's GPU"""
+        return (self.tree is not None and 2 <= len(self.tree[0]) <= 4
+                and all(0 <= int(dsc["kfun"]) <= FFGP_KFUN_LINEAR for dsc in self.tree[0]) and self.d == 1
+                and 1 <= self.n <= _lib.FFGP_ACQ_MAX_N and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D and isinstance(X0, torch.Tensor) and X0.is_cuda
+                and X0.device == self.dev and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1 and X0.shape[1] == self.D)
+
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_add_all=0.0, var_floor=1e-12,
-                             betas=(0.9, 0.999), eps=1e-8, state=None):
+                             betas=(0.9, 0.999), eps=1e-8, state=None, fuse_composed=False):
         """`steps` Adam iterations of the reference's acquisition optimiser on this frozen posterior
         (Bayesian_optimization/acq.py:48-68: zero_grad(); loss = -acq(X).sum(); loss.backward(); Adam.step()), from the start points
         X0 [Q, D] (left untouched).  acq = "ucb": mean + kappa sqrt(max(var, var_floor)); "ei": acq.py:161-181 with f_best, xi.
@@ -217,14 +226,17 @@ class Posterior:
         otherwise the per-step loop -- `predict_diff` and torch.optim.Adam -- which covers composed kernels, LinearKernel, several
         outputs (the values of a point's outputs are summed, as the reference's `.sum()` does) and larger n.
         The fused call rebuilds the handle's inverted diagonal blocks from the factor (one extra launch per call), so its result
-        depends on the factor alone; later `predict` / `predict_diff` calls then solve with those blocks (see `predict_diff`)."""
+        depends on the factor alone; later `predict` / `predict_diff` calls then solve with those blocks (see `predict_diff`).
+        `fuse_composed=True` opts a composed kernel in: when `acq_tree_fusable(X0)` and steps <= 4096 the loop is ONE launch as well
+        (ffgp_acq_optimize_tree, csrc/acq_tree.hip: Sum / Product trees of 2-4 leaves, LinearKernel included), with the same return
+        values, `state` contract and state["fused"] = True; otherwise, and by default, such a posterior takes the per-step loop."""
         acq = str(acq).lower()
         if acq not in ("ucb", "ei"):
             raise ValueError("acq must be 'ucb' or 'ei', got %r" % (acq,))
         # one posterior is the stack of one member with coefficient 1: the checks, the per-step loop and the fused call live there
-        return _SinglePosterior([self], [1.0]).optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
-                                                                    var_floor=var_floor, betas=betas, eps=eps, var_adds=[var_add_all],
-                                                                    state=state)
+        single = _TreePosterior if fuse_composed and self.tree is not None else _SinglePosterior
+        return single([self], [1.0]).optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
+                                                          var_floor=var_floor, betas=betas, eps=eps, var_adds=[var_add_all], state=state)
 
     @torch.no_grad()
     def append(self, X_new, Y_new):
@@ -441,6 +453,24 @@ class _SinglePosterior(PosteriorStack):
                             w_dev=m.w.data_ptr(), amp_dev=m.amp.data_ptr(), clamp_min=float(m.clamp), kfun=int(m.kfun[0]),
                             kparam=float(m.kfun[1]), var_add_all=va[0], **acq_fields)
         check(lib.ffgp_acq_optimize(m._h(), C.byref(p), *call), "ffgp_acq_optimize")
+
+
+class _TreePosterior(PosteriorStack):
+    """`Posterior.optimize_acquisition(..., fuse_composed=True)` on a composed kernel: the stack of that one member, whose fused call
+    is ffgp_acq_optimize_tree (csrc/acq_tree.hip) on the posterior's own descriptor tree"""
+
+    def acq_fusable(self, X0):
+        return self.F == 1 and self.members[0].acq_tree_fusable(X0)
+
+    def _acq_call(self, va, lv, acq_fields, accumulate_grad, call):
+        assert self.F == 1 and lv is None and not accumulate_grad, "ffgp_acq_optimize_tree serves one posterior, without levels or accumulation"
+        m = self.members[0]
+        if m.alpha is None:
+            m._solve_alpha()
+        alpha = m.alpha.reshape(-1).contiguous()
+        p = _lib.AcqTreeProblem(n=m.n, D=m.D, d=1, X_dev=m.X.data_ptr(), L_dev=m.W.data_ptr(), ldl=m.ld, alpha_dev=alpha.data_ptr(),
+                                tree=C.pointer(m.tree[2]), var_add_all=va[0], **acq_fields)
+        check(lib.ffgp_acq_optimize_tree(m._h(), C.byref(p), *call), "ffgp_acq_optimize_tree")
 
 
 class PosteriorCache:

@@ -671,6 +671,39 @@ typedef struct {
 int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
                             double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* The single-posterior loop of ffgp_acq_optimize on a posterior whose kernel is a COMPOSITION -- the reference's own
+   Bayesian-optimisation model runs on SumKernel(LinearKernel(1), MaternKernel(1)) (Bayesian_optimization/cigp.py:119; cigp_v10.py:81;
+   two_fidelity_models/ResGP.py:25, AR_autoRegression.py:31) -- in ONE launch (csrc/acq_tree.hip).  `tree`: 2-4 leaves in the canonical
+   forms of ffgp_ktree, every FFGP_KFUN_* profile, FFGP_KFUN_LINEAR (center_dev NULL = the origin) and FFGP_KFUN_RQ included; X_dev,
+   L_dev (ldl), alpha_dev, d = 1 and var_add_all as in ffgp_acq_problem, within the same limits FFGP_ACQ_MAX_N / FFGP_ACQ_MAX_D /
+   FFGP_ACQ_MAX_STEPS for every tree shape and leaf count.  Per query point x and training row i the leaves' values are
+       radial:  v_e = amp_e phi_e(max(s_e, clamp_e)),  s_e = sum_k w_ek^2 (X_ik - x_k)^2        linear:  v_e = amp_e sum_k w_ek^2 (x_k - c_ek)(X_ik - c_ek)
+   k_i = the tree on (v_e), its nodes rounded one by one as ffgp_assemble_tree rounds them; mean = k^T alpha, V = L^-1 k and
+       var = k(x, x) - |V|^2 + var_add_all,    k(x, x) = the tree on the self values amp_e phi_e(max(0, clamp_e)) | amp_e sum_k w_ek^2 (x_k - c_ek)^2
+   (a linear leaf makes k(x, x) depend on x: the loss gradient gains -(da/dvar) dk(x, x)/dx, as autograd through
+   kernel(x, x).diagonal() gives it).  The input gradient is sum_i c_i sum_e (dk_i/dv_e) dv_e/dx with ffgp_acq_optimize's c_i, the
+   dk/dv_e from the tree's reverse sweep, dv_e/dx = -amp_e (-2 phi_e') w_e^2 o (x - X_i) (zero where s_e < clamp_e) for a radial leaf
+   and amp_e w_e^2 o (X_i - c_e) for a linear one.  acq: FFGP_ACQ_UCB or FFGP_ACQ_EI as defined there (FFGP_ACQ_UCB_VAR stays the
+   stack entry's).  Xq, state [2, Q, D], trace, hist, grad, step0, opt and evaluate mode (steps = 0) keep ffgp_acq_optimize's contract;
+   a point's trajectory does not depend on which other points share the call.
+   FFGP_ERR_ARG, before anything is enqueued (Xq, state and trace untouched): a null pointer (tree, its leaf array and a leaf's w_dev /
+   amp_dev included; hist_dev, grad_dev and a linear leaf's center_dev may be NULL), n_leaves outside 2..4, an unknown shape, op or
+   leaf kfun, n outside 1..FFGP_ACQ_MAX_N, D outside 1..FFGP_ACQ_MAX_D, steps outside 0..FFGP_ACQ_MAX_STEPS, d != 1, ldl < n, acq not
+   UCB or EI, Q <= 0, step0 < 0.  Synchronous; returns 0.                                                                         */
+typedef struct {
+  int n, D, d;
+  const double* X_dev;
+  const double* L_dev;
+  int ldl;
+  const double* alpha_dev;
+  const ffgp_ktree* tree;
+  double var_add_all, var_floor;
+  int acq;
+  double kappa, xi, f_best;
+} ffgp_acq_tree_problem;
+int ffgp_acq_optimize_tree(ffgp_handle* h, const ffgp_acq_tree_problem* p, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                           double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another
