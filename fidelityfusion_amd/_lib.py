@@ -119,6 +119,12 @@ class AcqStack(C.Structure):
                 ("kappa", C.c_double), ("xi", C.c_double), ("f_best", C.c_double), ("accumulate_grad", C.c_int)]
 
 
+class AcqChain(C.Structure):
+    """ffgp_acq_chain: the members of a NAR chain (a host array; members[0] on x, the others on [x, mean below]), the per-point levels
+    and the acquisition on the top member's posterior (ffgp_acq_optimize_chain); the fields are ffgp_acq_stack's"""
+    _fields_ = AcqStack._fields_
+
+
 FFGP_ACQ_UCB, FFGP_ACQ_EI = 0, 1
 FFGP_ACQ_UCB_VAR = 2             # ffgp_acq_optimize_stack only
 FFGP_ACQ_MAX_MEMBERS = 8
@@ -196,6 +202,7 @@ EXPORTS = {
     "ffgp_acq_optimize": (C.c_int, [C.c_void_p, C.POINTER(AcqProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_tree": (C.c_int, [C.c_void_p, C.POINTER(AcqTreeProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_stack": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
+    "ffgp_acq_optimize_chain": (C.c_int, [C.c_void_p, C.POINTER(AcqChain), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),

@@ -7,13 +7,15 @@ kernel of the kernel's sizes; otherwise -- and for acquisition objects on arbitr
 points are the caller's: the reference draws them inside the function, in fp32.  PI, KG and PF are not provided: the reference gives
 them no gradient or a random one.
 `optimize_acqf_mf` is the same loop on the posterior of a multi-fidelity stack (AR, ResGP: a list of per-fidelity `cigp`), the
-drivers' MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 -- every fidelity level in one launch (`PosteriorStack`, csrc/acq_stack.hip)."""
+drivers' MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 -- every fidelity level in one launch (`PosteriorStack`, csrc/acq_stack.hip).
+`optimize_acqf_nar` is that loop on NAR (FidelityFusion_Models/NAR.py:30-61), whose upper fidelities take the lower fidelity's predicted
+mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip)."""
 import inspect
 import math
 
 import torch
 
-from .posterior import Posterior, PosteriorStack
+from .posterior import Posterior, PosteriorChain, PosteriorStack
 
 
 def _norm_cdf(z):
@@ -133,5 +135,30 @@ def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001,
         noise.append(float(m.log_beta.detach().exp().pow(-1)))
     stack = PosteriorStack(members, coefs)
     X, trace, hist, _ = stack.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
+                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad)
+    return select_best(X0, trace, hist) if return_best_only else X
+
+
+def optimize_acqf_nar(models, data, X0, level=None, steps=10, lr=0.001, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12,
+                      accumulate_grad=False, return_best_only=True):
+    """The multi-fidelity drivers' acquisition optimiser (DMF_acq.py:226-262) on the posterior of NAR (FidelityFusion_Models/NAR.py:30-61):
+    `models` is the NAR trainer's `gpr_list` (frozen `cigp`), data[0] = (x_0, y_0), data[f > 0] = the 'concat-f' set the trainer stored:
+    inputs [x, y_low_mean] and y, possibly as the list [y, y_var] (`cigp.forward` ignores y_var; y[0] is used, as `optimize_acqf_mf`
+    does).  Member f is model f's cached posterior with that model's 1 / beta added to its variance; member f > 0 is queried at
+    [x, mean of member f - 1] and the model reports the mean and variance of the member a point stops at.  `level` (int or [Q]) is each
+    start point's `to_fidelity` (None: the top level), so the drivers' loop over the fidelities is ONE call; acq, `accumulate_grad` and
+    the return value as in `optimize_acqf_mf`."""
+    if X0 is None:
+        raise ValueError("optimize_acqf_nar needs the start points X0 [Q, D]")
+    models = list(models)
+    if len(data) != len(models):
+        raise ValueError("data holds one (x, y) pair per model")
+    members, noise = [], []
+    for m, (x, y) in zip(models, data):
+        y = y[0] if isinstance(y, list) else y
+        members.append(m._cached_posterior(x, y)[0])
+        noise.append(float(m.log_beta.detach().exp().pow(-1)))
+    chain = PosteriorChain(members)
+    X, trace, hist, _ = chain.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
                                                    level=level, var_adds=noise, accumulate_grad=accumulate_grad)
     return select_best(X0, trace, hist) if return_best_only else X

@@ -258,16 +258,17 @@ static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid
 }
 
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
-            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree) {
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree, bool chain) {
   if (!h || !s || !Xq_dev || !trace_dev || Q <= 0 || steps < 0 || steps > FFGP_ACQ_MAX_STEPS || step0 < 0) return FFGP_ERR_ARG;
   if (steps > 0 && (!opt || !state_dev)) return FFGP_ERR_ARG;
   if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members || (tree && s->F != 1)) return FFGP_ERR_ARG;
   if (s->acq != FFGP_ACQ_UCB && s->acq != FFGP_ACQ_EI && s->acq != FFGP_ACQ_UCB_VAR) return FFGP_ERR_ARG;
   const int F = s->F, D = s->members[0].D;
+  if (chain && D > FFGP_ACQ_MAX_D - 1) return FFGP_ERR_ARG;      // the members above the first take [x, mean below]: D + 1 inputs
   for (int f = 0; f < F; ++f) {
     const ffgp_acq_member& p = s->members[f];
     if (!p.X_dev || !p.L_dev || !p.alpha_dev || (!tree && (!p.w_dev || !p.amp_dev))) return FFGP_ERR_ARG;
-    if (p.n < 1 || p.n > FFGP_ACQ_MAX_N || p.D < 1 || p.D > FFGP_ACQ_MAX_D || p.D != D || p.d != 1) return FFGP_ERR_ARG;
+    if (p.n < 1 || p.n > FFGP_ACQ_MAX_N || p.D < 1 || p.D > FFGP_ACQ_MAX_D || p.D != ((chain && f > 0) ? D + 1 : D) || p.d != 1) return FFGP_ERR_ARG;
     if (p.ldl < p.n || p.ldl > INT_MAX) return FFGP_ERR_ARG;
     if (!tree && (p.kfun < FFGP_KFUN_SE || p.kfun > FFGP_KFUN_RQ)) return FFGP_ERR_ARG;      // (the linear kernel's k(x, x) depends on x)
   }

@@ -1,5 +1,5 @@
 // What the acquisition optimisers' kernels share (acq.hip: one frozen posterior; acq_stack.hip: a stack of them; acq_tree.hip: one
-// posterior on a composed kernel): a 256-thread
+// posterior on a composed kernel; acq_chain.hip: a chain of them, each fed the mean of the one below): a 256-thread
 // workgroup owns 16 query points, K_s / V / B live in LDS as [np][16] images, and V = L^-1 K_s, B = L^-T V are v_mfma_f64_16x16x4_f64
 // block chains whose A operand, L^-1, is read from global memory / L2 with one block of prefetch.  The host side exists once: acq_run
 // (acq_stack.hip) serves both entries, a single posterior as the stack of one member.
@@ -83,6 +83,8 @@ struct AcqStackArgs {
 // Checks the call, forms every member's L^-1 and the bias-correction table in handle workspace, launches through `launch` and waits.
 // `tree` (ffgp_acq_optimize_tree only, checked by that entry): the one member's kernel is this composition, so the member carries no
 // w_dev / amp_dev / kfun of its own and those three checks are skipped; it is handed on to `launch`.
+// `chain` (ffgp_acq_optimize_chain only): the per-member dimension rule is members[0].D = D <= FFGP_ACQ_MAX_D - 1 and D + 1 above it,
+// instead of one D for all; AcqStackArgs.D stays the D of the query points.
 typedef int (*acq_launch_fn)(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree* tree);
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
-            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree = nullptr);
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree = nullptr, bool chain = false);

@@ -91,6 +91,23 @@ int main() {
     EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     mem[1].d = 1; mem[0].alpha_dev = nullptr;
     EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    // the chain entry (NAR): the stack entry's driver with the D / D + 1 rule, and its own refusal of a coefficient other than 1
+    mem[0].alpha_dev = &x; mem[1].D = 2;
+    ffgp_acq_chain chn;
+    std::memset(&chn, 0, sizeof chn);
+    chn.F = 2; chn.members = mem; chn.acq = FFGP_ACQ_UCB_VAR;
+    EXPECT(ffgp_acq_optimize_chain(nullptr, &chn, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_chain(fake, nullptr, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    EXPECT(ffgp_acq_optimize_chain(fake, &chn, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].D = 1;                             // the second member must take D + 1 inputs
+    EXPECT(ffgp_acq_optimize_chain(fake, &chn, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].D = 2; mem[1].mean_coef = 0.8;
+    EXPECT(ffgp_acq_optimize_chain(fake, &chn, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[1].mean_coef = 1.0; mem[0].D = FFGP_ACQ_MAX_D; mem[1].D = FFGP_ACQ_MAX_D + 1;
+    EXPECT(ffgp_acq_optimize_chain(fake, &chn, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    chn.members = nullptr;
+    EXPECT(ffgp_acq_optimize_chain(fake, &chn, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    mem[0].D = 1; mem[1].D = 1; mem[0].alpha_dev = nullptr;
     // the single-posterior entry builds its one-member stack on the host and forwards: its refusals, next to the stack entry's
     ffgp_acq_problem ap;
     std::memset(&ap, 0, sizeof ap);

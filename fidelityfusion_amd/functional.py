@@ -8,7 +8,7 @@ back on the input's device and dtype.  Arithmetic is fp64 on the device whatever
 Round 4 split the former 1 600-line module by subject; this file re-exports every name:
     nlml.py       the fused likelihood calls (effective / raw parameters, batches, composed kernels), fused posterior
     linalg.py     kernel matrices, Cholesky with passenger rows, conditional Gaussian, GEMM, subset matching, small eigh
-    posterior.py  the kept factor (`Posterior`, `PosteriorCache`) and stacks of them (`PosteriorStack`)
+    posterior.py  the kept factor (`Posterior`, `PosteriorCache`) and stacks and chains of them (`PosteriorStack`, `PosteriorChain`)
     blocks.py     several blocks in flight on one GPU (`concurrent_blocks`, `threaded_blocks`)
     kdesc.py, _common.py   descriptor packing, shared plumbing
 Module state lives where it is used: set `nlml_module.DEFER_RAW_ERRORS` through `defer_raw_errors(True / False)`.
@@ -27,7 +27,7 @@ from .linalg import (_CondGauss, _EighSmall, _GaussNLLFromCov, _gemm, _KernelMat
 from .nlml import (RAGGED_CHAIN_MAX_N, SMALL_BATCH_MAX_d, SMALL_BATCH_MAX_D, SMALL_BATCH_MAX_N, _NLML, _NLMLPair, _NLMLRaw, _NLMLRawMany, _problem, _raw_pending,
                    _settle_raw, many_batchable, nlml, nlml_many, nlml_pair, nlml_raw, nlml_raw_many, pair_inputs_plain, predict, raw_many_ok,
                    raw_ok, raw_path)
-from .posterior import Posterior, PosteriorCache, PosteriorCacheMixin, PosteriorStack, _PosteriorQuery
+from .posterior import Posterior, PosteriorCache, PosteriorCacheMixin, PosteriorChain, PosteriorStack, _PosteriorQuery
 
 SUBMODULES = (nlml_module, linalg, posterior, blocks)     # every module that calls the library through its own `lib` name
 

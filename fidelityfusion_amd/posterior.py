@@ -473,6 +473,70 @@ class _TreePosterior(PosteriorStack):
         check(lib.ffgp_acq_optimize_tree(m._h(), C.byref(p), *call), "ffgp_acq_optimize_tree")
 
 
+class PosteriorChain(PosteriorStack):
+    """A chain of frozen per-fidelity posteriors queried as ONE model: the posterior of the reference's NAR
+    (FidelityFusion_Models/NAR.py:30-61).  members[0] is a `Posterior` on x [D]; members[f > 0] are posteriors on [x, m_{f-1}(x)],
+    the lower member's predicted mean as one more input column (D + 1 inputs).  The model's mean and variance are those of the member a
+    point stops at (`level`, the reference's `to_fidelity`); the lower members' variances are discarded, as the reference discards
+    them.  The acquisition loop, its buffers and its return values are `PosteriorStack`'s."""
+
+    def __init__(self, members):
+        members = list(members)
+        if not members or not all(isinstance(m, Posterior) for m in members):
+            raise ValueError("members must be a non-empty list of Posterior")
+        D = members[0].D
+        if any(m.dev != members[0].dev for m in members) or any(m.D != D + 1 for m in members[1:]):
+            raise ValueError("the members of a PosteriorChain share one device; members[0] takes D inputs, the others D + 1")
+        self.members = members
+        self.mean_coefs = self.var_coefs = [1.0] * len(members)      # reserved by the C entry: a chain member has no weight
+        self.dev, self.D, self.F = members[0].dev, D, len(members)
+
+    def predict_diff(self, Xs, level=None, var_adds=None):
+        """The mean [nt, 1] and variance [nt] of the member each point stops at (`level`: int or [nt], None = the top member),
+        differentiable w.r.t. Xs through the whole chain: member f is queried at [Xs, mean of member f - 1]; `var_adds[f]` is member
+        f's noise (its 1 / beta).  A per-point level selects by exact 0 / 1 masks."""
+        va = self._var_adds(var_adds)
+        lv = self._level(level, Xs.shape[0])
+        top = self.F - 1 if lv is None else int(lv.max())
+        Xd = Xs.to(device=self.dev, dtype=torch.float64)
+        mean = var = low = None
+        for f in range(top + 1):
+            z = Xd if f == 0 else torch.cat([Xd, low.reshape(-1, 1)], dim=-1)
+            m, v = self.members[f].predict_diff(z, full_cov=False, var_add_all=va[f])
+            low = m
+            if lv is None:
+                mean, var = m, v
+            else:
+                on = (lv == f).to(torch.float64)
+                mean = m * on.unsqueeze(1) if mean is None else mean + m * on.unsqueeze(1)
+                var = v * on if var is None else var + v * on
+        return mean, var
+
+    def acq_fusable(self, X0):
+        """whether `optimize_acquisition` from X0 takes the one-launch call (ffgp_acq_optimize_chain): at most 8 members, each ONE
+        radial library kernel with one output and n <= 256, D + 1 <= 16, the start points fp64 [Q, D] on the chain's GPU"""
+        def member_ok(m):
+            return (m.tree is None and 0 <= int(m.kfun[0]) < FFGP_KFUN_LINEAR and m.d == 1 and 1 <= m.n <= _lib.FFGP_ACQ_MAX_N)
+        return (self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D - 1 and all(member_ok(m) for m in self.members)
+                and isinstance(X0, torch.Tensor) and X0.is_cuda and X0.device == self.dev and X0.dtype == torch.float64 and X0.dim() == 2
+                and X0.shape[0] >= 1 and X0.shape[1] == self.D)
+
+    def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12, betas=(0.9, 0.999),
+                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None):
+        """`PosteriorStack.optimize_acquisition` on the chain's posterior: the same arguments, the same return tuple
+        (X, trace, hist, state).  ONE kernel launch (ffgp_acq_optimize_chain, csrc/acq_chain.hip) when `acq_fusable(X0)` and
+        steps <= 4096 -- only the member a point stops at pays for the triangular solves -- otherwise the per-step loop on
+        `predict_diff` and torch.optim.Adam (composed kernels, n > 256, D + 1 > 16, more than 8 members); state["fused"] says which."""
+        return super().optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
+                                            betas=betas, eps=eps, level=level, var_adds=var_adds, accumulate_grad=accumulate_grad, state=state)
+
+    def _acq_call(self, va, lv, acq_fields, accumulate_grad, call):
+        keep = []
+        c = _lib.AcqChain(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
+                          accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
+        check(lib.ffgp_acq_optimize_chain(self.members[0]._h(), C.byref(c), *call), "ffgp_acq_optimize_chain")
+
+
 class PosteriorCache:
     """Keeps the `Posterior` of a model while the SAME tensor objects (training inputs, targets, every parameter) come
     back with unchanged in-place version counters: in-place updates bump `_version`, `p.data = ...` moves the pointer,

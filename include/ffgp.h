@@ -671,6 +671,32 @@ typedef struct {
 int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
                             double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* The same loop on a CHAIN of frozen posteriors -- the drivers' acquisition optimiser on NAR (FidelityFusion_Models/NAR.py:30-61), whose
+   upper fidelities take the lower fidelity's predicted MEAN as one more input column -- in ONE launch (csrc/acq_chain.hip).
+   members[0] is a posterior on x [D], 1 <= D <= FFGP_ACQ_MAX_D - 1; members[f > 0] are posteriors on z = [x, m_{f-1}], D + 1 inputs;
+   every member within ffgp_acq_optimize's limits otherwise.  Per query point x with s = min(level[q], F - 1) (level_dev NULL: F - 1):
+       m_0 = k_0(X_0, x)^T alpha_0,    z_f = [x, m_{f-1}],  m_f = k_f(Z_f, z_f)^T alpha_f   for f = 1..s,
+       mean = m_s,    var = amp_s - |L_s^-1 k_s(Z_s, z_s)|^2 + var_add_all_s
+   -- the lower members contribute no variance, as NAR.forward discards cov_pred_low -- and the acquisition value on (mean, var):
+   FFGP_ACQ_UCB, FFGP_ACQ_EI and FFGP_ACQ_UCB_VAR exactly as ffgp_acq_optimize_stack defines them.  The loss is -sum a; its gradient
+   is taken through the whole chain (d m_f / d m_{f-1} included) and Adam acts on the D coordinates of x only.  Only the member a point
+   stops at pays for the triangular chains; the others cost two O(n D) sweeps.  A point's trajectory does not depend on its tile, its
+   neighbours or their levels, and level = k everywhere is the chain cut after member k, bit for bit.  Xq [Q, D], trace, hist, grad,
+   step0, opt, evaluate mode (steps = 0), state_dev [2 | 3, Q, D] and accumulate_grad keep ffgp_acq_optimize_stack's contract, the
+   workspace and the handle's inverted diagonal blocks likewise.  mean_coef / var_coef of a chain member are reserved and must be 1.0.
+   FFGP_ERR_ARG, before anything is enqueued (Xq, state and trace untouched): everything ffgp_acq_optimize_stack refuses (its rule
+   "members whose D differ" reads here: members[f > 0].D != members[0].D + 1), members[0].D outside 1..FFGP_ACQ_MAX_D - 1, a
+   coefficient other than 1.  level values are read as min(level, F - 1); a point with a negative level stops at no member: its value
+   is 0, its gradient 0 and it does not move.  Synchronous; returns 0.                                                            */
+typedef struct {
+  int F; const ffgp_acq_member* members;   /* host array; members[0].D = D, members[f>0].D = D + 1 */
+  const int* level_dev;      /* [Q] or NULL = top */
+  double var_floor; int acq; double kappa, xi, f_best;
+  int accumulate_grad;
+} ffgp_acq_chain;
+int ffgp_acq_optimize_chain(ffgp_handle* h, const ffgp_acq_chain* c, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                            double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* The single-posterior loop of ffgp_acq_optimize on a posterior whose kernel is a COMPOSITION -- the reference's own
    Bayesian-optimisation model runs on SumKernel(LinearKernel(1), MaternKernel(1)) (Bayesian_optimization/cigp.py:119; cigp_v10.py:81;
    two_fidelity_models/ResGP.py:25, AR_autoRegression.py:31) -- in ONE launch (csrc/acq_tree.hip).  `tree`: 2-4 leaves in the canonical
