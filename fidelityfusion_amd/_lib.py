@@ -169,6 +169,8 @@ EXPORTS = {
                                             C.c_double, _dp, C.c_int, _dp, C.c_int]),
     "ffgp_syevj_small": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, C.c_long, _dp, C.c_int, C.c_long, _dp, C.c_long,
                                    C.c_int]),
+    "ffgp_syev_lds": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, C.c_long, _dp, C.c_int, C.c_long, _dp, C.c_long,
+                                C.c_int, C.c_void_p]),
     "ffgp_syevd": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int]),
     "ffgp_sy2sb": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int]),
     "ffgp_sb2st_reflector_doubles": (C.c_long, [C.c_int]),

@@ -73,6 +73,13 @@ int ffgp_syevj_small(ffgp_handle* h, const double* M, int n, int ldm, int batch,
   return ffgp_syevj_small_impl(h, M, n, ldm, batch, strideM, Q, ldq, strideQ, evals, strideE, descending);
 }
 
+int ffgp_syev_lds(ffgp_handle* h, const double* M, int n, int ldm, int batch, long strideM, double* Q, int ldq, long strideQ,
+                  double* evals, long strideE, int descending, int* info) {
+  if (!h) return FFGP_ERR_ARG;
+  FFGP_HIP(hipSetDevice(h->device));
+  return ffgp_syev_lds_impl(h, M, n, ldm, batch, strideM, Q, ldq, strideQ, evals, strideE, descending, info);
+}
+
 int ffgp_gemm_batched(ffgp_handle* h, int opa, int opb, int lower_tiles, const double* A, int lda, long strideA, const double* B,
                       int ldb, long strideB, double* C, int ldc, long strideC, int m, int n, int k, double alpha, double beta,
                       int batch) {

@@ -417,6 +417,8 @@ int ffgp_rows_in_impl(ffgp_handle* h, const double* X1, int n1, const double* X2
 
 int ffgp_syevj_small_impl(ffgp_handle* h, const double* M, int n, int ldm, int batch, long strideM, double* Q, int ldq,
                           long strideQ, double* evals, long strideE, int descending);
+int ffgp_syev_lds_impl(ffgp_handle* h, const double* M, int n, int ldm, int batch, long strideM, double* Q, int ldq, long strideQ,
+                       double* evals, long strideE, int descending, int* info);
 // ---- workspace (handle.hip)
 int ffgp_ensure_ws(ffgp_handle* h, size_t bytes);
 // zero `bytes` (a multiple of 4) on the handle's stream with a kernel: small fills on the captured (graph) path go through this

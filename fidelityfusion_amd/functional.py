@@ -21,7 +21,7 @@ from .blocks import (_mark_used_on, _pending, _slot_args, _threaded_blocks_run, 
                      threaded_blocks, wait)
 from .kdesc import (FFGP_KFUN_LINEAR, FFGP_KOP_PRODUCT, FFGP_KOP_SUM, FFGP_TREE_BALANCED, FFGP_TREE_CHAIN, _PAIR_KEYS, _pair_descs,
                     _pair_grad_buffers, _pair_grads_out, _pair_split, _tree_spec)
-from .linalg import (_CondGauss, _EighSmall, _GaussNLLFromCov, _gemm, _KernelMatrix, _KernelPair, _MatmulNT, _pad_ld, _syevj_small,
+from .linalg import (_CondGauss, _EighSmall, _GaussNLLFromCov, _gemm, _KernelMatrix, _KernelPair, _MatmulNT, _pad_ld, _syev_lds, _syev_lds_checked, _syevj_small,
                      add_diagonal, cholesky, cholesky_with_rows, conditional_gaussian, eigh_small, gaussian_ll_v2,
                      gaussian_nll_from_cov, kernel_matrix, kernel_on_device, kernel_pair, matmul_nt, rows_in)
 from .nlml import (RAGGED_CHAIN_MAX_N, SMALL_BATCH_MAX_d, SMALL_BATCH_MAX_D, SMALL_BATCH_MAX_N, _NLML, _NLMLPair, _NLMLRaw, _NLMLRawMany, _problem, _raw_pending,

@@ -8,7 +8,8 @@ Same constructor, parameters (`noise_variance`, the shared kernel, `grid`, `mapp
 What runs where: the covariance matrices come from the library's assembly (differentiable `kernel_matrix`), every
 mode product -- the O(N^2 prod(d)) part: 550 GFLOP each at N = 8192, d = 64 x 64 -- runs on the fp64 matrix-core
 GEMM (`functional.matmul_nt`, forward and backward).  Symmetric eigendecompositions: matrices up to 64 x 64 -- the
-per-mode kernels -- run on the hand-written LDS Jacobi solver (`ffgp_syevj_small`); the N x N input kernel runs on the
+per-mode kernels -- run on the hand-written LDS Jacobi solver (`ffgp_syevj_small`); an input kernel of 65 ... `LDS_EIGH_MAX_N`
+rows can run in one launch on the one-image LDS solver (`ffgp_syev_lds`; see the constant below); a larger N x N input kernel runs on the
 library's two-stage solver (`eigh.eigh` -> `ffgp_syevd`: band reduction, bulge chasing, divide & conquer, two
 back-transformations; 0.26 s at N = 8192 where rocSOLVER's syevd takes 0.66 s).  No vendor library is called anywhere in
 this module (the GPU tests substitute their own `eigen_pairs` built on torch.linalg.eigh as the comparator); "jacobi" is the
@@ -37,12 +38,14 @@ import torch.nn as nn
 from . import functional as F
 
 
-EIGENSOLVER = "ffgp"    # n > 64: "ffgp" = the library's two-stage solver (default); "jacobi" = its block Jacobi (slow cross-check)
+EIGENSOLVER = "ffgp"    # n > LDS_EIGH_MAX_N: "ffgp" = the library's two-stage solver (default); "jacobi" = its block Jacobi (slow cross-check)
+LDS_EIGH_MAX_N = 128    # 64 < n <= this: the one-workgroup LDS solver (ffgp_syev_lds, n <= 128); 64 sends every n > 64 to EIGENSOLVER's route
 
 
 class eigen_pairs:
     """matrices up to 64 x 64 (the per-mode kernels; tiny input sets) go to the hand-written LDS Jacobi solver
-    (`ffgp_syevj_small`), larger ones -- the N x N input kernel -- to the library's two-stage solver (`ffgp_syevd`).
+    (`ffgp_syevj_small`), 64 < n <= `LDS_EIGH_MAX_N` to the one-workgroup, one-launch LDS solver (`ffgp_syev_lds`), larger ones --
+    the N x N input kernel -- to the library's two-stage solver (`ffgp_syevd`).
     Reference: `eigen_pairs`, two_fidelity_models/hogp_simple.py:15-19.
 
     There is no vendor or CPU route: the matrix must live on the MI355X.  The pairs of an n > 64 matrix are computed on a
@@ -55,6 +58,10 @@ class eigen_pairs:
             raise F._lib.FFGPError("eigen_pairs: the matrix must be on the GPU (fidelityfusion_amd has no CPU path)")
         if matrix.shape[0] <= 64:
             self.value, self.vector = F.eigh_small(matrix)
+        elif matrix.shape[0] <= LDS_EIGH_MAX_N:
+            with torch.no_grad():
+                ev, Q = F._syev_lds_checked(matrix.detach().to(torch.float64)[None])      # (NaN eigenvalues if the kernel's status is not 0)
+                self.value, self.vector = ev[0], Q[0]
         elif EIGENSOLVER in ("ffgp", "jacobi"):
             from . import eigh as _eigh
             with torch.no_grad():

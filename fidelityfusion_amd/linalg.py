@@ -414,14 +414,41 @@ def _syevj_small(M, descending=False):
     return ev, Q
 
 
+@torch.no_grad()
+def _syev_lds(M, descending=False, info=False):
+    """batched one-workgroup eigensolver for [B, n, n] (n <= 128, lower triangle read) device tensors on the one-image LDS kernel
+    (ffgp_syev_lds: one-sided Jacobi): (evals [B, n], Q [B, n, n]); info=True appends the kernel's int32 status [B] (0 = converged)"""
+    dev = M.device
+    h = _lib.handle(dev.index)
+    _lib.bind_stream(h, dev.index)
+    B, n = M.shape[0], M.shape[-1]
+    M = M.contiguous()
+    Q = torch.empty((B, n, n), dtype=torch.float64, device=dev)
+    ev = torch.empty((B, n), dtype=torch.float64, device=dev)
+    st = torch.zeros((B,), dtype=torch.int32, device=dev) if info else None
+    check(lib.ffgp_syev_lds(h, _ptr(M), n, n, B, n * n, _ptr(Q), n, n * n, _ptr(ev), n, 1 if descending else 0,
+                            _ptr(st) if info else None), "ffgp_syev_lds")
+    return (ev, Q, st) if info else (ev, Q)
+
+
+@torch.no_grad()
+def _syev_lds_checked(M):
+    """`_syev_lds` for callers that go on computing on the device: (evals, Q) with the eigenvalues of every matrix whose status is
+    not 0 -- the sweep cap was reached, or the input held a NaN / Inf -- replaced by NaN.  No host synchronisation: an unconverged
+    decomposition cannot pass for a converged one, it poisons what is computed from it, as a NaN input always did."""
+    ev, Q, st = _syev_lds(M, info=True)
+    return torch.where((st != 0).unsqueeze(-1), torch.full_like(ev, float("nan")), ev), Q
+
+
 class _EighSmall(torch.autograd.Function):
-    """torch.linalg.eigh for one symmetric matrix with n <= 64 on the hand-written LDS Jacobi kernel (ffgp_syevj_small),
-    with the standard backward  gK = sym( U (diag(g_lambda) + (U^T g_U) o E) U^T ),  E_ij = 1 / (lambda_j - lambda_i)."""
+    """torch.linalg.eigh for one symmetric matrix with n <= 128 on the hand-written LDS Jacobi kernels (n <= 64: ffgp_syevj_small,
+    two-sided; 64 < n <= 128: ffgp_syev_lds, one-sided on one LDS image), with the standard backward -- the same for both --  gK = sym( U (diag(g_lambda) + (U^T g_U) o E) U^T ),  E_ij = 1 / (lambda_j - lambda_i)."""
 
     @staticmethod
     def forward(ctx, K):
         dev = _device_of(K)
-        ev, Q = _syevj_small(_dev(K, dev)[None])
+        Kd = _dev(K, dev)[None]
+        ev, Q = _syevj_small(Kd) if K.shape[-1] <= 64 else _syev_lds_checked(Kd)
         ctx.save_for_backward(ev[0], Q[0])
         ctx.meta = (K.dtype, K.device)
         return ev[0].to(device=K.device, dtype=K.dtype), Q[0].to(device=K.device, dtype=K.dtype)
@@ -445,5 +472,6 @@ class _EighSmall(torch.autograd.Function):
 
 
 def eigh_small(K):
-    """(eigenvalues ascending [n], eigenvectors [n, n]) of a symmetric K with n <= 64, differentiable"""
+    """(eigenvalues ascending [n], eigenvectors [n, n]) of a symmetric K with n <= 128, differentiable: n <= 64 runs on
+    ffgp_syevj_small as before, 64 < n <= 128 on ffgp_syev_lds (eigenvalues NaN if its status is not 0); the backward pass is the same"""
     return _EighSmall.apply(K)

@@ -348,6 +348,22 @@ int ffgp_kernel_grad(ffgp_handle* h, const double* X1_dev, int n1, const double*
 int ffgp_syevj_small(ffgp_handle* h, const double* M_dev, int n, int ldm, int batch, long strideM, double* Q_dev, int ldq,
                      long strideQ, double* evals_dev, long strideE, int descending);
 
+/* Batched symmetric eigendecomposition of `batch` matrices M_b [n, n] for 1 <= n <= FFGP_SYEV_LDS_MAX_N (the LOWER triangle is
+ * read, as ffgp_syevd does; M is not modified): one workgroup per matrix, one launch, enqueued on the handle's stream only.  One
+ * fp64 image of the matrix is all the CU's LDS holds at n = 128, so this is a one-sided (Hestenes) Jacobi on the positive definite
+ * G = M + s I (s from Gershgorin's bound and the Frobenius norm): the orthogonalised, normalised columns are the eigenvectors and
+ * the eigenvalues are their Rayleigh quotients against M.  Q_b's columns are the eigenvectors, evals_b the eigenvalues, ascending
+ * (descending != 0: descending; ties by index as ffgp_syevj_small).  info_dev [batch] (may be NULL): 0 where matrix b converged,
+ * else the number of column pairs its last sweep still rotated (every loop is bounded).  A NaN or Inf anywhere in the lower triangle
+ * (or a row whose absolute sum overflows) gives NaN in every output of that matrix and info = n.
+ * A zero matrix gives zeros and the identity.  FFGP_ERR_ARG, with nothing enqueued, for n outside 1..128, ldm < n, ldq < n or a
+ * null M / Q / evals; batch <= 0 is FFGP_OK.  Replaces torch.linalg.eigh on the N x N input kernel of the HOGP block at the
+ * reference's experiment sizes (two_fidelity_models/hogp_simple.py:15-19,97-100 on the 100 low-fidelity points of
+ * Experiments/GAR_Aligned/exp_aligned.py:66-99), where ffgp_syevd's stage chain is dozens of launches and a host wait.          */
+#define FFGP_SYEV_LDS_MAX_N 128
+int ffgp_syev_lds(ffgp_handle* h, const double* M_dev, int n, int ldm, int batch, long strideM, double* Q_dev, int ldq,
+                  long strideQ, double* evals_dev, long strideE, int descending, int* info_dev);
+
 /* ---- symmetric eigensolver (the N x N `torch.linalg.eigh(K_x)` of the HOGP block) ------------------------------------------------
  * Full symmetric eigendecomposition A = Z diag(W) Z^T of a dense symmetric matrix (its LOWER triangle is read, as
  * torch.linalg.eigh's default UPLO does), eigenvalues ascending, eigenvectors in the COLUMNS of Z -- the contract of
