@@ -201,6 +201,8 @@ EXPORTS = {
                                           C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                       C.c_long, _dp, C.c_long]),
+    "ffgp_train_tree_lds_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
+                                          C.c_long, _dp, C.c_long]),
     "ffgp_acq_optimize": (C.c_int, [C.c_void_p, C.POINTER(AcqProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_tree": (C.c_int, [C.c_void_p, C.POINTER(AcqTreeProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_stack": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),

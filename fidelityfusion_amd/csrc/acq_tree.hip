@@ -4,7 +4,7 @@
 // SumKernel(LinearKernel(1), MaternKernel(1)); the loop is Bayesian_optimization/acq.py:48-68.  The plan is ffgp_acq_kernel's (acq.hip):
 // a 256-thread workgroup owns 16 query points and runs all the steps, V = L^-1 K_s and B = L^-T V are acq_tile.h's block chains on
 // [np][16] LDS images.  What differs:
-//   * k(X_i, x_j) is the tree of the leaves' values, its nodes rounded one by one as pair.hip's tree_op rounds them;
+//   * k(X_i, x_j) is the tree of the leaves' values, its nodes rounded one by one as pair.hip's tree_op rounds them (tree_ops.h);
 //   * there is no derivative image: up to four leaves' factors do not fit beside the three images, so the gradient pass re-evaluates the
 //     leaves from Xs (stage 1's arithmetic again, small beside the two chain passes) and runs the tree's reverse sweep per row.  Two
 //     images remain: K_s -> B, and V -> the gradient partials;
@@ -18,8 +18,9 @@
 #include <climits>
 
 #include "acq_tile.h"
+#include "tree_ops.h"
 
-#define ACQ_TREE_MAX 4
+#define ACQ_TREE_MAX FFGP_TREE_LEAVES
 
 struct AcqTreeLeaf {
   const double* w;       // [D]
@@ -51,52 +52,6 @@ static constexpr size_t acq_tree_lds_doubles(int np, int DM) {
 }
 static_assert(acq_tree_lds_doubles(FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D) * sizeof(double) <= 160 * 1024,
               "the tree acquisition kernel's LDS exceeds a CU's 160 KiB");
-
-// one node: separately rounded product / sum (pair.hip's tree_op)
-__device__ __forceinline__ double acq_tree_op(int op, double x, double y) {
-#pragma clang fp contract(off)
-  const double pr = x * y, sm = x + y;
-  return op == FFGP_KOP_PRODUCT ? pr : sm;
-}
-// the canonical trees of include/ffgp.h on the leaves' values (v[e] = 0 past the last leaf)
-__device__ __forceinline__ double acq_tree_eval(const AcqTreeArgs& a, const double (&v)[ACQ_TREE_MAX]) {
-  const double t0 = acq_tree_op(a.op[0], v[0], v[1]);
-  if (a.nl == 2) return t0;
-  if (a.nl == 3) return acq_tree_op(a.op[1], t0, v[2]);
-  if (a.shape == FFGP_TREE_BALANCED) return acq_tree_op(a.op[2], t0, acq_tree_op(a.op[1], v[2], v[3]));
-  return acq_tree_op(a.op[2], acq_tree_op(a.op[1], t0, v[2]), v[3]);
-}
-// d root / d leaf values (pair.hip's tree_back with upstream 1)
-__device__ __forceinline__ void acq_tree_back(const AcqTreeArgs& a, const double (&v)[ACQ_TREE_MAX], double (&gv)[ACQ_TREE_MAX]) {
-  const double t0 = acq_tree_op(a.op[0], v[0], v[1]);
-  double gt0 = 1.0;
-  gv[2] = 0.0;
-  gv[3] = 0.0;
-  if (a.nl == 3) {
-    const bool pr = a.op[1] == FFGP_KOP_PRODUCT;
-    gt0 = pr ? v[2] : 1.0;
-    gv[2] = pr ? t0 : 1.0;
-  }
-  if (a.nl == 4) {
-    const bool p1 = a.op[1] == FFGP_KOP_PRODUCT, p2 = a.op[2] == FFGP_KOP_PRODUCT;
-    if (a.shape == FFGP_TREE_BALANCED) {
-      const double t1 = acq_tree_op(a.op[1], v[2], v[3]);
-      gt0 = p2 ? t1 : 1.0;
-      const double gt1 = p2 ? t0 : 1.0;
-      gv[2] = p1 ? gt1 * v[3] : gt1;
-      gv[3] = p1 ? gt1 * v[2] : gt1;
-    } else {
-      const double t1 = acq_tree_op(a.op[1], t0, v[2]);
-      const double gt1 = p2 ? v[3] : 1.0;
-      gv[3] = p2 ? t1 : 1.0;
-      gt0 = p1 ? gt1 * v[2] : gt1;
-      gv[2] = p1 ? gt1 * t0 : gt1;
-    }
-  }
-  const bool p0 = a.op[0] == FFGP_KOP_PRODUCT;
-  gv[0] = p0 ? gt0 * v[1] : gt0;
-  gv[1] = p0 ? gt0 * v[0] : gt0;
-}
 
 // a leaf's bilinear form on (training row xr, query point xj): the squared scaled distance, or the scaled dot product about the centre
 template <int DM>
@@ -193,7 +148,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
           v[e] = lp[4 * e] * (lin[e] ? s : ffgp_kfun_val(a.k[e].kfun, lp[4 * e + 2], fmax(s, lp[4 * e + 1])));
         }
       }
-      const double kv = (i < n) ? acq_tree_eval(a, v) : 0.0;
+      const double kv = (i < n) ? ffgp_tree_eval(a, v) : 0.0;
       img0[i * 16 + j] = kv;
       msum = __builtin_fma(kv, al[i], msum);
     }
@@ -215,8 +170,8 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
         }
       }
     }
-    const double kss = acq_tree_eval(a, sv);
-    acq_tree_back(a, sv, gs);
+    const double kss = ffgp_tree_eval(a, sv);
+    ffgp_tree_back(a, sv, gs);
     __syncthreads();
     double mean = 0.0;
 #pragma unroll
@@ -294,7 +249,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
           }
         }
       }
-      acq_tree_back(a, v, gl);
+      ffgp_tree_back(a, v, gl);
 #pragma unroll
       for (int e = 0; e < ACQ_TREE_MAX; ++e) {
         if (e < nl) {

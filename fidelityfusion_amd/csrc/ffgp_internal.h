@@ -250,6 +250,10 @@ struct ffgp_handle {
   size_t train_tab_bytes;
   double* small_kbuf;   // ffgp_small_mfma_enqueue: the evaluate-mode launches' parked kernel values (8 models x 36 x 256 doubles)
   void* train_host;     // its pinned host mirror (staging of the table, read-back of the status words)
+  void* train_ttl;      // ffgp_train_tree_lds_raw (train_tree_lds.hip): [models | bias corrections | status words | the entries' per-leaf weights]
+  size_t train_ttl_bytes;
+  void* train_ttl_host; // pinned mirror of its first three parts
+  size_t train_ttl_host_bytes;
   int train_persist_off;  // option "train_persist" = 0: ffgp_train_raw never takes the one-launch trainer
   int* bt_info;         // [F] device status words (first non-positive pivot of each block)
   int* bt_info_host;    // pinned mirror

@@ -28,12 +28,8 @@
 // Covers: n <= 128, D <= 16, d <= 16, one radial-profile kernel, V1 likelihood, diag_add and diag_vec (no matrix / all-entries /
 // mean(K) extras, no learnable profile parameter): what cigp_v10 produces.  Everything else keeps the paths it had.
 #include "ffgp_internal.h"
-#include "diag_block.h"
+#include "train_tile.h"
 
-#define TR_T 512
-#define TR_N 128
-#define TR_D 16
-#define TR_Y 16
 #define TR_NRED 20        // values of the step's one workgroup reduction: ss, s_amp, tr G, log-det, tot[16]
 
 struct TrainModel {
@@ -103,81 +99,6 @@ __device__ __forceinline__ double tr_link_der(int kind, double p, double c) {
   }
 }
 
-// sum over the 64 lanes of the wave, in all of them: four DPP steps inside the rows of 16 lanes, then the rows exchanged by gfx950's
-// row swaps (the shuffle form, ds_bpermute, is an LDS crossbar round trip per step: 6 dependent trips per value)
-template <int CTRL>
-__device__ __forceinline__ double tr_dpp_add(double x) {
-  int lo = __double2loint(x), hi = __double2hiint(x);
-  lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
-  hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
-  return x + __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double tr_wsum(double x) {
-  x = tr_dpp_add<0xB1>(x);
-  x = tr_dpp_add<0x4E>(x);
-  x = tr_dpp_add<0x141>(x);
-  x = tr_dpp_add<0x140>(x);
-  {
-    const int lo = __double2loint(x), hi = __double2hiint(x);
-    const auto a = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const auto b = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    x = __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-  }
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-  const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-  return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
-}
-
-// block dealt to `wave` in round q of the assembly / the Sigma^-1 pass: the row-major enumeration has the expensive blocks of the Sigma^-1
-// pass first (block (bi, bj) costs nst - bi products), so the rounds run forwards and backwards in turn -- 16 products for the busiest
-// wave at n = 128 instead of 19.  Both passes MUST deal alike: the kernel values travel from one to the other by (block, lane) slot.
-__device__ __forceinline__ int tr_deal(int q, int wave) { return 8 * q + ((q & 1) ? 7 - wave : wave); }
-// acc += sum_{kb = k0}^{k1 - 1} op(P_kb) * Q_kb over 16 x 16 blocks, the NEXT block's operands requested before this block's four MFMAs
-// (a runtime loop of load-then-multiply rounds waits one LDS round trip per block).  P_kb at baseA + offA(kb): element (m, k) at
-// [m * lda + k], or (TA) the transposed block: (m, k) at [k * lda + m]; Q_kb at baseB + offB(kb): element (k, n) at [k * ldb + n].
-template <bool TA, class OA, class OB>
-__device__ __forceinline__ void tr_chain(d4_t& acc, int k0, int k1, const double* baseA, OA offA, int lda, const double* baseB, OB offB,
-                                         int ldb, int lane) {
-  if (k0 >= k1) return;
-  const int m = lane & 15, g = lane >> 4;
-  double a[4], b[4];
-  {
-    const double* pa = baseA + offA(k0);
-    const double* pb = baseB + offB(k0);
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) {
-      const int k = kq * 4 + g;
-      a[kq] = TA ? pa[k * lda + m] : pa[m * lda + k];
-      b[kq] = pb[k * ldb + m];
-    }
-  }
-  for (int kb = k0; kb < k1; ++kb) {
-    double an[4], bn[4];
-    const int kn = min(kb + 1, k1 - 1);      // (the last round re-reads its own block)
-    const double* pa = baseA + offA(kn);
-    const double* pb = baseB + offB(kn);
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) {
-      const int k = kq * 4 + g;
-      an[kq] = TA ? pa[k * lda + m] : pa[m * lda + k];
-      bn[kq] = pb[k * ldb + m];
-    }
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[kq], b[kq], acc, 0, 0, 0);
-#pragma unroll
-    for (int kq = 0; kq < 4; ++kq) {
-      a[kq] = an[kq];
-      b[kq] = bn[kq];
-    }
-  }
-}
-// accumulator (lane (g, c), register r = entry (g + 4 r, c)) -> the block's [16][17] home
-__device__ __forceinline__ void tr_store(double* dst, const d4_t& acc, int g, int c, double sign) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) dst[(g + 4 * r) * BLD + c] = sign * acc[r];
-}
-
 // LDS (doubles): S 36 * 272 | Xs [128][17] | Ym, Gam, Am [128][16] each | piv [128] | dvec [128] | small
 #define TR_OFF_XS (NBLK_LOWER * BLKSZ)
 #define TR_OFF_YM (TR_OFF_XS + TR_N * (TR_D + 1))
@@ -194,14 +115,6 @@ __device__ __forceinline__ void tr_store(double* dst, const d4_t& acc, int g, in
 #define TR_OFF_RES (TR_OFF_SMALL + TR_SMALL_DOUBLES + 9 * (TR_NRED_RES - TR_NRED))
 #define TR_LDS_DOUBLES_RES (TR_OFF_RES + 4 * TR_N + 16)
 static_assert(TR_LDS_DOUBLES_RES * sizeof(double) <= 160 * 1024, "the residual launch's LDS exceeds a CU's 160 KiB");
-
-// a uniform word / pointer parked in LDS, read where it is used: loop-invariant values hoisted out of the step loop stay in scalar
-// registers for the whole kernel, and the scalar file is full (its spills take vector registers the step's phases need)
-__device__ __forceinline__ int tr_lds_int(const int* p) { return __builtin_amdgcn_readfirstlane(*reinterpret_cast<const volatile int*>(p)); }
-__device__ __forceinline__ double* tr_lds_ptr(const int* p) {
-  const unsigned lo = (unsigned)tr_lds_int(p), hi = (unsigned)tr_lds_int(p + 1);
-  return reinterpret_cast<double*>(((unsigned long long)hi << 32) | lo);
-}
 
 // DM: the input dimensions the per-entry loops are unrolled for (8 or 16: every model of the launch has D <= DM)
 // TRAIN: every step of the loop with Adam inside; !TRAIN ("evaluate"): ONE pass that writes the value and the gradients out
@@ -375,97 +288,8 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     LDS_BARRIER();
     TR_PROF(1);
 
-    // ---- P2: blocked Cholesky over 16-column stages AND the inverse, two barriers per stage.
-    //   [A] wave 0 applies column jj - 1 to its diagonal block (jj, jj) and factors + inverts it in registers (F: the slot receives
-    //       inv(L_jj), the pivots go to piv[]); in its shadow the helper waves -- every wave that does not share wave 0's SIMD: fp64
-    //       MFMAs and the pivot loop's fp64 vector instructions use the same pipe -- apply column jj - 1 to all the other blocks and
-    //       compute row block jj - 1 of the inverse, X[s][j] = -inv(L_s) sum_{k=j}^{s-1} L[s][k] X[k][j], into registers;
-    //   [B] the inverse's row is stored over row jj - 1 of L (nobody reads it any more) and column jj is solved by all waves.
-    for (int jj = 0; jj < nst; ++jj) {
-      d4_t Xn[2];
-      if (wave == 0) {
-        double* Dj = S + blk_off(jj, jj);
-        d4_t upd = {0.0, 0.0, 0.0, 0.0};      // the one update still missing from this block: applied on the way into the registers
-        if (jj > 0) mma16<true>(upd, S + blk_off(jj, jj - 1), BLD, S + blk_off(jj, jj - 1), BLD, lane);
-        int cc = c, gg = g;
-        asm volatile("" : "+v"(cc), "+v"(gg));      // (opaque per iteration: the stage loop must not be specialised per jj)
-        double v[4], w[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] = Dj[(gg + 4 * r) * BLD + cc] - upd[r];
-          w[r] = (gg + 4 * r == cc) ? 1.0 : 0.0;
-        }
-        double rowA = bperm_d(v[0], cc);
-        double rowW = (cc == 0) ? 1.0 : 0.0;
-        {
-          double hA = bperm_d(v[0], 16 + cc), hW = (cc == 1) ? 1.0 : 0.0;
-          double pRow = 0.0, pt = 0.0, ptw = 0.0;
-          double dcur = row_bcast64<0>(rowA), ycur = __builtin_amdgcn_rcp(dcur);
-#define TR_F16(JJ) f16_step_dpp<JJ>(v, w, rowA, rowW, hA, hW, pRow, pt, ptw, dcur, ycur, cc, gg);
-          TR_F16(0) TR_F16(1) TR_F16(2) TR_F16(3) TR_F16(4) TR_F16(5) TR_F16(6) TR_F16(7) TR_F16(8) TR_F16(9) TR_F16(10) TR_F16(11)
-          TR_F16(12) TR_F16(13) TR_F16(14) TR_F16(15)
-#undef TR_F16
-        }
-        const int q = c >> 2;
-        const double dsel = (q == 0) ? v[0] : (q == 1) ? v[1] : (q == 2) ? v[2] : v[3];
-        const double dcol = bperm_d(dsel, 16 * (c & 3) + c);      // pivot of column c
-        const double rs = rsqrt_nr(dcol);
-        const unsigned long long nonpos = __ballot(!(dcol > 0.0)) & 0xffffull;
-        const int bad = nonpos ? __ffsll((long long)nonpos) : 0;
-        if (g == 0) piv[jj * 16 + c] = dcol;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int i = g + 4 * r;
-          const double rsi = bperm_d(rs, i);
-          Dj[i * BLD + c] = (i >= c) ? w[r] * rsi : 0.0;       // inv(L_jj)
-        }
-        if (bad && lane == 0 && jj * 16 + bad <= n && flags[0] == 0) flags[0] = jj * 16 + bad;
-      } else if (hidx >= 0 && jj > 0) {
-        // column jj - 1 reaches every block (i, k), jj <= k <= i, but (jj, jj)
-        const int m = nst - jj;
-        for (int t = 1 + hidx; t < m * (m + 1) / 2; t += nh) {
-          int a, b;
-          blk_unrank(t, a, b);
-          const int i = jj + a, k = jj + b;
-          d4_t acc = {0.0, 0.0, 0.0, 0.0};
-          mma16<true>(acc, S + blk_off(i, jj - 1), BLD, S + blk_off(k, jj - 1), BLD, lane);
-          double* dst = S + blk_off(i, k);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dst[(g + 4 * r) * BLD + c] -= acc[r];
-        }
-        // row block s = jj - 1 of the inverse, columns hidx and hidx + nh, kept in registers until row s of L is dead
-        const int s_ = jj - 1;
-#pragma unroll
-        for (int q2 = 0; q2 < 2; ++q2) {
-          const int j = hidx + q2 * nh;
-          if (j >= s_) continue;
-          d4_t T = {0.0, 0.0, 0.0, 0.0};
-          tr_chain<false>(T, j, s_, S + blk_off(s_, 0), [](int k) { return k * BLKSZ; }, BLD, S, [j](int k) { return blk_off(k, j); }, BLD, lane);
-          d4_t acc = {0.0, 0.0, 0.0, 0.0};
-          const double* Ws = S + blk_off(s_, s_);
-#pragma unroll
-          for (int kq = 0; kq < 4; ++kq) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * BLD + kq * 4 + g], T[kq], acc, 0, 0, 0);
-          Xn[q2] = acc;
-        }
-      }
-      LDS_BARRIER();
-      TR_PROF(2);
-      if (hidx >= 0 && jj > 0) {
-#pragma unroll
-        for (int q2 = 0; q2 < 2; ++q2) {
-          const int j = hidx + q2 * nh;
-          if (j < jj - 1) tr_store(S + blk_off(jj - 1, j), Xn[q2], g, c, -1.0);
-        }
-      }
-      // solve: L[i][jj] = S[i][jj] inv(L_jj)^T for the block rows below
-      for (int i = jj + 1 + wave; i < nst; i += 8) {
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-        mma16<true>(acc, S + blk_off(i, jj), BLD, S + blk_off(jj, jj), BLD, lane);
-        tr_store(S + blk_off(i, jj), acc, g, c, 1.0);
-      }
-      LDS_BARRIER();
-      TR_PROF(3);
-    }
+    // ---- P2: blocked Cholesky over 16-column stages AND the inverse, two barriers per stage (train_tile.h)
+    TR_FACTOR_STAGES(S, piv, flags, n, nst, lane, wave, g, c, hidx, nh, TR_PROF)
     if (flags[0] != 0) {       // (uniform: every thread reads the same word behind the barrier)
       failed = flags[0];
       if (TRAIN) {
@@ -481,45 +305,21 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       }
       break;
     }
-    // ---- the last row block of the inverse (s = nst - 1), one column per wave
-    if (nst > 1) {
-      const int s_ = nst - 1, j = wave;
-      d4_t X = {0.0, 0.0, 0.0, 0.0};
-      if (j < s_) {
-        d4_t T = {0.0, 0.0, 0.0, 0.0};
-        tr_chain<false>(T, j, s_, S + blk_off(s_, 0), [](int k) { return k * BLKSZ; }, BLD, S, [j](int k) { return blk_off(k, j); }, BLD, lane);
-        const double* Ws = S + blk_off(s_, s_);
-#pragma unroll
-        for (int kq = 0; kq < 4; ++kq) X = __builtin_amdgcn_mfma_f64_16x16x4f64(Ws[c * BLD + kq * 4 + g], T[kq], X, 0, 0, 0);
-      }
-      LDS_BARRIER();
-      if (j < s_) tr_store(S + blk_off(s_, j), X, g, c, -1.0);
-      LDS_BARRIER();
-    }
+    tr_inverse_last_row(S, nst, lane, wave, g, c);
     TR_PROF(5);
 
     // ---- P3: Gamma = W Y, A = W^T Gamma on the matrix cores (W = L^-1, lower; the d <= 16 target columns are one block column): wave w
     //      owns block row w of Gamma (w + 1 products) and block row 7 - w of A (w + 1 products)
     {
-      if (wave < nst) {
-        const int bi = wave;
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-        tr_chain<false>(acc, 0, bi + 1, S + blk_off(bi, 0), [](int kb) { return kb * BLKSZ; }, BLD, Ym, [](int kb) { return kb * 16 * TR_Y; },
-                        TR_Y, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Gam[(bi * 16 + g + 4 * r) * TR_Y + c] = acc[r];
-      }
+      tr_gamma_rows(S, Ym, Gam, nst, lane, wave, g, c);
       LDS_BARRIER();
       double ay = 0.0;      // residual members: this lane's part of sum A .* y_low
       isres = RESID && tr_lds_int(rmode) != 0;
-      if (7 - wave < nst) {
-        const int bi = 7 - wave;
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-        tr_chain<true>(acc, bi, nst, S, [bi](int kb) { return blk_off(kb, bi); }, BLD, Gam, [](int kb) { return kb * 16 * TR_Y; }, TR_Y, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Am[(bi * 16 + g + 4 * r) * TR_Y + c] = acc[r];
+      d4_t acc = {0.0, 0.0, 0.0, 0.0};
+      if (tr_alpha_rows(S, Gam, Am, nst, lane, wave, g, c, acc)) {
         if (isres) {      // (y_low requested after the chain, not under it: four more live values there cost the <8> instantiation its
                           //  spill-free allocation)
+          const int bi = 7 - wave;
           const double* yl = tr_lds_ptr(rmode + 2);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {

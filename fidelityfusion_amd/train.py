@@ -5,7 +5,8 @@ as ONE call of ffgp_train_raw: likelihood, closed-form gradients and torch.optim
 the loss trace returned, the factorisation status read once.  Through the drop-in modules a step costs 0.28-0.32 ms at N <= 128 (one
 Python round trip, one autograd graph, one status read-back); here it costs its GPU work.
 Models whose kernel is a SumKernel / ProductKernel tree of up to four library kernels -- SumKernel(LinearKernel, MaternKernel) is the
-kernel of the reference's demos and two-fidelity models -- take the same route through ffgp_train_tree_raw (launch per stage, every size).
+kernel of the reference's demos and two-fidelity models -- take the same route through ffgp_train_tree_raw (launch per stage, every size),
+or, with `tree_one_launch=True` and at most TREE_ONE_LAUNCH_MAX_N points, through ffgp_train_tree_lds_raw: one launch for all their steps.
 """
 import ctypes as C
 
@@ -17,6 +18,8 @@ from ._lib import FFGP_LL_V1, Problem, check, lib
 
 TRAIN_MAX_MODELS = 16      # models per ffgp_train_raw call (include/ffgp.h); longer lists are trained in chunks
 TRAIN_THREADS = 4          # host threads (handle + stream each) that train the larger models of one call side by side
+TREE_ONE_LAUNCH_MAX_N = 128   # composed-kernel models up to this size take ffgp_train_tree_lds_raw under `tree_one_launch=True`: the largest
+                              # N at which it beat the launch-per-stage call by more than the run's spread (profiles/train_tree_lds_bench.txt)
 
 
 class AdamState:
@@ -147,7 +150,7 @@ def _residual_ok(res, x):
     return True
 
 
-def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None):
+def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None, tree_one_launch=False):
     """`steps` Adam iterations on every model of `models` (independent `cigp` models, `xs[f]`, `ys[f]` their training data; y may be
     `[y, y_var]`), each exactly the reference's iteration (FidelityFusion_Models/ResGP.py:82-88): loss = -negative_log_likelihood,
     gradients of the three raw parameters, torch.optim.Adam(lr, betas, eps) update.  Returns `(trace, state)`:
@@ -163,6 +166,12 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     of that call's models at that step.  A composed-kernel model given a `residual=` link is NOT fused: it (and with it the whole
     `train_many` call, state["fused"] = False) keeps the reference's loop, as do compositions with a RationalQuadraticKernel leaf, a
     module used as two leaves, or kernel.FUSE_PAIRS = False.
+    `tree_one_launch=True` sends the composed-kernel models of at most TREE_ONE_LAUNCH_MAX_N points with D <= 16 and d <= 16 through
+    ffgp_train_tree_lds_raw instead, up to 16 per call: ONE kernel launch for all their steps (csrc/train_tree_lds.hip, a persistent
+    workgroup per model), with the plain small models' failure rule -- a not-PD Sigma stops that model alone, the others of the call
+    complete their steps.  The Adam state has the same layout on both routes, so a `state` may be continued with either value of the
+    keyword; the two routes agree to rounding, not bit for bit.  Every other model is routed as without the keyword.
+    state["tree_one_launch"] lists the indices of the models that took this route in the last call.
     A Sigma that is not positive definite raises torch.linalg.LinAlgError as the reference's loop would; the failing model's parameters
     then hold the values they had when that step began (the other small models of the same call have completed their steps; the
     optimiser state of a failed call is not advanced).
@@ -198,6 +207,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     if state is None:
         state = {"fused": fused, "chunks": {}, "opts": [None] * nF}
     state["residual_targets"] = [None] * nF
+    state["tree_one_launch"] = []
     if not fused or not state["fused"]:
         if state["fused"]:
             raise ValueError("train_many: this state belongs to fused training; the models no longer qualify for it")
@@ -277,7 +287,10 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         return p, tk, P
 
     def run_tree(idx):
-        """one ffgp_train_tree_raw call for the composed-kernel models `idx` (<= 16); Adam state [exp_avg (P) | exp_avg_sq (P)] per model"""
+        """one ffgp_train_tree_raw call -- ffgp_train_tree_lds_raw for a chunk of `one_launch` -- for the composed-kernel models `idx`
+        (<= 16); Adam state [exp_avg (P) | exp_avg_sq (P)] per model"""
+        name = "ffgp_train_tree_lds_raw" if idx[0] in one_launch else "ffgp_train_tree_raw"
+        fn = getattr(lib, name)
         h = _lib.handle(dev.index)
         _lib.bind_stream(h, dev.index)
         P = (Problem * len(idx))()
@@ -287,8 +300,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
             P[j], L[j], n_ = describe_tree(f, keep)
             npar.append(n_)
         return launch(idx, 2 * max(npar), lambda st, tr: check(
-            lib.ffgp_train_tree_raw(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), st.stride, int(st.step), tr.data_ptr(),
-                                    tr.stride(0)), "ffgp_train_tree_raw"))
+            fn(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), st.stride, int(st.step), tr.data_ptr(), tr.stride(0)), name))
 
     def launch(idx, stride, call):
         """the chunk's Adam state and trace rows around one library call `call(state, trace rows)`; returns the status"""
@@ -340,12 +352,17 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     trees = {f for f in range(nF) if _is_tree(elig[f])}
     small = [f for f in range(nF) if f not in trees and shapes[f][0] <= F.SMALL_BATCH_MAX_N and shapes[f][1] <= F.SMALL_BATCH_MAX_D
              and shapes[f][2] <= F.SMALL_BATCH_MAX_d]
-    small_trees = [f for f in sorted(trees) if shapes[f][0] <= F.SMALL_BATCH_MAX_N]
-    large = [f for f in range(nF) if f not in set(small) and f not in set(small_trees)]
+    # ... and under `tree_one_launch` those the LDS trainer covers form calls of ffgp_train_tree_lds_raw, up to 16 per call.
+    one_launch = {f for f in trees if tree_one_launch and shapes[f][0] <= TREE_ONE_LAUNCH_MAX_N and shapes[f][1] <= F.SMALL_BATCH_MAX_D
+                  and shapes[f][2] <= F.SMALL_BATCH_MAX_d}
+    lds_trees = sorted(one_launch)
+    small_trees = [f for f in sorted(trees) if shapes[f][0] <= F.SMALL_BATCH_MAX_N and f not in one_launch]
+    large = [f for f in range(nF) if f not in set(small) and f not in set(small_trees) and f not in one_launch]
+    state["tree_one_launch"] = lds_trees
     if len(small) == 1:      # (a lone small model gains nothing from the batch kernel: its own call folds the tail launches)
         large, small = sorted(large + small), []
     rcs = []
-    for group in (small, small_trees):
+    for group in (small, small_trees, lds_trees):
         for c0 in range(0, len(group), TRAIN_MAX_MODELS):
             rcs.append((group[c0:c0 + TRAIN_MAX_MODELS], run(group[c0:c0 + TRAIN_MAX_MODELS])))
     if len(large) >= 2 and _lib.current_slot() == 0:

@@ -604,6 +604,24 @@ typedef struct {
 int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, int steps, const ffgp_adam* opt,
                         double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 
+/* ffgp_train_tree_raw's job for SMALL members in ONE launch (csrc/train_tree_lds.hip): a persistent workgroup per model keeps Sigma,
+   its factor, the raw parameters of every leaf and their Adam moments in LDS and runs all `steps` iterations inside the kernel, as
+   ffgp_train_raw's one-launch form does for a single radial kernel.  The parameter list, the ffgp_problem / ffgp_tree_links
+   description and the state layout -- [exp_avg (P) | exp_avg_sq (P)] in the canonical leaf order, stride state_stride >= 2 P -- are
+   ffgp_train_tree_raw's, so one optimiser can be continued through either call; the arithmetic is not (the leaves are evaluated per
+   entry from X and w^2, the factorisation is the LDS trainer's): the two agree to rounding, not bit for bit.
+   Covers n <= 128, D <= 16, d <= 16, F <= 16, the V1 likelihood, diag_add and diag_vec, trees of 2-4 leaves in the FFGP_TREE_CHAIN /
+   FFGP_TREE_BALANCED shapes with Sum / Product nodes, leaves FFGP_KFUN_SE ... FFGP_KFUN_MATERN52 (w_dev one broadcast value or D) and
+   FFGP_KFUN_LINEAR (centre at the origin, given, or trained).  FFGP_ERR_ARG, with nothing enqueued and nothing written, for anything
+   else: what ffgp_train_tree_raw refuses (a FFGP_KFUN_RQ leaf, n_leaves outside 2..4, F outside 1..16, ...), and n > 128, D > 16,
+   d > 16, the V2 likelihood, add_mat_dev, add_all, mean_jitter.
+   Return value and failure semantics are ffgp_train_raw's ONE-LAUNCH form, not ffgp_train_tree_raw's: a Sigma that is not positive
+   definite stops that member alone at that step -- its trace holds NaN from there on, its parameters and moments the values they had
+   when the step began -- the other members complete their steps, and the call returns the pivot status of the first failing member
+   (in the caller's order), else 0.  Synchronous.                                                                              */
+int ffgp_train_tree_lds_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, int steps, const ffgp_adam* opt,
+                            double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
+
 /* K Adam steps of an ACQUISITION optimiser on a frozen posterior in ONE launch -- the reference's second hot loop
    (Bayesian_optimization/acq.py:48-68: `raw_samples` <= 500 query points, `num_restarts` = 30 iterations of zero_grad();
    loss = -acq(X).sum(); loss.backward(); Adam.step(), the model untouched).  The loss is a sum of per-point terms and Adam is

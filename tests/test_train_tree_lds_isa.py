@@ -1,0 +1,59 @@
+"""Build-time check of the one-launch composed-kernel trainer (csrc/train_tree_lds.hip; no GPU needed: hipcc cross-compiles): each
+instantiation of its kernel runs entirely in registers and LDS -- no private (scratch) segment, no vector register spilled -- its
+dynamic LDS request fits the CU's 160 KiB, and it is compiled for the 512 threads it is launched with.  Metadata only, as
+test_eig_lds_isa.py."""
+import os
+import re
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LDS_PER_CU = 160 * 1024
+
+
+@pytest.fixture(scope="module")
+def kernels():
+    """{kernel name: its metadata block (amdhsa.kernels) as a dict of the integer fields}"""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from check_isa import device_asm
+    asm = device_asm("train_tree_lds.hip")
+    ks = asm[asm.index("amdhsa.kernels:"):]
+    out = {}
+    for blk in re.split(r"\n  - ", ks)[1:]:
+        m = re.search(r"\.name:\s+(\S+)", blk)
+        if m:
+            out[m.group(1)] = {k: int(v) for k, v in re.findall(r"\.([a-z_]+):\s+(\d+)\n", blk)}
+    return out
+
+
+def _dynamic_lds_bytes():
+    """the host's request, TTL_LDS_DOUBLES of train_tree_lds.hip restated: the block image, X [128][17], three [128][16] images, pivots
+    and the diagonal extra, the leaves' tables, four rows of 136 (raw parameters, two moments, totals), 8 scalars and the int table"""
+    blocks, ints = 36 * 16 * 17, 136 + 4 + 5 + 3 + 16
+    return (blocks + 128 * 17 + 3 * 128 * 16 + 2 * 128 + (3 * 4 * 16 + 4 * 4) + 4 * 136 + 8 + ints // 2) * 8
+
+
+def test_the_two_instantiations_are_there(kernels):
+    assert len(kernels) == 2 and all("ffgp_train_tree_lds_kernel" in name for name in kernels), sorted(kernels)
+    assert any("ILi8E" in name for name in kernels) and any("ILi16E" in name for name in kernels)
+
+
+def test_no_scratch_and_no_spilled_vector_register(kernels):
+    for name, meta in kernels.items():
+        assert meta["private_segment_fixed_size"] == 0, (name, meta)
+        assert meta["vgpr_spill_count"] == 0, (name, meta)
+
+
+def test_lds_fits_the_cu_and_the_launch_matches_the_bounds(kernels):
+    src = open(os.path.join(ROOT, "fidelityfusion_amd", "csrc", "train_tree_lds.hip")).read()
+    for piece in ("#define TTL_OFF_XS (NBLK_LOWER * BLKSZ)", "#define TTL_OFF_PAR (TTL_OFF_LEAF + 3 * TTL_L * TR_D + 4 * TTL_L)",
+                  "#define TTL_OFF_SC (TTL_OFF_PAR + 4 * TTL_PPAD)", "#define TTL_OFF_INT (TTL_OFF_SC + 8)",
+                  "#define TTL_INTS (TTL_PPAD + 4 + 5 + 3 + 16)", "#define TTL_LDS_DOUBLES (TTL_OFF_INT + TTL_INTS / 2)", "#define TTL_PPAD 136"):
+        assert piece in src, piece      # the formula restated above
+    assert src.count("dim3(TR_T), TTL_LDS_DOUBLES * sizeof(double)") == 2      # both launches: 512 threads, this request
+    tile = open(os.path.join(ROOT, "fidelityfusion_amd", "csrc", "train_tile.h")).read()
+    assert "#define TR_T 512" in tile
+    for name, meta in kernels.items():
+        assert meta["max_flat_workgroup_size"] == 512, (name, meta)
+        assert meta["group_segment_fixed_size"] + _dynamic_lds_bytes() <= LDS_PER_CU, (name, meta)

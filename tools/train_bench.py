@@ -4,7 +4,9 @@
 python tools/train_bench.py tree [steps]: the same for the reference's demo kernel SumKernel(LinearKernel, MaternKernel) -- train_many
 (ffgp_train_tree_raw) against the per-step loop these models ran on before, both in this process, alternating, three rounds each
 after a warm-up of either; and, for information, the single-kernel Matern model of the same size through the launch-per-stage trainer
-(option train_persist = 0): what the tree pass costs per step."""
+(option train_persist = 0): what the tree pass costs per step.  At N <= train.TREE_ONE_LAUNCH_MAX_N a further column: the same models
+through train_many(..., tree_one_launch=True) (ffgp_train_tree_lds_raw: one launch for all the steps), which has to beat the
+launch-per-stage call by more than the spread of either over the run's three rounds."""
 import os
 import sys
 import time
@@ -59,16 +61,22 @@ def timed(fn):
 
 
 def tree_mode():
-    from fidelityfusion_amd import _lib
+    from fidelityfusion_amd import _lib, train
     print("SumKernel(LinearKernel(2), MaternKernel(2, nu = 2.5)), d = 1, %d Adam steps; ms per call: median [min .. max] of 3 alternating rounds" % steps)
-    for n, F in ((16, 1), (32, 1), (128, 1), (300, 1), (1024, 1), (64, 16)):
-        fused, looped = make(n, 2, 1, F, "tree"), make(n, 2, 1, F, "tree")
+    for n, F in ((16, 1), (32, 1), (64, 1), (128, 1), (300, 1), (1024, 1), (64, 16)):
+        fused, looped, lds = make(n, 2, 1, F, "tree"), make(n, 2, 1, F, "tree"), make(n, 2, 1, F, "tree")
+        one = n <= train.TREE_ONE_LAUNCH_MAX_N
         _, st = train_many(*fused, 5)
         assert st["fused"] is True, "the tree model was not trained by the library call"
         loop(*looped, 5)
-        t_many, t_loop = [], []
+        if one:
+            _, st = train_many(*lds, 5, tree_one_launch=True)
+            assert st["tree_one_launch"] == list(range(F)), "the tree models did not take the one-launch route"
+        t_many, t_loop, t_lds = [], [], []
         for _ in range(3):
             t_many.append(timed(lambda: train_many(*fused, steps)))
+            if one:
+                t_lds.append(timed(lambda: train_many(*lds, steps, tree_one_launch=True)))
             t_loop.append(timed(lambda: loop(*looped, steps)))
         _lib.set_option("train_persist", 0, 0)
         try:
@@ -77,12 +85,17 @@ def tree_mode():
             t_single = sorted(timed(lambda: train_many(*single, steps)) for _ in range(3))
         finally:
             _lib.set_option("train_persist", 1, 0)
-        t_many.sort(), t_loop.sort()
+        t_many.sort(), t_loop.sort(), t_lds.sort()
         print("N=%5d F=%2d  train_many %8.2f [%8.2f .. %8.2f] (%.3f ms/step/model)   per-step loop %8.2f [%8.2f .. %8.2f] (%.3f)   x%.1f"
               "   | single Matern, launch per stage: %8.2f (%.3f ms/step/model)"
               % (n, F, t_many[1], t_many[0], t_many[2], t_many[1] / steps / F, t_loop[1], t_loop[0], t_loop[2], t_loop[1] / steps / F,
                  t_loop[1] / t_many[1], t_single[1], t_single[1] / steps / F), flush=True)
         assert t_many[2] < t_loop[0], "train_many is not ahead of the per-step loop at N = %d, F = %d" % (n, F)
+        if one:
+            spread = max(t_many[2] - t_many[0], t_lds[2] - t_lds[0])
+            print("              one launch %8.2f [%8.2f .. %8.2f] (%.4f ms/step/model)   x%.1f against launch per stage (spread %.2f)"
+                  % (t_lds[1], t_lds[0], t_lds[2], t_lds[1] / steps / F, t_many[1] / t_lds[1], spread), flush=True)
+            assert t_many[1] - t_lds[1] > spread, "the one-launch route is not ahead of launch per stage at N = %d, F = %d" % (n, F)
 
 
 if mode == "tree":
