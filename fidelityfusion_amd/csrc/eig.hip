@@ -37,6 +37,21 @@ __global__ __launch_bounds__(256) void ffgp_syevj64_kernel(SyevjArgs a) {
     V[i][j] = (i == j) ? 1.0 : 0.0;
   }
   __syncthreads();
+  // The sweeps decide on sums of squares and skip rotations below an absolute 1e-300: a matrix of entries ~1e-160 would "converge"
+  // with its off-diagonal untouched.  So the image is brought to max-abs in [1, 2) by a power of two (exact) and the eigenvalues are
+  // taken back at the end: the rotations of 2^k M are those of M, bit for bit.
+  double amax = 0.0;
+  for (int idx = tid; idx < EJ * EJ; idx += 256) amax = fmax(amax, fabs(A[idx >> 6][idx & 63]));
+  for (int o = 32; o > 0; o >>= 1) amax = fmax(amax, __shfl_xor(amax, o));
+  if ((tid & 63) == 0) red[tid >> 6] = amax;
+  __syncthreads();
+  const int sexp = ffgp_pow2_exp(fmax(fmax(red[0], red[1]), fmax(red[2], red[3])));
+  const double unscale = __builtin_amdgcn_ldexp(1.0, sexp);
+  if (sexp != 0) {   // uniform
+    const double sigma = __builtin_amdgcn_ldexp(1.0, -sexp);
+    for (int idx = tid; idx < EJ * EJ; idx += 256) A[idx >> 6][idx & 63] *= sigma;
+  }
+  __syncthreads();
   for (int sweep = 0; sweep < a.max_sweeps; ++sweep) {
     // convergence: off-diagonal mass against the diagonal's
     double off = 0.0, dia = 0.0;
@@ -133,7 +148,7 @@ __global__ __launch_bounds__(256) void ffgp_syevj64_kernel(SyevjArgs a) {
       r += before ? 1 : 0;
     }
     rank_[tid] = r;
-    if (!pad_i && a.evals) a.evals[(size_t)blockIdx.x * a.sE + r] = di;
+    if (!pad_i && a.evals) a.evals[(size_t)blockIdx.x * a.sE + r] = di * unscale;
   }
   __syncthreads();
   double* __restrict__ Q = a.Q + (size_t)blockIdx.x * a.sQ;

@@ -89,6 +89,16 @@ __device__ __forceinline__ double ffgp_exp_fast(double x, const ExpCoef& e) {
   return __builtin_amdgcn_ldexp(p, (int)n);
 }
 
+// Scale covariance of the eigensolvers: e = ilogb(m) for the largest magnitude m of a matrix, kept in [-1021, 1021] so that both
+// 2^-e and 2^e are normal numbers; 0 for m = 0 (and for a NaN).  ldexp(1, -e) brings the matrix to max-abs in [1, 2) and ldexp(1, e)
+// takes the eigenvalues back: powers of two, so neither multiplication rounds (short of the denormal range) and a matrix times 2^k
+// is solved on the very image the matrix itself is.
+__device__ __forceinline__ int ffgp_pow2_exp(double m) {
+  if (!(m > 0.0)) return 0;
+  const int e = ((__double2hiint(m) >> 20) & 0x7ff) - 1023;   // denormal: -1023, Inf: 1024 -- both clamped
+  return min(max(e, -1021), 1021);
+}
+
 // GEMM operand layouts.  "K-major": element (row, k) at P[row*ld + k]; "MN-major": at P[k*ld + row].
 enum { OP_KMAJOR = 0, OP_MNMAJOR = 1 };
 // tile scheduling modes: full rectangle / lower-triangular tiles of a symmetric update

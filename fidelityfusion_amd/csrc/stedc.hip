@@ -20,6 +20,11 @@
 //                 ascending order of the merged eigenvalues
 //     GEMM        Q_new = Q_old S on the fp64 matrix cores (one batched launch for the level's equal merges, one for a ragged last)
 // Kernel matrices deflate massively (their spectrum clusters at 0); nothing here depends on that.
+//
+// Scale: the deflation test rho |z_j| <= 8 eps max(max|d|, max|z|) is dlaed2's, and like dlaed2 it is a test for a matrix of norm ~1
+// (z is a row of an orthogonal matrix whatever the matrix is; rho and d scale with it): on a matrix of norm 1e-20 it deflates every
+// merge completely and returns the leaves' eigenvalues.  dstedc scales to norm 1 first; here dc_scale multiplies d and e by the power
+// of two that brings max(|d|, |e|) into [1, 2) (exact, on the device) and dc_unscale takes the eigenvalues back.
 #include "ffgp_internal.h"
 #include "syevd_internal.h"
 
@@ -445,9 +450,38 @@ __global__ __launch_bounds__(256) void dc_leaf_fill(const double* __restrict__ d
   }
 }
 
+// d, e -> sigma d, sigma e (e[n - 1] = 0) with sigma = 2^-ilogb(max(|d_i|, |e_i|, i < n - 1)), 1 for the zero matrix; scal[0] = 1 / sigma.
+// One workgroup: n <= 32768 is 32 entries per thread.
+__global__ __launch_bounds__(1024) void dc_scale(const double* __restrict__ d, const double* __restrict__ e, int n, double* __restrict__ dsc,
+                                                 double* __restrict__ esc, double* __restrict__ scal) {
+  __shared__ double red[16];
+  const int tid = threadIdx.x;
+  double m = 0.0;
+  for (int i = tid; i < n; i += 1024) {
+    m = fmax(m, fabs(d[i]));
+    if (i < n - 1) m = fmax(m, fabs(e[i]));
+  }
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+  if ((tid & 63) == 0) red[tid >> 6] = m;
+  __syncthreads();
+  m = red[0];
+  for (int w = 1; w < 16; ++w) m = fmax(m, red[w]);
+  const int sexp = ffgp_pow2_exp(m);
+  const double sigma = __builtin_amdgcn_ldexp(1.0, -sexp);
+  for (int i = tid; i < n; i += 1024) {
+    dsc[i] = sigma * d[i];
+    esc[i] = (i < n - 1) ? sigma * e[i] : 0.0;
+  }
+  if (tid == 0) scal[0] = __builtin_amdgcn_ldexp(1.0, sexp);
+}
+__global__ __launch_bounds__(256) void dc_unscale(double* __restrict__ lam, int n, const double* __restrict__ scal) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) lam[i] *= scal[0];
+}
+
 size_t ffgp_stedc_ws_doubles(int n) {
-  // Z ping-pong partner + S: 2 n^2;  leaf images n * 64;  ~20 vectors of n (ints counted as doubles)
-  return (size_t)2 * n * n + (size_t)n * 64 + (size_t)24 * n + 1024;
+  // Z ping-pong partner + S: 2 n^2;  leaf images n * 64;  ~22 vectors of n (ints counted as doubles)
+  return (size_t)2 * n * n + (size_t)n * 64 + (size_t)26 * n + 1024;
 }
 
 // d, e [n] (e[n-1] ignored) -> lam [n] ascending, Z [n, ldz] eigenvectors in columns.  n a multiple of 64.
@@ -459,7 +493,11 @@ int ffgp_stedc_impl(ffgp_handle* h, const double* d, const double* e, int n, dou
   double* M = S + (size_t)n * n;            // leaf images
   double* v = M + (size_t)n * 64;
   DcLevel p;
-  p.n = n; p.e = e;
+  p.n = n;
+  double* dsc = v; v += n;
+  double* esc = v; v += n;
+  double* scal = v; v += 8;
+  p.e = esc;
   double* lamA = v; v += n;
   double* lamB = v; v += n;
   p.z = v; v += n;
@@ -488,7 +526,8 @@ int ffgp_stedc_impl(ffgp_handle* h, const double* d, const double* e, int n, dou
   p.S = S; p.lds = n;
   // leaves
   const int nl = n / 64;
-  hipLaunchKernelGGL(dc_leaf_fill, dim3(nl), dim3(256), 0, st, d, e, n, M);
+  hipLaunchKernelGGL(dc_scale, dim3(1), dim3(1024), 0, st, d, e, n, dsc, esc, scal);
+  hipLaunchKernelGGL(dc_leaf_fill, dim3(nl), dim3(256), 0, st, dsc, esc, n, M);
   // ping-pong so that the last level writes into the caller's Z
   int levels = 0;
   for (int bs = 128; bs / 2 < n; bs *= 2) ++levels;
@@ -542,5 +581,7 @@ int ffgp_stedc_impl(ffgp_handle* h, const double* d, const double* e, int n, dou
     int tl = ldc; ldc = ldo; ldo = tl;
     double* tlam = lcur; lcur = loth; loth = tlam;
   }
+  hipLaunchKernelGGL(dc_unscale, dim3((n + 255) / 256), dim3(256), 0, st, lam, n, scal);
+  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
   return FFGP_OK;
 }

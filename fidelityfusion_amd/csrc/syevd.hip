@@ -107,14 +107,57 @@ int ffgp_q1_apply_impl(ffgp_handle* h, const double* Y, int ldy, int n, double* 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// padding to a multiple of 64: decoupled diagonal entries above the spectrum (Gershgorin) -- every reflector component on a
-// padded row is exactly zero, so they never mix with the problem and their eigenpairs come out last
+// The image the stages work on: the lower triangle mirrored, times the power of two sigma that brings the largest entry into [1, 2)
+// (sy2sb and sb2st form reflector norms from squares, which are denormal or zero at 1e-160 and overflow at 1e160; a power of two
+// rounds nothing, and the eigenvalues are multiplied by 1 / sigma at the end), padded to a multiple of 64 with decoupled diagonal
+// entries above the image's spectrum (Gershgorin: twice its largest absolute row sum; 1 for the zero matrix) -- every reflector
+// component on a padded row is exactly zero, so they never mix with the problem and their eigenpairs come out last.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void syevd_rowsum(const double* __restrict__ A, int n, int lda, double* __restrict__ rs) {
+__device__ __forceinline__ double syevd_block_max(double s, double* red) {   // max over the 256 threads, in all of them
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]);
+    __syncthreads();
+  }
+  return red[0];
+}
+// rm[r] = max_{j <= r} |A[r][j]|
+__global__ __launch_bounds__(256) void syevd_rowmax(const double* __restrict__ A, int n, int lda, double* __restrict__ rm) {
   __shared__ double red[256];
   const int r = blockIdx.x;
   double s = 0.0;
-  for (int j = threadIdx.x; j < n; j += 256) s += fabs(A[(size_t)r * lda + j]);
+  for (int j = threadIdx.x; j <= r; j += 256) s = fmax(s, fabs(A[(size_t)r * lda + j]));
+  s = syevd_block_max(s, red);
+  if (threadIdx.x == 0) rm[r] = s;
+}
+// scal[0] = sigma, scal[1] = 1 / sigma
+__global__ __launch_bounds__(256) void syevd_sigma(const double* __restrict__ rm, int n, double* __restrict__ scal) {
+  __shared__ double red[256];
+  double s = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) s = fmax(s, rm[j]);
+  const int sexp = ffgp_pow2_exp(syevd_block_max(s, red));
+  if (threadIdx.x == 0) {
+    scal[0] = __builtin_amdgcn_ldexp(1.0, -sexp);
+    scal[1] = __builtin_amdgcn_ldexp(1.0, sexp);
+  }
+}
+__global__ __launch_bounds__(256) void syevd_pad(const double* __restrict__ A, int n, int lda, double* __restrict__ Ap, int np,
+                                                 const double* __restrict__ scal) {
+  const int r = blockIdx.x;
+  const double sigma = scal[0];
+  for (int j = threadIdx.x; j < np; j += 256) {
+    double v = 0.0;
+    if (r < n && j < n) v = sigma * ((j <= r) ? A[(size_t)r * lda + j] : A[(size_t)j * lda + r]);   // the lower triangle, mirrored
+    Ap[(size_t)r * np + j] = v;
+  }
+}
+// rs[r] = sum_j |Ap[r][j]|, r < n
+__global__ __launch_bounds__(256) void syevd_rowsum(const double* __restrict__ Ap, int n, int np, double* __restrict__ rs) {
+  __shared__ double red[256];
+  const int r = blockIdx.x;
+  double s = 0.0;
+  for (int j = threadIdx.x; j < n; j += 256) s += fabs(Ap[(size_t)r * np + j]);
   red[threadIdx.x] = s;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) {
@@ -123,27 +166,20 @@ __global__ __launch_bounds__(256) void syevd_rowsum(const double* __restrict__ A
   }
   if (threadIdx.x == 0) rs[r] = red[0];
 }
-__global__ __launch_bounds__(256) void syevd_max(const double* __restrict__ rs, int n, double* __restrict__ out) {
+// the np - n < 64 padded diagonal entries
+__global__ __launch_bounds__(256) void syevd_pad_diag(const double* __restrict__ rs, int n, double* __restrict__ Ap, int np) {
   __shared__ double red[256];
   double s = 0.0;
   for (int j = threadIdx.x; j < n; j += 256) s = fmax(s, rs[j]);
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + o]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = 2.0 * red[0] + 1.0;
+  s = syevd_block_max(s, red);
+  const double big = (s > 0.0) ? 2.0 * s : 1.0;
+  const int r = n + threadIdx.x;
+  if (r < np) Ap[(size_t)r * np + r] = big * (1.0 + (double)(r - n) / 64.0);
 }
-__global__ __launch_bounds__(256) void syevd_pad(const double* __restrict__ A, int n, int lda, double* __restrict__ Ap, int np,
-                                                 const double* __restrict__ big) {
-  const int r = blockIdx.x;
-  for (int j = threadIdx.x; j < np; j += 256) {
-    double v = 0.0;
-    if (r < n && j < n) v = (j <= r) ? A[(size_t)r * lda + j] : A[(size_t)j * lda + r];   // the lower triangle, mirrored
-    else if (r == j) v = big[0] * (1.0 + (double)(r - n) / 64.0);
-    Ap[(size_t)r * np + j] = v;
-  }
+__global__ __launch_bounds__(256) void syevd_unscale(const double* __restrict__ lam, int n, const double* __restrict__ scal,
+                                                     double* __restrict__ W) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) W[i] = lam[i] * scal[1];
 }
 
 struct SyevdPlan {
@@ -206,9 +242,13 @@ extern "C" int ffgp_syevd(ffgp_handle* h, const double* A_dev, int n, int lda, d
   FFGP_CHECK(ffgp_ensure_ews(h, s.total * sizeof(double)));
   s = syevd_plan(h->ews, n);
   const int np = s.np;
-  hipLaunchKernelGGL(syevd_rowsum, dim3(n), dim3(256), 0, st, A_dev, n, lda, s.scal + 64);
-  hipLaunchKernelGGL(syevd_max, dim3(1), dim3(256), 0, st, s.scal + 64, n, s.scal);
+  hipLaunchKernelGGL(syevd_rowmax, dim3(n), dim3(256), 0, st, A_dev, n, lda, s.scal + 64);
+  hipLaunchKernelGGL(syevd_sigma, dim3(1), dim3(256), 0, st, s.scal + 64, n, s.scal);
   hipLaunchKernelGGL(syevd_pad, dim3(np), dim3(256), 0, st, A_dev, n, lda, s.Ap, np, s.scal);
+  if (np > n) {
+    hipLaunchKernelGGL(syevd_rowsum, dim3(n), dim3(256), 0, st, s.Ap, n, np, s.scal + 64);
+    hipLaunchKernelGGL(syevd_pad_diag, dim3(1), dim3(256), 0, st, s.scal + 64, n, s.Ap, np);
+  }
   if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
   FFGP_CHECK(ffgp_sy2sb_impl(h, s.Ap, np, np, s.AB, s.Y, np, s.Tpan, s.ws1));
   const int ncols = (n + 31) / 32 * 32;   // the padding's eigenpairs are the last columns: never transformed
@@ -220,7 +260,8 @@ extern "C" int ffgp_syevd(ffgp_handle* h, const double* A_dev, int n, int lda, d
   FFGP_CHECK(ffgp_q1_apply_impl(h, s.Y, np, np, s.Zt, np, ncols, s.ws4, 0));
   FFGP_HIP(hipMemcpy2DAsync(Z_dev, (size_t)ldz * sizeof(double), s.Zt, (size_t)np * sizeof(double), (size_t)n * sizeof(double), n,
                             hipMemcpyDeviceToDevice, st));
-  FFGP_HIP(hipMemcpyAsync(W_dev, s.lam, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(syevd_unscale, dim3((n + 255) / 256), dim3(256), 0, st, s.lam, n, s.scal, W_dev);
+  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
   return syevd_check_watchdog(h, s.prog, np);
 }
 

@@ -344,7 +344,9 @@ int ffgp_kernel_grad(ffgp_handle* h, const double* X1_dev, int n1, const double*
 /* Batched symmetric eigendecomposition of `batch` matrices M_b [n, n] (n <= 64; both triangles read), hand-written
  * two-sided cyclic Jacobi, one workgroup per matrix in LDS: Q_b's columns are the eigenvectors, evals_b the eigenvalues,
  * ascending (descending != 0: descending).  Replaces torch.linalg.eigh for the per-mode kernels of the HOGP block
- * (two_fidelity_models/hogp_simple.py:17-19,99-100) and is the inner solver of functional.eigh's blocked one-sided Jacobi. */
+ * (two_fidelity_models/hogp_simple.py:17-19,99-100) and is the inner solver of functional.eigh's blocked one-sided Jacobi.
+ * Scale: every matrix is loaded times the power of two that brings its largest entry into [1, 2), and its eigenvalues are
+ * multiplied back (both exact), so the convergence test and the rotations see the same image for M and for 2^k M.            */
 int ffgp_syevj_small(ffgp_handle* h, const double* M_dev, int n, int ldm, int batch, long strideM, double* Q_dev, int ldq,
                      long strideQ, double* evals_dev, long strideE, int descending);
 
@@ -373,7 +375,14 @@ int ffgp_syev_lds(ffgp_handle* h, const double* M_dev, int n, int ldm, int batch
  * band -> tridiagonal (bulge chasing, one wavefront per sweep, pipelined through progress counters), tridiagonal divide &
  * conquer on the device (secular equation per root, Gu-Eisenstat vectors, merges as GEMMs), back-transformation with the
  * chase's reflectors (blocked WY on the matrix cores) and with the panels' (256-wide block reflectors, GEMMs).
- * n <= 32768 (workspace ~ 10 n^2 doubles).  A is not modified.  Synchronises the handle's stream before returning.                                       */
+ * n <= 32768 (workspace ~ 10 n^2 doubles).  A is not modified.  Synchronises the handle's stream before returning.
+ * Scale contract: the solver is scale-covariant for finite A.  Every stage works on sigma A, sigma the power of two that brings the
+ * largest |a_ij| of the lower triangle into [1, 2) (found on the device; 1 for the zero matrix), and W is multiplied by 1 / sigma
+ * at the end; neither multiplication rounds, so ffgp_syevd(2^k A) returns exactly 2^k W and the same Z, bit for bit, as long as
+ * no entry of sigma A or of the returned W falls into the denormal range.  Errors are relative to ||A||, whatever ||A|| is: entries
+ * of 1e-160 or 1e150, whose squares are not representable, are solved as well as entries of order 1.  The rows and columns that
+ * pad n to a multiple of 64 carry a diagonal of twice the largest absolute row sum of sigma A (1 for the zero matrix).  Only the
+ * lower triangle decides sigma and the padding for n > 64; for n <= 64 (ffgp_syevj_small) both triangles are read.             */
 int ffgp_syevd(ffgp_handle* h, const double* A_dev, int n, int lda, double* W_dev, double* Z_dev, int ldz);
 
 /* The stages of ffgp_syevd on caller-owned buffers (n a multiple of 64, 64 <= n <= 32768) -- LAPACK's dsytrd_sy2sb / dsytrd_sb2st /
@@ -381,9 +390,14 @@ int ffgp_syevd(ffgp_handle* h, const double* A_dev, int n, int lda, double* W_de
  *   ffgp_sy2sb   A [n, n] full symmetric, DESTROYED -> AB [n, 64] band storage (element (r, c), 0 <= r - c <= 32, at AB[c * 64 + r - c])
  *                and Y [n, ldy]: the panels' unit-lower Householder blocks (panel p in columns 32p.., rows 32p + 32..; zero elsewhere)
  *   ffgp_sb2st   AB (destroyed) -> d [n], e [n] (e[n-1] = 0) and the chase's reflectors (refl: ffgp_sb2st_reflector_doubles(n) doubles)
- *   ffgp_stedc   (d, e) -> W [n] ascending, Z [n, ldz] eigenvectors of the tridiagonal matrix in columns
+ *   ffgp_stedc   (d, e) -> W [n] ascending, Z [n, ldz] eigenvectors of the tridiagonal matrix in columns.  Scale-covariant like
+ *                ffgp_syevd: the divide and conquer runs on sigma d, sigma e with sigma the power of two that brings
+ *                max(|d_i|, |e_i|) into [1, 2) -- its deflation tolerance (LAPACK dlaed2's) is one for a matrix of norm ~1, as in
+ *                dstedc, which scales first -- and W is multiplied by 1 / sigma: ffgp_stedc(2^k d, 2^k e) = (2^k W, Z) exactly.
  *   ffgp_ormq2   Z[:, :ncols] <- Q2 Z   (the chase's reflectors);   ffgp_ormq1   Z[:, :ncols] <- Q1 Z   (the panels')
- * so that A = (Q1 Q2 Z) diag(W) (Q1 Q2 Z)^T.                                                                                   */
+ * so that A = (Q1 Q2 Z) diag(W) (Q1 Q2 Z)^T.
+ * ffgp_sy2sb and ffgp_sb2st do NOT scale: they form reflector norms from sums of squares, so the caller passes a matrix whose squared
+ * entries neither underflow nor overflow (ffgp_syevd hands them its scaled image, entries of magnitude < 2).                      */
 int ffgp_sy2sb(ffgp_handle* h, double* A_dev, int n, int lda, double* AB_dev, double* Y_dev, int ldy);
 long ffgp_sb2st_reflector_doubles(int n);
 int ffgp_sb2st(ffgp_handle* h, double* AB_dev, int n, double* d_dev, double* e_dev, double* refl_dev);

@@ -549,10 +549,30 @@ def merge_S(d1, d2, zraw, rho):
     return lam[order], S[:, order]
 
 
+def pow2_scale(m):
+    """sigma = 2^-ilogb(m), the power of two that brings m into [1, 2) (1 for m = 0); the exponent is kept where sigma and 1 / sigma
+    are both normal numbers.  Multiplying by it adds no rounding (device: dc_scale, syevd_sigma, the load of the LDS Jacobi)."""
+    m = float(m)
+    if not m > 0.0 or not np.isfinite(m):
+        return 1.0
+    ex = int(np.frexp(m)[1]) - 1                 # ilogb
+    return float(np.ldexp(1.0, -min(max(ex, -1021), 1021)))
+
+
 def stedc(d, e, leaf=64):
-    """eigen-decomposition of the symmetric tridiagonal (d, e) by divide and conquer; leaves by numpy's eigh (device: LDS Jacobi)"""
+    """eigen-decomposition of the symmetric tridiagonal (d, e[:n-1]) by divide and conquer.  The deflation tolerance of merge_S compares
+    rho |z_j| with max|d| and max|z|, and z is a row of an orthogonal matrix: it is a tolerance for a matrix of norm ~1 (LAPACK's
+    dlaed2 has the same formula, dstedc scales to norm 1 first).  So the recursion runs on sigma d, sigma e with the power of two
+    sigma of pow2_scale(max(|d|, |e|)), and the eigenvalues are multiplied by 1 / sigma: exact both ways."""
     d = np.array(d, dtype=np.float64)
-    e = np.array(e, dtype=np.float64)
+    e = np.array(e, dtype=np.float64)[:max(d.size - 1, 0)]
+    sigma = pow2_scale(max(np.abs(d).max(initial=0.0), np.abs(e).max(initial=0.0)))
+    lam, Q = _stedc(d * sigma, e * sigma, leaf)
+    return lam * (1.0 / sigma), Q
+
+
+def _stedc(d, e, leaf):
+    """the recursion of stedc on the scaled matrix; leaves by numpy's eigh (device: LDS Jacobi)"""
     n = d.size
     if n <= leaf:
         T = np.diag(d) + np.diag(e, 1) + np.diag(e, -1)
@@ -564,8 +584,8 @@ def stedc(d, e, leaf=64):
     d1, d2 = d[:n1].copy(), d[n1:].copy()
     d1[-1] -= ab
     d2[0] -= ab
-    l1, Q1 = stedc(d1, e[:n1 - 1], leaf)
-    l2, Q2 = stedc(d2, e[n1:], leaf)
+    l1, Q1 = _stedc(d1, e[:n1 - 1], leaf)
+    l2, Q2 = _stedc(d2, e[n1:], leaf)
     sgn = 1.0 if beta >= 0 else -1.0
     zraw = np.concatenate([Q1[-1, :], sgn * Q2[0, :]])
     lam, S = merge_S(l1, l2, zraw, ab)
@@ -577,14 +597,21 @@ def stedc(d, e, leaf=64):
 
 # ----------------------------------------------------------------------------------------------------------------------
 def eigh_twostage(A, b=32, leaf=512, g=32, agg=8):
-    """the whole route on an n x n symmetric matrix; n is padded to a multiple of 64 with decoupled diagonal entries above the
-    spectrum (they never mix: every reflector component on a padded row is exactly zero)"""
+    """the whole route on an n x n symmetric matrix (its lower triangle), scaled by the power of two that brings its largest entry
+    into [1, 2) -- the stages form reflector norms from squares, which under- or overflow at the matrix's own scale -- and padded
+    to a multiple of 64 with decoupled diagonal entries above the scaled image's spectrum (twice its largest absolute row sum; 1
+    for the zero matrix; they never mix: every reflector component on a padded row is exactly zero).  The eigenvalues are
+    multiplied by 1 / sigma at the end."""
     A = np.asarray(A, dtype=np.float64)
     n = A.shape[0]
+    A = np.tril(A) + np.tril(A, -1).T
+    sigma = pow2_scale(np.abs(A).max(initial=0.0))
     npad = (n + 63) // 64 * 64
     Ap = np.zeros((npad, npad))
-    Ap[:n, :n] = A
-    big = 2.0 * np.abs(A).sum(1).max() + 1.0
+    Ap[:n, :n] = A * sigma
+    big = 2.0 * np.abs(Ap).sum(1).max()
+    if big == 0.0:
+        big = 1.0
     for i in range(n, npad):
         Ap[i, i] = big * (1.0 + (i - n) / 64.0)
     Bd, panels = sy2sb(Ap, b, leaf)
@@ -592,4 +619,4 @@ def eigh_twostage(A, b=32, leaf=512, g=32, agg=8):
     lam, Z = stedc(d, e)
     Z = apply_q2(refl, npad, b, Z, g)
     Z = apply_q1(panels, Z, agg)
-    return lam[:n], Z[:n, :n]
+    return lam[:n] * (1.0 / sigma), Z[:n, :n]

@@ -5,6 +5,7 @@ with Householder reconstruction on rank-deficient panels)."""
 import numpy as np
 import pytest
 
+import eig_cases as C
 from oracle import eigh_twostage as E
 
 
@@ -74,3 +75,40 @@ def test_end_to_end_vs_lapack(kind):
     assert np.abs(lam - ref).max() < 1e-13 * np.abs(ref).max()
     assert np.abs(Z.T @ Z - np.eye(n)).max() < 1e-13
     assert np.linalg.norm((Z * lam) @ Z.T - A) < 1e-13 * np.linalg.norm(A) * 4
+
+
+# ---- scale covariance and the classic hard inputs of the divide and conquer: the CPU twins of the device tests of the same names in
+# ---- test_gpu_syevd.py (same inputs, same bounds: eig_cases.py), so that the model and the kernels stay restatements of each other
+@pytest.mark.parametrize("scale", C.STAGE3_SCALES)
+def test_stage3_scaled(scale):
+    """the deflation test of a merge is a test for a matrix of norm ~1: without the normalisation of stedc every merge deflates
+    completely at 1e-20 (eigenvalues of the leaves, 1.7e-2 off; orthogonality stays perfect), and 1e-6 loses six digits of the residual"""
+    d, e = C.random_tridiagonal(256)
+    W, Z = E.stedc(d * scale, e[:-1] * scale)
+    C.check_stage3(d * scale, e * scale, W, Z, scale, "model stage 3")
+
+
+@pytest.mark.parametrize("k", C.STAGE3_POW2)
+def test_stage3_power_of_two_scaling_is_exact(k):
+    d, e = C.random_tridiagonal(256)
+    W, Z = E.stedc(d, e[:-1])
+    Wk, Zk = E.stedc(d * 2.0 ** k, e[:-1] * 2.0 ** k)
+    assert np.array_equal(Wk, W * 2.0 ** k) and np.array_equal(Zk, Z)
+
+
+@pytest.mark.parametrize("name", C.HARD_CASES)
+def test_stage3_hard_cases(name):
+    d, e = C.hard_case(name)
+    W, Z = E.stedc(d, e[:-1])
+    C.check_stage3(d, e, W, Z, 1.0, "model " + name)
+    if name in C.CONSTANT_CASES:
+        assert np.all(W == C.CONSTANT_CASES[name])
+
+
+@pytest.mark.parametrize("scale", C.SYEVD_SCALES)
+@pytest.mark.parametrize("kind", ["rand", "kern"])
+def test_syevd_scaled(kind, scale):
+    """n = 130: padded to 192, so the padding's diagonal has to follow the matrix's scale too"""
+    A = C.syevd_matrix(kind, 130)
+    W, Z = E.eigh_twostage(A * scale, b=16, leaf=64, g=16, agg=4)
+    C.check_syevd(A * scale, W, Z, scale, "model " + kind)

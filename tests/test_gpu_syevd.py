@@ -6,21 +6,11 @@ import numpy as np
 import pytest
 import torch
 
+import eig_cases as C
+from eig_cases import kernel_matrix as _kernel_matrix, random_sym as _random_sym
+
 pytestmark = [pytest.mark.gpu, pytest.mark.noisy]   # (noisy: beside a background load by default, tests/conftest.py)
 DEV = "cuda:0"
-
-
-def _kernel_matrix(n, D, ls, seed=0):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    X = torch.rand((n, D), generator=g, dtype=torch.float64)
-    d = torch.cdist(X / ls, X / ls)
-    return torch.exp(-0.5 * d * d)
-
-
-def _random_sym(n, seed=0):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    M = torch.randn((n, n), generator=g, dtype=torch.float64)
-    return M + M.T
 
 
 def _band_dense(AB, b=32):
@@ -142,6 +132,83 @@ def test_stage3_divide_and_conquer(n, kind):
     assert np.abs(W - ref).max() <= 1e-14 * scale * max(1.0, np.sqrt(n) / 8)
     assert np.abs(Z.T @ Z - np.eye(n)).max() <= 2e-13
     assert np.abs((Z * W) @ Z.T - T).max() <= 1e-13 * scale
+
+
+def _stedc(d, e):
+    from fidelityfusion_amd import eigh as E
+    W, Z = E.stedc(torch.from_numpy(d).to(DEV), torch.from_numpy(e).to(DEV))
+    torch.cuda.synchronize()
+    return W, Z
+
+
+_unscaled = {}
+
+
+def _stedc_unscaled():
+    """stage 3 on the n = 256 random tridiagonal matrix, once"""
+    if "stedc" not in _unscaled:
+        _unscaled["stedc"] = _stedc(*C.random_tridiagonal(256))
+    return _unscaled["stedc"]
+
+
+@pytest.mark.parametrize("scale", C.STAGE3_SCALES)
+def test_stage3_scaled(scale):
+    """The deflation test of a merge (rho |z_j| <= 8 eps max(max|d|, max|z|), dlaed2's) is a test for a matrix of norm ~1: z is a row
+    of an orthogonal matrix whatever the matrix, rho and d scale with it.  Without the normalisation of dc_scale every merge deflates
+    completely at 1e-20 -- the leaves' eigenvalues come back, 1e-1 ||T|| off, with perfectly orthogonal vectors -- and at 1e-6 the
+    residual loses three digits (measured on the CPU restatement of the parent: tests/test_eigh_model.py has the twin of this test)."""
+    d, e = C.random_tridiagonal(256)
+    W, Z = _stedc(d * scale, e * scale)
+    C.check_stage3(d * scale, e * scale, W.cpu().numpy(), Z.cpu().numpy(), scale, "stage 3")
+
+
+@pytest.mark.parametrize("k", C.STAGE3_POW2)
+def test_stage3_power_of_two_scaling_is_exact(k):
+    """the normalisation is a power of two, so 2^k T is solved on the very image T is: no tolerance"""
+    d, e = C.random_tridiagonal(256)
+    W, Z = _stedc_unscaled()
+    Wk, Zk = _stedc(d * 2.0 ** k, e * 2.0 ** k)
+    assert torch.equal(Wk, W * 2.0 ** k)
+    assert torch.equal(Zk, Z)
+
+
+@pytest.mark.parametrize("name", C.HARD_CASES)
+def test_stage3_hard_cases(name):
+    """the stress matrices of the divide and conquer -- Wilkinson's, and W21 blocks glued by 1e-8, whose clusters of ~13 eigenvalues within
+    1e-8 go through the close-pair rotations, the secular solver and the Gu-Eisenstat vectors (the suite's other clustered case has
+    off-diagonals of 1e-14 and deflates trivially); an exactly zero (and a negative zero) off-diagonal on a leaf boundary (rho = 0); the
+    zero matrix and the identity (exact); constant diagonals; five leaves (merges with an empty second half, a ragged last GEMM)"""
+    d, e = C.hard_case(name)
+    W, Z = _stedc(d, e)
+    W, Z = W.cpu().numpy(), Z.cpu().numpy()
+    C.check_stage3(d, e, W, Z, 1.0, name)
+    if name in C.CONSTANT_CASES:
+        assert np.all(W == C.CONSTANT_CASES[name])
+
+
+@pytest.mark.parametrize("scale", C.SYEVD_SCALES)
+@pytest.mark.parametrize("n", C.SYEVD_SIZES)
+@pytest.mark.parametrize("kind", ["rand", "kern"])
+def test_syevd_scaled(kind, n, scale):
+    """the whole solver at the scales of a residual matrix or of a kernel with a small signal variance: the LDS Jacobi (n <= 64) decides
+    on sums of squares, the band reduction and the chase form reflector norms from squares, the padding's diagonal has to follow the
+    matrix and stage 3's deflation wants norm ~1 -- all of them work on a power-of-two multiple of the matrix with entries of order 1"""
+    from fidelityfusion_amd import eigh as E
+    A = C.syevd_matrix(kind, n)
+    W, Z = E.eigh(torch.from_numpy(A * scale).to(DEV))
+    C.check_syevd(A * scale, W.cpu().numpy(), Z.cpu().numpy(), scale, kind)
+
+
+@pytest.mark.parametrize("k", C.SYEVD_POW2)
+@pytest.mark.parametrize("n", [40, 130, 256])
+def test_syevd_power_of_two_scaling_is_exact(n, k):
+    from fidelityfusion_amd import eigh as E
+    if n not in _unscaled:
+        _unscaled[n] = E.eigh(_random_sym(n, n).to(DEV))
+    W, Z = _unscaled[n]
+    Wk, Zk = E.eigh((_random_sym(n, n) * 2.0 ** k).to(DEV))
+    assert torch.equal(Wk, W * 2.0 ** k)
+    assert torch.equal(Zk, Z)
 
 
 @pytest.mark.parametrize("n,kind", [(1, "rand"), (7, "rand"), (64, "kern"), (65, "rand"), (130, "kern"), (257, "kern1"), (600, "rand"),
