@@ -146,10 +146,15 @@ int ffgp_kernel_input_weights_tree(ffgp_handle* h, const double* X1, int n1, con
   return ffgp_pair_wt_impl(h, X1, n1, X2, n2, D, t, dK, ldk, Wt, ldw, leaf_stride);
 }
 
-/* (re)build the inverted 128x128 diagonal blocks of a factor (also the diag-kernel timing hook of tools/) */
+/* (re)build the inverted 128x128 diagonal blocks of a factor.  The call is the caller saying "this buffer changed behind the handle's
+   back": both keys are dropped first, so the rebuild starts at block 0 and the super-block inverses are rebuilt by the next sweep that
+   wants them.  (The incremental "the factor only grew" route of ffgp_refresh_dinv is for the solves' own ensure_* path: a refill with
+   MORE rows at a keyed address would otherwise keep the old factor's leading blocks.) */
 int ffgp_trtri_diag(ffgp_handle* h, const double* L, int n, int ldl) {
   if (!h || !L) return FFGP_ERR_ARG;
   FFGP_HIP(hipSetDevice(h->device));
+  h->dinv_L = nullptr;
+  h->sinv_L = nullptr;
   return ffgp_refresh_dinv(h, L, n, ldl);
 }
 

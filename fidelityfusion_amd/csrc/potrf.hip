@@ -698,8 +698,9 @@ int ffgp_ensure_dinv(ffgp_handle* h, int n) {
 // factor this handle did not just produce)
 int ffgp_refresh_dinv(ffgp_handle* h, const double* L, int n, int ldl) {
   // a factor that only GREW since the store was built (rows appended to the same buffer, functional.Posterior.append)
-  // keeps its leading blocks: rebuild from the last, possibly partial, old block on -- unless the store must be
-  // re-allocated, which drops its content
+  // keeps its leading blocks: rebuild from the last, possibly partial, old block on (a store that has to be re-allocated for
+  // the larger factor keeps its content: ffgp_ensure_dinv copies it).  Only the solves' own ensure_* route gets here with a
+  // matching address: ffgp_trtri_diag drops the keys first, its rebuild is always a full one
   int b_first = 0;
   if (!h->use_naive && h->dinv_L == L && h->dinv_ld == ldl && h->dinv_n > 0 && n > h->dinv_n)
     b_first = h->dinv_n / NB;

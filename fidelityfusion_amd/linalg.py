@@ -252,12 +252,13 @@ class _CondGauss(torch.autograd.Function):
             n = factor.n
             L = factor.W[:n]
             V = Ksd.clone()
-            check(lib.ffgp_trsm_lower(factor._h(), _ptr(factor.W), n, factor.ld, _ptr(V), V.shape[1], V.shape[1]), "ffgp_trsm_lower")
+            check(lib.ffgp_trsm_lower(factor._h_factor(), _ptr(factor.W), n, factor.ld, _ptr(V), V.shape[1], V.shape[1]), "ffgp_trsm_lower")
             Vt = V.T.contiguous()
             Gt = factor.Gamma.T.contiguous()
         mu = _gemm(dev, 0, 0, Vt, Gt, Vt.shape[0], d, Vt.shape[1], 1.0)
         cov = _dev(K_ss, dev) - _gemm(dev, 0, 0, Vt, Vt, Vt.shape[0], Vt.shape[0], Vt.shape[1], 1.0)
         ctx.saved = (L, Gt, Vt, dev)
+        ctx.factor = factor
         ctx.meta = [(t.shape, t.dtype, t.device) for t in (y, Sigma, K_s, K_ss)]
         odt = y.dtype if y.dtype.is_floating_point else torch.float64
         return mu.to(device=y.device, dtype=odt), cov.to(device=K_ss.device, dtype=K_ss.dtype)
@@ -266,8 +267,16 @@ class _CondGauss(torch.autograd.Function):
     def backward(ctx, Gmu, Gc):
         L, Gt, Vt, dev = ctx.saved
         n, d, nt = L.shape[0], Gt.shape[0], Vt.shape[0]
-        h = _lib.handle(dev.index)
-        _lib.bind_stream(h, dev.index)
+        if ctx.factor is not None:
+            h = ctx.factor._h_factor()                       # the Posterior's buffer: announced only to a slot that has not seen it
+        else:
+            # L is a copy of the factor at its own address (ld = n) that no handle factored, solved on the slot of the thread that
+            # runs backward -- not necessarily the forward's.  The caching allocator hands a later call's L this address again, and
+            # (address, n, n) is all the handle's cached inverses are keyed on: announce the factor (include/ffgp.h, contract of
+            # ffgp_trtri_diag).  It is the rebuild a key mismatch pays anyway.
+            h = _lib.handle(dev.index)
+            _lib.bind_stream(h, dev.index)
+            check(lib.ffgp_trtri_diag(h, _ptr(L), n, L.stride(0)), "ffgp_trtri_diag")
         X = torch.cat([Gt, Vt], 0).T.contiguous()            # [n, d + nt]  ->  [alpha | B] = L^-T [Gamma | V]
         check(lib.ffgp_trsm_lower_t(h, _ptr(L), n, L.stride(0), _ptr(X), d + nt, X.stride(0)), "ffgp_trsm_lower_t")
         alpha, B = X[:, :d].contiguous(), X[:, d:].contiguous()

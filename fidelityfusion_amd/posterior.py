@@ -30,7 +30,7 @@ class _PosteriorQuery(torch.autograd.Function):
         Ksd = _dev(Ks, dev)
         mean = _gemm(dev, 1, 1, Ksd, post.alpha, nt, post.d, n, 1.0)
         V = Ksd.clone()
-        check(lib.ffgp_trsm_lower(post._h(), _ptr(post.W), n, post.ld, _ptr(V), nt, nt), "ffgp_trsm_lower")
+        check(lib.ffgp_trsm_lower(post._h_factor(), _ptr(post.W), n, post.ld, _ptr(V), nt, nt), "ffgp_trsm_lower")
         if full_cov:
             var = _dev(Kss, dev) - _gemm(dev, 1, 1, V, V, nt, nt, n, 1.0)
         else:
@@ -51,7 +51,7 @@ class _PosteriorQuery(torch.autograd.Function):
         dKss = None
         if Gv is not None:
             B = V.clone()
-            check(lib.ffgp_trsm_lower_t(post._h(), _ptr(post.W), n, post.ld, _ptr(B), nt, nt), "ffgp_trsm_lower_t")   # Sigma^-1 K_s
+            check(lib.ffgp_trsm_lower_t(post._h_factor(), _ptr(post.W), n, post.ld, _ptr(B), nt, nt), "ffgp_trsm_lower_t")   # Sigma^-1 K_s
             g = _dev(Gv, dev)
             if full_cov:
                 dKs = dKs - _gemm(dev, 0, 0, B, (g + g.T).contiguous(), n, nt, nt, 1.0)
@@ -109,6 +109,7 @@ class Posterior:
         self.X = torch.empty((self.cap, D), dtype=torch.float64, device=dev)
         self.X[:n] = Xd
         self.n, self.D, self.d = n, D, d
+        self._keyed = (_lib.current_slot(), self.W.data_ptr())   # the handle slot whose cached inverses follow this buffer (`_h_factor`)
         h = self._h()
         self._assemble(Xd, Xd, self.W, self.ld, lower=1, diag=True)
         self.W[n:n + d, :n] = Yd.T
@@ -133,6 +134,20 @@ class Posterior:
         _lib.bind_stream(h, self.dev.index)
         return h
 
+    def _h_factor(self):
+        """the calling thread's handle for a call that reads the factor through the handle's cached inverses (the triangular solves).
+        Those are keyed on (address, n, ld) alone and follow the factor only on the slot that factored this buffer or was last told
+        about it; any other slot has never seen the factor, and its key may well name this very address -- the W of a dropped
+        Posterior of the same shapes, recycled by the caching allocator.  Such a slot is told first (ffgp_trtri_diag, the contract in
+        include/ffgp.h: the rebuild a key mismatch pays anyway) and becomes the slot that is followed; so is every slot after the
+        buffer itself was replaced (`append` past the capacity, a deep copy)."""
+        h = self._h()
+        keyed = (_lib.current_slot(), self.W.data_ptr())
+        if keyed != self._keyed:
+            check(lib.ffgp_trtri_diag(h, _ptr(self.W), self.n, self.ld), "ffgp_trtri_diag")
+            self._keyed = keyed
+        return h
+
     def _assemble(self, A, B, out, ld, lower, diag):
         if self.tree is not None:
             check(lib.ffgp_assemble_tree(self._h(), _ptr(A), A.shape[0], _ptr(B), B.shape[0], self.D, C.byref(self.tree[2]),
@@ -145,7 +160,7 @@ class Posterior:
 
     def _solve_alpha(self):
         self.alpha = self.Gamma.clone()
-        check(lib.ffgp_trsm_lower_t(self._h(), _ptr(self.W), self.n, self.ld, _ptr(self.alpha), self.d, self.d),
+        check(lib.ffgp_trsm_lower_t(self._h_factor(), _ptr(self.W), self.n, self.ld, _ptr(self.alpha), self.d, self.d),
               "ffgp_trsm_lower_t")
 
     @torch.no_grad()
@@ -161,7 +176,7 @@ class Posterior:
         Ks = torch.empty((n, nt), dtype=torch.float64, device=dev)
         self._assemble(self.X[:n], Xsd, Ks, nt, lower=0, diag=False)
         mean = _gemm(dev, 1, 1, Ks, self.alpha, nt, self.d, n, 1.0)                 # K_s^T alpha
-        check(lib.ffgp_trsm_lower(self._h(), _ptr(self.W), n, self.ld, _ptr(Ks), nt, nt), "ffgp_trsm_lower")   # V = L^-1 K_s
+        check(lib.ffgp_trsm_lower(self._h_factor(), _ptr(self.W), n, self.ld, _ptr(Ks), nt, nt), "ffgp_trsm_lower")   # V = L^-1 K_s
         if full_cov:
             var = torch.empty((nt, nt), dtype=torch.float64, device=dev)
             self._assemble(Xsd, Xsd, var, nt, lower=0, diag=False)
@@ -242,7 +257,7 @@ class Posterior:
     def append(self, X_new, Y_new):
         """Extend the factor by k points: the new block row of L is a TRSM on the cached factor, the new diagonal
         block a k x k Cholesky of the Schur complement."""
-        dev, n, h = self.dev, self.n, self._h()
+        dev, n = self.dev, self.n
         Xn, Yn = _dev(X_new, dev), _dev(Y_new, dev)
         _check_same_D(self.X, Xn, "X_new")
         if Yn.dim() != 2 or Yn.shape != (Xn.shape[0], self.d):
@@ -258,7 +273,7 @@ class Posterior:
             self.W, self.X, self.cap, self.ld = W, Xb, cap, ld
         B = torch.empty((n, k), dtype=torch.float64, device=dev)
         self._assemble(self.X[:n], Xn, B, k, lower=0, diag=False)
-        check(lib.ffgp_trsm_lower(h, _ptr(self.W), n, self.ld, _ptr(B), k, k), "ffgp_trsm_lower")        # L^-1 K_nk = L21^T
+        check(lib.ffgp_trsm_lower(self._h_factor(), _ptr(self.W), n, self.ld, _ptr(B), k, k), "ffgp_trsm_lower")   # L^-1 K_nk = L21^T
         ks = _pad_ld(k)
         S = torch.zeros((k, ks), dtype=torch.float64, device=dev)
         self._assemble(Xn, Xn, S, ks, lower=0, diag=True)

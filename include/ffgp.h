@@ -430,7 +430,10 @@ int ffgp_kernel_input_weights(ffgp_handle* h, const double* X1_dev, int n1, cons
    inverted super-blocks built on top of it -- is keyed on (L_dev, n, ldl) only.  A factor passed to those calls must be
    unmodified since the ffgp_potrf / ffgp_potrf_rows / ffgp_trtri_diag call ON THIS HANDLE that keyed the store.  If the
    contents at that address changed any other way (a buffer refilled by the caller, a factor written by another handle,
-   a recycled allocation), call ffgp_trtri_diag again (or ffgp_invalidate) before solving with it.              */
+   a recycled allocation), call ffgp_trtri_diag again (or ffgp_invalidate) before solving with it.  ffgp_trtri_diag always
+   rebuilds from block 0, whatever the store was keyed on before.
+   One change needs no call: rows APPENDED below an unmodified leading factor at the same address and ldl (n grows, the
+   first n_old rows are untouched) -- the next solve keeps the inverses of the complete leading blocks and builds the rest.  */
 int ffgp_trtri_diag(ffgp_handle* h, const double* L_dev, int n, int ldl);
 
 /* Drop the handle's cached inverses (diagonal blocks and super-blocks): the next triangular solve rebuilds them from
