@@ -91,6 +91,13 @@ class Residual(C.Structure):
                 ("v_high_dev", _dp), ("v_high_stride", C.c_long), ("rho_last_dev", _dp)]
 
 
+class CarLink(C.Structure):
+    """ffgp_car_link: a CAR member of ffgp_train_car_raw (b_dev NULL = a plain model)"""
+    _fields_ = [("b_dev", _dp), ("zls_dev", _dp), ("zamp_dev", _dp), ("zeps", C.c_double), ("z1_dev", C.c_void_p), ("z2_dev", C.c_void_p),
+                ("nz", C.c_int), ("lf", C.c_double), ("hf", C.c_double), ("y_low_dev", _dp), ("y_high_dev", _dp), ("b_last_dev", _dp),
+                ("z1d_dev", _dp), ("z2d_dev", _dp)]
+
+
 class AcqProblem(C.Structure):
     """ffgp_acq_problem: a frozen posterior and the acquisition on it (ffgp_acq_optimize)"""
     _fields_ = [("n", C.c_int), ("D", C.c_int), ("d", C.c_int), ("X_dev", _dp), ("L_dev", _dp), ("ldl", C.c_int), ("alpha_dev", _dp),
@@ -199,6 +206,8 @@ EXPORTS = {
                                  _dp, C.c_long]),
     "ffgp_train_residual_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(Residual), C.c_int,
                                           C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
+    "ffgp_train_car_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(CarLink), C.c_int,
+                                     C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                       C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_lds_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,

@@ -389,11 +389,13 @@ int ffgp_small_enqueue(ffgp_handle* h, const ffgp_problem* p, const ffgp_links* 
 bool ffgp_small2_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_grads* g);
 bool ffgp_small_batch_ok(const ffgp_problem* p, const ffgp_grads* g);
 // train.hip: K Adam steps of F small models in ONE launch (one persistent workgroup per model)
-bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r = nullptr);
+bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r = nullptr,
+                           const ffgp_car_link* cr = nullptr);
 bool ffgp_small_mfma_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_grads* g);      // one likelihood (+ gradients), n <= 128: same kernel, no Adam
 int ffgp_small_mfma_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g, int info_max);
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
-                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r = nullptr);
+                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r = nullptr,
+                       const ffgp_car_link* cr = nullptr);
 int ffgp_small_batch_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g);
 // ---- assemble.hip, solve.hip, grad.hip, pair.hip, join.hip, eig.hip: the stages the host drivers string together
 int ffgp_assemble_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const double* w,

@@ -25,7 +25,15 @@
 // that lives in LDS beside the other raw parameters; dloss/drho = -sum A .* y_low - sum_i G_ii sgn(s_i) v_low,ii is one more total of
 // the step's reduction and rho is a fourth Adam parameter.  y_low / y_high are read from global memory (no room for two more [128][16]
 // images), the two diagonals sit in LDS.  Plain members may share the launch: the residual code is skipped for them.
-// Covers: n <= 128, D <= 16, d <= 16, one radial-profile kernel, V1 likelihood, diag_add and diag_vec (no matrix / all-entries /
+// V2 members (tr_body<DM, true, false, true>, ffgp_train_v2_kernel; GP_basic's likelihood, GaussianProcess/gp_basic.py:130-143): the value is
+// 1/2 |A|^2 + d sum log L_ii + 1/2 n d log(2 pi) with A = Sigma^-1 Y, so the step needs B = Sigma^-1 A as well: G = d/2 Sigma^-1 -
+// 1/2 (A B^T + B A^T).  There is no room for a fourth [128][16] image: L^-1 A goes over Gamma, B over the targets, and Y is read
+// again from global memory at the start of every step.  V1 and V2 members of one call are launched separately.
+// CAR members (tr_body<DM, true, false, V2, true>, ffgp_train_car_kernel; train_CAR's fidelities above 0, CAR_ContinuousAutoRegression.py:
+// 116-142): the targets r = y_high - exp(b) y_low and the effective amplitude link(amp_raw) * s(b, l_z, sigma_z) -- the Monte-Carlo fidelity
+// integral, car_scale_wave in train_tile.h -- are re-formed at every step; b, l_z, sigma_z are three more Adam parameters, kept with their
+// moments, the samples and the partials of s behind the reduction's extra total (dloss/db needs sum dloss/dr .* y_low).  Launches of their own.
+// Covers: n <= 128, D <= 16, d <= 16, one radial-profile kernel, V1 likelihood (V2: plain and CAR members), diag_add and diag_vec (no matrix / all-entries /
 // mean(K) extras, no learnable profile parameter): what cigp_v10 produces.  Everything else keeps the paths it had.
 #include "ffgp_internal.h"
 #include "train_tile.h"
@@ -56,6 +64,15 @@ struct TrainResid {
   const double* vl; const double* vh;    // optional diagonals: entry i at vl[i * vl_stride], vh[i * vh_stride] (both or neither)
   long vl_stride, vh_stride;
   double* rho_last;                      // optional [1]: rho at the start of the last step taken
+};
+// a CAR member's link (ffgp_car_link): every member of a CAR launch has one
+struct TrainCar {
+  double* b; double* zls; double* zamp;  // [1] each, RAW, updated in place when the kernel ends
+  double zeps, lf, hf;
+  const float* z1; const float* z2; int nz;
+  const double* z1d; const double* z2d;  // the samples as fp64 draws (then z1 / z2 are not read)
+  const double* yl; const double* yh;    // [n, d]
+  double* b_last;                        // optional [1]: b at the start of the last step taken
 };
 struct TrainCommon {
   int steps;
@@ -115,14 +132,24 @@ __device__ __forceinline__ double tr_link_der(int kind, double p, double c) {
 #define TR_OFF_RES (TR_OFF_SMALL + TR_SMALL_DOUBLES + 9 * (TR_NRED_RES - TR_NRED))
 #define TR_LDS_DOUBLES_RES (TR_OFF_RES + 4 * TR_N + 16)
 static_assert(TR_LDS_DOUBLES_RES * sizeof(double) <= 160 * 1024, "the residual launch's LDS exceeds a CU's 160 KiB");
+// CAR launches: the reduction has one more total as well (sum dloss/dr .* y_low), then z1 | z2 [128] each (fp32 draws widened, or fp64 draws),
+// b, l_z, sigma_z with their moments [4] x 3 (raw / mom / mo2 have no room for nw + 5 parameters), s and its partials, b at the start of
+// the step and zeps, lf, hf [8], rsum [8], the parked words [8]: y_low, y_high, b, l_z, sigma_z, b_last, nz, the samples' format
+#define TR_OFF_CAR TR_OFF_RES
+#define TR_LDS_DOUBLES_CAR (TR_OFF_CAR + 2 * TR_N + 12 + 8 + 8 + 8)
+static_assert(TR_LDS_DOUBLES_CAR * sizeof(double) <= 160 * 1024, "the CAR launch's LDS exceeds a CU's 160 KiB");
 
 // DM: the input dimensions the per-entry loops are unrolled for (8 or 16: every model of the launch has D <= DM)
 // TRAIN: every step of the loop with Adam inside; !TRAIN ("evaluate"): ONE pass that writes the value and the gradients out
 // RESID (with TRAIN only): members with R.rho set are residual models (see the head of this file)
-template <int DM, bool TRAIN, bool RESID = false>
-__device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& cm, const TrainResid* Rp = nullptr) {
+// V2 (with TRAIN, without RESID): the FFGP_LL_V2 likelihood of GP_basic (see the head of this file)
+// CAR (with TRAIN, without RESID): every member is a CAR member (see the head of this file)
+template <int DM, bool TRAIN, bool RESID = false, bool V2 = false, bool CAR = false>
+__device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& cm, const TrainResid* Rp = nullptr, const TrainCar* Cp = nullptr) {
   static_assert(TRAIN || !RESID, "residual members train");
-  constexpr int NRED = RESID ? TR_NRED_RES : TR_NRED;
+  static_assert(!V2 || (TRAIN && !RESID), "the V2 likelihood: plain and CAR members of the training loop");
+  static_assert(!CAR || (TRAIN && !RESID), "CAR members train, in launches of their own");
+  constexpr int NRED = (RESID || CAR) ? TR_NRED_RES : TR_NRED;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   double* S = lds;
   double* Xs = lds + TR_OFF_XS;
@@ -147,13 +174,22 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   double* rho0 = rsum + 8;                 // [1]   rho at the start of the current step
   int* rmode = reinterpret_cast<int*>(rho0 + 1);      // [0] 0 plain member, 1 residual, 2 residual with diagonals; [2..9] y_low, y_high,
                                                       // rho, rho_last (read through tr_lds_int / tr_lds_ptr)
+  double* zs = lds + TR_OFF_CAR;           // CAR members: z1 [128] | z2 [128]
+  double* craw = zs + 2 * TR_N;            // [4] raw b, l_z, sigma_z (parameters nw + 2 .. nw + 4)
+  double* cmom = craw + 4;                 // [4] their exp_avg
+  double* cmo2 = cmom + 4;                 // [4] their exp_avg_sq
+  double* cs = cmo2 + 4;                   // [8] s, ds/db, ds/dl_z, ds/dsigma_z of the current step, b at its start; zeps, lf, hf
+  double* ceb = cmo2 + 3;                  // [1] exp(b) of the current step (the fourth slot of cmo2)
+  double* csum = cs + 8;                   // [8] per-wave sums of dloss/dr .* y_low
+  int* cptr = reinterpret_cast<int*>(csum + 8);       // [0..11] y_low, y_high, b, l_z, sigma_z, b_last (read through tr_lds_ptr); [12] nz,
+                                                      // [13] 1: fp32 draws (the link is not read again after the set-up)
   bool isres = RESID && Rp->rho != nullptr;           // (for the set-up only: the step loop reads rmode)
   bool hasv = isres && Rp->vl != nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = lane >> 4, c = lane & 15;
   const int n = M.n, D = M.D, d = M.d, nw = M.nw;
   const int nst = (n + 15) >> 4, nblk = nst * (nst + 1) / 2;
-  const int npar = nw + 2 + (isres ? 1 : 0);      // (a residual member's rho is raw[nw + 2])
+  const int npar = nw + 2 + (isres ? 1 : 0) + (CAR ? 3 : 0);      // (a residual member's rho is raw[nw + 2]; a CAR member's three: craw)
   const double oscale = (M.l.out_scale != 0.0) ? M.l.out_scale : 1.0;
   ExpCoef ec;
   ffgp_exp_load(ec);
@@ -162,7 +198,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   // targets, Gamma and A live as [128][16] images, zero beyond (n, d): the matrix-core products read them without guards
   for (int idx = tid; idx < TR_N * TR_Y; idx += TR_T) {
     const int i = idx >> 4, q = idx & 15;
-    Ym[idx] = (!isres && i < n && q < d) ? M.Y[i * d + q] : 0.0;      // (a residual member's are formed at every step)
+    Ym[idx] = (!CAR && !isres && i < n && q < d) ? M.Y[i * d + q] : 0.0;      // (a residual or CAR member's are formed at every step)
     Gam[idx] = 0.0;
     Am[idx] = 0.0;
   }
@@ -179,11 +215,38 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     }
   }
   if (tid < npar) {
-    if (isres && tid == nw + 2) raw[tid] = Rp->rho[0];
-    else raw[tid] = (tid < nw) ? M.w[tid] : (tid == nw ? M.amp[0] : (M.dadd ? M.dadd[0] : 0.0));
-    if (TRAIN) {
-      mom[tid] = M.state[tid];
-      mo2[tid] = M.state[npar + tid];
+    if (CAR && tid >= nw + 2) {
+      const int k = tid - nw - 2;
+      craw[k] = (k == 0) ? Cp->b[0] : ((k == 1) ? Cp->zls[0] : Cp->zamp[0]);
+      cmom[k] = M.state[tid];
+      cmo2[k] = M.state[npar + tid];
+      if (k == 0) ceb[0] = exp(craw[0]);
+    } else {
+      if (isres && tid == nw + 2) raw[tid] = Rp->rho[0];
+      else raw[tid] = (tid < nw) ? M.w[tid] : (tid == nw ? M.amp[0] : (M.dadd ? M.dadd[0] : 0.0));
+      if (TRAIN) {
+        mom[tid] = M.state[tid];
+        mo2[tid] = M.state[npar + tid];
+      }
+    }
+  }
+  if constexpr (CAR) {
+    if (tid < 2 * TR_N) {      // the samples, zero beyond nz (never read there)
+      const int k = tid & (TR_N - 1);
+      if (Cp->z1d) zs[tid] = (k < Cp->nz) ? ((tid < TR_N) ? Cp->z1d[k] : Cp->z2d[k]) : 0.0;
+      else zs[tid] = (k < Cp->nz) ? (double)((tid < TR_N) ? Cp->z1[k] : Cp->z2[k]) : 0.0;
+    }
+    if (tid == 0) {
+      const double* pv[6] = {Cp->yl, Cp->yh, Cp->b, Cp->zls, Cp->zamp, Cp->b_last};
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        const unsigned long long u = reinterpret_cast<unsigned long long>(pv[k]);
+        cptr[2 * k] = (int)(unsigned)u;
+        cptr[2 * k + 1] = (int)(unsigned)(u >> 32);
+      }
+      cptr[12] = Cp->nz;
+      cptr[13] = Cp->z1d == nullptr ? 1 : 0;
+      cs[5] = Cp->zeps; cs[6] = Cp->lf; cs[7] = Cp->hf;
     }
   }
   for (int t = wave; t < NBLK_LOWER; t += 8) {
@@ -226,6 +289,31 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     for (int idx = tid; idx < n * D; idx += TR_T) {      // (shifted by the first point: only differences enter the kernel)
       const int i = idx / D, k = idx - i * D;
       Xs[i * (TR_D + 1) + k] = (M.X[idx] - M.X[k]) * wv[k];
+    }
+    if constexpr (V2 && !CAR) {      // (B took the targets' image in the previous step: Y again from global memory, as residual members re-form theirs)
+      for (int idx = tid; idx < n * TR_Y; idx += TR_T) {
+        const int i = idx >> 4, q = idx & 15;
+        if (q < d) Ym[idx] = M.Y[i * d + q];
+      }
+    }
+    if constexpr (CAR) {      // this step's targets r = y_high - exp(b) y_low (a product, then a difference: never contracted), and by wave 1 the
+                              // fidelity integral s with its partials: the effective amplitude link(amp_raw) * s
+      const double* yl = tr_lds_ptr(cptr);
+      const double* yh = tr_lds_ptr(cptr + 2);
+      const double eb = ceb[0];      // exp(b), refreshed by the thread that updated b
+      for (int idx = tid; idx < n * TR_Y; idx += TR_T) {
+        const int i = idx >> 4, q = idx & 15;
+        if (q < d) Ym[idx] = __dsub_rn(yh[i * d + q], __dmul_rn(eb, yl[i * d + q]));
+      }
+      if (wave == 1) {
+        double o[4];
+        car_scale_wave(craw[0], craw[1], craw[2], cs[5], zs, zs + TR_N, tr_lds_int(cptr + 13) != 0, tr_lds_int(cptr + 12), cs[6], cs[7], lane, o);
+        if (lane == 0) {
+          cs[0] = o[0]; cs[1] = o[1]; cs[2] = o[2]; cs[3] = o[3];
+          cs[4] = craw[0];
+          sc[0] = tr_link_val(M.l.amp_link, raw[nw], M.l.amp_c) * o[0];
+        }
+      }
     }
     isres = RESID && tr_lds_int(rmode) != 0;
     if (isres) {      // this step's targets r = y_high - rho y_low and diagonal extra |s|, s = v_high - rho v_low, rounded as torch's
@@ -334,6 +422,13 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       }
       LDS_BARRIER();
     }
+    if constexpr (V2) {      // B = Sigma^-1 A: the same two chains once more -- W A over Gamma (dead once A exists), B over the targets' image
+      tr_gamma_rows(S, Am, Gam, nst, lane, wave, g, c);
+      LDS_BARRIER();
+      d4_t accb = {0.0, 0.0, 0.0, 0.0};
+      tr_alpha_rows(S, Gam, Ym, nst, lane, wave, g, c, accb);
+      LDS_BARRIER();
+    }
     TR_PROF(6);
 
     // ---- P5: per lane partial sums -- ss (value), s_amp, tr G, tot[k] (length scales); Sigma^-1 block by block on the matrix cores.
@@ -347,7 +442,23 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     for (int k = 0; k < DM; ++k) tk[k] = 0.0;
     const double lpiv = (tid < n) ? log(piv[tid]) : 0.0;
 #pragma unroll
-    for (int q = 0; q < TR_N * TR_Y / TR_T; ++q) ss = __builtin_fma(Gam[tid + TR_T * q], Gam[tid + TR_T * q], ss);
+    for (int q = 0; q < TR_N * TR_Y / TR_T; ++q) {      // V1: Y^T Sigma^-1 Y = |Gamma|^2; V2: |Sigma^-1 Y|^2 = |A|^2
+      const double e_ = V2 ? Am[tid + TR_T * q] : Gam[tid + TR_T * q];
+      ss = __builtin_fma(e_, e_, ss);
+    }
+    if constexpr (CAR) {      // this wave's part of sum dloss/dr .* y_low (dloss/dr = A, V2: B in the targets' image), over the image
+      const double* yl = tr_lds_ptr(cptr);
+      const double* dr = V2 ? Ym : Am;
+      double cy = 0.0;
+      int t0_ = tid;      // (opaque per step: the loop's offsets into y_low are otherwise hoisted out of the step loop and spilled across it)
+      asm volatile("" : "+v"(t0_));
+      for (int idx = t0_; idx < n * TR_Y; idx += TR_T) {
+        const int i = idx >> 4, q = idx & 15;
+        if (q < d) cy = __builtin_fma(dr[idx], yl[i * d + q], cy);
+      }
+      cy = tr_wsum(cy);
+      if (lane == 0) csum[wave] = cy;
+    }
     for (int q_ = 0; q_ < 5 && (TRAIN || M.want_grad); ++q_) {
       const int t = tr_deal(q_, wave);
       if (t >= nblk) continue;
@@ -376,7 +487,11 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
           sq += dsq[k];
         }
         double aa = 0.0;
-        for (int q = 0; q < d; ++q) aa = __builtin_fma(Am[i * TR_Y + q], Am[j * TR_Y + q], aa);
+        if constexpr (V2) {      // G = d/2 Sigma^-1 - 1/2 (A B^T + B A^T), B in the targets' image
+          for (int q = 0; q < d; ++q) aa = __builtin_fma(Am[i * TR_Y + q], Ym[j * TR_Y + q], __builtin_fma(Ym[i * TR_Y + q], Am[j * TR_Y + q], aa));
+        } else {
+          for (int q = 0; q < d; ++q) aa = __builtin_fma(Am[i * TR_Y + q], Am[j * TR_Y + q], aa);
+        }
         const bool live = (i < n && j <= i);
         const double gv = live ? 0.5 * (double)d * accr - 0.5 * aa : 0.0;
         const double sym = (i == j) ? 1.0 : 2.0;
@@ -431,6 +546,14 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
           tot[NRED - 1] = -a - x;
         }
       }
+      if constexpr (CAR) {
+        if (tid == 64) {      // sum dloss/dr .* y_low, beside wave 0's totals
+          double a = 0.0;
+#pragma unroll
+          for (int wv_ = 0; wv_ < 8; ++wv_) a += csum[wv_];
+          tot[NRED - 1] = a;
+        }
+      }
       LDS_BARRIER();
     }
     TR_PROF(8);
@@ -465,7 +588,11 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     }
     if (tid == 0) M.trace[step] = value;
     isres = RESID && tr_lds_int(rmode) != 0;
-    if (tid < nw + 2 + (isres ? 1 : 0)) {
+    if (tid < nw + 2 + (isres ? 1 : 0) + (CAR ? 3 : 0)) {
+      // (CAR: the slot opaque per step -- the loop-invariant addresses of a member's last three parameters, their moments and partials are
+      //  otherwise hoisted out of the step loop and spilled across it)
+      int slot_ = tid;
+      if constexpr (CAR) asm volatile("" : "+v"(slot_));
       double gr;
       if (tid < nw) {
         if (!M.l.w_broadcast) {
@@ -477,19 +604,30 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         }
       } else if (tid == nw) {
         gr = oscale * tot[1] * tr_link_der(M.l.amp_link, raw[nw], M.l.amp_c);
+        if constexpr (CAR) gr *= cs[0];      // (tot[1] = T, with respect to the effective amplitude link(amp_raw) * s)
+      } else if (CAR && slot_ > nw + 1) {      // b, l_z, sigma_z: dloss/ds = T link(amp_raw) times the partials of s; b's targets term
+        const double dls = tot[1] * tr_link_val(M.l.amp_link, raw[nw], M.l.amp_c);
+        const int k = slot_ - nw - 2;
+        gr = oscale * dls * cs[1 + k];
+        if (k == 0) gr = oscale * (dls * cs[1] - ceb[0] * tot[NRED - 1]);
       } else if (!isres || tid == nw + 1) {
         gr = oscale * tot[2] * tr_link_der(M.l.dadd_link, raw[nw + 1], M.l.dadd_c);
       } else {
         gr = oscale * tot[NRED - 1];      // rho (raw = effective)
       }
+      // (a CAR member's last three parameters and their moments live in craw / cmom / cmo2)
+      double* const pr_ = (CAR && slot_ > nw + 1) ? craw + (slot_ - nw - 2) : raw + slot_;
+      double* const pm_ = (CAR && slot_ > nw + 1) ? cmom + (slot_ - nw - 2) : mom + slot_;
+      double* const pv_ = (CAR && slot_ > nw + 1) ? cmo2 + (slot_ - nw - 2) : mo2 + slot_;
       const double bc1 = cm.bc[2 * step], bc2s = cm.bc[2 * step + 1];
-      const double m1 = mom[tid] + (gr - mom[tid]) * (1.0 - cm.b1);          // exp_avg.lerp_(grad, 1 - beta1)
-      const double v1 = mo2[tid] * cm.b2 + (1.0 - cm.b2) * gr * gr;           // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-      mom[tid] = m1;
-      mo2[tid] = v1;
+      const double m1 = pm_[0] + (gr - pm_[0]) * (1.0 - cm.b1);              // exp_avg.lerp_(grad, 1 - beta1)
+      const double v1 = pv_[0] * cm.b2 + (1.0 - cm.b2) * gr * gr;             // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
+      pm_[0] = m1;
+      pv_[0] = v1;
       const double denom = sqrt(v1) / bc2s + cm.eps;
-      const double pnew = raw[tid] + (-(cm.lr / bc1)) * (m1 / denom);         // param.addcdiv_(exp_avg, denom, value = -step_size)
-      raw[tid] = pnew;
+      const double pnew = pr_[0] + (-(cm.lr / bc1)) * (m1 / denom);           // param.addcdiv_(exp_avg, denom, value = -step_size)
+      pr_[0] = pnew;
+      if (CAR && tid == nw + 2) ceb[0] = exp(pnew);
       // the next step's effective value (nobody reads wv / sc between the reduction's barrier and the one below)
       if (tid < nw) {
         if (!M.l.w_broadcast) {
@@ -500,7 +638,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         }
       } else if (tid == nw) {
         sc[0] = tr_link_val(M.l.amp_link, pnew, M.l.amp_c);
-      } else if (!isres || tid == nw + 1) {
+      } else if ((!isres && !(CAR && tid > nw + 1)) || tid == nw + 1) {      // (a CAR member's s is re-formed at the start of the step)
         sc[1] = tr_link_val(M.l.dadd_link, pnew, M.l.dadd_c);
       }
     }
@@ -509,8 +647,21 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   }
   // ---- parameters and moments back to the caller's tensors (a failed step left them as they were when it began)
   if (RESID) isres = tr_lds_int(rmode) != 0;
-  const int npe = nw + 2 + (isres ? 1 : 0);
-  if (TRAIN && tid < npe) {
+  const int npe = nw + 2 + (isres ? 1 : 0) + (CAR ? 3 : 0);
+  if (CAR && tid > nw + 1) {
+    if (tid < npe) {
+      const int k = tid - nw - 2;
+      // (a pointer per lane: tr_lds_ptr makes its word wave-uniform)
+      const unsigned long long u = ((unsigned long long)(unsigned)cptr[5 + 2 * k] << 32) | (unsigned)cptr[4 + 2 * k];
+      reinterpret_cast<double*>(u)[0] = craw[k];
+      if (k == 0) {
+        double* bl = tr_lds_ptr(cptr + 10);
+        if (bl) bl[0] = cs[4];
+      }
+      M.state[tid] = cmom[k];
+      M.state[npe + tid] = cmo2[k];
+    }
+  } else if (TRAIN && tid < npe) {
     if (tid < nw) M.w[tid] = raw[tid];
     else if (tid == nw) M.amp[0] = raw[tid];
     else if (!isres || tid == nw + 1) M.dadd[0] = raw[tid];
@@ -537,6 +688,19 @@ __global__ __launch_bounds__(TR_T) void ffgp_train_resid_kernel(const TrainModel
   const TrainModel M = tab[blockIdx.x];
   tr_body<DM, true, true>(M, cm, rtab + blockIdx.x);
 }
+// FFGP_LL_V2 members (GP_basic): a launch of their own, so that the V1 kernels keep their code and registers
+template <int DM>
+__global__ __launch_bounds__(TR_T) void ffgp_train_v2_kernel(const TrainModel* __restrict__ tab, TrainCommon cm) {
+  const TrainModel M = tab[blockIdx.x];
+  tr_body<DM, true, false, true>(M, cm);
+}
+// CAR members (ffgp_train_car_raw), by likelihood; ctab[f] is member f's link
+template <int DM, bool V2>
+__global__ __launch_bounds__(TR_T) void ffgp_train_car_kernel(const TrainModel* __restrict__ tab, const TrainCar* __restrict__ ctab,
+                                                              TrainCommon cm) {
+  const TrainModel M = tab[blockIdx.x];
+  tr_body<DM, true, false, V2, true>(M, cm, nullptr, ctab + blockIdx.x);
+}
 // evaluate mode: up to eight models per launch, their descriptions by value (the enqueue-only entry points must not stage anything in
 // host memory that a later call could overwrite)
 #define TR_EVAL_BATCH 8
@@ -549,13 +713,17 @@ __global__ __launch_bounds__(TR_T) void ffgp_small_mfma_kernel(TrainEvalBatch b,
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r) {
+bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, const ffgp_car_link* cr) {
   if (h->train_persist_off || h->use_naive || h->timing) return false;
   if (p->n <= 0 || p->n > TR_N || p->D <= 0 || p->D > TR_D || p->d <= 0 || p->d > TR_Y) return false;
   if (p->cov_dev || p->pair || p->tree || p->add_mat_dev || p->add_all != 0.0 || p->mean_jitter != 0.0) return false;
-  const bool res = r && r->rho_dev;      // (a residual member's targets come from r: its Y_dev is ignored)
+  const bool car = cr && cr->b_dev;
+  if (car && (r || cr->nz <= 0 || cr->nz > TR_N)) return false;
+  const bool res = (r && r->rho_dev) || car;      // (a residual or CAR member's targets come from its link: its Y_dev is ignored)
   if (!p->X_dev || (!res && !p->Y_dev) || !p->w_dev || !p->amp_dev || !p->diag_add_dev) return false;
-  if (p->kfun < FFGP_KFUN_SE || p->kfun > FFGP_KFUN_RQ || p->ll_variant != FFGP_LL_V1) return false;
+  if (p->kfun < FFGP_KFUN_SE || p->kfun > FFGP_KFUN_RQ) return false;
+  if (p->ll_variant == FFGP_LL_V2) return !res || car;      // (ffgp_train_v2_kernel: plain members, diag_add under any link; CAR members)
+  if (p->ll_variant != FFGP_LL_V1) return false;
   (void)l;
   return true;
 }
@@ -563,7 +731,7 @@ bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ff
 // steps of F models (each must pass ffgp_train_persist_ok), one launch; synchronous.  Returns 0 or the pivot status of the first
 // model (in the caller's order) whose Sigma was not positive definite at some step.
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
-                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r) {
+                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r, const ffgp_car_link* cr) {
   static bool attr_set[64] = {false};
   if (h->device >= 0 && h->device < 64 && !attr_set[h->device]) {
     FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_persist_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -574,16 +742,42 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
                                  TR_LDS_DOUBLES_RES * (int)sizeof(double)));
     FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_resid_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  TR_LDS_DOUBLES_RES * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_v2_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_v2_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
+    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
     attr_set[h->device] = true;
   }
-  bool any_res = false;
+  bool any_res = false, any_car = false;
   for (int f = 0; f < F && r; ++f) any_res = any_res || r[f].rho_dev != nullptr;
+  for (int f = 0; f < F && cr; ++f) any_car = any_car || cr[f].b_dev != nullptr;
+  // four classes of members, a launch each: V1 (plain and residual), V2, CAR on V1, CAR on V2.  pos[f] = model f's row of the tables and
+  // of the status words: class after class, the caller's order inside a class; cbeg[k] = the first row of class k
+  auto cls = [&](int f) { return ((cr && cr[f].b_dev) ? 2 : 0) + (p[f].ll_variant == FFGP_LL_V2 ? 1 : 0); };
+  std::vector<int> pos(F);
+  int cbeg[5] = {0, 0, 0, 0, 0};
+  for (int k = 0, q = 0; k < 4; ++k) {
+    cbeg[k] = q;
+    for (int f = 0; f < F; ++f)
+      if (cls(f) == k) pos[f] = q++;
+    cbeg[k + 1] = q;
+  }
+  const int nv1 = cbeg[1];
   // one device block: [F models | F residual links (residual launches) | 2 steps bias corrections | 2 F status ints | F x 36 x 256 kernel
   // values]; its first four parts are staged in pinned host memory owned by the handle (an asynchronous copy from a temporary would have
   // to be waited for)
   const size_t tab_bytes = (size_t)F * sizeof(TrainModel);
   const size_t res_off = (tab_bytes + 255) / 256 * 256;
-  const size_t bc_off = any_res ? res_off + ((size_t)F * sizeof(TrainResid) + 255) / 256 * 256 : res_off;
+  const size_t car_off = any_res ? res_off + ((size_t)F * sizeof(TrainResid) + 255) / 256 * 256 : res_off;
+  const size_t bc_off = any_car ? car_off + ((size_t)F * sizeof(TrainCar) + 255) / 256 * 256 : car_off;
   const size_t info_off = bc_off + ((size_t)2 * steps * sizeof(double) + 255) / 256 * 256;
   const size_t head = info_off + (size_t)2 * F * sizeof(int);
   const size_t k_off = (head + 255) / 256 * 256;
@@ -610,7 +804,7 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
   TrainModel* tm = reinterpret_cast<TrainModel*>(host);
   for (int f = 0; f < F; ++f) {
     const ffgp_problem& q = p[f];
-    TrainModel& m = tm[f];
+    TrainModel& m = tm[pos[f]];
     m.n = q.n; m.D = q.D; m.d = q.d; m.nw = l[f].w_broadcast ? 1 : q.D;
     m.X = q.X_dev; m.Y = q.Y_dev;
     m.w = const_cast<double*>(q.w_dev); m.amp = const_cast<double*>(q.amp_dev); m.dadd = const_cast<double*>(q.diag_add_dev);
@@ -619,18 +813,33 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     m.clamp = q.clamp_min; m.rinv = (q.kparam != 0.0) ? 1.0 / q.kparam : 1.0; m.pi_const = q.pi_const; m.kfun = q.kfun;
     m.state = state_dev + (size_t)f * state_stride;
     m.trace = trace_dev + (size_t)f * trace_stride;
-    m.kbuf = reinterpret_cast<double*>(dev + k_off) + (size_t)f * NBLK_LOWER * 256;
+    m.kbuf = reinterpret_cast<double*>(dev + k_off) + (size_t)pos[f] * NBLK_LOWER * 256;
     m.want_grad = 1;
   }
   if (any_res) {
     TrainResid* tr = reinterpret_cast<TrainResid*>(host + res_off);
     for (int f = 0; f < F; ++f) {
       const ffgp_residual& q = r[f];
-      tr[f].rho = q.rho_dev;
+      TrainResid& t = tr[pos[f]];
+      t.rho = q.rho_dev;
       if (!q.rho_dev) continue;
-      tr[f].yl = q.y_low_dev; tr[f].yh = q.y_high_dev;
-      tr[f].vl = q.v_low_dev; tr[f].vh = q.v_high_dev; tr[f].vl_stride = q.v_low_stride; tr[f].vh_stride = q.v_high_stride;
-      tr[f].rho_last = q.rho_last_dev;
+      t.yl = q.y_low_dev; t.yh = q.y_high_dev;
+      t.vl = q.v_low_dev; t.vh = q.v_high_dev; t.vl_stride = q.v_low_stride; t.vh_stride = q.v_high_stride;
+      t.rho_last = q.rho_last_dev;
+    }
+  }
+  if (any_car) {
+    TrainCar* tc = reinterpret_cast<TrainCar*>(host + car_off);
+    for (int f = 0; f < F; ++f) {
+      const ffgp_car_link& q = cr[f];
+      if (!q.b_dev) continue;
+      TrainCar& t = tc[pos[f]];
+      t.b = q.b_dev; t.zls = q.zls_dev; t.zamp = q.zamp_dev;
+      t.zeps = q.zeps; t.lf = q.lf; t.hf = q.hf;
+      t.z1 = q.z1_dev; t.z2 = q.z2_dev; t.nz = q.nz;
+      t.z1d = q.z1d_dev; t.z2d = q.z2d_dev;
+      t.yl = q.y_low_dev; t.yh = q.y_high_dev;
+      t.b_last = q.b_last_dev;
     }
   }
   double* bc = reinterpret_cast<double*>(host + bc_off);
@@ -653,21 +862,45 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     FFGP_HIP(hipMalloc(&cm.prof, 12 * sizeof(long)));
     FFGP_HIP(hipMemset(cm.prof, 0, 12 * sizeof(long)));
   }
-  int Dmax = 0;
-  for (int f = 0; f < F; ++f) Dmax = std::max(Dmax, p[f].D);
+  int Dm[4] = {0, 0, 0, 0};
+  for (int f = 0; f < F; ++f) Dm[cls(f)] = std::max(Dm[cls(f)], p[f].D);
+  const int Dmax = Dm[0], Dmax2 = Dm[1];
   const TrainResid* rtab = reinterpret_cast<const TrainResid*>(dev + res_off);
-  if (any_res && Dmax <= 8)
-    hipLaunchKernelGGL(ffgp_train_resid_kernel<8>, dim3(F), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
+  if (nv1 == 0) {
+  } else if (any_res && Dmax <= 8)
+    hipLaunchKernelGGL(ffgp_train_resid_kernel<8>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
                        reinterpret_cast<const TrainModel*>(dev), rtab, cm);
   else if (any_res)
-    hipLaunchKernelGGL(ffgp_train_resid_kernel<16>, dim3(F), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
+    hipLaunchKernelGGL(ffgp_train_resid_kernel<16>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
                        reinterpret_cast<const TrainModel*>(dev), rtab, cm);
   else if (Dmax <= 8)
-    hipLaunchKernelGGL(ffgp_train_persist_kernel<8>, dim3(F), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream,
+    hipLaunchKernelGGL(ffgp_train_persist_kernel<8>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream,
                        reinterpret_cast<const TrainModel*>(dev), cm);
   else
-    hipLaunchKernelGGL(ffgp_train_persist_kernel<16>, dim3(F), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream,
+    hipLaunchKernelGGL(ffgp_train_persist_kernel<16>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream,
                        reinterpret_cast<const TrainModel*>(dev), cm);
+  for (int k = 1; k < 4; ++k) {      // the other classes: rows cbeg[k] .. cbeg[k + 1] - 1 of the tables and of the status words
+    const int nk = cbeg[k + 1] - cbeg[k];
+    if (nk == 0) continue;
+    TrainCommon c2 = cm;
+    c2.info = cm.info + cbeg[k];
+    c2.fail_step = cm.fail_step + cbeg[k];
+    const TrainModel* tab2 = reinterpret_cast<const TrainModel*>(dev) + cbeg[k];
+    const TrainCar* ctab = reinterpret_cast<const TrainCar*>(dev + car_off) + cbeg[k];
+    const size_t lds_car = TR_LDS_DOUBLES_CAR * sizeof(double);
+    if (k == 1 && Dmax2 <= 8)
+      hipLaunchKernelGGL(ffgp_train_v2_kernel<8>, dim3(nk), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream, tab2, c2);
+    else if (k == 1)
+      hipLaunchKernelGGL(ffgp_train_v2_kernel<16>, dim3(nk), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream, tab2, c2);
+    else if (k == 2 && Dm[2] <= 8)
+      hipLaunchKernelGGL((ffgp_train_car_kernel<8, false>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
+    else if (k == 2)
+      hipLaunchKernelGGL((ffgp_train_car_kernel<16, false>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
+    else if (Dm[3] <= 8)
+      hipLaunchKernelGGL((ffgp_train_car_kernel<8, true>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
+    else
+      hipLaunchKernelGGL((ffgp_train_car_kernel<16, true>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
+  }
   if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
   int* st = reinterpret_cast<int*>(host + info_off);
   FFGP_HIP(hipMemcpyAsync(st, cm.info, (size_t)2 * F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -687,7 +920,7 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     fprintf(stderr, " | sum %.2f\n", tot);
   }
   for (int f = 0; f < F; ++f)
-    if (st[f] != 0) return st[f];
+    if (st[pos[f]] != 0) return st[pos[f]];
   return FFGP_OK;
 }
 

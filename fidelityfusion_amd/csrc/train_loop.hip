@@ -4,6 +4,7 @@
 #include <memory>
 
 #include "drivers.h"
+#include "train_tile.h"
 
 // ---- K training steps in ONE call -------------------------------------------------------------------------------------------
 // The reference's hot loop (FidelityFusion_Models/ResGP.py:78-112: per fidelity 100-1000 iterations of zero_grad / loss =
@@ -115,12 +116,110 @@ extern "C" __global__ void ffgp_resid_grad(ffgp_resid_slot rs, double* __restric
   if (threadIdx.x == 0) gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + rs.nw[f] + 2] = -part[0];
 }
 
+// CAR members of the launch-per-stage loop (ffgp_train_car_raw): per step their targets r = y_high - exp(b) y_low and the effective
+// amplitude link(amp_raw) * s are formed before the likelihood call -- which reads that amplitude under the identity link -- and
+// dloss/db is reduced and the chain rule for amp, l_z, sigma_z applied after it
+struct ffgp_car_slot {
+  double* b[FFGP_TRAIN_MAXF];            // null: a plain member
+  double* zls[FFGP_TRAIN_MAXF];
+  double* zamp[FFGP_TRAIN_MAXF];
+  const double* amp_raw[FFGP_TRAIN_MAXF];
+  const float* z1[FFGP_TRAIN_MAXF];
+  const float* z2[FFGP_TRAIN_MAXF];
+  const double* z1d[FFGP_TRAIN_MAXF];    // fp64 draws (then z1 / z2 are not read)
+  const double* z2d[FFGP_TRAIN_MAXF];
+  const double* yl[FFGP_TRAIN_MAXF];
+  const double* yh[FFGP_TRAIN_MAXF];
+  double* r[FFGP_TRAIN_MAXF];            // [n, d] targets
+  const double* gY[FFGP_TRAIN_MAXF];     // [n, d] dloss/dr
+  double* sv[FFGP_TRAIN_MAXF];           // [8] link(amp_raw) * s (the likelihood's amplitude) | s, ds/db, ds/dl_z, ds/dsigma_z | exp(b)
+  double* b_last[FFGP_TRAIN_MAXF];
+  double zeps[FFGP_TRAIN_MAXF], lf[FFGP_TRAIN_MAXF], hf[FFGP_TRAIN_MAXF], amp_c[FFGP_TRAIN_MAXF];
+  long nd[FFGP_TRAIN_MAXF];
+  int nz[FFGP_TRAIN_MAXF], nw[FFGP_TRAIN_MAXF], amp_link[FFGP_TRAIN_MAXF];
+};
+extern "C" __global__ void ffgp_car_form(ffgp_car_slot cs) {
+  const int f = blockIdx.y;
+  if (!cs.b[f]) return;
+  __shared__ double zs[256];      // z1 [128] | z2 [128]: fp32 draws widened, or fp64 draws
+  const double b = cs.b[f][0];
+  const double eb = exp(b);
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t < cs.nd[f]) cs.r[f][t] = __dsub_rn(cs.yh[f][t], __dmul_rn(eb, cs.yl[f][t]));
+  if (blockIdx.x != 0) return;
+  {
+    const int k = threadIdx.x & 127, hi = threadIdx.x >> 7;
+    double z = 0.0;
+    if (k < cs.nz[f]) z = cs.z1d[f] ? (hi ? cs.z2d[f][k] : cs.z1d[f][k]) : (double)(hi ? cs.z2[f][k] : cs.z1[f][k]);
+    zs[threadIdx.x] = z;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {      // (one wave: the fidelity integral, train_tile.h)
+    double o[4];
+    car_scale_wave(b, cs.zls[f][0], cs.zamp[f][0], cs.zeps[f], zs, zs + 128, cs.z1d[f] == nullptr, cs.nz[f], cs.lf[f], cs.hf[f],
+                   (int)threadIdx.x, o);
+    if (threadIdx.x == 0) {
+      double* sv = cs.sv[f];
+      sv[0] = ffgp_link_val(cs.amp_link[f], cs.amp_raw[f][0], cs.amp_c[f]) * o[0];
+      sv[1] = o[0]; sv[2] = o[1]; sv[3] = o[2]; sv[4] = o[3];
+      sv[5] = eb;
+      if (cs.b_last[f]) cs.b_last[f][0] = b;
+    }
+  }
+}
+// gbuf slot nw holds T = dloss/d(effective amplitude) (the likelihood ran under the identity link; the output scale is inside):
+// slots nw, nw + 2 .. nw + 4 <- the gradients of amp_raw, b, l_z, sigma_z (one workgroup per member, fixed order)
+extern "C" __global__ void ffgp_car_grad(ffgp_car_slot cs, double* __restrict__ gbuf) {
+  const int f = blockIdx.x;
+  if (!cs.b[f]) return;
+  __shared__ double part[256];
+  double x = 0.0;
+  for (long t = threadIdx.x; t < cs.nd[f]; t += 256) x = __builtin_fma(cs.gY[f][t], cs.yl[f][t], x);
+  part[threadIdx.x] = x;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double* g = gbuf + (size_t)f * FFGP_TRAIN_GSTRIDE + cs.nw[f];
+    const double* sv = cs.sv[f];
+    const double T = g[0], ar = cs.amp_raw[f][0];
+    const double dls = T * ffgp_link_val(cs.amp_link[f], ar, cs.amp_c[f]);
+    g[0] = T * ffgp_link_der(cs.amp_link[f], ar, cs.amp_c[f]) * sv[1];
+    g[2] = dls * sv[2] - sv[5] * part[0];
+    g[3] = dls * sv[3];
+    g[4] = dls * sv[4];
+  }
+}
+// ffgp_adam_kernel for a call with CAR members: raw gradients from gbuf, nw + 5 parameters for a CAR member (w, amp, diag_add, b, l_z,
+// sigma_z), nw + 2 for a plain one; the status words are kept by the likelihood's own epilogue
+extern "C" __global__ void ffgp_adam_car_kernel(int F, ffgp_train_slot sl, ffgp_car_slot cs, const double* __restrict__ gbuf,
+                                                double* __restrict__ state, long state_stride, double lr, double b1, double b2, double eps,
+                                                double bc1, double bc2_sqrt, const double* __restrict__ loss, double* __restrict__ trace,
+                                                long trace_stride, int step, const int* __restrict__ info) {
+  const int f = blockIdx.x;
+  if (f >= F) return;
+  const int bad = info[0] | info[1];
+  const int nw = sl.nw[f];
+  const int npar = nw + 2 + (cs.b[f] ? 3 : 0);
+  if (threadIdx.x == 0) trace[(size_t)f * trace_stride + step] = bad ? __builtin_nan("") : loss[f];
+  if (bad) return;
+  const int i = threadIdx.x;
+  if (i >= npar) return;
+  double* par = (i < nw) ? sl.w[f] + i
+                         : (i == nw ? sl.amp[f] : (i == nw + 1 ? sl.dadd[f] : (i == nw + 2 ? cs.b[f] : (i == nw + 3 ? cs.zls[f] : cs.zamp[f]))));
+  double* m = state + (size_t)f * state_stride + i;
+  ffgp_adam_update(par, m, m + npar, gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + i], lr, b1, b2, eps, bc1, bc2_sqrt);
+}
+
 static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, int steps,
-                      const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+                      const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride,
+                      const ffgp_car_link* cr = nullptr) {
   if (!h || !p || !l || !opt || !state_dev || !trace_dev || F <= 0 || F > FFGP_TRAIN_MAXF || steps <= 0 || step0 < 0 || trace_stride < steps)
     return FFGP_ERR_ARG;
   ffgp_train_slot sl;
-  bool all_small = true, any_res = false;
+  bool all_small = true, any_res = false, any_car = false;
   for (int f = 0; f < F; ++f) {
     const ffgp_problem& q = p[f];
     if (!q.w_dev || !q.amp_dev || !q.diag_add_dev || q.cov_dev || q.pair || q.tree || q.D <= 0 || q.D > 128 || q.n <= 0 || q.d <= 0) return FFGP_ERR_ARG;
@@ -128,8 +227,14 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
     if (res && (!r[f].y_low_dev || !r[f].y_high_dev || !q.X_dev || (!r[f].v_low_dev) != (!r[f].v_high_dev) ||
                 (r[f].v_low_dev && (r[f].v_low_stride < 0 || r[f].v_high_stride < 0))))
       return FFGP_ERR_ARG;
+    const bool car = cr && cr[f].b_dev;
+    if (car && (r || !cr[f].zls_dev || !cr[f].zamp_dev || (!cr[f].z1d_dev) != (!cr[f].z2d_dev) ||
+                (!cr[f].z1d_dev && (!cr[f].z1_dev || !cr[f].z2_dev)) || cr[f].nz <= 0 || cr[f].nz > 128 ||
+                !cr[f].y_low_dev || !cr[f].y_high_dev || !q.X_dev))
+      return FFGP_ERR_ARG;
+    any_car = any_car || car;
     const int nw = l[f].w_broadcast ? 1 : q.D;
-    if (state_stride < 2 * (nw + 2 + (res ? 1 : 0))) return FFGP_ERR_ARG;
+    if (state_stride < 2 * (nw + 2 + (res ? 1 : 0) + (car ? 3 : 0))) return FFGP_ERR_ARG;
     sl.w[f] = const_cast<double*>(q.w_dev);
     sl.amp[f] = const_cast<double*>(q.amp_dev);
     sl.dadd[f] = const_cast<double*>(q.diag_add_dev);
@@ -140,8 +245,8 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
   FFGP_HIP(hipSetDevice(h->device));
   {   // every model small enough for one workgroup: the whole loop is ONE launch (train.hip)
     bool persist = true;
-    for (int f = 0; f < F && persist; ++f) persist = ffgp_train_persist_ok(h, p + f, l + f, r ? r + f : nullptr);
-    if (persist) return ffgp_train_persist(h, F, p, l, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, r);
+    for (int f = 0; f < F && persist; ++f) persist = ffgp_train_persist_ok(h, p + f, l + f, r ? r + f : nullptr, cr ? cr + f : nullptr);
+    if (persist) return ffgp_train_persist(h, F, p, l, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, r, cr);
   }
   if (!h->train_g) {
     FFGP_HIP(hipMalloc(&h->train_g, (size_t)FFGP_TRAIN_MAXF * (FFGP_TRAIN_GSTRIDE + 1) * sizeof(double)));
@@ -180,6 +285,35 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
       pq[f].diag_stride = 1;
     }
   }
+  ffgp_car_slot cs;
+  memset(&cs, 0, sizeof(cs));
+  if (any_car) {      // per CAR member [r (n d) | dloss/dr (n d) | sv (8)], freed when the call returns
+    size_t tot = 0;
+    for (int f = 0; f < F; ++f)
+      if (cr[f].b_dev) tot += 2 * (size_t)p[f].n * p[f].d + 8;
+    FFGP_HIP(hipMalloc(&rbuf, tot * sizeof(double)));
+    rbuf_owner.reset(rbuf);
+    size_t off = 0;
+    for (int f = 0; f < F; ++f) {
+      if (!cr[f].b_dev) continue;
+      const long nd = (long)p[f].n * p[f].d;
+      cs.b[f] = cr[f].b_dev; cs.zls[f] = cr[f].zls_dev; cs.zamp[f] = cr[f].zamp_dev;
+      cs.amp_raw[f] = p[f].amp_dev; cs.amp_link[f] = l[f].amp_link; cs.amp_c[f] = l[f].amp_c;
+      cs.z1[f] = cr[f].z1_dev; cs.z2[f] = cr[f].z2_dev; cs.nz[f] = cr[f].nz;
+      cs.z1d[f] = cr[f].z1d_dev; cs.z2d[f] = cr[f].z2d_dev;
+      cs.zeps[f] = cr[f].zeps; cs.lf[f] = cr[f].lf; cs.hf[f] = cr[f].hf;
+      cs.yl[f] = cr[f].y_low_dev; cs.yh[f] = cr[f].y_high_dev;
+      cs.r[f] = rbuf + off; cs.gY[f] = cs.r[f] + nd; cs.sv[f] = cs.r[f] + 2 * nd;
+      cs.b_last[f] = cr[f].b_last_dev;
+      cs.nd[f] = nd; cs.nw[f] = sl.nw[f];
+      off += 2 * nd + 8;
+      rmax = std::max(rmax, nd);
+      pq[f].Y_dev = cs.r[f];
+      pq[f].amp_dev = cs.sv[f];          // link(amp_raw) * s, read under the identity link: its gradient slot receives T
+      lk[f].amp_link = FFGP_LINK_ID;
+      lk[f].amp_c = 0.0;
+    }
+  }
   for (int f = 0; f < F; ++f) {
     memset(&g[f], 0, sizeof(ffgp_grads));
     g[f].g_w_dev = gbuf + (size_t)f * FFGP_TRAIN_GSTRIDE;
@@ -189,6 +323,7 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
       g[f].g_Y_dev = const_cast<double*>(rs.gY[f]);
       if (rs.vl[f]) g[f].g_diag_vec_dev = const_cast<double*>(rs.gdv[f]);
     }
+    if (cs.b[f]) g[f].g_Y_dev = const_cast<double*>(cs.gY[f]);
     all_small = all_small && ffgp_small_batch_ok(&pq[f], &g[f]);
   }
   p = pq.data();
@@ -197,10 +332,12 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
   // (the one-kernel paths -- n <= 40, or option small_finish -- apply the links inside their kernel and write raw gradients)
   const bool one_kernel = ffgp_small_ok(h, p, &g[0]) || ffgp_small2_ok(h, p, &g[0]);
   h->defer_info_copy = 1;      // (the per-call read-back of the status word: once, after the loop)
-  h->fold_info = (F == 1) ? 1 : 0;   // one model: the Adam kernel clears / accumulates the status words (see ffgp_adam_kernel)
+  h->fold_info = (F == 1 && !any_car) ? 1 : 0;   // one model: the Adam kernel clears / accumulates the status words (see ffgp_adam_kernel;
+                                                  // a call with CAR members leaves them to the likelihood's epilogue)
   int lrc = FFGP_OK;
   for (int k = 0; k < steps && lrc == FFGP_OK; ++k) {
     if (any_res) hipLaunchKernelGGL(ffgp_resid_form, dim3((unsigned)((rmax + 255) / 256), F), dim3(256), 0, h->stream, rs);
+    if (any_car) hipLaunchKernelGGL(ffgp_car_form, dim3((unsigned)((rmax + 255) / 256), F), dim3(256), 0, h->stream, cs);
     if (all_small && F > 1) {
       if ((lrc = ffgp_zero_async(h, h->d_info, sizeof(int))) != FFGP_OK) break;
       if ((lrc = ffgp_small_batch_enqueue(h, F, p, lk.data(), loss, g.data())) != FFGP_OK) break;
@@ -212,6 +349,12 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
     if (any_res) hipLaunchKernelGGL(ffgp_resid_grad, dim3(F), dim3(256), 0, h->stream, rs, gbuf);
     const double t = (double)(step0 + k + 1);
     const double bc1 = 1.0 - std::pow(opt->beta1, t), bc2 = 1.0 - std::pow(opt->beta2, t);
+    if (any_car) {
+      hipLaunchKernelGGL(ffgp_car_grad, dim3(F), dim3(256), 0, h->stream, cs, gbuf);
+      hipLaunchKernelGGL(ffgp_adam_car_kernel, dim3(F), dim3(192), 0, h->stream, F, sl, cs, gbuf, state_dev, state_stride, opt->lr, opt->beta1,
+                         opt->beta2, opt->eps, bc1, std::sqrt(bc2), loss, trace_dev, trace_stride, k, h->d_info);
+      continue;
+    }
     hipLaunchKernelGGL(ffgp_adam_kernel, dim3(F), dim3(192), 0, h->stream, F, sl, gbuf, state_dev, state_stride, opt->lr, opt->beta1,
                        opt->beta2, opt->eps, bc1, std::sqrt(bc2), loss, trace_dev, trace_stride, k, h->d_info, h->fold_info,
                        (h->fold_info && !one_kernel) ? h->d_link + 256 : (const double*)nullptr, lk[0], p[0].D,
@@ -243,6 +386,12 @@ int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const 
                             const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
   if (!r) return FFGP_ERR_ARG;
   return train_impl(h, F, p, l, r, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
+}
+
+int ffgp_train_car_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_car_link* c, int steps,
+                       const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+  if (!c) return FFGP_ERR_ARG;
+  return train_impl(h, F, p, l, nullptr, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, c);
 }
 
 }  // extern "C"

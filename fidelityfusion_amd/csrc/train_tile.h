@@ -228,3 +228,44 @@ __device__ __forceinline__ bool tr_alpha_rows(const double* S, const double* Gam
   for (int r = 0; r < 4; ++r) Am[(bi * 16 + g + 4 * r) * TR_Y + c] = acc[r];
   return true;
 }
+
+// ---- CAR members (ffgp_train_car_raw): the Monte-Carlo fidelity integral of fidelity_kernel_MCMC and its partials, by ONE wave (all 64
+//      lanes call; z1 / z2: the samples as doubles -- fp32 draws widened, f32 set, or fp64 draws).  With l = |lz| + zeps, w2 = (hf - lf)^2:
+//        e_i = u_i - 1/2 ((z1_i - z2_i) / l)^2,  m = mean_i exp(e_i),  s = |sz| m w2
+//      u_i in binary32, as torch evaluates `-b * (z1 - hf) - b * (z2 - hf)` (a 0-dim fp64 parameter times an fp32 tensor), never
+//      contracted; z1 / l - z2 / l two fp64 divisions of the widened samples; from exp on fp64.  fp64 draws (!f32; torch's default
+//      dtype float64): u_i is the same expression in fp64.  The partials are plain fp64.
+//      out[0] = s, out[1] = ds/db, out[2] = ds/dlz, out[3] = ds/dsz (sgn(0) = 0), the same in every lane.  The one copy: the one-launch
+//      trainer (train.hip) and the launch-per-stage loop (train_loop.hip) both call it, so the two routes form the same s bit for bit.
+__device__ __forceinline__ void car_scale_wave(double b, double lz, double sz, double zeps, const double* z1, const double* z2, bool f32,
+                                               int nz, double lf, double hf, int lane, double out[4]) {
+  const double l = fabs(lz) + zeps;
+  const float nb = -(float)b, hff = (float)hf;
+  double se = 0.0, sb = 0.0, sl = 0.0;
+  for (int i = lane; i < nz; i += 64) {
+    const double x1 = z1[i], x2 = z2[i];
+    double u;
+    if (f32) {      // (the widened samples convert back exactly)
+      const float a1 = __fsub_rn((float)x1, hff), a2 = __fsub_rn((float)x2, hff);
+      u = (double)__fadd_rn(__fmul_rn(nb, a1), __fmul_rn(nb, a2));
+    } else {
+      u = __dadd_rn(__dmul_rn(-b, __dsub_rn(x1, hf)), __dmul_rn(-b, __dsub_rn(x2, hf)));
+    }
+    const double dd = __dsub_rn(x1 / l, x2 / l);
+    const double ex = exp(__dsub_rn(u, 0.5 * __dmul_rn(dd, dd)));
+    const double dz = x1 - x2;
+    se += ex;
+    sb += ex * ((x1 - hf) + (x2 - hf));
+    sl += ex * (dz * dz);
+  }
+  se = tr_wsum(se);
+  sb = tr_wsum(sb);
+  sl = tr_wsum(sl);
+  const double dlt = hf - lf, asz = fabs(sz);
+  const double m = se / (double)nz;
+  const double mw = __dmul_rn(__dmul_rn(m, dlt), dlt);      // z_part.mean() * (hf - lf) * (hf - lf)
+  out[0] = asz * mw;
+  out[1] = -asz * dlt * dlt * (sb / (double)nz);
+  out[2] = asz * dlt * dlt * ((lz > 0.0) ? 1.0 : ((lz < 0.0) ? -1.0 : 0.0)) * (sl / (double)nz) / (l * l * l);
+  out[3] = ((sz > 0.0) ? 1.0 : ((sz < 0.0) ? -1.0 : 0.0)) * mw;
+}

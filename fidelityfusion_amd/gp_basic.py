@@ -15,6 +15,7 @@ from . import functional as F
 def _kfun(k):
     return k.kfun() if hasattr(k, "kfun") else (0, 1.0)
 from .gp_computation_pack import _check_method
+from .train import train_many  # noqa: F401  (K Adam steps per library call; a GP_basic trains on -log_likelihood)
 
 _METHODS_FWD = ("cholesky1", "cholesky3", "direct")
 _METHODS_LL = ("cholesky1", "cholesky2", "cholesky3", "direct", "torch_distribution_MN1", "torch_distribution_MN2")

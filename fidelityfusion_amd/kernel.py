@@ -288,3 +288,73 @@ class MaternKernel_scalarLengthScale(nn.Module):
         K = sv.pow(2) * torch.pow(1.0 + torch.sqrt(3.0 * sqdist) / ls.pow(2), -nu)
         odt = x1.dtype if x1.dtype.is_floating_point else torch.float64
         return K.to(device=x1.device, dtype=odt)
+
+
+class FidelityKernelMCMC(nn.Module):
+    """CAR's fidelity kernel (FidelityFusion_Models/CAR_ContinuousAutoRegression.py:14-67, same constructor): kernel1(x1, x2) times the
+    scalar s = |signal_variance| * (hf - lf)^2 * mean_i exp(-b (z1_i - hf) - b (z2_i - hf) - 1/2 ((z1_i - z2_i) / l)^2), l = |length_scales|
+    + eps, a Monte-Carlo integral over the fidelity indicator with 100 uniform sample pairs drawn after `torch.manual_seed(105)` on EVERY
+    call (the reference reseeds the global generator there; kept).  `scale()` is plain torch on the host, so autograd reaches b,
+    length_scales and signal_variance; the scalar is folded into the base kernel's amplitude (`effective`), so a stationary kernel1 keeps
+    the GP modules on the fused path.  `car_links()` describes the kernel on its RAW parameters for `train_many(..., car=)`, which forms s
+    and its partials on the device (ffgp_train_car_raw)."""
+    _ffgp_device_aware = True
+    N_SAMPLES = 100
+
+    def __init__(self, input_dim, kernel1, lf, hf, b, initial_length_scale=1.0, initial_signal_variance=1.0, eps=1e-3):
+        super().__init__()
+        self.kernel1 = kernel1
+        self.b = b
+        self.lf = lf
+        self.hf = hf
+        self.length_scales = nn.Parameter(torch.ones(input_dim) * initial_length_scale)
+        self.signal_variance = nn.Parameter(torch.tensor([initial_signal_variance]))
+        self.eps = eps
+        self.seed = 105
+
+    def samples(self):
+        """the reference's draws (z1, z2), in torch's default dtype, on the host; reseeds the global generator as the reference does"""
+        torch.manual_seed(self.seed)
+        z1 = torch.rand(self.N_SAMPLES) * (self.hf - self.lf) + self.lf
+        z2 = torch.rand(self.N_SAMPLES) * (self.hf - self.lf) + self.lf
+        return z1, z2
+
+    def scale(self):
+        length_scales = torch.abs(self.length_scales) + self.eps
+        z1, z2 = self.samples()
+        ls = length_scales.cpu()
+        dist_z = (z1 / ls - z2 / ls) ** 2
+        b = self.b.cpu()
+        z_part = (-b * (z1 - self.hf) - b * (z2 - self.hf) - 0.5 * dist_z).exp()
+        z_part_mc = z_part.mean() * (self.hf - self.lf) * (self.hf - self.lf)
+        return self.signal_variance.abs().cpu() * z_part_mc
+
+    @property
+    def effective(self):
+        # hasattr(kernel, "effective") is how the GP modules pick the fused path: only a stationary base kernel has it
+        if not hasattr(self.kernel1, "effective"):
+            raise AttributeError("effective")
+        return self._effective
+
+    def _effective(self):
+        w, amp, clamp = self.kernel1.effective()
+        return w, amp * self.scale().to(amp.device), clamp
+
+    def kfun(self):
+        return self.kernel1.kfun() if hasattr(self.kernel1, "kfun") else (0, 1.0)
+
+    def car_links(self):
+        """{"base": kernel1's `links()` (None when it has none), "l_z", "sigma_z", "b": the raw parameters, "eps", "lf", "hf",
+        "z1", "z2": the sample vectors of one reference step (host tensors in the default dtype; the global generator is left as that
+        step leaves it)}"""
+        z1, z2 = self.samples()
+        base = self.kernel1.links() if hasattr(self.kernel1, "links") else None
+        return {"base": base, "l_z": self.length_scales, "sigma_z": self.signal_variance, "b": self.b, "eps": float(self.eps),
+                "lf": float(self.lf), "hf": float(self.hf), "z1": z1, "z2": z2}
+
+    def forward(self, x1, x2):
+        K = self.kernel1(x1, x2)
+        return self.scale().to(K.device) * K
+
+
+fidelity_kernel_MCMC = FidelityKernelMCMC

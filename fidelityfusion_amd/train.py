@@ -25,7 +25,8 @@ TREE_ONE_LAUNCH_MAX_N = 128   # composed-kernel models up to this size take ffgp
 class AdamState:
     """torch.optim.Adam's per-parameter state of the models of one `train_many` chunk, kept on the device between calls:
     buf[f] = [exp_avg (nw + 2) | exp_avg_sq (nw + 2)] in the order length scales, signal variance, log_beta (a residual model:
-    [exp_avg (nw + 3) | exp_avg_sq (nw + 3)], rho last); `step` = updates taken.
+    [exp_avg (nw + 3) | exp_avg_sq (nw + 3)], rho last; a `GP_basic`: noise_variance in log_beta's place; a CAR model: [exp_avg (nw + 5) |
+    exp_avg_sq (nw + 5)] in the order length scales, signal variance, noise_variance, b, l_z, sigma_z); `step` = updates taken.
     A chunk of composed-kernel models (ffgp_train_tree_raw): buf[f] = [exp_avg (P) | exp_avg_sq (P)], P = sum over the leaves of
     (length scales + 1 + the centre's D for a LinearKernel) + 1, in the order leaf by leaf in the tree's canonical leaf order
     (`kernel._Pair.tree_links`: length scales, signal variance, centre), then log_beta."""
@@ -40,13 +41,16 @@ def _jitter_and_pi():
 
 
 def _eligible(model, x, y):
-    """the model's links when ffgp_train_raw can train it: a `cigp` with a library kernel whose raw-parameter path applies (everything
+    """the model's links when ffgp_train_raw can train it: a `cigp` (or a `GP_basic`: `_eligible_gp_basic`) with a library kernel whose raw-parameter path applies (everything
     on one GPU in fp64, no learnable profile parameter, no gradient-carrying inputs), all three parameters trainable"""
     from . import functional as F
     if isinstance(y, list):
         y, y_var = y[0], y[1]
     else:
         y_var = None
+    from .gp_basic import GP_basic
+    if isinstance(model, GP_basic):
+        return _eligible_gp_basic(model, x, y, y_var)
     if not (hasattr(model, "kernel") and hasattr(model, "log_beta")):
         return None
     if y_var is not None and not F.raw_ok(y_var):
@@ -62,6 +66,83 @@ def _eligible(model, x, y):
     if {id(q) for q in model.parameters()} != {id(lk["w"]), id(lk["amp"]), id(model.log_beta)}:
         return None      # a kernel with further learnable parameters (MaternKernel's rho is a constant; RQ's alpha is not)
     return lk, y, y_var
+
+
+def _eligible_gp_basic(model, x, y, y_var):
+    """`_eligible` for a `GP_basic` (GaussianProcess/gp_basic.py): Sigma = K + noise_variance^2 I without jitter and the FFGP_LL_V2
+    likelihood.  The links dict carries the two differences from a `cigp`: "diag" = (raw diagonal parameter, its link, its constant)
+    and "ll" = (variant, pi).  A list y (the FULL y_var matrix enters Sigma), a composed kernel or further parameters: the reference's loop."""
+    import math
+    from . import functional as F
+    if y_var is not None or not isinstance(y, torch.Tensor) or hasattr(model.kernel, "tree_links"):
+        return None
+    nv = model.noise_variance
+    with torch.enable_grad():
+        lk = F.raw_path(model.kernel, x, y, nv)
+    if lk is None or isinstance(lk.get("kparam"), torch.Tensor) or y.requires_grad or nv.numel() != 1:
+        return None
+    if not (lk["w"].requires_grad and lk["amp"].requires_grad and nv.requires_grad):
+        return None
+    if {id(q) for q in model.parameters()} != {id(lk["w"]), id(lk["amp"]), id(nv)}:
+        return None
+    lk = dict(lk)
+    lk["diag"] = (nv, _lib.LINK_SQUARE, 0.0)
+    lk["ll"] = (_lib.FFGP_LL_V2, math.pi)
+    return lk, y, None
+
+
+def _eligible_car(model, x, car):
+    """`_eligible` for one of train_CAR's fidelities above 0 (`car` = (b, y_low, y_high)): a `GP_basic` (or `cigp`) over a
+    `kernel.FidelityKernelMCMC` whose base kernel is a library radial kernel with `links()`, a one-element l_z, everything on one GPU in
+    fp64, and exactly the six groups of parameters -- the base kernel's two, l_z, sigma_z, b, the noise parameter -- all trainable.
+    The links dict is the base kernel's, with "car" = the kernel's `car_links()` (the samples of this call inside)."""
+    import math
+    from . import functional as F
+    from .kdesc import FFGP_KFUN_LINEAR
+    b, yl, yh = car
+    k = model.kernel
+    cl = k.car_links()      # (draws the samples: the global generator is left as one reference step leaves it)
+    lk = cl["base"]
+    from .gp_basic import GP_basic
+    v1 = hasattr(model, "log_beta")
+    if not (v1 or isinstance(model, GP_basic)):
+        return None
+    dpar = model.log_beta if v1 else model.noise_variance
+    if lk is None or lk["kfun"] == FFGP_KFUN_LINEAR or isinstance(lk.get("kparam"), torch.Tensor) or cl["l_z"].numel() != 1:
+        return None
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.shape[1] <= 128 and isinstance(yl, torch.Tensor) and isinstance(yh, torch.Tensor)):
+        return None
+    pars = [lk["w"], lk["amp"], dpar, cl["l_z"], cl["sigma_z"], b]
+    if not F.raw_ok(x, yl, yh, *pars):
+        return None
+    if yh.dim() != 2 or yh.shape[0] != x.shape[0] or yl.shape != yh.shape or x.requires_grad or yl.requires_grad or yh.requires_grad:
+        return None
+    if lk["w"].numel() not in (1, x.shape[1]) or lk["amp"].numel() != 1 or dpar.numel() != 1 or cl["sigma_z"].numel() != 1 or b.numel() != 1:
+        return None
+    if not all(t.requires_grad and t.is_leaf for t in pars) or cl["z1"].numel() > 128:
+        return None
+    if len({id(t) for t in pars}) != 6 or {id(q) for q in model.parameters()} != {id(t) for t in pars}:
+        return None
+    lk = dict(lk)
+    lk["car"] = cl
+    if not v1:
+        lk["diag"] = (dpar, _lib.LINK_SQUARE, 0.0)
+        lk["ll"] = (_lib.FFGP_LL_V2, math.pi)
+    return lk, yh, None
+
+
+def _car_targets(car, b):
+    """train_CAR's residual at this b (CAR_ContinuousAutoRegression.py:134-136): [y_high - exp(b) * y_low, None]"""
+    with torch.no_grad():
+        return [car[2] - b.exp() * car[1], None]
+
+
+def _loss(m, x, y):
+    """the loss the reference's loops minimise: -negative_log_likelihood of a `cigp`, -log_likelihood of a `GP_basic` (train_CAR,
+    CAR_ContinuousAutoRegression.py:116-142)"""
+    if hasattr(m, "negative_log_likelihood"):
+        return -m.negative_log_likelihood(x, y)
+    return (-m.log_likelihood(x, y)).sum()
 
 
 def _eligible_tree(model, x, y, y_var):
@@ -107,11 +188,13 @@ def _residual_targets(res, rho):
         return [yh - rho * yl, None if vl is None else (vh - rho * vl).abs()]
 
 
-def _reference_loop(models, xs, ys, steps, lr, betas, eps, opts, residual=None, targets=None):
-    """the reference's loop itself (one torch.optim.Adam per model, rho in a residual model's): models that the fused call cannot train"""
+def _reference_loop(models, xs, ys, steps, lr, betas, eps, opts, residual=None, targets=None, car=None):
+    """the reference's loop itself (one torch.optim.Adam per model, rho in a residual model's; a CAR model's b is one of its own
+    parameters): models that the fused call cannot train"""
     trace = torch.empty((len(models), steps), dtype=torch.float64)
     for f, (m, x, y) in enumerate(zip(models, xs, ys)):
         res = residual[f] if residual is not None else None
+        cr = car[f] if car is not None else None
         if opts[f] is None:
             opts[f] = torch.optim.Adam(list(m.parameters()) + ([res[0]] if res is not None else []), lr=lr, betas=betas, eps=eps)
         for k in range(steps):
@@ -121,7 +204,11 @@ def _reference_loop(models, xs, ys, steps, lr, betas, eps, opts, residual=None, 
                 y = [yh - rho * yl, (vh - rho * vl).abs()] if vl is not None else yh - rho * yl
                 if k == steps - 1:
                     targets[f] = [y[0].detach(), y[1].detach()] if vl is not None else [y.detach(), None]
-            loss = -m.negative_log_likelihood(x, y)
+            if cr is not None:       # train_CAR's residual at the current b, with its graph (CAR_ContinuousAutoRegression.py:132-139)
+                y = cr[2] - cr[0].exp() * cr[1]
+                if k == steps - 1:
+                    targets[f] = [y.detach(), None]
+            loss = _loss(m, x, y)
             loss.backward()
             opts[f].step()
             trace[f, k] = float(loss.detach())
@@ -150,12 +237,14 @@ def _residual_ok(res, x):
     return True
 
 
-def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None, tree_one_launch=False):
+def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None, tree_one_launch=False, car=None):
     """`steps` Adam iterations on every model of `models` (independent `cigp` models, `xs[f]`, `ys[f]` their training data; y may be
     `[y, y_var]`), each exactly the reference's iteration (FidelityFusion_Models/ResGP.py:82-88): loss = -negative_log_likelihood,
     gradients of the three raw parameters, torch.optim.Adam(lr, betas, eps) update.  Returns `(trace, state)`:
     trace [F, steps] (float64, on the models' device) = the loss of model f at step k BEFORE that step's update -- what the reference
     prints -- and `state`, to be passed back in to continue the same optimisers (`state=None`: fresh optimisers).
+    `GP_basic` models (noise_variance^2 on the diagonal, no jitter, the FFGP_LL_V2 likelihood; loss = -log_likelihood as train_CAR's
+    loop minimises it) with a library kernel and a plain-tensor y train the same way, and may share a call with `cigp` models.
     Models on one GPU in fp64 with a library kernel are trained by ffgp_train_raw, up to 16 per call (small models -- N <= 128, D,
     d <= 16 -- take ONE kernel launch for ALL their steps: csrc/train.hip, a persistent workgroup per model); anything else runs the
     reference's loop through the drop-in modules.
@@ -182,7 +271,15 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     None): every step trains it on y_high - rho * y_low -- y_low, y_high tensors [n, d] (subset form) or [mean, var] lists with var [n, n]
     (then |v_high - rho * v_low| is the y_var whose diagonal enters Sigma) -- and rho (a one-element fp64 parameter) is a fourth Adam
     parameter, updated in place like the others.  state["residual_targets"][f] = [res_mean, res_var] (res_var None in the subset form)
-    is that residual at the rho of the start of the last step, computed with torch: what train_AR hands to add_data."""
+    is that residual at the rho of the start of the last step, computed with torch: what train_AR hands to add_data.
+    `car[f]` = (b, y_low, y_high) makes model f one of train_CAR's fidelities above 0 (CAR_ContinuousAutoRegression.py:116-142; `ys[f]`
+    is then None): a `GP_basic` over a `kernel.FidelityKernelMCMC` whose `b` is that very tensor, trained on y_high - exp(b) * y_low
+    under kernel1 * s(b, l_z, sigma_z); six groups of parameters move per step -- the base kernel's two, l_z, sigma_z, b and
+    noise_variance (ffgp_train_car_raw: one launch for all steps up to 128 points, launch per stage above).  The Monte-Carlo samples are
+    drawn once per call, after `torch.manual_seed(105)`, which leaves the global generator as one reference step leaves it.
+    state["residual_targets"][f] = [y_high - exp(b) * y_low, None] at the b of the start of the last step.  A tree or
+    RationalQuadraticKernel base kernel, an l_z of several elements or CPU tensors: the reference's loop, same return values.
+    `car=` and `residual=` on one model raise ValueError."""
     models, xs, ys = list(models), list(xs), list(ys)
     nF = len(models)
     if not (nF == len(xs) == len(ys)) or steps <= 0:
@@ -194,12 +291,26 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         for f, res in enumerate(residual):
             if res is not None and (ys[f] is not None or len(res) != 3):
                 raise ValueError("train_many: a residual model takes (rho, y_low, y_high) and ys[f] = None")
-            if res is None and ys[f] is None:
+            if res is None and ys[f] is None and (car is None or car[f] is None):
                 raise ValueError("train_many: model %d has neither targets nor a residual link" % f)
+    if car is not None:
+        car = list(car)
+        if len(car) != nF:
+            raise ValueError("train_many: car must have one entry per model")
+        for f, cr in enumerate(car):
+            if cr is None:
+                continue
+            if residual is not None and residual[f] is not None:
+                raise ValueError("train_many: model %d has both a car and a residual link" % f)
+            if ys[f] is not None or len(cr) != 3:
+                raise ValueError("train_many: a CAR model takes (b, y_low, y_high) and ys[f] = None")
+            if not hasattr(models[f].kernel, "car_links") or models[f].kernel.b is not cr[0]:
+                raise ValueError("train_many: a CAR model's kernel is a FidelityKernelMCMC whose b is the tensor given in car=")
+    car_of = (lambda f: car[f]) if car is not None else (lambda f: None)
     res_of = (lambda f: residual[f]) if residual is not None else (lambda f: None)
     # a residual model's eligibility is judged on its y_high (same shape as its targets) and its link
     ys_e = [ys[f] if res_of(f) is None else _split_residual(res_of(f))[2] for f in range(nF)]
-    elig = [_eligible(m, x, y) for m, x, y in zip(models, xs, ys_e)]
+    elig = [_eligible(m, x, y) if car_of(f) is None else _eligible_car(m, x, car_of(f)) for f, (m, x, y) in enumerate(zip(models, xs, ys_e))]
     for f in range(nF):
         if res_of(f) is not None and elig[f] is not None and (_is_tree(elig[f]) or not _residual_ok(res_of(f), xs[f])):
             elig[f] = None      # (a composed kernel with a residual link: the reference's loop -- ffgp_train_tree_raw has no residual members)
@@ -211,7 +322,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     if not fused or not state["fused"]:
         if state["fused"]:
             raise ValueError("train_many: this state belongs to fused training; the models no longer qualify for it")
-        trace = _reference_loop(models, xs, ys, steps, lr, betas, eps, state["opts"], residual, state["residual_targets"])
+        trace = _reference_loop(models, xs, ys, steps, lr, betas, eps, state["opts"], residual, state["residual_targets"], car)
         return trace, state
     JITTER, PI = _jitter_and_pi()
     from . import functional as F
@@ -220,6 +331,8 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     trace = torch.empty((nF, steps), dtype=torch.float64, device=dev)
     opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
     rho_last = {f: torch.empty_like(res_of(f)[0].detach()) for f in range(nF) if res_of(f) is not None}
+    b_last = {f: torch.empty_like(car_of(f)[0].detach()) for f in range(nF) if car_of(f) is not None}
+    zdev = {}      # the CAR members' samples on the device (alive until the calls have returned)
 
     def describe(f):
         lk, y, y_var = elig[f]
@@ -228,18 +341,19 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         p = Problem()
         p.n, p.D, p.d = n, D, y.shape[1]
         p.X_dev, p.Y_dev, p.w_dev, p.amp_dev = x.data_ptr(), y.data_ptr(), lk["w"].data_ptr(), lk["amp"].data_ptr()
-        p.diag_add_dev = m.log_beta.data_ptr()
+        dpar, dlink, dc = lk["diag"] if "diag" in lk else (m.log_beta, _lib.LINK_EXP_NEG, JITTER)
+        p.diag_add_dev = dpar.data_ptr()
         p.clamp_min = lk["clamp"]
         if y_var is not None:
             p.diag_stride = y_var.shape[1] + 1 if y_var.dim() == 2 else 1
             p.diag_vec_dev = y_var.data_ptr()
-        p.ll_variant, p.pi_const = FFGP_LL_V1, PI
+        p.ll_variant, p.pi_const = lk["ll"] if "ll" in lk else (FFGP_LL_V1, PI)
         kp = lk.get("kparam")
         p.kfun, p.kparam = lk["kfun"], (1.0 if kp is None else float(kp))
         ll = _lib.Links()
         ll.w_link, ll.w_c, ll.w_broadcast = lk["w_link"], lk["w_c"], 1 if lk["w"].numel() == 1 and D > 1 else 0
         ll.amp_link, ll.amp_c = lk["amp_link"], 0.0
-        ll.dadd_link, ll.dadd_c = _lib.LINK_EXP_NEG, JITTER
+        ll.dadd_link, ll.dadd_c = dlink, dc
         ll.out_scale = 1.0          # the value is the loss the reference minimises: -negative_log_likelihood = +nll
         rs = _lib.Residual()
         if res_of(f) is not None:
@@ -250,7 +364,19 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
                 rs.v_low_dev, rs.v_low_stride = vl.data_ptr(), vl.stride(0) + vl.stride(1)
                 rs.v_high_dev, rs.v_high_stride = vh.data_ptr(), vh.stride(0) + vh.stride(1)
             rs.rho_last_dev = rho_last[f].data_ptr()
-        return p, ll, rs, lk["w"].numel() + (1 if res_of(f) is not None else 0)
+        cl = _lib.CarLink()
+        if car_of(f) is not None:
+            c, (b, yl, yh) = lk["car"], car_of(f)
+            z1, z2 = zdev[f] = (c["z1"].to(dev).contiguous(), c["z2"].to(dev).contiguous())
+            cl.b_dev, cl.zls_dev, cl.zamp_dev, cl.zeps = b.data_ptr(), c["l_z"].data_ptr(), c["sigma_z"].data_ptr(), c["eps"]
+            if z1.dtype == torch.float64:      # (drawn under torch.set_default_dtype(float64): other numbers, all of the scalar in fp64)
+                cl.z1d_dev, cl.z2d_dev = z1.data_ptr(), z2.data_ptr()
+            else:
+                zdev[f] = z1, z2 = z1.float(), z2.float()
+                cl.z1_dev, cl.z2_dev = z1.data_ptr(), z2.data_ptr()
+            cl.nz, cl.lf, cl.hf = z1.numel(), c["lf"], c["hf"]
+            cl.y_low_dev, cl.y_high_dev, cl.b_last_dev = yl.data_ptr(), yh.data_ptr(), b_last[f].data_ptr()
+        return p, ll, rs, cl, lk["w"].numel() + (1 if res_of(f) is not None else 0) + (3 if car_of(f) is not None else 0)
 
     def describe_tree(f, keep):
         """model f with a composed kernel: its problem (the tree's leaves on their RAW parameters) and ffgp_tree_links; P = its number
@@ -328,12 +454,17 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         P = (Problem * len(idx))()
         L = (_lib.Links * len(idx))()
         R = (_lib.Residual * len(idx))()
+        Cl = (_lib.CarLink * len(idx))()
         nws = []
         for j, f in enumerate(idx):
-            P[j], L[j], R[j], nw = describe(f)
+            P[j], L[j], R[j], Cl[j], nw = describe(f)
             nws.append(nw)
         anyres = any(res_of(f) is not None for f in idx)
         stride = 2 * (max(nws) + 2)
+        if any(car_of(f) is not None for f in idx):      # (never in one chunk with residual members: `groups` below)
+            return launch(idx, stride, lambda st, tr: check(
+                lib.ffgp_train_car_raw(h, len(idx), P, L, Cl, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
+                                       tr.data_ptr(), tr.stride(0)), "ffgp_train_car_raw"))
         if anyres:
             return launch(idx, stride, lambda st, tr: check(
                 lib.ffgp_train_residual_raw(h, len(idx), P, L, R, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
@@ -357,12 +488,17 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
                   and shapes[f][2] <= F.SMALL_BATCH_MAX_d}
     lds_trees = sorted(one_launch)
     small_trees = [f for f in sorted(trees) if shapes[f][0] <= F.SMALL_BATCH_MAX_N and f not in one_launch]
-    large = [f for f in range(nF) if f not in set(small) and f not in set(small_trees) and f not in one_launch]
+    large = [f for f in range(nF) if f not in set(small) and f not in set(small_trees) and f not in one_launch]      # (set(small): CAR ones too)
     state["tree_one_launch"] = lds_trees
+    # (CAR members have an entry point of their own: their small ones form chunks apart from the plain and residual models')
+    small_car = [f for f in small if car_of(f) is not None]
+    small = [f for f in small if car_of(f) is None]
     if len(small) == 1:      # (a lone small model gains nothing from the batch kernel: its own call folds the tail launches)
         large, small = sorted(large + small), []
+    if len(small_car) == 1:
+        large, small_car = sorted(large + small_car), []
     rcs = []
-    for group in (small, small_trees, lds_trees):
+    for group in (small, small_car, small_trees, lds_trees):
         for c0 in range(0, len(group), TRAIN_MAX_MODELS):
             rcs.append((group[c0:c0 + TRAIN_MAX_MODELS], run(group[c0:c0 + TRAIN_MAX_MODELS])))
     if len(large) >= 2 and _lib.current_slot() == 0:
@@ -384,4 +520,6 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
             _raise_not_pd(rc, "linalg.cholesky (train_many, model%s %s)" % ("s" if len(idx) > 1 else "", ", ".join(map(str, idx))))
     for f, rl in rho_last.items():      # train_AR's data for the fidelity: the residual at the rho of the start of the last step
         state["residual_targets"][f] = _residual_targets(res_of(f), rl.reshape(res_of(f)[0].shape))
+    for f, bl in b_last.items():        # train_CAR's data for the fidelity: the residual at the b of the start of the last step
+        state["residual_targets"][f] = _car_targets(car_of(f), bl.reshape(car_of(f)[0].shape))
     return trace, state

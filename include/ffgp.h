@@ -550,7 +550,8 @@ int ffgp_nlml_fused_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ff
    the number of steps already taken; trace_dev[f * trace_stride + k] = loss of model f at step k, evaluated BEFORE that step's
    update (what the reference prints).  Returns 0, or the pivot status of the first step whose Sigma was not positive definite
    (torch.linalg.LinAlgError in the reference's loop): from that step on no parameter moves and the trace holds NaN.  Synchronous.
-   ONE LAUNCH FOR THE WHOLE LOOP (round 6, csrc/train.hip): when every model has n <= 128, D <= 16, d <= 16, the V1 likelihood and no
+   ONE LAUNCH FOR THE WHOLE LOOP (round 6, csrc/train.hip): when every model has n <= 128, D <= 16, d <= 16, the V1 likelihood -- or the V2
+   likelihood (GP_basic: ll_variant = FFGP_LL_V2 with diag_add under any link; V1 and V2 members of one call get a launch each) -- and no
    Sigma extra but diag_add / diag_vec -- what the reference's experiments run (Experiments/GAR_Aligned/exp_aligned.py:66-74: 100 low-
    against 4..32 high-fidelity points) -- the call is one kernel launch: a persistent workgroup per model keeps Sigma, its factor, the
    inverse, the parameters and the Adam moments in LDS and runs all `steps` iterations inside the kernel (option "train_persist" = 0
@@ -587,6 +588,49 @@ int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const 
                             const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 int ffgp_nlml_fused_small_batch_async(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, double* nll_dev,
                                       const ffgp_grads* g);
+
+/* ffgp_train_raw with CAR members -- train_CAR's fidelities above 0 (FidelityFusion_Models/CAR_ContinuousAutoRegression.py:116-142):
+   model f trains on the targets r = y_high - exp(b) * y_low (a product, then a difference, rounded as ffgp_train_residual_raw rounds
+   its own) under the kernel kernel1(x, x') * s(b, l_z, sigma_z), the Monte-Carlo fidelity integral of fidelity_kernel_MCMC (:14-67)
+   over the nz sample pairs (z1_i, z2_i).  With l = |l_z| + zeps and w2 = (hf - lf)^2:
+       e_i = u_i - 1/2 ((z1_i - z2_i) / l)^2,   m = mean_i exp(e_i),   s = |sigma_z| m w2,
+       u_i = fl32(fl32(fl32(-b) * fl32(z1_i - hf)) + fl32(fl32(-b) * fl32(z2_i - hf)))
+   -- u_i in binary32 because torch evaluates `-b * (z1 - hf)`, a 0-dim fp64 parameter times an fp32 tensor, in binary32; z1 / l - z2 / l
+   is two fp64 divisions of the widened samples; everything from exp on is fp64.  (Under torch.set_default_dtype(float64) the reference
+   draws its samples in fp64 and nothing is binary32: pass those draws as z1d_dev / z2d_dev, and u_i = fl64(fl64(-b (z1_i - hf)) +
+   fl64(-b (z2_i - hf))).)  The effective amplitude is link(amp_raw) * s; both
+   the targets and s are re-formed from the current b, l_z, sigma_z at every step.  Six groups of parameters move per step (same lr,
+   betas, eps): with T = dloss/d(effective amplitude),
+       dloss/damp_raw = T s link'(amp_raw),       dloss/ds = T link(amp_raw),
+       ds/dsigma_z = sgn(sigma_z) m w2,           ds/dl_z = |sigma_z| w2 sgn(l_z) mean_i[exp(e_i) (z1_i - z2_i)^2] / l^3,
+       ds/db = -|sigma_z| w2 mean_i[exp(e_i) ((z1_i - hf) + (z2_i - hf))],
+       dloss/db = dloss/ds * ds/db - exp(b) * sum(dloss/dr .* y_low)          (sgn(0) = 0; dloss/dr = A for V1, B for V2)
+   and the derivatives of s in plain fp64 (the reference's ds/db is rounded to binary32 by autograd: 7e-8 relative, a documented
+   deviation).  The base model's likelihood may be V1 or V2 (GP_basic gives V2).  c[f].b_dev = NULL is a plain model, exactly as
+   ffgp_train_raw trains it; plain and CAR members may share a call.  For a CAR member p[f].Y_dev is ignored and its Adam state is
+   [exp_avg (nw + 5) | exp_avg_sq (nw + 5)] in the order w, amp, diag_add, b, l_z, sigma_z.  b_last_dev, when set, receives the b at the
+   start of the last step taken (train_CAR keeps y_high - exp(b) y_low at that b as the fidelity's data).  Routing: one launch for all
+   steps when every member has n <= 128, D, d <= 16 (csrc/train.hip; V2 members included), else launch per stage -- before the
+   likelihood a small kernel forms r and link(amp_raw) * s, after it another reduces dloss/db and applies the chain rule.  Trace,
+   status, option "train_persist" and failure semantics are ffgp_train_raw's: in one-launch form a not-PD member stops alone and its
+   parameters, b included, are those of the step's start.                                                                        */
+typedef struct {
+  double* b_dev;                 /* [1] raw b, updated in place; NULL = a plain model */
+  double* zls_dev;               /* [1] raw length scale of the fidelity kernel */
+  double* zamp_dev;              /* [1] raw signal variance of the fidelity kernel */
+  double zeps;                   /* 1e-3 in the reference */
+  const float* z1_dev;           /* [nz] the Monte-Carlo samples */
+  const float* z2_dev;           /* [nz] */
+  int nz;                        /* 1 .. 128 */
+  double lf, hf;
+  const double* y_low_dev;       /* [n, d] */
+  const double* y_high_dev;      /* [n, d] */
+  double* b_last_dev;            /* optional [1]: b at the start of the last step taken */
+  const double* z1d_dev;         /* optional [nz] each: the samples as fp64 DRAWS (torch's default dtype set to float64: torch.rand */
+  const double* z2d_dev;         /* then yields other numbers, not wider ones); z1_dev / z2_dev are ignored, u_i is fp64 arithmetic */
+} ffgp_car_link;
+int ffgp_train_car_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, const ffgp_car_link* c, int steps,
+                       const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 
 /* ffgp_train_raw for models whose kernel is a COMPOSITION -- SumKernel / ProductKernel trees of 2-4 leaves (ffgp_ktree), the kernel of
    the reference's own demos and of every two-fidelity model (SumKernel(LinearKernel, MaternKernel): GaussianProcess/cigp_v10.py:81,111,
