@@ -98,6 +98,23 @@ class CarLink(C.Structure):
                 ("z1d_dev", _dp), ("z2d_dev", _dp)]
 
 
+class HogpModel(C.Structure):
+    """ffgp_hogp_model: one HOGP block of ffgp_train_hogp_raw on its raw parameters"""
+    _fields_ = [("n", C.c_int), ("D", C.c_int), ("X_dev", _dp), ("nmodes", C.c_int), ("dims", C.c_int * 3), ("Y_dev", _dp), ("w_dev", _dp),
+                ("amp_dev", _dp), ("noise_dev", _dp), ("clamp_min", C.c_double), ("kfun", C.c_int), ("kparam", C.c_double)]
+
+
+class HogpResidual(C.Structure):
+    """ffgp_hogp_residual: a residual member of ffgp_train_hogp_raw (V_dev NULL = a plain block)"""
+    _fields_ = [("V_dev", _dp), ("y_low_dev", _dp), ("y_high_dev", _dp), ("l", C.c_int), ("V_row_stride", C.c_long),
+                ("V_col_stride", C.c_long)]
+
+
+class HogpCache(C.Structure):
+    """ffgp_hogp_cache: where ffgp_train_hogp_raw leaves the last step's K_m, eigenpairs, A and g (any pointer may be NULL)"""
+    _fields_ = [("K_dev", _dp * 4), ("evals_dev", _dp * 4), ("evecs_dev", _dp * 4), ("A_dev", _dp), ("g_dev", _dp)]
+
+
 class AcqProblem(C.Structure):
     """ffgp_acq_problem: a frozen posterior and the acquisition on it (ffgp_acq_optimize)"""
     _fields_ = [("n", C.c_int), ("D", C.c_int), ("d", C.c_int), ("X_dev", _dp), ("L_dev", _dp), ("ldl", C.c_int), ("alpha_dev", _dp),
@@ -212,6 +229,9 @@ EXPORTS = {
                                       C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_lds_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                           C.c_long, _dp, C.c_long]),
+    "ffgp_train_hogp_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(HogpModel), C.POINTER(Links), C.POINTER(HogpResidual), C.c_int,
+                                      C.POINTER(Adam), _dp, C.c_long, C.POINTER(C.c_long), _dp, C.c_long, C.POINTER(HogpCache),
+                                      C.POINTER(C.c_int)]),
     "ffgp_acq_optimize": (C.c_int, [C.c_void_p, C.POINTER(AcqProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_tree": (C.c_int, [C.c_void_p, C.POINTER(AcqTreeProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_stack": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),

@@ -129,6 +129,46 @@ int main() {
     EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     ap.kfun = FFGP_KFUN_SE; ap.acq = FFGP_ACQ_UCB_VAR;      // the stack entry only
     EXPECT(ffgp_acq_optimize(fake, &ap, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    // K Adam steps of HOGP blocks: every refusal of ffgp_train_hogp_raw comes before the handle is dereferenced or anything is enqueued
+    {
+      ffgp_hogp_model hm;
+      std::memset(&hm, 0, sizeof hm);
+      hm.n = 4; hm.D = 2; hm.nmodes = 2; hm.dims[0] = 3; hm.dims[1] = 2; hm.kfun = FFGP_KFUN_SE; hm.kparam = 1.0;
+      hm.X_dev = hm.Y_dev = &x;
+      hm.w_dev = hm.amp_dev = hm.noise_dev = &x;
+      ffgp_hogp_residual hr;
+      std::memset(&hr, 0, sizeof hr);
+      const long s0 = 0;
+      auto call = [&](ffgp_handle* hh, int F, const ffgp_hogp_residual* r, long stride) {
+        return ffgp_train_hogp_raw(hh, F, &hm, &lk, r, 3, &ad, &x, stride, &s0, &x, 3, nullptr, nullptr);
+      };
+      EXPECT(call(nullptr, 1, nullptr, 8) == FFGP_ERR_ARG);
+      EXPECT(call(fake, 0, nullptr, 8) == FFGP_ERR_ARG);
+      EXPECT(call(fake, 17, nullptr, 8) == FFGP_ERR_ARG);
+      EXPECT(call(fake, 1, nullptr, 7) == FFGP_ERR_ARG);                 // state_stride < 2 (nw + 2), nw = D = 2
+      EXPECT(ffgp_train_hogp_raw(fake, 1, &hm, &lk, nullptr, 3, &ad, &x, 8, &s0, &x, 2, nullptr, nullptr) == FFGP_ERR_ARG);   // trace_stride < steps
+      EXPECT(ffgp_train_hogp_raw(fake, 1, &hm, &lk, nullptr, 3, &ad, &x, 8, nullptr, &x, 3, nullptr, nullptr) == FFGP_ERR_ARG);
+      hm.n = 0;   EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.n = FFGP_SYEV_LDS_MAX_N + 1; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.n = 4; hm.nmodes = 0; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.nmodes = 4; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.nmodes = 2; hm.dims[1] = 65; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.dims[1] = 0; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.nmodes = 3; hm.dims[0] = 16; hm.dims[1] = 16; hm.dims[2] = 17;      // every mode <= 64, the product 4352 > FFGP_HOGP_MAX_OUT
+      EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.dims[0] = hm.dims[1] = hm.dims[2] = 64; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.nmodes = 2; hm.dims[0] = 3; hm.dims[2] = 0;
+      hm.dims[1] = 2; hm.noise_dev = nullptr; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.noise_dev = &x; hm.Y_dev = nullptr; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);      // a plain block needs its targets
+      hm.Y_dev = &x; hm.kfun = FFGP_KFUN_RQ; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);
+      hm.kfun = FFGP_KFUN_SE; hm.D = 1; lk.w_broadcast = 1; EXPECT(call(fake, 1, nullptr, 8) == FFGP_ERR_ARG);   // one raw value for ONE column
+      lk.w_broadcast = 0; hm.D = 2;
+      hr.V_dev = &x; hr.l = 2;                                           // a residual member without its fields, with too small a state
+      EXPECT(call(fake, 1, &hr, 64) == FFGP_ERR_ARG);
+      hr.y_low_dev = hr.y_high_dev = &x; hr.l = 65; EXPECT(call(fake, 1, &hr, 64) == FFGP_ERR_ARG);
+      hr.l = 2; EXPECT(call(fake, 1, &hr, 2 * (2 + 2 + 2 * 2) - 1) == FFGP_ERR_ARG);
+      hr.V_row_stride = -1; hr.V_col_stride = 1; EXPECT(call(fake, 1, &hr, 64) == FFGP_ERR_ARG);
+    }
     std::printf("asan_host_check: no device -- argument / no-device paths clean\n");
     return 0;
   }

@@ -683,6 +683,78 @@ int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp
 int ffgp_train_tree_lds_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, int steps, const ffgp_adam* opt,
                             double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 
+/* K Adam steps of F <= 16 independent HOGP blocks in ONE call (csrc/train_hogp.hip) -- train_GAR's loop
+   (FidelityFusion_Models/GAR.py:76-126: per fidelity 100-1000 iterations of HOGP_simple.log_likelihood / backward / Adam at 4..100
+   points with 8 x 8 ... 64 x 64 outputs).  Launch per stage, no host synchronisation inside the loop, the status read once at the end.
+   Model f: n points X_dev [n, D], targets Y_dev [n, d_1, ..., d_M] (M = nmodes in 1..3, every d_m <= 64, prod d_m <= FFGP_HOGP_MAX_OUT = 4096 -- two
+   images of a sample's tensor live in LDS --, n <= FFGP_SYEV_LDS_MAX_N),
+   ONE shared radial kernel on its raw parameters (w_dev: nw = 1 value with links.w_broadcast or D == 1, else D; amp_dev; kfun, kparam,
+   clamp_min and links as for ffgp_train_raw -- dadd_link / dadd_c / out_scale are not read) and noise_dev [1], the raw
+   noise_variance: tau = 1 / noise_variance, no jitter.  Mode m's inputs are the grid 0..d_m-1 as a float column, repeated in nw
+   columns, formed by the call itself.  Per step, model by model (a model's arithmetic never depends on its companions):
+     targets     a plain block uses Y_dev; a residual block r = y_high - y_low x_last V with the current V (a product, a difference)
+     assembly    raw -> effective parameters (ffgp_link_val), K_0 [n, n] and K_1 ... K_M in one launch of ffgp_assemble's kernel
+     eigenpairs  ffgp_syevj_small's kernel for n <= 64 and every mode matrix, ffgp_syev_lds's for 64 < n <= 128, ascending
+     forward     A = ((lambda_0 lambda_1) ...) + tau, T_1 = Y x_m U_m^T, W = T_1 / A, g = W x_m U_m,
+                 loss = (1/2 nd log 2 pi + 1/2 sum log A + 1/2 sum T_1 W) / nd          (nd = n prod d, the true pi)
+     backward    dtau = 1/2 sum(1/A - W^2), c_m = the contraction of 1/A with the other modes' eigenvalues,
+                 dK_m = 1/2 (U_m diag(c_m) U_m^T - g_(m) P_(m)^T), P = g x_{m' != m} K_m', everything times 1 / nd; dK_0 ... dK_M go
+                 through ffgp_kernel_grad's kernels onto the effective parameters, the M + 1 contributions are summed (matrix 0 first),
+                 then one link derivative each; d noise = -dtau / noise^2; a residual block: dV = -(g / nd contracted with y_low over
+                 all but the last mode) [h, l]
+     Adam        ffgp_adam_update on [w (nw) | amp | noise | V (h l, residual blocks only)]; the step's loss, evaluated before the
+                 update, goes to trace_dev[f * trace_stride + k]
+   Every sum has a fixed order (no floating-point atomics, no cross-workgroup waits), every loop is bounded.  The number of launches
+   per step depends on M and on whether the block is residual, never on n or d_m.  The call's buffers live in the
+   handle's workspace, kept between calls.  Everything is enqueued on the
+   handle's stream except the eigensolvers, which are independent one-workgroup kernels: those of a step (all models') are dealt
+   over the handle's stream and its two side streams, forked and joined by events, and the call returns with all three drained.
+   Adam state per model at stride state_stride >= 2 P doubles, P = nw + 2 (+ h l): [exp_avg (P) | exp_avg_sq (P)]; step0[f] = the
+   updates model f has already taken (its bias corrections use step0[f] + k + 1).
+   Residual members (r != NULL and r[f].V_dev != NULL) are train_GAR's fidelities above 0: only the LAST mode's matrix of Tensor_linear
+   acts (the reference applies every mode product to the input, gp_computation_pack.py:155-158), V_dev [h, l] is that matrix, raw,
+   updated in place (strided: V_row_stride / V_col_stride; the Adam state and the trace see it row-major); y_low_dev [n, d_1, ..., d_{M-1}, l], y_high_dev [n, d_1, ..., d_{M-1}, h] with h = d_M; Y_dev is ignored.
+   Caches (c may be NULL, as may any pointer in it): of the LAST step taken, i.e. for the parameters that step started from, K_m, their
+   eigenvalues and eigenvectors (columns), A and g -- what HOGP_simple.forward reads.
+   Failure: a model whose loss is not finite at some step (a non-positive entry of A after noise_variance crossed zero) or whose
+   eigensolver reports a non-zero info stops alone: its trace holds NaN from that step on, its parameters and moments keep the values
+   that step began with; the others complete.  fail_step (host, [F], may be NULL) receives the failing step of each model or -1.
+   Returns 0, or 1 + f + 16 * k for the first failure (smallest step k, then smallest model f).  FFGP_ERR_ARG with nothing enqueued:
+   F outside 1..16, n outside 1..128, nmodes outside 1..3, a dim outside 1..64, prod d_m > 4096, D outside 1..128, null buffers, a broadcast-link
+   mismatch (w_broadcast != 0 names ONE raw value for D > 1 columns: with D == 1 it is refused), l outside 1..64, state_stride < 2 P, trace_stride < steps.  Synchronous. */
+#define FFGP_HOGP_MAX_OUT 4096
+typedef struct {
+  int n, D;
+  const double* X_dev;        /* [n, D] */
+  int nmodes;                 /* 1 .. 3 */
+  int dims[3];                /* each 1 .. 64, their product <= FFGP_HOGP_MAX_OUT */
+  const double* Y_dev;        /* [n, d_1, ..., d_M]; ignored for a residual member */
+  double* w_dev;              /* raw length scale(s), updated in place */
+  double* amp_dev;            /* [1] raw signal variance, updated in place */
+  double* noise_dev;          /* [1] raw noise_variance, updated in place */
+  double clamp_min;
+  int kfun;                   /* FFGP_KFUN_SE ... FFGP_KFUN_MATERN52 */
+  double kparam;
+} ffgp_hogp_model;
+typedef struct {
+  double* V_dev;              /* [h, l] raw, updated in place; NULL = a plain block */
+  const double* y_low_dev;    /* [n, ..., l] */
+  const double* y_high_dev;   /* [n, ..., h] */
+  int l;                      /* 1 .. 64 */
+  long V_row_stride;          /* element (a, b) of V at V_dev[a * V_row_stride + b * V_col_stride]; both 0 = row-major (l, 1). */
+  long V_col_stride;          /* (Tensor_linear's bilinear initialisation is a transposed view: strides (1, h))               */
+} ffgp_hogp_residual;
+typedef struct {
+  double* K_dev[4];           /* K_0 [n, n], K_m [d_m, d_m] */
+  double* evals_dev[4];       /* ascending */
+  double* evecs_dev[4];       /* columns */
+  double* A_dev;              /* [n, d_1, ..., d_M] */
+  double* g_dev;              /* [n, d_1, ..., d_M] */
+} ffgp_hogp_cache;
+int ffgp_train_hogp_raw(ffgp_handle* h, int F, const ffgp_hogp_model* m, const ffgp_links* links, const ffgp_hogp_residual* r, int steps,
+                        const ffgp_adam* opt, double* state_dev, long state_stride, const long* step0, double* trace_dev,
+                        long trace_stride, const ffgp_hogp_cache* c, int* fail_step);
+
 /* K Adam steps of an ACQUISITION optimiser on a frozen posterior in ONE launch -- the reference's second hot loop
    (Bayesian_optimization/acq.py:48-68: `raw_samples` <= 500 query points, `num_restarts` = 30 iterations of zero_grad();
    loss = -acq(X).sum(); loss.backward(); Adam.step(), the model untouched).  The loss is a sum of per-point terms and Adam is
