@@ -115,6 +115,8 @@ struct GemmArgs {
   int total_tiles;
   int grid;            // gridDim.x (= total_tiles, or split_at + 4 * (tiles handed out as quarters))
   int split_at;        // 128-tile launches: blocks >= split_at process 64 x 64 quarters of the tiles [split_at, all) (INT_MAX = none)
+  int slab_at;         // 128-tile lower-mode launches: blocks >= slab_at process 16-row slabs of the rows below tiles_m * 128 (INT_MAX = none)
+  int light;           // ... and their diagonal tiles take the rotated k loop (option syrk_light_tiles, decided by gemm_plan)
   int band_log2;       // tile order: bands of 2^band_log2 tile rows, column-major inside a band
   int pad_lds;         // bytes of unused dynamic LDS requested at launch (occupancy control)
   int fast;            // alpha = +-1, beta in {0,1}, offsets fit 32 bits: interior tiles take the scalar-addressed form
@@ -140,7 +142,7 @@ struct GemmRagMember {
   double* C;
   int m, n, k;
   int lda, ldb, ldc;
-  int tiles_m, tiles_n, total_tiles, grid, split_at;
+  int tiles_m, tiles_n, total_tiles, grid, split_at, slab_at, light;
   int fast, avec, bvec;
 };
 struct GemmRag {
@@ -203,6 +205,7 @@ struct ffgp_handle {
   int la_carry_n;       // ... (default 12288; also the largest member a ragged chain accepts)
   int la_carry_rows;    // ... (default 8192)
   int diag_attr_set;    // dynamic-LDS attributes set on this handle's device (launch_diag, ffgp_potrf_ragged): 1 inverse-only kernel, 2 / 4 v4
+  int syrk_light_tiles; // option "syrk_light_tiles" (default 1): passenger-row slabs (<= 32 rows) and rotated-loop diagonal tiles in the 128-tile lower-mode launches
   int split_rem_max;    // split tail of the 128-tile launches: quarter the last (tiles mod 256) tiles when that is <= this (0 = off)
   int polite_m;         // trailing updates with fewer rows than this run one workgroup per CU (0 = never)
   bool own_stream;

@@ -48,8 +48,17 @@ extern "C" int ffgp_debug_set_trace(void* p) {
       }                                                                                             \
     }                                                                                               \
   } while (0)
+// ... and which tile it worked on: (ti << 32 | tj) in slot 4, the tile's extent in rows (128 / 64 quarter / 16 slab) in slot 5
+#define FFGP_TRACE_TILE(ti, tj, rows)                                                               \
+  do {                                                                                              \
+    if (tid == 0 && ffgp_trace_buf) {                                                               \
+      ffgp_trace_buf[(size_t)bid * 8 + 4] = ((unsigned long long)(unsigned)(ti) << 32) | (unsigned)(tj); \
+      ffgp_trace_buf[(size_t)bid * 8 + 5] = (unsigned long long)(rows);                             \
+    }                                                                                               \
+  } while (0)
 #else
 #define FFGP_TRACE(slot)
+#define FFGP_TRACE_TILE(ti, tj, rows)
 #endif
 
 // Tile geometry: TS x TS output tile per 256-thread workgroup, 4 waves as 2 x 2, each wave (TS/2) x (TS/2)
@@ -353,12 +362,21 @@ __device__ __forceinline__ void gload_buf(__amdgpu_buffer_rsrc_t r, const unsign
   for (int i = 0; i < Geo<TS>::NLD; ++i) v[i] = __builtin_bit_cast(d2_t, (gemm_v4u)__builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[i], 0, 0));
 }
 
-template <int OPA, int OPB, bool NEG>
+//
+// DIAG = true is the diagonal tile of a lower-mode launch (ti == tj) on the same loop.  Its values must be the general tile's, which
+// start every accumulator from zero and combine alpha * acc + beta * C once at the end (the interior form above accumulates onto C
+// and rounds differently), so it is instantiated without the negate-A modifier, `load_c` is false, and its own epilogue stores only
+// where col <= row.  The wave of the strictly-upper quadrant (wm = 0, wn = 1) takes part in the loads, the LDS stores and the barriers
+// but issues no MFMA and stores nothing.  DIAG = false compiles to the loop it was before the parameter existed.
+template <int OPA, int OPB, bool NEG, bool DIAG = false>
 __device__ __forceinline__ void gemm_tile_fast128(const char* __restrict__ baseA, const char* __restrict__ baseB, size_t stepA, size_t stepB,
                                                   char* __restrict__ baseC, size_t row4_bytes, unsigned voffC, bool load_c, double* smem,
                                                   int nkt, int tid, const unsigned (&voffA)[4], const unsigned (&voffB)[4],
-                                                  const int (&offA)[4], const int (&offB)[4], int trace_bid) {
+                                                  const int (&offA)[4], const int (&offB)[4], int trace_bid, double alpha = 0.0,
+                                                  double beta = 0.0) {
   constexpr int TS = 128, W = 4;
+  const int wave_d = DIAG ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;      // (wm, wn) = (wave >> 1, wave & 1)
+  const bool mma = !DIAG || wave_d != 1;
   constexpr int BUFA = opbuf<OPA, TS>(), BUFB = opbuf<OPB, TS>(), STAGE = BUFA + BUFB;
   constexpr int subA = (OPA == OP_KMAJOR) ? 256 : 16;
   constexpr int subB = (OPB == OP_KMAJOR) ? 256 : 16;
@@ -371,9 +389,11 @@ __device__ __forceinline__ void gemm_tile_fast128(const char* __restrict__ baseA
   } while (0)
 #define GEMM_MFMA(a, b)                                                 \
   do {                                                                  \
-    _Pragma("unroll") for (int i = 0; i < W; ++i)                       \
-      _Pragma("unroll") for (int j = 0; j < W; ++j)                     \
-        acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, NEG ? 1 : 0); /* blgp bit 0: -A */ \
+    if (!DIAG || mma) {                                                 \
+      _Pragma("unroll") for (int i = 0; i < W; ++i)                     \
+        _Pragma("unroll") for (int j = 0; j < W; ++j)                   \
+          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, NEG ? 1 : 0); /* blgp bit 0: -A */ \
+    }                                                                   \
     GEMM_PIN();                                                         \
   } while (0)
   d2_t ra[4], rb[4];
@@ -442,6 +462,47 @@ __device__ __forceinline__ void gemm_tile_fast128(const char* __restrict__ baseA
 #ifdef FFGP_GEMM_TRACE
   if (tid == 0 && ffgp_trace_buf) ffgp_trace_buf[(size_t)trace_bid * 8 + 2] = __builtin_readcyclecounter();
 #endif
+  if constexpr (DIAG) {
+    // alpha * acc + beta * C where col <= row: everything in the wave below the diagonal (wm = 1, wn = 0); in the two waves on it the
+    // 16 x 16 tiles with i > j, and the lanes with row >= col of those with i == j.  (The whole tile is inside C, so the C loads need
+    // no clamp; the 16-row groups are pipelined as in the general epilogue.)
+    if (!mma) return;
+    const bool below = wave_d == 2;
+    const int lrow = (tid & 63) >> 4, lcol = tid & 15;
+    const bool use_c = (beta != 0.0);
+    double cv[2][4][W];
+    auto load_group = [&](int i, double (&dst)[4][W]) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const char* rowb = baseC + (size_t)(i * 4 + r) * row4_bytes;
+#pragma unroll
+        for (int j = 0; j < W; ++j) dst[r][j] = *reinterpret_cast<const double*>(rowb + voffC + j * 128);
+      }
+    };
+    if (use_c) {
+      load_group(0, cv[0]);
+    } else {
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int j = 0; j < W; ++j) cv[b][r][j] = 0.0;
+    }
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+      if (use_c && i + 1 < W) load_group(i + 1, cv[(i + 1) & 1]);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        char* rowb = baseC + (size_t)(i * 4 + r) * row4_bytes;
+#pragma unroll
+        for (int j = 0; j < W; ++j)
+          if (below || i > j || (i == j && 4 * r + lrow >= lcol))
+            *reinterpret_cast<double*>(rowb + voffC + j * 128) = alpha * acc[i][j][r] + beta * cv[i & 1][r][j];
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int i = 0; i < W; ++i)
 #pragma unroll
@@ -501,7 +562,9 @@ __device__ __forceinline__ void gemm_mainloop(const GemmArgs& p, const double* _
 // that a launch can mix shapes (see the split tail in ffgp_gemm_f64).
 template <int OPA, int OPB, int MODE, int TM, int TN>
 __device__ __forceinline__ void gemm_one_tile(const GemmArgs& p, const double* __restrict__ Ag, const double* __restrict__ Bg,
-                                              double* __restrict__ Cg, double* smem, int ti, int tj, const int tid, const int bid) {
+                                              double* __restrict__ Cg, double* smem, int ti, int tj, const int tid, const int bid,
+                                              const bool general = false) {
+  // general: the tile takes the general form even where the fast form would serve (a quarter of a diagonal 128-tile, see gemm_block)
   constexpr int WM = Geo<TM>::WT, WN = Geo<TN>::WT;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -525,7 +588,11 @@ __device__ __forceinline__ void gemm_one_tile(const GemmArgs& p, const double* _
     // (p.pack: the panel of the removed direct form, which took these tiles over -- the launcher always leaves it null)
     if (p.pack && fast_ab && interior && kt0 == 0 && kt1 * BK == p.k && !(MODE == TILES_LOWER && m0 < n0 + TN)) return;
   }
-  if (fast_ab && interior && kt0 < kt1 && !(MODE == TILES_LOWER && m0 < n0 + TN)) {
+  // a lower-mode launch's diagonal tile takes the general form below -- or, in a launch planned with light tiles (GemmArgs::light:
+  // K-major operands, no triangular k ranges), the rotated loop in its DIAG form, which gives the general form's values
+  const bool diag = (MODE == TILES_LOWER && m0 < n0 + TN);
+  constexpr bool DIAG_FAST = (TM == 128 && TN == 128 && MODE == TILES_LOWER && OPA == OP_KMAJOR && OPB == OP_KMAJOR);
+  if (fast_ab && interior && kt0 < kt1 && !general && (!diag || (DIAG_FAST && p.light))) {
     const size_t k0 = (size_t)kt0 * BK;
     const char* bA = reinterpret_cast<const char*>(Ag) +
                      ((OPA == OP_KMAJOR) ? ((size_t)m0 * p.lda + k0) : (k0 * p.lda + m0)) * 8;
@@ -541,6 +608,14 @@ __device__ __forceinline__ void gemm_one_tile(const GemmArgs& p, const double* _
     lane_byte_offsets<OPB, TN>(p.ldb, tid, voffB);
     const unsigned voffC = (unsigned)((wm * (TM / 2) + (lane >> 4)) * p.ldc + wn * (TN / 2) + (lane & 15)) * 8u;
     if constexpr (TM == 128 && TN == 128) {   // the rotated k loop
+      if constexpr (DIAG_FAST) {
+        if (diag) {
+          gemm_tile_fast128<OPA, OPB, false, true>(bA, bB, stepA, stepB, bC, row4, voffC, false, smem, kt1 - kt0, tid, voffA, voffB, offA, offB, bid,
+                                                   p.alpha, p.beta);
+          FFGP_TRACE(3);
+          return;
+        }
+      }
       if (p.alpha < 0.0)
         gemm_tile_fast128<OPA, OPB, true>(bA, bB, stepA, stepB, bC, row4, voffC, p.beta != 0.0, smem, kt1 - kt0, tid, voffA, voffB, offA, offB, bid);
       else
@@ -618,13 +693,128 @@ __device__ __forceinline__ void gemm_one_tile(const GemmArgs& p, const double* _
   FFGP_TRACE(3);
 }
 
-// the work of one workgroup of a GEMM launch: block id -> tile (or quarter tile of the split tail) -> gemm_one_tile
+// ------------------------------------------------------------------------------------------------------------
+// Passenger-row slab.  The likelihood factors [Sigma; Y^T] with its d right-hand sides as extra rows below the matrix, so every
+// trailing update has m = n + d: one more tile row whose 128 x 128 tiles would each run a whole MFMA chain for d of their 128 rows.
+// When that last tile row holds at most 32 rows (gemm_plan: GemmArgs::slab_at) it is covered by light workgroups instead, one per 16
+// rows x 128 columns: its four waves take 32 columns each (1 x 2 MFMA tiles, an eighth of a tile's MFMAs), rows at or beyond m are
+// clamped on load and masked on store.  Per element the arithmetic is the general tile's -- the same v_mfma_f64_16x16x4 chain over k
+// in the same order from a zero accumulator (same LDS images and fragment offsets), then alpha * acc + beta * C -- so the values are
+// its bit for bit.  With 8 MFMAs per wave and k-tile this is a latency shape: PD k-tiles of operands are kept in flight in registers,
+// as the 32-row tiles do.  K-major operands, 16-byte loads, k a multiple of BK, n0 + 128 <= n (all guaranteed by the plan).
+// ------------------------------------------------------------------------------------------------------------
+template <int PD>
+__device__ __forceinline__ void gemm_slab16(const GemmArgs& p, const double* __restrict__ Ag, const double* __restrict__ Bg,
+                                            double* __restrict__ Cg, double* smem, int m0, int n0, const int tid, const int bid) {
+  constexpr int BUFA = 16 * 16, BUFB = opbuf<OP_KMAJOR, 128>(), STAGE = BUFA + BUFB;     // 2 x 18 KiB of the kernel's 64
+  static_assert((PD & 1) == 0, "even prefetch depth: the LDS stage parity is compile-time");
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int offA[4], offB[4];
+  frag_offsets<OP_KMAJOR, 128>(lane, 0, offA);
+  frag_offsets<OP_KMAJOR, 128>(lane, wave * 32, offB);
+  const int nkt = p.k / BK;
+  // A slab: 16 rows x 16 k = 128 16-byte chunks, one per thread of waves 0 and 1; B: the 128-row operand tile of the 128-tiles
+  const bool has_a = wave < 2;
+  const int arow = (tid >> 3) & 15, ach = tid & 7;
+  const char* pA = reinterpret_cast<const char*>(Ag) + ((size_t)min(m0 + arow, p.m - 1) * p.lda + ach * 2) * 8;
+  const int sa = arow * 16 + ((ach ^ ((arow >> 1) & 7)) << 1);
+  const char* pB = reinterpret_cast<const char*>(Bg) + (size_t)n0 * p.ldb * 8;
+  unsigned voffB[4];
+  lane_byte_offsets<OP_KMAJOR, 128>(p.ldb, tid, voffB);
+  constexpr size_t step = (size_t)BK * 8;
+  d2_t ra[PD], rb[PD][4];
+#pragma unroll
+  for (int s = 0; s < PD; ++s) {
+    ra[s] = (d2_t){0.0, 0.0};
+    if (s < nkt) {
+      if (has_a) ra[s] = *reinterpret_cast<const d2_t*>(pA + s * step);
+      gload_fast<128>(pB + s * step, voffB, rb[s]);
+    }
+  }
+  d4_t acc[2];
+  acc[0] = acc[1] = (d4_t){0.0, 0.0, 0.0, 0.0};
+  if (has_a) *reinterpret_cast<d2_t*>(smem + sa) = ra[0];
+  sstore<OP_KMAJOR, 128>(smem + BUFA, tid, rb[0]);
+  __syncthreads();
+  FFGP_TRACE(1);
+  pA += (size_t)PD * step;   // next k-tile to fetch
+  pB += (size_t)PD * step;
+  for (int kt0 = 0; kt0 < nkt; kt0 += PD) {
+#pragma unroll
+    for (int u = 0; u < PD; ++u) {
+      const int kt = kt0 + u;
+      if (kt >= nkt) break;
+      const double* sA = smem + (u & 1) * STAGE;
+      const double* sB = sA + BUFA;
+      if (kt + PD < nkt) {   // slot u was drained into LDS one step ago
+        if (has_a) ra[u] = *reinterpret_cast<const d2_t*>(pA);
+        gload_fast<128>(pB, voffB, rb[u]);
+        pA += step;
+        pB += step;
+      }
+#pragma unroll
+      for (int kq = 0; kq < 4; ++kq) {
+        const double a = sA[offA[kq]];
+        const double b0 = sB[offB[kq]], b1 = sB[offB[kq] + 256];
+        acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc[1], 0, 0, 0);
+      }
+      if (kt + 1 < nkt) {
+        double* dA = smem + ((u & 1) ^ 1) * STAGE;
+        if (has_a) *reinterpret_cast<d2_t*>(dA + sa) = ra[(u + 1) % PD];
+        sstore<OP_KMAJOR, 128>(dA + BUFA, tid, rb[(u + 1) % PD]);
+      }
+      __syncthreads();
+    }
+  }
+  FFGP_TRACE(2);
+  // epilogue: lane holds rows (lane >> 4) + 4r, column lane & 15 of each accumulator tile; the columns are below the diagonal (m0 >= n)
+  const double alpha = p.alpha, beta = p.beta;
+  const bool use_c = (beta != 0.0);
+  const int row0 = m0 + (lane >> 4);
+  const int col0 = n0 + wave * 32 + (lane & 15);
+  double cv[4][2];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int rowc = min(row0 + 4 * r, p.m - 1);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) cv[r][j] = use_c ? Cg[(size_t)rowc * p.ldc + col0 + j * 16] : 0.0;
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = row0 + 4 * r;
+    if (row < p.m) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) Cg[(size_t)row * p.ldc + col0 + j * 16] = alpha * acc[j][r] + beta * cv[r][j];
+    }
+  }
+  FFGP_TRACE(3);
+}
+
+// the work of one workgroup of a GEMM launch: block id -> tile (or quarter tile of the split tail, or passenger-row slab) -> gemm_one_tile
 template <int OPA, int OPB, int MODE, int TM, int TN>
 __device__ __forceinline__ void gemm_block(const GemmArgs& p, const double* __restrict__ Ag, const double* __restrict__ Bg,
                                            double* __restrict__ Cg, double* smem, const int tid, const int bid) {
   // One workgroup per tile.  (A persistent 2-per-CU grid was measured and dropped: it keeps the two workgroups of
   // a CU in lock-step, so their prologues and epilogues coincide instead of hiding under each other's k loop.)
   FFGP_TRACE(0);
+  if constexpr (TM == 128 && TN == 128 && MODE == TILES_LOWER && OPA == OP_KMAJOR && OPB == OP_KMAJOR) {
+    // Passenger-row slabs (gemm_slab16): the launch's tile counts cover the whole 128-row tile rows only, and the rows below them go
+    // to the LAST workgroups of the grid, column tile by column tile.  Not through the XCD remap below: the edge row ends the tile
+    // order, so one XCD would get all of these near-free workgroups, finish early and leave the launch time to the other seven;
+    // here the hardware deals them round-robin, and they start as slots free up under the last round of whole tiles.
+    if (bid >= p.slab_at) {
+      const int s = bid - p.slab_at;
+      const int mw = p.tiles_m * 128;
+      const int per = (p.m - mw + 15) >> 4;      // slabs per column tile (1 or 2)
+      const int tj = __builtin_amdgcn_readfirstlane(s / per);
+      const int sl = __builtin_amdgcn_readfirstlane(s - tj * per);
+      FFGP_TRACE_TILE(p.tiles_m, tj, 16);
+      gemm_slab16<FFGP_PD_SMALL>(p, Ag, Bg, Cg, smem, mw + 16 * sl, tj * 128, tid, bid);
+      return;
+    }
+  }
   if constexpr (TM == 128 && TN == 128) {
     // Split tail: equal-sized tiles finish in rounds of (resident workgroups) and the last round is mostly idle CUs.
     // The launcher may therefore hand the last `split` 128-tiles of the tile order out as quarter tiles (64 x 64), placed
@@ -636,7 +826,11 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& p, const double* __re
       const int ti = __builtin_amdgcn_readfirstlane(2 * Ti + ((q >> 1) & 1));
       const int tj = __builtin_amdgcn_readfirstlane(2 * Tj + (q & 1));
       if (ti * 64 >= p.m || tj * 64 >= p.n || (MODE == TILES_LOWER && tj > ti)) return;
-      gemm_one_tile<OPA, OPB, MODE, 64, 64>(p, Ag, Bg, Cg, smem, ti, tj, tid, bid);
+      FFGP_TRACE_TILE(ti, tj, 64);
+      // The unsplit launch computes a diagonal tile in the general form (zero accumulators, alpha * acc + beta * C once), all four
+      // quadrants of it; its strictly-lower quadrant would take the 64-tile's fast form here, which accumulates onto C and rounds
+      // differently.  It keeps the general form, so that a split launch gives the unsplit launch's values bit for bit.
+      gemm_one_tile<OPA, OPB, MODE, 64, 64>(p, Ag, Bg, Cg, smem, ti, tj, tid, bid, MODE == TILES_LOWER && Ti == Tj);
       return;
     }
   }
@@ -655,6 +849,7 @@ __device__ __forceinline__ void gemm_block(const GemmArgs& p, const double* __re
   // wave-uniform by construction; pin them to SGPRs so every tile base below is scalar arithmetic
   ti = __builtin_amdgcn_readfirstlane(ti);
   tj = __builtin_amdgcn_readfirstlane(tj);
+  FFGP_TRACE_TILE(ti, tj, TM);
   gemm_one_tile<OPA, OPB, MODE, TM, TN>(p, Ag, Bg, Cg, smem, ti, tj, tid, bid);
 }
 
@@ -689,7 +884,7 @@ __global__ __launch_bounds__(256, 2) void ffgp_gemm_f64_rag(GemmRag q) {
   p.m = r.m; p.n = r.n; p.k = r.k;
   p.lda = r.lda; p.ldb = r.ldb; p.ldc = r.ldc;
   p.tiles_m = r.tiles_m; p.tiles_n = r.tiles_n; p.total_tiles = r.total_tiles;
-  p.grid = r.grid; p.split_at = r.split_at;
+  p.grid = r.grid; p.split_at = r.split_at; p.slab_at = r.slab_at; p.light = r.light;
   p.fast = r.fast; p.avec = r.avec; p.bvec = r.bvec;
   gemm_block<OPA, OPB, MODE, TM, TN>(p, p.A, p.B, p.C, smem, tid, blockIdx.x);
 }
@@ -953,6 +1148,26 @@ static int gemm_plan(ffgp_handle* h, int opa, int opb, int mode, int syrk_tag, c
   a.fast = ((alpha == 1.0 || alpha == -1.0) && (beta == 0.0 || beta == 1.0) && (size_t)lda * 8 * 130 < 0xffffffffull &&
             (size_t)ldb * 8 * 130 < 0xffffffffull && (size_t)ldc * 8 * 130 < 0xffffffffull)
                ? 1 : 0;
+  // Light tiles of the symmetric update (option syrk_light_tiles, see gemm_slab16 and gemm_tile_fast128<.., DIAG>): in a 128-tile
+  // lower-mode launch of K-major operands in the fast form, the diagonal tiles take the rotated loop, and a last tile row of r <= 32
+  // rows is planned out of the tile order -- tile counts, XCD remap, bands and split tail are those of m - r rows -- and handed to
+  // slab workgroups at the end of the grid.  r <= 32: a slab is a latency shape and holds its slot for 0.44 of a tile's time at
+  // k = 512 for an eighth of its MFMAs (docs/experiments.md), so two slabs are 0.88 of the edge tile's slot they replace and three
+  // would hold a slot longer than the tile.  In-place and triangular launches, other layouts, k not a multiple of the k-tile and a
+  // partial last COLUMN tile keep the general tiles.  Decided here, per member, so a ragged or batched launch takes every member as
+  // its single call would.
+  a.light = 0;
+  a.slab_at = 0x7fffffff;
+  int slabs = 0;
+  if (h->syrk_light_tiles && tsm == 128 && tsn == 128 && mode == TILES_LOWER && kk && alias == 0 && tri == 0 && dec_batch == 1 && a.fast &&
+      a.avec && a.bvec && k % BK == 0) {
+    a.light = 1;
+    const int r = m % 128;
+    if (r >= 1 && r <= 32 && n % 128 == 0) {      // (m >= n: the m - r whole rows still cover the n columns)
+      a.total_tiles = count_tiles(mode, m - r, n, 128, 128, a.tiles_m, a.tiles_n);
+      slabs = a.tiles_n * ((r + 15) / 16);
+    }
+  }
   a.grid = a.total_tiles;
   a.split_at = 0x7fffffff;
   a.band_log2 = GEMM_BAND_LOG2;
@@ -966,6 +1181,10 @@ static int gemm_plan(ffgp_handle* h, int opa, int opb, int mode, int syrk_tag, c
       a.total_tiles = a.split_at;          // the XCD remap permutes the whole-tile part only
       a.grid = a.split_at + 4 * rem;
     }
+  }
+  if (slabs > 0) {
+    a.slab_at = a.grid;
+    a.grid += slabs;
   }
   // "Polite" trailing update: once the factorisation is bound by its dependency chain (trailing matrix below polite_m
   // rows) the 128-tile SYRK is launched with LDS padding so that only one of its workgroups fits a CU.  Alone it still
@@ -1235,6 +1454,7 @@ int ffgp_gemm_launch_rag(ffgp_handle* h, int mode, int syrk_tag, int R, const Ge
         mm.m = a.m; mm.n = a.n; mm.k = a.k;
         mm.lda = a.lda; mm.ldb = a.ldb; mm.ldc = a.ldc;
         mm.tiles_m = a.tiles_m; mm.tiles_n = a.tiles_n; mm.total_tiles = a.total_tiles; mm.grid = a.grid; mm.split_at = a.split_at;
+        mm.slab_at = a.slab_at; mm.light = a.light;
         mm.fast = a.fast; mm.avec = a.avec; mm.bvec = a.bvec;
         gx = std::max(gx, a.grid);
         flops += 2.0 * (double)a.k * ((double)a.n * ((double)a.n + 1.0) * 0.5 + ((double)a.m - (double)a.n) * (double)a.n);

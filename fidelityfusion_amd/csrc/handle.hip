@@ -200,6 +200,7 @@ int ffgp_create(int device, ffgp_handle** out) {
   h->tile32_threshold = 1024;
   h->polite_m = 6144;
   h->split_rem_max = 180;
+  h->syrk_light_tiles = 1;
   h->super_block = 1024;
   h->splitk_min_k = 1024;
   h->skinny_max_n = 8;
@@ -363,6 +364,7 @@ static const ffgp_option k_options[] = {
     {"lookahead", &ffgp_handle::lookahead, OPT_INT},
     {"polite_m", &ffgp_handle::polite_m, OPT_INT},
     {"split_rem_max", &ffgp_handle::split_rem_max, OPT_INT},
+    {"syrk_light_tiles", &ffgp_handle::syrk_light_tiles, OPT_BOOL},
     {"asm_mm", &ffgp_handle::asm_mm, OPT_INT},
     {"asm_mm_grid", &ffgp_handle::asm_mm_grid, OPT_INT, 1.0},
     {"asm_mm_min", &ffgp_handle::asm_mm_min, OPT_INT},

@@ -204,6 +204,9 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
                         stream's kernels always find free registers and LDS),
             "split_rem_max" (default 180: a 128-tile launch whose tile count leaves a remainder <= this modulo the 256 CUs
                         hands those last tiles out as 64 x 64 quarters -- same bits, a shorter last round; 0 = never),
+            "syrk_light_tiles" (default 1: in the 128-tile symmetric updates a last tile row of at most 32 rows -- the passenger
+                        rows of a likelihood with d <= 32 outputs -- runs as 16-row slabs, and the diagonal tiles run on the fast
+                        tile's k loop without their strictly-upper quadrant -- same bits; 0 = general tiles for both),
             "super_block" / "super_min_n" (default 1024 / 2048: triangular sweeps on factors of at least super_min_n rows go
                         through inverted super_block x super_block diagonal blocks; 0 = always block by block),
             "skinny_max_n" (default 8: products with at most this many output columns run on the matrix-vector kernels; 0 = never),

@@ -4,6 +4,10 @@ Builds fidelityfusion_amd/libffgp_trace.so with -DFFGP_GEMM_TRACE (every workgro
 first operand tile in LDS, end of the k loop, end of the epilogue), runs one launch and prints where a tile's
 wall time goes.      python tools/trace_gemm.py build      (here, cross-compile)
                      python tools/trace_gemm.py run [syrk|gemm] [m] [k] [slots]   (on the GPU box)
+                     python tools/trace_gemm.py classes [n] [r] [k] [reps] [syrk_light_tiles]
+                         lower-mode launch with m = n + r, tile forced to 128: k-loop and whole-tile cycles per tile class
+                         (interior / diagonal / last-row edge tile, 16-row slab of the passenger rows)
+FFGP_TRACE_SO names another trace library (a build of another commit).
 """
 import ctypes as C
 import os
@@ -12,7 +16,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "fidelityfusion_amd", "csrc")
-SO = os.path.join(ROOT, "fidelityfusion_amd", "libffgp_trace.so")
+SO = os.environ.get("FFGP_TRACE_SO") or os.path.join(ROOT, "fidelityfusion_amd", "libffgp_trace.so")
 
 
 def build():
@@ -108,9 +112,60 @@ def run(kind="syrk", m=16384, k=512, slots=0):
         print("    tile %5d: %8.1f %8.1f %8.1f %8.1f" % (i, start[i], kl0[i], kl1[i], end[i]))
 
 
+def classes(n=8192, r=1, k=512, reps=3, light=-1):
+    import numpy as np
+    import torch
+    lib = C.CDLL(SO)
+    h = C.c_void_p()
+    assert lib.ffgp_create(0, C.byref(h)) == 0
+    lib.ffgp_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
+    lib.ffgp_gemm.argtypes = [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                             C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
+    assert lib.ffgp_set_option(h, b"gemm_tile", 128.0) == 0
+    if light >= 0:      # (a library from before the option exists refuses the key: its path is the old one)
+        assert lib.ffgp_set_option(h, b"syrk_light_tiles", float(light)) == 0
+    m = n + r
+    dev = "cuda:0"
+    A = torch.rand((m, k), device=dev, dtype=torch.float64) - 0.5
+    Cm = torch.zeros((m, n), device=dev, dtype=torch.float64)
+    tn = n // 128
+    rows = tn * (tn + 1) // 2 + 9 * tn      # whole tiles + an edge row of tiles or its slabs
+    buf = torch.zeros((rows, 8), device=dev, dtype=torch.int64)
+
+    def launch():
+        return lib.ffgp_gemm(h, 0, 0, 1, 0, A.data_ptr(), k, A.data_ptr(), k, Cm.data_ptr(), n, m, n, k, -1.0, 1.0)
+    for _ in range(2):
+        assert launch() == 0
+    torch.cuda.synchronize()
+    print("classes: n=%d m=%d k=%d syrk_light_tiles=%d lib=%s" % (n, m, k, light, os.path.basename(SO)))
+    for rep in range(reps):
+        buf.zero_()
+        torch.cuda.synchronize()
+        assert lib.ffgp_debug_set_trace(C.c_void_p(buf.data_ptr())) == 0
+        launch()
+        torch.cuda.synchronize()
+        lib.ffgp_debug_set_trace(None)
+        t = buf.cpu().numpy()
+        t = t[t[:, 3] != 0]
+        ti, tj, ext = t[:, 4] >> 32, t[:, 4] & 0xffffffff, t[:, 5]
+        wall = t[:, 7].astype(np.float64) / 100.0
+        kloop, whole = t[:, 2] - t[:, 1], t[:, 3] - t[:, 0]
+        cls = {"interior": (ext == 128) & (ti > tj) & (ti < tn), "diagonal": (ext == 128) & (ti == tj),
+               "edge": (ext == 128) & (ti >= tn), "slab16": ext == 16}
+        line = ["rep %d: workgroups %d, launch span %.1f us" % (rep, len(t), wall.max() - wall.min())]
+        for name, sel in cls.items():
+            if sel.any():      # (the general tile has no stamp 1: its figure is tile start -> end of the k loop, prologue included)
+                kl = np.where(t[sel, 1] != 0, kloop[sel], t[sel, 2] - t[sel, 0])
+                line.append("%s n=%d k-loop%s p50 %d whole p50 %d" % (name, sel.sum(), "" if (t[sel, 1] != 0).all() else "+prologue",
+                                                                      np.median(kl), np.median(whole[sel])))
+        print(" ; ".join(line))
+
+
 if __name__ == "__main__":
     if sys.argv[1] == "build":
         build()
+    elif sys.argv[1] == "classes":
+        classes(*[int(x) for x in sys.argv[2:]])
     else:
         a = sys.argv[2:]
         run(a[0] if a else "syrk", int(a[1]) if len(a) > 1 else 16384, int(a[2]) if len(a) > 2 else 512,
