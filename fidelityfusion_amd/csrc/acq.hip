@@ -14,28 +14,21 @@
 //   5. torch.optim.Adam's update (ffgp_adam_update) by the thread that owns (j, dim): x, exp_avg and exp_avg_sq live in its registers
 //      for the whole call
 // Nothing of a point's arithmetic depends on its column or tile: a point run alone follows the same trajectory bit for bit.
+// The load, the reductions, stages 2 and 3, the acquisition value, the owner's prologue, step and write-back and the launch are
+// acq_tile.h's, one copy for this kernel and its three descendants; stage 1 and the gradient pass are written out here.
 #include "acq_tile.h"
 
+// the one posterior as a stack member (its two coefficients are not read) and the loop's arguments
 struct AcqArgs {
-  const double* X;       // [n, D]
-  const double* Linv;    // [np, ldx], zero above the diagonal and in the padding
-  const double* alpha;   // [n]
-  const double* w;       // [D]
-  const double* amp;
-  const double* bc;      // [2 steps] bias corrections
-  double* Xq;            // [Q, D]
-  double* state;         // [2, Q, D] or null (evaluate mode)
-  double* trace;         // [max(steps, 1), Q]
-  double* hist;          // [steps + 1, Q, D] or null
-  double* grad;          // [Q, D] or null
-  int n, np, D, ldx, Q, steps, kfun, acq;
-  double clamp, rinv, var_add, var_floor, kappa, xi, f_best, lr, b1, b2, eps;
+  AcqStackMember m;
+  AcqLoop c;
 };
 
 template <int DM>
 __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
   extern __shared__ double acq_lds[];
-  const int np = a.np, nb = np >> 4, n = a.n, D = a.D;
+  const AcqLoop& c = a.c;
+  const int np = a.m.np, nb = np >> 4, n = a.m.n;
   const size_t img = (size_t)np * 16;
   double* img0 = acq_lds;                                              // K_s, then B = Sigma^-1 K_s
   double* img1 = img0 + img;                                           // V = L^-1 K_s, then the gradient partials
@@ -47,38 +40,15 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
   double* redm = w2 + DM;
   double* redv = redm + 256;
 
-  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4, wave = tid >> 6, lane = tid & 63, g = lane >> 4;
-  const int q0 = blockIdx.x * ACQ_TILE;
-  const double amp = a.amp[0];
+  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4;
+  const double amp = a.m.amp[0];
 
-  for (int idx = tid; idx < np * DM; idx += ACQ_T) {
-    const int i = idx / DM, dd = idx % DM;
-    Xs[idx] = (i < n && dd < D) ? a.X[(size_t)i * D + dd] : 0.0;
-  }
-  for (int i = tid; i < np; i += ACQ_T) al[i] = (i < n) ? a.alpha[i] : 0.0;
-  if (tid < DM) {
-    const double wv = (tid < D) ? a.w[tid] : 0.0;
-    w2[tid] = wv * wv;
-  }
-  // the owner of (point j, dimension rg) keeps that coordinate and its Adam moments in registers for the whole call; the columns of a
-  // ragged last tile repeat the last point and write nothing
-  const int qo = q0 + j;
-  const bool owner = rg < DM, live = owner && rg < D && qo < a.Q;
-  double xo = 0.0, mo = 0.0, vo = 0.0;
-  if (owner) {
-    const size_t e = (size_t)min(qo, a.Q - 1) * D + rg;
-    if (rg < D) {
-      xo = a.Xq[e];
-      if (a.steps > 0) {
-        mo = a.state[e];
-        vo = a.state[(size_t)a.Q * D + e];
-      }
-    }
-    xq[j * DM + rg] = xo;
-  }
+  acq_load_rows<DM>(Xs, al, a.m.X, a.m.alpha, n, np, c.D, tid);
+  acq_load_w2<DM>(w2, a.m.w, c.D, tid);
+  AcqOwner o = acq_owner_load<DM>(c, xq, tid);
   __syncthreads();
 
-  const int iters = a.steps > 0 ? a.steps : 1;
+  const int iters = c.steps > 0 ? c.steps : 1;
   for (int k = 0; k < iters; ++k) {
     // ---- 1. K_s, derivative factors, mean
     double xj[DM];
@@ -87,69 +57,23 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
     double msum = 0.0;
     for (int p = 0; p < nb; ++p) {
       const int i = 16 * p + rg;
-      double s = 0.0;
-#pragma unroll
-      for (int dd = 0; dd < DM; ++dd) {
-        const double df = Xs[i * DM + dd] - xj[dd];
-        s = __builtin_fma(w2[dd] * df, df, s);
-      }
-      const double sc = fmax(s, a.clamp);
+      const double s = acq_sqdist<DM>(Xs + i * DM, xj, w2);
+      const double sc = fmax(s, a.m.clamp);
       const bool in = i < n;
-      const double kv = in ? amp * ffgp_kfun_val(a.kfun, a.rinv, sc) : 0.0;
+      const double kv = in ? amp * ffgp_kfun_val(a.m.kfun, a.m.rinv, sc) : 0.0;
       img0[i * 16 + j] = kv;
-      img2[i * 16 + j] = (in && s >= a.clamp) ? amp * ffgp_kfun_m2d(a.kfun, a.rinv, sc) : 0.0;
+      img2[i * 16 + j] = (in && s >= a.m.clamp) ? amp * ffgp_kfun_m2d(a.m.kfun, a.m.rinv, sc) : 0.0;
       msum = __builtin_fma(kv, al[i], msum);
     }
-    redm[rg * 16 + j] = msum;
-    __syncthreads();
-    double mean = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mean += redm[r * 16 + j];
+    const double mean = acq_rowgroup_sum(redm, msum, rg, j);
 
-    // ---- 2. V = L^-1 K_s, |V_j|^2
-    double vvp = 0.0;
-    for (int q = 0; q < 4; ++q) {
-      const int bi = acq_deal(q, wave);
-      if (bi >= nb) continue;
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
-      acq_chain<false>(acc, 0, bi + 1, a.Linv, bi, a.ldx, img0, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        img1[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-        vvp = __builtin_fma(acc[r], acc[r], vvp);
-      }
-    }
-    redv[rg * 16 + j] = vvp;
-    __syncthreads();
-    double vv = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) vv += redv[r * 16 + j];
-
-    // ---- 3. B = L^-T V (into the image of K_s)
-    for (int q = 0; q < 4; ++q) {
-      const int bi = acq_deal(q, wave);
-      if (bi >= nb) continue;
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
-      acq_chain<true>(acc, bi, nb, a.Linv, bi, a.ldx, img1, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) img0[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-    }
+    // ---- 2. V = L^-1 K_s, |V_j|^2;  3. B = L^-T V (into the image of K_s)
+    const double vv = acq_solve_images(a.m.Linv, np, nb, img0, img1, redv, tid);
 
     // ---- 4. the acquisition value and its derivatives with respect to mean and variance
-    const double var = amp - vv + a.var_add;      // phi(0) = 1 for every radial profile
+    const double var = amp - vv + a.m.var_add;      // phi(0) = 1 for every radial profile
     double av, gm, gv;
-    if (a.acq == FFGP_ACQ_UCB) {
-      const double sd = sqrt(fmax(var, a.var_floor));
-      av = mean + a.kappa * sd;
-      gm = 1.0;
-      gv = (var >= a.var_floor) ? a.kappa * 0.5 / sd : 0.0;      // torch's clamp_min: no gradient below the floor
-    } else {
-      const double sd = sqrt(var), s = fmax(sd, 1e-9), u = mean - a.f_best - a.xi, Z = u / s;
-      const double Phi = 0.5 * erfc(-Z * 0.70710678118654752440), phi = exp(-0.5 * Z * Z) * 0.39894228040143267794;
-      av = u * Phi + s * phi;
-      gm = Phi;                                   // Phi and phi are constants of the reference's backward pass: exact all the same
-      gv = (sd >= 1e-9) ? phi * 0.5 / sd : 0.0;
-    }
+    acq_value(c.acq, mean, var, c.var_floor, c.kappa, c.xi, c.f_best, av, gm, gv);
     __syncthreads();
 
     // ---- the input gradient: partial sums over this thread's rows, then over the 16 row groups in a fixed order
@@ -158,8 +82,8 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
     for (int dd = 0; dd < DM; ++dd) ga[dd] = 0.0;
     for (int p = 0; p < nb; ++p) {
       const int i = 16 * p + rg;
-      const double c = -(gm * al[i] - 2.0 * gv * img0[i * 16 + j]);
-      const double wt = c * img2[i * 16 + j];
+      const double ci = -(gm * al[i] - 2.0 * gv * img0[i * 16 + j]);
+      const double wt = ci * img2[i * 16 + j];
 #pragma unroll
       for (int dd = 0; dd < DM; ++dd) ga[dd] = __builtin_fma(wt, xj[dd] - Xs[i * DM + dd], ga[dd]);
     }
@@ -167,55 +91,16 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
     for (int dd = 0; dd < DM; ++dd) img1[(rg * DM + dd) * 16 + j] = ga[dd];
     __syncthreads();
 
-    // ---- 5. outputs and Adam, by the owner of (j, rg)
-    if (owner) {
-      double gsum = 0.0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) gsum += img1[(r * DM + rg) * 16 + j];
-      const double gx = -w2[rg] * gsum;
-      if (live) {
-        const size_t e = (size_t)qo * D + rg;
-        if (rg == 0) a.trace[(size_t)k * a.Q + qo] = av;
-        if (a.hist) a.hist[(size_t)k * a.Q * D + e] = xo;
-        if (a.grad && k == iters - 1) a.grad[e] = gx;
-      }
-      if (a.steps > 0 && rg < D)
-        ffgp_adam_update(&xo, &mo, &vo, gx, a.lr, a.b1, a.b2, a.eps, a.bc[2 * k], a.bc[2 * k + 1]);
-      xq[j * DM + rg] = xo;
-    }
+    // ---- 5. outputs and Adam, by the owner of (j, rg): w^2 is the one kernel's, so it multiplies the row sum
+    if (o.owner) acq_owner_step<DM>(c, o, xq, k, iters, av, -w2[rg] * acq_partial_sum<DM>(img1, rg, j), tid);
     __syncthreads();
   }
-  if (live && a.steps > 0) {
-    const size_t e = (size_t)qo * D + rg;
-    a.Xq[e] = xo;
-    a.state[e] = mo;
-    a.state[(size_t)a.Q * D + e] = vo;
-    if (a.hist) a.hist[(size_t)a.steps * a.Q * D + e] = xo;
-  }
-}
-
-template <int DM>
-static int acq_launch(ffgp_handle* h, const AcqArgs& a, int grid) {
-  const size_t lds = acq_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
-  // set on every call: the attribute belongs to the current device, and a host-side "already set" table would be shared state between
-  // the threads of different handles (a host-side call, nothing is enqueued)
-  FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_acq_kernel<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(ffgp_acq_kernel<DM>, dim3(grid), dim3(ACQ_T), acq_lds_doubles(a.np, DM) * sizeof(double), h->stream, a);
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-  return FFGP_OK;
+  acq_owner_store(c, o, tid);
 }
 
 static int acq_single_launch(ffgp_handle* h, const AcqStackArgs& s, int grid, const ffgp_ktree*) {
-  const AcqStackMember& m = s.m[0];
-  AcqArgs a;
-  a.X = m.X; a.Linv = m.Linv; a.alpha = m.alpha; a.w = m.w; a.amp = m.amp; a.bc = s.bc;
-  a.Xq = s.Xq; a.state = s.state; a.trace = s.trace; a.hist = s.hist; a.grad = s.grad;
-  a.n = m.n; a.np = m.np; a.D = s.D; a.ldx = m.np; a.Q = s.Q; a.steps = s.steps; a.kfun = m.kfun; a.acq = s.acq;
-  a.clamp = m.clamp; a.rinv = m.rinv; a.var_add = m.var_add; a.var_floor = s.var_floor; a.kappa = s.kappa; a.xi = s.xi; a.f_best = s.f_best;
-  a.lr = s.lr; a.b1 = s.b1; a.b2 = s.b2; a.eps = s.eps;
-  if (s.D <= 2) return acq_launch<2>(h, a, grid);
-  if (s.D <= 8) return acq_launch<8>(h, a, grid);
-  return acq_launch<16>(h, a, grid);
+  const AcqArgs a = {s.m[0], s.c};
+  return acq_by_dm(s.c.D, [&](auto dm) { return acq_launch<dm()>(h, ffgp_acq_kernel<dm()>, acq_lds_doubles, a.m.np, a, grid); });
 }
 
 // One posterior is the stack of one member with both coefficients 1, no levels and no accumulation: the checks, the workspace, the

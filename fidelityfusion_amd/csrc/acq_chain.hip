@@ -28,13 +28,6 @@
 
 #include "acq_tile.h"
 
-// a workgroup-uniform value kept in a vector register (acq_stack.hip: the scalar file does not hold the member table's fields)
-template <class T>
-__device__ __forceinline__ T acq_in_vgpr(T x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
 // LDS in doubles, sized by the largest member: two [np][16] images (K_s then B; V, at least 256 DM: it also carries the gradient
 // partials), X [np][DM], alpha [np], the tile's points [16][DM], w^2 [DM], two [16][16] reduction pads, the [F][16] pad of the u's
 static constexpr size_t acq_chain_lds_doubles(int np, int DM) {
@@ -46,7 +39,9 @@ static_assert(acq_chain_lds_doubles(FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D) * sizeof(dou
 template <int DM>
 __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
   extern __shared__ double acq_lds[];
-  const int D = a.D;                                                      // the coordinates of x; members above 0 have D + 1 <= DM inputs
+  AcqLoop c = a.c;
+  acq_park_pointers(c);      // (acq_tile.h: the scalar file does not hold them beside the member table's fields)
+  const int D = c.D;                                                      // the coordinates of x; members above 0 have D + 1 <= DM inputs
   const size_t imgmax = (size_t)a.npmax * 16;
   double* img0 = acq_lds;                                                 // K_s, then B = Sigma^-1 K_s
   double* img1 = img0 + imgmax;                                           // V = L^-1 K_s; after the sweeps the gradient partials
@@ -58,52 +53,28 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
   double* redv = redm + 256;
   double* upad = redv + 256;                                              // [F][16]: u = m_{f-1} per column
 
-  double* const trace = acq_in_vgpr(a.trace);
-  double* const hist = acq_in_vgpr(a.hist);
-  double* const grad = acq_in_vgpr(a.grad);
-  double* const state = acq_in_vgpr(a.state);
-  double* const Xq = acq_in_vgpr(a.Xq);
-  const double* const bc = acq_in_vgpr(a.bc);
-
-  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4, wave = tid >> 6, lane = tid & 63, g = lane >> 4;
+  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4;
   const int q0 = blockIdx.x * ACQ_TILE;
   // this column's level, the number of members the tile needs and the set of levels its columns stop at: the same for every thread
   // of the workgroup (the columns of a ragged last tile repeat the last point).  A negative level matches no member: value 0, gradient 0
   int lev = a.F - 1, fcount = a.F;
   unsigned tops = 1u << (a.F - 1);
-  if (a.level) {
-    lev = min(a.level[min(q0 + j, a.Q - 1)], a.F - 1);
+  if (c.level) {
+    lev = min(c.level[min(q0 + j, c.Q - 1)], a.F - 1);
     int top = -1;
     tops = 0u;
-    for (int c = 0; c < ACQ_TILE; ++c) {
-      const int l = min(a.level[min(q0 + c, a.Q - 1)], a.F - 1);
+    for (int cc = 0; cc < ACQ_TILE; ++cc) {
+      const int l = min(c.level[min(q0 + cc, c.Q - 1)], a.F - 1);
       top = max(top, l);
       if (l >= 0) tops |= 1u << l;
     }
     fcount = top + 1;
   }
-  // the owner of (point j, dimension rg) keeps that coordinate, its Adam moments and its gradient accumulator in registers
-  const int qo = q0 + j;
-  const bool owner = rg < DM, live = owner && rg < D && qo < a.Q;
-  const size_t plane = (size_t)a.Q * D;
-  double xo = 0.0, mo = 0.0, vo = 0.0, go = 0.0;
-  if (owner) {
-    const size_t e = (size_t)min(qo, a.Q - 1) * D + rg;
-    if (rg < D) {
-      xo = Xq[e];
-      if (a.steps > 0) {
-        mo = state[e];
-        vo = state[plane + e];
-        if (a.accumulate) go = state[2 * plane + e];
-      }
-    }
-    xq[j * DM + rg] = xo;
-  }
+  AcqOwner o = acq_owner_load<DM>(c, xq, tid);
   __syncthreads();
+  acq_park_constants(c);
 
-  const double var_floor = acq_in_vgpr(a.var_floor), kappa = acq_in_vgpr(a.kappa), xi = acq_in_vgpr(a.xi), f_best = acq_in_vgpr(a.f_best);
-  const double lr = acq_in_vgpr(a.lr), b1 = acq_in_vgpr(a.b1), b2 = acq_in_vgpr(a.b2), eps = acq_in_vgpr(a.eps);
-  const int iters = a.steps > 0 ? a.steps : 1;
+  const int iters = c.steps > 0 ? c.steps : 1;
   for (int k = 0; k < iters; ++k) {
     double xj[DM], G[DM];
 #pragma unroll
@@ -125,15 +96,8 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
 
       // ---- 0. this member's X, alpha, w^2 (the previous pass has to be done with them)
       __syncthreads();
-      for (int idx = tid; idx < np * DM; idx += ACQ_T) {
-        const int i = idx / DM, dd = idx % DM;
-        Xs[idx] = (i < n && dd < Df) ? mX[(size_t)i * Df + dd] : 0.0;
-      }
-      for (int i = tid; i < np; i += ACQ_T) al[i] = (i < n) ? malpha[i] : 0.0;
-      if (tid < DM) {
-        const double wv = (tid < Df) ? mw[tid] : 0.0;
-        w2[tid] = wv * wv;
-      }
+      acq_load_rows<DM>(Xs, al, mX, malpha, n, np, Df, tid);
+      acq_load_w2<DM>(w2, mw, Df, tid);
       if (fwd) {
         if (rg == 0) upad[f * 16 + j] = u;
       } else {
@@ -151,74 +115,23 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
         double msum = 0.0;
         for (int p = 0; p < nb; ++p) {
           const int i = 16 * p + rg;
-          double s = 0.0;
-#pragma unroll
-          for (int dd = 0; dd < DM; ++dd) {
-            const double df = Xs[i * DM + dd] - xj[dd];
-            s = __builtin_fma(w2[dd] * df, df, s);
-          }
+          const double s = acq_sqdist<DM>(Xs + i * DM, xj, w2);
           const double kv = (i < n) ? amp * ffgp_kfun_val(kfun, rinv, fmax(s, clamp)) : 0.0;
           img0[i * 16 + j] = kv;
           msum = __builtin_fma(kv, al[i], msum);
         }
-        redm[rg * 16 + j] = msum;
-        __syncthreads();
-        double mf = 0.0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) mf += redm[r * 16 + j];
+        const double mf = acq_rowgroup_sum(redm, msum, rg, j);
         u = mf;      // the next member's last input
         if (!((tops >> f) & 1u)) continue;      // no column of the tile stops here: the chains are not needed
 
-        // ---- 2. V = L^-1 K_s, |V_j|^2
-        double vvp = 0.0;
-        for (int q = 0; q < 4; ++q) {
-          const int bi = acq_deal(q, wave);
-          if (bi >= nb) continue;
-          d4_t acc = {0.0, 0.0, 0.0, 0.0};
-          acq_chain<false>(acc, 0, bi + 1, mb.Linv, bi, np, img0, lane);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            img1[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-            vvp = __builtin_fma(acc[r], acc[r], vvp);
-          }
-        }
-        redv[rg * 16 + j] = vvp;
-        __syncthreads();
-        double vv = 0.0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) vv += redv[r * 16 + j];
-
-        // ---- 3. B = L^-T V (into the image of K_s)
-        for (int q = 0; q < 4; ++q) {
-          const int bi = acq_deal(q, wave);
-          if (bi >= nb) continue;
-          d4_t acc = {0.0, 0.0, 0.0, 0.0};
-          acq_chain<true>(acc, bi, nb, mb.Linv, bi, np, img1, lane);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) img0[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-        }
+        // ---- 2. V = L^-1 K_s, |V_j|^2;  3. B = L^-T V (into the image of K_s)
+        const double vv = acq_solve_images(mb.Linv, np, nb, img0, img1, redv, tid);
         __syncthreads();
 
         // ---- 4. the acquisition value and its derivatives with respect to mean and variance, for the columns that stop here
         on = lev == f;
-        const double mean = mf, var = amp - vv + vadd;      // phi(0) = 1 for every radial profile
         double avf;
-        if (a.acq == FFGP_ACQ_UCB) {
-          const double sd = sqrt(fmax(var, var_floor));
-          avf = mean + kappa * sd;
-          gm = 1.0;
-          gv = (var >= var_floor) ? kappa * 0.5 / sd : 0.0;      // torch's clamp_min: no gradient below the floor
-        } else if (a.acq == FFGP_ACQ_UCB_VAR) {
-          avf = mean + kappa * var;
-          gm = 1.0;
-          gv = kappa;
-        } else {
-          const double sd = sqrt(var), s = fmax(sd, 1e-9), uu = mean - f_best - xi, Z = uu / s;
-          const double Phi = 0.5 * erfc(-Z * 0.70710678118654752440), phi = exp(-0.5 * Z * Z) * 0.39894228040143267794;
-          avf = uu * Phi + s * phi;
-          gm = Phi;                                   // Phi and phi are constants of the reference's backward pass: exact all the same
-          gv = (sd >= 1e-9) ? phi * 0.5 / sd : 0.0;
-        }
+        acq_value(c.acq, mf, amp - vv + vadd, c.var_floor, c.kappa, c.xi, c.f_best, avf, gm, gv);      // phi(0) = 1 for every radial profile
         av = on ? avf : av;
       } else {
         on = lev > f;
@@ -228,12 +141,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
       double gua = 0.0;
       for (int p = 0; p < nb; ++p) {
         const int i = 16 * p + rg;
-        double s = 0.0;
-#pragma unroll
-        for (int dd = 0; dd < DM; ++dd) {
-          const double df = Xs[i * DM + dd] - xj[dd];
-          s = __builtin_fma(w2[dd] * df, df, s);
-        }
+        const double s = acq_sqdist<DM>(Xs + i * DM, xj, w2);
         const double dk = (i < n && s >= clamp) ? amp * ffgp_kfun_m2d(kfun, rinv, fmax(s, clamp)) : 0.0;
         const double up = fwd ? gm * al[i] - 2.0 * gv * img0[i * 16 + j] : -gu * al[i];
         const double ci = on ? up * dk : 0.0;      // a select, not a product: a switched-off column may carry anything
@@ -245,11 +153,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
         }
       }
       if (f > 0) {      // d(-a)/dm_{f-1}: the u part, over the 16 row groups in a fixed order
-        redm[rg * 16 + j] = gua;
-        __syncthreads();
-        double gs = 0.0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gs += redm[r * 16 + j];
+        const double gs = acq_rowgroup_sum(redm, gua, rg, j);
         gu = on ? gs : gu;
       }
     }
@@ -260,52 +164,15 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
     __syncthreads();
 
     // ---- outputs and Adam, by the owner of (j, rg)
-    if (owner) {
-      double gx = 0.0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) gx += img1[(r * DM + rg) * 16 + j];
-      if (live) {
-        const size_t e = (size_t)qo * D + rg;
-        if (rg == 0) trace[(size_t)k * a.Q + qo] = av;
-        if (hist) hist[(size_t)k * a.Q * D + e] = xo;
-        if (grad && k == iters - 1) grad[e] = gx;
-      }
-      if (a.steps > 0 && rg < D) {
-        if (a.accumulate) {
-          go += gx;
-          gx = go;
-        }
-        ffgp_adam_update(&xo, &mo, &vo, gx, lr, b1, b2, eps, bc[2 * k], bc[2 * k + 1]);
-      }
-      xq[j * DM + rg] = xo;
-    }
+    if (o.owner) acq_owner_step<DM>(c, o, xq, k, iters, av, acq_partial_sum<DM>(img1, rg, j), tid);
     __syncthreads();
   }
-  if (live && a.steps > 0) {
-    const size_t e = (size_t)qo * D + rg;
-    Xq[e] = xo;
-    state[e] = mo;
-    state[plane + e] = vo;
-    if (a.accumulate) state[2 * plane + e] = go;
-    if (hist) hist[(size_t)a.steps * a.Q * D + e] = xo;
-  }
-}
-
-template <int DM>
-static int acq_chain_launch(ffgp_handle* h, const AcqStackArgs& a, int grid) {
-  const size_t lds = acq_chain_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
-  // set on every call, as acq.hip does: the attribute belongs to the current device
-  FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_chain_acq_kernel<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(ffgp_chain_acq_kernel<DM>, dim3(grid), dim3(ACQ_T), acq_chain_lds_doubles(a.npmax, DM) * sizeof(double), h->stream, a);
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-  return FFGP_OK;
+  acq_owner_store(c, o, tid);
 }
 
 // the template is chosen on D + 1, the upper members' input dimension (acq_run has checked D <= FFGP_ACQ_MAX_D - 1)
 static int acq_chain_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree*) {
-  if (a.D + 1 <= 2) return acq_chain_launch<2>(h, a, grid);
-  if (a.D + 1 <= 8) return acq_chain_launch<8>(h, a, grid);
-  return acq_chain_launch<16>(h, a, grid);
+  return acq_by_dm(a.c.D + 1, [&](auto dm) { return acq_launch<dm()>(h, ffgp_chain_acq_kernel<dm()>, acq_chain_lds_doubles, a.npmax, a, grid); });
 }
 
 // The coefficients are checked here (reserved: a chain member has no weight of its own); everything else is the stack entry's driver

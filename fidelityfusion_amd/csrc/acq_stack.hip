@@ -8,6 +8,7 @@
 //   0. X_f, alpha_f and w_f^2 are reloaded into LDS (at most 32 KiB from L2, against ~256 KiB of L_f^-1 traffic for the same member),
 //      every row up to np_f written: a member smaller than its predecessor must not see the predecessor's rows
 //   1.-3. K_s, the derivative factors, mean_f, V = L_f^-1 K_s, |V_j|^2, B = L_f^-T V: acq.hip's stages on images of np_f rows
+//         (the load, the reductions, stages 2 and 3, the acquisition value and the owner's step are acq_tile.h's, one copy for all four kernels)
 //   4. mean += on c_f mean_f, var += on c'_f (amp_f - |V_j|^2 + var_add_f), on = (f <= level_j) as an exact 0 / 1 factor, and the two
 //      running gradient partials over this thread's rows,
 //          Gm += on c_f  w_f^2 o sum_i alpha_i amp (-2 phi') (x_j - X_i),    Gv += on c'_f w_f^2 o sum_i B_i amp (-2 phi') (x_j - X_i)
@@ -22,18 +23,12 @@
 
 #include "acq_tile.h"
 
-// A workgroup-uniform value kept in a vector register: the member table's fields on top of acq.hip's arguments are more uniform
-// values than the scalar file holds, and the vector file has the room (a scalar spill would cost the kernel a private segment).
-template <class T>
-__device__ __forceinline__ T acq_in_vgpr(T x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
 template <int DM>
 __global__ __launch_bounds__(ACQ_T) void ffgp_stack_acq_kernel(AcqStackArgs a) {
   extern __shared__ double acq_lds[];
-  const int D = a.D;
+  AcqLoop c = a.c;
+  acq_park_pointers(c);      // (acq_tile.h: the scalar file does not hold them beside the member table's fields)
+  const int D = c.D;
   const size_t imgmax = (size_t)a.npmax * 16;
   double* img0 = acq_lds;                                                 // K_s, then B = Sigma^-1 K_s
   double* img1 = img0 + imgmax;                                           // V = L^-1 K_s; after the members the gradient partials
@@ -45,46 +40,22 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_stack_acq_kernel(AcqStackArgs a) {
   double* redm = w2 + DM;
   double* redv = redm + 256;
 
-  double* const trace = acq_in_vgpr(a.trace);
-  double* const hist = acq_in_vgpr(a.hist);
-  double* const grad = acq_in_vgpr(a.grad);
-  double* const state = acq_in_vgpr(a.state);
-  double* const Xq = acq_in_vgpr(a.Xq);
-  const double* const bc = acq_in_vgpr(a.bc);
-
-  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4, wave = tid >> 6, lane = tid & 63, g = lane >> 4;
+  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4;
   const int q0 = blockIdx.x * ACQ_TILE;
   // this column's level, and the number of members the tile needs: the same for every thread of the workgroup (the columns of a
   // ragged last tile repeat the last point)
   int lev = a.F - 1, fcount = a.F;
-  if (a.level) {
-    lev = min(a.level[min(q0 + j, a.Q - 1)], a.F - 1);
+  if (c.level) {
+    lev = min(c.level[min(q0 + j, c.Q - 1)], a.F - 1);
     int top = -1;
-    for (int c = 0; c < ACQ_TILE; ++c) top = max(top, a.level[min(q0 + c, a.Q - 1)]);
+    for (int cc = 0; cc < ACQ_TILE; ++cc) top = max(top, c.level[min(q0 + cc, c.Q - 1)]);
     fcount = min(top, a.F - 1) + 1;
   }
-  // the owner of (point j, dimension rg) keeps that coordinate, its Adam moments and its gradient accumulator in registers
-  const int qo = q0 + j;
-  const bool owner = rg < DM, live = owner && rg < D && qo < a.Q;
-  const size_t plane = (size_t)a.Q * D;
-  double xo = 0.0, mo = 0.0, vo = 0.0, go = 0.0;
-  if (owner) {
-    const size_t e = (size_t)min(qo, a.Q - 1) * D + rg;
-    if (rg < D) {
-      xo = Xq[e];
-      if (a.steps > 0) {
-        mo = state[e];
-        vo = state[plane + e];
-        if (a.accumulate) go = state[2 * plane + e];
-      }
-    }
-    xq[j * DM + rg] = xo;
-  }
+  AcqOwner o = acq_owner_load<DM>(c, xq, tid);
   __syncthreads();
+  acq_park_constants(c);
 
-  const double var_floor = acq_in_vgpr(a.var_floor), kappa = acq_in_vgpr(a.kappa), xi = acq_in_vgpr(a.xi), f_best = acq_in_vgpr(a.f_best);
-  const double lr = acq_in_vgpr(a.lr), b1 = acq_in_vgpr(a.b1), b2 = acq_in_vgpr(a.b2), eps = acq_in_vgpr(a.eps);
-  const int iters = a.steps > 0 ? a.steps : 1;
+  const int iters = c.steps > 0 ? c.steps : 1;
   for (int k = 0; k < iters; ++k) {
     double xj[DM], Gm[DM], Gv[DM];
 #pragma unroll
@@ -106,27 +77,15 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_stack_acq_kernel(AcqStackArgs a) {
 
       // ---- 0. this member's X, alpha, w^2 (the previous member's gradient pass has to be done with them)
       __syncthreads();
-      for (int idx = tid; idx < np * DM; idx += ACQ_T) {
-        const int i = idx / DM, dd = idx % DM;
-        Xs[idx] = (i < n && dd < D) ? mX[(size_t)i * D + dd] : 0.0;
-      }
-      for (int i = tid; i < np; i += ACQ_T) al[i] = (i < n) ? malpha[i] : 0.0;
-      if (tid < DM) {
-        const double wv = (tid < D) ? mw[tid] : 0.0;
-        w2[tid] = wv * wv;
-      }
+      acq_load_rows<DM>(Xs, al, mX, malpha, n, np, D, tid);
+      acq_load_w2<DM>(w2, mw, D, tid);
       __syncthreads();
 
       // ---- 1. K_s, derivative factors, mean_f (every row below np_f is written)
       double msum = 0.0;
       for (int p = 0; p < nb; ++p) {
         const int i = 16 * p + rg;
-        double s = 0.0;
-#pragma unroll
-        for (int dd = 0; dd < DM; ++dd) {
-          const double df = Xs[i * DM + dd] - xj[dd];
-          s = __builtin_fma(w2[dd] * df, df, s);
-        }
+        const double s = acq_sqdist<DM>(Xs + i * DM, xj, w2);
         const double sc = fmax(s, clamp);
         const bool in = i < n;
         const double kv = in ? amp * ffgp_kfun_val(kfun, rinv, sc) : 0.0;
@@ -134,40 +93,10 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_stack_acq_kernel(AcqStackArgs a) {
         img2[i * 16 + j] = (in && s >= clamp) ? amp * ffgp_kfun_m2d(kfun, rinv, sc) : 0.0;
         msum = __builtin_fma(kv, al[i], msum);
       }
-      redm[rg * 16 + j] = msum;
-      __syncthreads();
-      double mf = 0.0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) mf += redm[r * 16 + j];
+      const double mf = acq_rowgroup_sum(redm, msum, rg, j);
 
-      // ---- 2. V = L^-1 K_s, |V_j|^2
-      double vvp = 0.0;
-      for (int q = 0; q < 4; ++q) {
-        const int bi = acq_deal(q, wave);
-        if (bi >= nb) continue;
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-        acq_chain<false>(acc, 0, bi + 1, mb.Linv, bi, np, img0, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          img1[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-          vvp = __builtin_fma(acc[r], acc[r], vvp);
-        }
-      }
-      redv[rg * 16 + j] = vvp;
-      __syncthreads();
-      double vv = 0.0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) vv += redv[r * 16 + j];
-
-      // ---- 3. B = L^-T V (into the image of K_s)
-      for (int q = 0; q < 4; ++q) {
-        const int bi = acq_deal(q, wave);
-        if (bi >= nb) continue;
-        d4_t acc = {0.0, 0.0, 0.0, 0.0};
-        acq_chain<true>(acc, bi, nb, mb.Linv, bi, np, img1, lane);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) img0[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-      }
+      // ---- 2. V = L^-1 K_s, |V_j|^2;  3. B = L^-T V (into the image of K_s)
+      const double vv = acq_solve_images(mb.Linv, np, nb, img0, img1, redv, tid);
       __syncthreads();
 
       // ---- 4. the member's share of mean, variance and the two gradient partials
@@ -188,73 +117,21 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_stack_acq_kernel(AcqStackArgs a) {
 
     // ---- the acquisition value and its derivatives with respect to mean and variance
     double av, gm, gv;
-    if (a.acq == FFGP_ACQ_UCB) {
-      const double sd = sqrt(fmax(var, var_floor));
-      av = mean + kappa * sd;
-      gm = 1.0;
-      gv = (var >= var_floor) ? kappa * 0.5 / sd : 0.0;      // torch's clamp_min: no gradient below the floor
-    } else if (a.acq == FFGP_ACQ_UCB_VAR) {
-      av = mean + kappa * var;
-      gm = 1.0;
-      gv = kappa;
-    } else {
-      const double sd = sqrt(var), s = fmax(sd, 1e-9), u = mean - f_best - xi, Z = u / s;
-      const double Phi = 0.5 * erfc(-Z * 0.70710678118654752440), phi = exp(-0.5 * Z * Z) * 0.39894228040143267794;
-      av = u * Phi + s * phi;
-      gm = Phi;                                   // Phi and phi are constants of the reference's backward pass: exact all the same
-      gv = (sd >= 1e-9) ? phi * 0.5 / sd : 0.0;
-    }
+    acq_value(c.acq, mean, var, c.var_floor, c.kappa, c.xi, c.f_best, av, gm, gv);
     // the last member's V has been read (the barrier after stage 3): its image takes the partials of d(-a)/dx
 #pragma unroll
     for (int dd = 0; dd < DM; ++dd) img1[(rg * DM + dd) * 16 + j] = gm * Gm[dd] - 2.0 * gv * Gv[dd];
     __syncthreads();
 
     // ---- outputs and Adam, by the owner of (j, rg)
-    if (owner) {
-      double gx = 0.0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) gx += img1[(r * DM + rg) * 16 + j];
-      if (live) {
-        const size_t e = (size_t)qo * D + rg;
-        if (rg == 0) trace[(size_t)k * a.Q + qo] = av;
-        if (hist) hist[(size_t)k * a.Q * D + e] = xo;
-        if (grad && k == iters - 1) grad[e] = gx;
-      }
-      if (a.steps > 0 && rg < D) {
-        if (a.accumulate) {
-          go += gx;
-          gx = go;
-        }
-        ffgp_adam_update(&xo, &mo, &vo, gx, lr, b1, b2, eps, bc[2 * k], bc[2 * k + 1]);
-      }
-      xq[j * DM + rg] = xo;
-    }
+    if (o.owner) acq_owner_step<DM>(c, o, xq, k, iters, av, acq_partial_sum<DM>(img1, rg, j), tid);
     __syncthreads();
   }
-  if (live && a.steps > 0) {
-    const size_t e = (size_t)qo * D + rg;
-    Xq[e] = xo;
-    state[e] = mo;
-    state[plane + e] = vo;
-    if (a.accumulate) state[2 * plane + e] = go;
-    if (hist) hist[(size_t)a.steps * a.Q * D + e] = xo;
-  }
-}
-
-template <int DM>
-static int acq_stack_launch(ffgp_handle* h, const AcqStackArgs& a, int grid) {
-  const size_t lds = acq_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
-  // set on every call, as acq.hip does: the attribute belongs to the current device
-  FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_stack_acq_kernel<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(ffgp_stack_acq_kernel<DM>, dim3(grid), dim3(ACQ_T), acq_lds_doubles(a.npmax, DM) * sizeof(double), h->stream, a);
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-  return FFGP_OK;
+  acq_owner_store(c, o, tid);
 }
 
 static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree*) {
-  if (a.D <= 2) return acq_stack_launch<2>(h, a, grid);
-  if (a.D <= 8) return acq_stack_launch<8>(h, a, grid);
-  return acq_stack_launch<16>(h, a, grid);
+  return acq_by_dm(a.c.D, [&](auto dm) { return acq_launch<dm()>(h, ffgp_stack_acq_kernel<dm()>, acq_lds_doubles, a.npmax, a, grid); });
 }
 
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
@@ -313,11 +190,12 @@ int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, doubl
     bc[2 * k + 1] = std::sqrt(1.0 - std::pow(opt->beta2, t));
   }
   FFGP_HIP(hipMemcpyAsync(bc_dev, bc.data(), bc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  a.level = s->level_dev; a.bc = bc_dev;
-  a.Xq = Xq_dev; a.state = state_dev; a.trace = trace_dev; a.hist = hist_dev; a.grad = grad_dev;
-  a.F = F; a.npmax = npmax; a.D = D; a.Q = Q; a.steps = steps; a.acq = s->acq; a.accumulate = s->accumulate_grad ? 1 : 0;
-  a.var_floor = s->var_floor; a.kappa = s->kappa; a.xi = s->xi; a.f_best = s->f_best;
-  a.lr = opt ? opt->lr : 0.0; a.b1 = opt ? opt->beta1 : 0.0; a.b2 = opt ? opt->beta2 : 0.0; a.eps = opt ? opt->eps : 0.0;
+  AcqLoop& c = a.c;
+  c.level = s->level_dev; c.bc = bc_dev;
+  c.Xq = Xq_dev; c.state = state_dev; c.trace = trace_dev; c.hist = hist_dev; c.grad = grad_dev;
+  a.F = F; a.npmax = npmax; c.D = D; c.Q = Q; c.steps = steps; c.acq = s->acq; c.accumulate = s->accumulate_grad ? 1 : 0; c.pad = 0;
+  c.var_floor = s->var_floor; c.kappa = s->kappa; c.xi = s->xi; c.f_best = s->f_best;
+  c.lr = opt ? opt->lr : 0.0; c.b1 = opt ? opt->beta1 : 0.0; c.b2 = opt ? opt->beta2 : 0.0; c.eps = opt ? opt->eps : 0.0;
   const int grid = (Q + ACQ_TILE - 1) / ACQ_TILE;
   FFGP_CHECK(launch(h, a, grid, tree));
   FFGP_HIP(hipStreamSynchronize(h->stream));

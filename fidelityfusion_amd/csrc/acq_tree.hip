@@ -30,18 +30,10 @@ struct AcqTreeLeaf {
   int kfun, pad;
 };
 struct AcqTreeArgs {
-  const double* X;       // [n, D]
-  const double* Linv;    // [np, np], zero above the diagonal and in the padding
-  const double* alpha;   // [n]
-  const double* bc;      // [2 steps] bias corrections
-  double* Xq;            // [Q, D]
-  double* state;         // [2, Q, D] or null (evaluate mode)
-  double* trace;         // [max(steps, 1), Q]
-  double* hist;          // [steps + 1, Q, D] or null
-  double* grad;          // [Q, D] or null
+  AcqStackMember m;      // X, Linv, alpha, n, np, var_add of the one posterior; its kernel is the tree below
+  AcqLoop c;
   AcqTreeLeaf k[ACQ_TREE_MAX];
-  int n, np, D, Q, steps, acq, nl, shape, op[3];
-  double var_add, var_floor, kappa, xi, f_best, lr, b1, b2, eps;
+  int nl, shape, op[3];
 };
 
 // LDS in doubles: two [np][16] images (the second at least 256 DM: it also carries the gradient partials), X [np][DM], alpha [np], the
@@ -56,24 +48,18 @@ static_assert(acq_tree_lds_doubles(FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D) * sizeof(doub
 // a leaf's bilinear form on (training row xr, query point xj): the squared scaled distance, or the scaled dot product about the centre
 template <int DM>
 __device__ __forceinline__ double acq_tree_form(bool lin, const double* xr, const double (&xj)[DM], const double* w2, const double* cen) {
+  if (!lin) return acq_sqdist<DM>(xr, xj, w2);
   double s = 0.0;
-  if (lin) {
 #pragma unroll
-    for (int dd = 0; dd < DM; ++dd) s = __builtin_fma(w2[dd] * (xj[dd] - cen[dd]), xr[dd] - cen[dd], s);
-  } else {
-#pragma unroll
-    for (int dd = 0; dd < DM; ++dd) {
-      const double df = xr[dd] - xj[dd];
-      s = __builtin_fma(w2[dd] * df, df, s);
-    }
-  }
+  for (int dd = 0; dd < DM; ++dd) s = __builtin_fma(w2[dd] * (xj[dd] - cen[dd]), xr[dd] - cen[dd], s);
   return s;
 }
 
 template <int DM>
 __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
   extern __shared__ double acq_lds[];
-  const int np = a.np, nb = np >> 4, n = a.n, D = a.D, nl = a.nl;
+  const AcqLoop& c = a.c;
+  const int np = a.m.np, nb = np >> 4, n = a.m.n, D = c.D, nl = a.nl;
   const size_t img = (size_t)np * 16;
   double* img0 = acq_lds;                                              // K_s, then B = Sigma^-1 K_s
   double* img1 = img0 + img;                                           // V = L^-1 K_s, then the gradient partials
@@ -86,24 +72,16 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
   double* redm = lp + 4 * ACQ_TREE_MAX;
   double* redv = redm + 256;
 
-  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4, wave = tid >> 6, lane = tid & 63, g = lane >> 4;
-  const int q0 = blockIdx.x * ACQ_TILE;
+  const int tid = threadIdx.x, j = tid & 15, rg = tid >> 4;
   bool lin[ACQ_TREE_MAX];
 #pragma unroll
   for (int e = 0; e < ACQ_TREE_MAX; ++e) lin[e] = a.k[e].kfun == FFGP_KFUN_LINEAR;
 
-  for (int idx = tid; idx < np * DM; idx += ACQ_T) {
-    const int i = idx / DM, dd = idx % DM;
-    Xs[idx] = (i < n && dd < D) ? a.X[(size_t)i * D + dd] : 0.0;
-  }
-  for (int i = tid; i < np; i += ACQ_T) al[i] = (i < n) ? a.alpha[i] : 0.0;
+  acq_load_rows<DM>(Xs, al, a.m.X, a.m.alpha, n, np, D, tid);
 #pragma unroll
   for (int e = 0; e < ACQ_TREE_MAX; ++e) {
-    if (e < nl && tid < DM) {
-      const double wv = (tid < D) ? a.k[e].w[tid] : 0.0;
-      w2[e * DM + tid] = wv * wv;
-      cen[e * DM + tid] = (tid < D && lin[e] && a.k[e].center) ? a.k[e].center[tid] : 0.0;
-    }
+    if (e < nl) acq_load_w2<DM>(w2 + e * DM, a.k[e].w, D, tid);
+    if (e < nl && tid < DM) cen[e * DM + tid] = (tid < D && lin[e] && a.k[e].center) ? a.k[e].center[tid] : 0.0;
     if (e < nl && tid == 0) {
       const double amp = a.k[e].amp[0];
       lp[4 * e] = amp;
@@ -112,25 +90,10 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
       lp[4 * e + 3] = lin[e] ? 0.0 : amp * ffgp_kfun_val(a.k[e].kfun, a.k[e].rinv, fmax(0.0, a.k[e].clamp));
     }
   }
-  // the owner of (point j, dimension rg) keeps that coordinate and its Adam moments in registers for the whole call; the columns of a
-  // ragged last tile repeat the last point and write nothing
-  const int qo = q0 + j;
-  const bool owner = rg < DM, live = owner && rg < D && qo < a.Q;
-  double xo = 0.0, mo = 0.0, vo = 0.0;
-  if (owner) {
-    const size_t e = (size_t)min(qo, a.Q - 1) * D + rg;
-    if (rg < D) {
-      xo = a.Xq[e];
-      if (a.steps > 0) {
-        mo = a.state[e];
-        vo = a.state[(size_t)a.Q * D + e];
-      }
-    }
-    xq[j * DM + rg] = xo;
-  }
+  AcqOwner o = acq_owner_load<DM>(c, xq, tid);
   __syncthreads();
 
-  const int iters = a.steps > 0 ? a.steps : 1;
+  const int iters = c.steps > 0 ? c.steps : 1;
   for (int k = 0; k < iters; ++k) {
     // ---- 1. K_s, mean; k(x, x) and its reverse sweep
     double xj[DM];
@@ -152,7 +115,6 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
       img0[i * 16 + j] = kv;
       msum = __builtin_fma(kv, al[i], msum);
     }
-    redm[rg * 16 + j] = msum;
     double sv[ACQ_TREE_MAX], gs[ACQ_TREE_MAX];
 #pragma unroll
     for (int e = 0; e < ACQ_TREE_MAX; ++e) {
@@ -172,55 +134,15 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
     }
     const double kss = ffgp_tree_eval(a, sv);
     ffgp_tree_back(a, sv, gs);
-    __syncthreads();
-    double mean = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) mean += redm[r * 16 + j];
+    const double mean = acq_rowgroup_sum(redm, msum, rg, j);
 
-    // ---- 2. V = L^-1 K_s, |V_j|^2
-    double vvp = 0.0;
-    for (int q = 0; q < 4; ++q) {
-      const int bi = acq_deal(q, wave);
-      if (bi >= nb) continue;
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
-      acq_chain<false>(acc, 0, bi + 1, a.Linv, bi, np, img0, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        img1[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-        vvp = __builtin_fma(acc[r], acc[r], vvp);
-      }
-    }
-    redv[rg * 16 + j] = vvp;
-    __syncthreads();
-    double vv = 0.0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) vv += redv[r * 16 + j];
-
-    // ---- 3. B = L^-T V (into the image of K_s)
-    for (int q = 0; q < 4; ++q) {
-      const int bi = acq_deal(q, wave);
-      if (bi >= nb) continue;
-      d4_t acc = {0.0, 0.0, 0.0, 0.0};
-      acq_chain<true>(acc, bi, nb, a.Linv, bi, np, img1, lane);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) img0[(16 * bi + g + 4 * r) * 16 + j] = acc[r];
-    }
+    // ---- 2. V = L^-1 K_s, |V_j|^2;  3. B = L^-T V (into the image of K_s)
+    const double vv = acq_solve_images(a.m.Linv, np, nb, img0, img1, redv, tid);
 
     // ---- 4. the acquisition value and its derivatives with respect to mean and variance
-    const double var = kss - vv + a.var_add;
+    const double var = kss - vv + a.m.var_add;
     double av, gm, gv;
-    if (a.acq == FFGP_ACQ_UCB) {
-      const double sd = sqrt(fmax(var, a.var_floor));
-      av = mean + a.kappa * sd;
-      gm = 1.0;
-      gv = (var >= a.var_floor) ? a.kappa * 0.5 / sd : 0.0;      // torch's clamp_min: no gradient below the floor
-    } else {
-      const double sd = sqrt(var), s = fmax(sd, 1e-9), u = mean - a.f_best - a.xi, Z = u / s;
-      const double Phi = 0.5 * erfc(-Z * 0.70710678118654752440), phi = exp(-0.5 * Z * Z) * 0.39894228040143267794;
-      av = u * Phi + s * phi;
-      gm = Phi;                                   // Phi and phi are constants of the reference's backward pass: exact all the same
-      gv = (sd >= 1e-9) ? phi * 0.5 / sd : 0.0;
-    }
+    acq_value(c.acq, mean, var, c.var_floor, c.kappa, c.xi, c.f_best, av, gm, gv);
     __syncthreads();
 
     // ---- the input gradient: the leaves again from Xs, the reverse sweep per row; partial sums over this thread's rows, then over the
@@ -230,7 +152,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
     for (int dd = 0; dd < DM; ++dd) ga[dd] = 0.0;
     for (int p = 0; p < nb; ++p) {
       const int i = 16 * p + rg;
-      const double c = (i < n) ? -(gm * al[i] - 2.0 * gv * img0[i * 16 + j]) : 0.0;
+      const double ci = (i < n) ? -(gm * al[i] - 2.0 * gv * img0[i * 16 + j]) : 0.0;
       double v[ACQ_TREE_MAX], dv[ACQ_TREE_MAX], gl[ACQ_TREE_MAX];
 #pragma unroll
       for (int e = 0; e < ACQ_TREE_MAX; ++e) {
@@ -253,7 +175,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
 #pragma unroll
       for (int e = 0; e < ACQ_TREE_MAX; ++e) {
         if (e < nl) {
-          const double wt = c * gl[e] * dv[e];
+          const double wt = ci * gl[e] * dv[e];
           if (lin[e]) {
 #pragma unroll
             for (int dd = 0; dd < DM; ++dd) ga[dd] = __builtin_fma(wt, w2[e * DM + dd] * (Xs[i * DM + dd] - cen[e * DM + dd]), ga[dd]);
@@ -269,65 +191,33 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
     __syncthreads();
 
     // ---- 5. outputs and Adam, by the owner of (j, rg): the row sum, and the self term -(da/dvar) dk(x, x)/dx of the linear leaves
-    if (owner) {
-      double gx = 0.0;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) gx += img1[(r * DM + rg) * 16 + j];
+    if (o.owner) {
+      double gx = acq_partial_sum<DM>(img1, rg, j);
       double ds = 0.0;
 #pragma unroll
       for (int e = 0; e < ACQ_TREE_MAX; ++e)
-        if (e < nl && lin[e]) ds = __builtin_fma(gs[e] * (2.0 * lp[4 * e]), w2[e * DM + rg] * (xo - cen[e * DM + rg]), ds);
+        if (e < nl && lin[e]) ds = __builtin_fma(gs[e] * (2.0 * lp[4 * e]), w2[e * DM + rg] * (o.x - cen[e * DM + rg]), ds);
       gx -= gv * ds;
-      if (live) {
-        const size_t e = (size_t)qo * D + rg;
-        if (rg == 0) a.trace[(size_t)k * a.Q + qo] = av;
-        if (a.hist) a.hist[(size_t)k * a.Q * D + e] = xo;
-        if (a.grad && k == iters - 1) a.grad[e] = gx;
-      }
-      if (a.steps > 0 && rg < D)
-        ffgp_adam_update(&xo, &mo, &vo, gx, a.lr, a.b1, a.b2, a.eps, a.bc[2 * k], a.bc[2 * k + 1]);
-      xq[j * DM + rg] = xo;
+      acq_owner_step<DM>(c, o, xq, k, iters, av, gx, tid);
     }
     __syncthreads();
   }
-  if (live && a.steps > 0) {
-    const size_t e = (size_t)qo * D + rg;
-    a.Xq[e] = xo;
-    a.state[e] = mo;
-    a.state[(size_t)a.Q * D + e] = vo;
-    if (a.hist) a.hist[(size_t)a.steps * a.Q * D + e] = xo;
-  }
-}
-
-template <int DM>
-static int acq_tree_launch(ffgp_handle* h, const AcqTreeArgs& a, int grid) {
-  const size_t lds = acq_tree_lds_doubles(FFGP_ACQ_MAX_N, DM) * sizeof(double);
-  // set on every call, as acq.hip does: the attribute belongs to the current device
-  FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_tree_acq_kernel<DM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(ffgp_tree_acq_kernel<DM>, dim3(grid), dim3(ACQ_T), acq_tree_lds_doubles(a.np, DM) * sizeof(double), h->stream, a);
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-  return FFGP_OK;
+  acq_owner_store(c, o, tid);
 }
 
 // the leaf table travels by value in the kernel's arguments
 static int acq_tree_launch_by_d(ffgp_handle* h, const AcqStackArgs& s, int grid, const ffgp_ktree* t) {
-  const AcqStackMember& m = s.m[0];
   AcqTreeArgs a = {};
-  a.X = m.X; a.Linv = m.Linv; a.alpha = m.alpha; a.bc = s.bc;
-  a.Xq = s.Xq; a.state = s.state; a.trace = s.trace; a.hist = s.hist; a.grad = s.grad;
+  a.m = s.m[0];
+  a.c = s.c;
   for (int e = 0; e < ACQ_TREE_MAX; ++e) {
     const ffgp_kdesc& k = t->leaf[e < t->n_leaves ? e : 0];      // (the entries past the last leaf are never read)
     a.k[e].w = k.w_dev; a.k[e].amp = k.amp_dev; a.k[e].center = (k.kfun == FFGP_KFUN_LINEAR) ? k.center_dev : nullptr;
     a.k[e].clamp = k.clamp_min; a.k[e].rinv = (k.kparam != 0.0) ? 1.0 / k.kparam : 1.0; a.k[e].kfun = k.kfun; a.k[e].pad = 0;
   }
-  a.n = m.n; a.np = m.np; a.D = s.D; a.Q = s.Q; a.steps = s.steps; a.acq = s.acq;
   a.nl = t->n_leaves; a.shape = (t->n_leaves == 4) ? t->shape : FFGP_TREE_CHAIN;
   for (int i = 0; i < 3; ++i) a.op[i] = (i + 1 < t->n_leaves) ? t->op[i] : FFGP_KOP_SUM;
-  a.var_add = m.var_add; a.var_floor = s.var_floor; a.kappa = s.kappa; a.xi = s.xi; a.f_best = s.f_best;
-  a.lr = s.lr; a.b1 = s.b1; a.b2 = s.b2; a.eps = s.eps;
-  if (s.D <= 2) return acq_tree_launch<2>(h, a, grid);
-  if (s.D <= 8) return acq_tree_launch<8>(h, a, grid);
-  return acq_tree_launch<16>(h, a, grid);
+  return acq_by_dm(s.c.D, [&](auto dm) { return acq_launch<dm()>(h, ffgp_tree_acq_kernel<dm()>, acq_tree_lds_doubles, a.m.np, a, grid); });
 }
 
 // The tree is checked here; everything else -- the remaining checks, the workspace, the triangular inverse, the bias corrections,

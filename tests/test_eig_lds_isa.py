@@ -1,7 +1,7 @@
 """Build-time check of the one-workgroup LDS eigensolver (csrc/eig_lds.hip; no GPU needed: hipcc cross-compiles): its kernel runs
 entirely in registers and LDS -- no private (scratch) segment, no vector register spilled, in each of its five instantiations
 (4 .. 8 rows of a column per lane) -- and its static LDS plus the dynamic request of the largest problem (n = 128: one [128][129]
-fp64 image and the waves' partial Rayleigh quotients) fits the CU's 160 KiB.  Metadata only, as test_acq_chain_isa.py."""
+fp64 image and the waves' partial Rayleigh quotients) fits the CU's 160 KiB.  Metadata only, as test_acq_isa.py."""
 import os
 import re
 import sys
