@@ -7,7 +7,9 @@ kernel of the kernel's sizes; otherwise -- and for acquisition objects on arbitr
 points are the caller's: the reference draws them inside the function, in fp32.  PI, KG and PF are not provided: the reference gives
 them no gradient or a random one.
 `optimize_acqf_mf` is the same loop on the posterior of a multi-fidelity stack (AR, ResGP: a list of per-fidelity `cigp`), the
-drivers' MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 -- every fidelity level in one launch (`PosteriorStack`, csrc/acq_stack.hip).
+drivers' MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 -- every fidelity level in one launch (`PosteriorStack`, csrc/acq_stack.hip);
+with `fuse_composed=True` also when fidelities run on SumKernel / ProductKernel trees, the reference's own
+SumKernel(LinearKernel, MaternKernel) of its two-fidelity AR and ResGP (csrc/acq_stack_tree.hip).
 `optimize_acqf_nar` is that loop on NAR (FidelityFusion_Models/NAR.py:30-61), whose upper fidelities take the lower fidelity's predicted
 mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip)."""
 import inspect
@@ -111,15 +113,16 @@ def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, 
 
 
 def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12,
-                     accumulate_grad=False, return_best_only=True):
+                     accumulate_grad=False, return_best_only=True, fuse_composed=False):
     """The multi-fidelity drivers' acquisition optimiser (DMF_acq.py:226-262) on the posterior of AR / ResGP
     (FidelityFusion_Models/AR_autoRegression.py:56-89): `models` is the trainers' `gpr_list` (frozen `cigp`), data[f] = (x_f, y_f) the
     data model f was trained on (for f > 0 the residuals), rho = (rho_0, ...) AR's scale factors -- None: all ones, ResGP.  Member f
     is model f's cached posterior with that model's 1 / beta added to its variance, weighted by (1, rho_0, rho_1, ...) in the mean
     and by the squares in the variance.  `level` (int or [Q]) is each start point's `to_fidelity` (None: the top level), so the
     drivers' loop over the fidelities is ONE call; acq = "ucb", "ei" or "ucb_var" (mean + kappa var, the drivers' UCB_MF with
-    kappa = 0.2 D); `accumulate_grad=True` omits zero_grad as the drivers' loop does.  Returns `select_best` on the trace, or the
-    final points with `return_best_only=False`."""
+    kappa = 0.2 D); `accumulate_grad=True` omits zero_grad as the drivers' loop does.  `fuse_composed=True` runs the loop in one launch
+    also when models carry composed kernels (`PosteriorStack.optimize_acquisition`, csrc/acq_stack_tree.hip); by default such a stack
+    takes the per-step loop.  Returns `select_best` on the trace, or the final points with `return_best_only=False`."""
     if X0 is None:
         raise ValueError("optimize_acqf_mf needs the start points X0 [Q, D]")
     models = list(models)
@@ -135,7 +138,7 @@ def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001,
         noise.append(float(m.log_beta.detach().exp().pow(-1)))
     stack = PosteriorStack(members, coefs)
     X, trace, hist, _ = stack.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
-                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad)
+                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad, fuse_composed=fuse_composed)
     return select_best(X0, trace, hist) if return_best_only else X
 
 

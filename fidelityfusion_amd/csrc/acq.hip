@@ -98,7 +98,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_acq_kernel(AcqArgs a) {
   acq_owner_store(c, o, tid);
 }
 
-static int acq_single_launch(ffgp_handle* h, const AcqStackArgs& s, int grid, const ffgp_ktree*) {
+static int acq_single_launch(ffgp_handle* h, const AcqStackArgs& s, int grid, const AcqTrees&) {
   const AcqArgs a = {s.m[0], s.c};
   return acq_by_dm(s.c.D, [&](auto dm) { return acq_launch<dm()>(h, ffgp_acq_kernel<dm()>, acq_lds_doubles, a.m.np, a, grid); });
 }

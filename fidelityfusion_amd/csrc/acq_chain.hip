@@ -171,7 +171,7 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_chain_acq_kernel(AcqStackArgs a) {
 }
 
 // the template is chosen on D + 1, the upper members' input dimension (acq_run has checked D <= FFGP_ACQ_MAX_D - 1)
-static int acq_chain_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree*) {
+static int acq_chain_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid, const AcqTrees&) {
   return acq_by_dm(a.c.D + 1, [&](auto dm) { return acq_launch<dm()>(h, ffgp_chain_acq_kernel<dm()>, acq_chain_lds_doubles, a.npmax, a, grid); });
 }
 

@@ -130,20 +130,41 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_stack_acq_kernel(AcqStackArgs a) {
   acq_owner_store(c, o, tid);
 }
 
-static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree*) {
+static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid, const AcqTrees&) {
   return acq_by_dm(a.c.D, [&](auto dm) { return acq_launch<dm()>(h, ffgp_stack_acq_kernel<dm()>, acq_lds_doubles, a.npmax, a, grid); });
 }
 
+// member p's kernel as a leaf record: its tree (checked by the entry), or the one leaf of its own radial kernel
+static AcqMemberTree acq_member_tree(const ffgp_acq_member& p, const ffgp_ktree* t) {
+  AcqMemberTree r = {};
+  r.nl = t ? t->n_leaves : 1;
+  r.shape = (t && t->n_leaves == 4) ? t->shape : FFGP_TREE_CHAIN;
+  for (int i = 0; i < 3; ++i) r.op[i] = (t && i + 1 < t->n_leaves) ? t->op[i] : FFGP_KOP_SUM;
+  for (int e = 0; e < r.nl; ++e) {
+    AcqLeaf& k = r.k[e];
+    if (t) {
+      const ffgp_kdesc& d = t->leaf[e];
+      k.w = d.w_dev; k.amp = d.amp_dev; k.center = (d.kfun == FFGP_KFUN_LINEAR) ? d.center_dev : nullptr;
+      k.clamp = d.clamp_min; k.rinv = (d.kparam != 0.0) ? 1.0 / d.kparam : 1.0; k.kfun = d.kfun;
+    } else {
+      k.w = p.w_dev; k.amp = p.amp_dev; k.center = nullptr;
+      k.clamp = p.clamp_min; k.rinv = (p.kparam != 0.0) ? 1.0 / p.kparam : 1.0; k.kfun = p.kfun;
+    }
+  }
+  return r;
+}
+
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
-            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree, bool chain) {
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* const* trees, bool chain, bool leaf_table) {
   if (!h || !s || !Xq_dev || !trace_dev || Q <= 0 || steps < 0 || steps > FFGP_ACQ_MAX_STEPS || step0 < 0) return FFGP_ERR_ARG;
   if (steps > 0 && (!opt || !state_dev)) return FFGP_ERR_ARG;
-  if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members || (tree && s->F != 1)) return FFGP_ERR_ARG;
+  if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members) return FFGP_ERR_ARG;
   if (s->acq != FFGP_ACQ_UCB && s->acq != FFGP_ACQ_EI && s->acq != FFGP_ACQ_UCB_VAR) return FFGP_ERR_ARG;
   const int F = s->F, D = s->members[0].D;
   if (chain && D > FFGP_ACQ_MAX_D - 1) return FFGP_ERR_ARG;      // the members above the first take [x, mean below]: D + 1 inputs
   for (int f = 0; f < F; ++f) {
     const ffgp_acq_member& p = s->members[f];
+    const bool tree = trees && trees[f];
     if (!p.X_dev || !p.L_dev || !p.alpha_dev || (!tree && (!p.w_dev || !p.amp_dev))) return FFGP_ERR_ARG;
     if (p.n < 1 || p.n > FFGP_ACQ_MAX_N || p.D < 1 || p.D > FFGP_ACQ_MAX_D || p.D != ((chain && f > 0) ? D + 1 : D) || p.d != 1) return FFGP_ERR_ARG;
     if (p.ldl < p.n || p.ldl > INT_MAX) return FFGP_ERR_ARG;
@@ -151,7 +172,7 @@ int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, doubl
   }
   FFGP_HIP(hipSetDevice(h->device));
   const int iters = steps > 0 ? steps : 1;
-  // workspace: [L_f^-1 (np_f x np_f, zero-padded), f = 0..F-1 | TRTRI scratch per member | bias corrections]
+  // workspace: [L_f^-1 (np_f x np_f, zero-padded), f = 0..F-1 | TRTRI scratch per member | bias corrections | leaf_table: the records]
   size_t xd = 0, td = 0;
   int npmax = 0;
   for (int f = 0; f < F; ++f) {
@@ -160,7 +181,7 @@ int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, doubl
     td += n * n / 4 + n * FFGP_NB + 16;
     npmax = (int)np > npmax ? (int)np : npmax;
   }
-  FFGP_CHECK(ffgp_ensure_ws(h, (xd + td + 2 * (size_t)iters) * sizeof(double)));
+  FFGP_CHECK(ffgp_ensure_ws(h, (xd + td + 2 * (size_t)iters) * sizeof(double) + (leaf_table ? F * sizeof(AcqMemberTree) : 0)));
   double* X = h->ws;
   double* T = X + xd;
   double* bc_dev = T + td;
@@ -190,6 +211,12 @@ int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, doubl
     bc[2 * k + 1] = std::sqrt(1.0 - std::pow(opt->beta2, t));
   }
   FFGP_HIP(hipMemcpyAsync(bc_dev, bc.data(), bc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  std::vector<AcqMemberTree> table(leaf_table ? F : 0);      // (lives until the wait below, as bc does)
+  AcqMemberTree* const table_dev = leaf_table ? reinterpret_cast<AcqMemberTree*>(bc_dev + bc.size()) : nullptr;
+  if (leaf_table) {
+    for (int f = 0; f < F; ++f) table[f] = acq_member_tree(s->members[f], trees ? trees[f] : nullptr);
+    FFGP_HIP(hipMemcpyAsync(table_dev, table.data(), table.size() * sizeof(AcqMemberTree), hipMemcpyHostToDevice, h->stream));
+  }
   AcqLoop& c = a.c;
   c.level = s->level_dev; c.bc = bc_dev;
   c.Xq = Xq_dev; c.state = state_dev; c.trace = trace_dev; c.hist = hist_dev; c.grad = grad_dev;
@@ -197,7 +224,7 @@ int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, doubl
   c.var_floor = s->var_floor; c.kappa = s->kappa; c.xi = s->xi; c.f_best = s->f_best;
   c.lr = opt ? opt->lr : 0.0; c.b1 = opt ? opt->beta1 : 0.0; c.b2 = opt ? opt->beta2 : 0.0; c.eps = opt ? opt->eps : 0.0;
   const int grid = (Q + ACQ_TILE - 1) / ACQ_TILE;
-  FFGP_CHECK(launch(h, a, grid, tree));
+  FFGP_CHECK(launch(h, a, grid, AcqTrees{trees, table_dev}));
   FFGP_HIP(hipStreamSynchronize(h->stream));
   return FFGP_OK;
 }

@@ -1,16 +1,18 @@
 // What the acquisition optimisers' kernels share (acq.hip: one frozen posterior; acq_stack.hip: a stack of them; acq_tree.hip: one
-// posterior on a composed kernel; acq_chain.hip: a chain of them, each fed the mean of the one below): a 256-thread
+// posterior on a composed kernel; acq_chain.hip: a chain of them, each fed the mean of the one below; acq_stack_tree.hip: a stack whose
+// members may carry composed kernels): a 256-thread
 // workgroup owns 16 query points, K_s / V / B live in LDS as [np][16] images, and V = L^-1 K_s, B = L^-T V are v_mfma_f64_16x16x4_f64
 // block chains whose A operand, L^-1, is read from global memory / L2 with one block of prefetch.  Every stage that is the same in its
 // callers stands here once, as a __device__ __forceinline__ function of thread (rg = tid >> 4, j = tid & 15) on query column j: the
 // member load, the squared distance, the row-group reduction, the two chain passes, the acquisition value, the owner thread's
 // prologue, step and write-back, and the launch.  What differs in substance -- the K_s row loop, the gradient pass, the loop over
-// members or leaves -- stays in the four files.  The host side exists once too: acq_run (acq_stack.hip) serves every entry, a single
+// members or leaves -- stays in the five files.  The host side exists once too: acq_run (acq_stack.hip) serves every entry, a single
 // posterior as the stack of one member.
 #pragma once
 #include <type_traits>
 
 #include "drivers.h"
+#include "tree_ops.h"
 
 #define ACQ_T 256
 #define ACQ_TILE 16
@@ -294,12 +296,46 @@ static int acq_by_dm(int d, F f) {
   return f(std::integral_constant<int, 16>());
 }
 
+// One leaf of a composed kernel as the tree kernels read it (acq_tree.hip: four by value in the kernel's arguments), and a member's
+// kernel as a record of leaves in device memory (ffgp_acq_optimize_stack_tree), one record per member.  A member with one radial library kernel is the one-leaf record nl = 1 of its own w / amp / clamp /
+// kfun / kparam.  Eight members of four leaves by value would be more uniform state than the scalar file holds (see acq_park_*), so
+// acq_run uploads the records into handle workspace behind the bias corrections and the kernel copies member f's into LDS.
+struct AcqLeaf {
+  const double* w;       // [D]
+  const double* amp;
+  const double* center;  // [D] or null (the origin); linear leaves only
+  double clamp, rinv;
+  int kfun, pad;
+};
+struct AcqMemberTree {
+  AcqLeaf k[FFGP_TREE_LEAVES];
+  int nl, shape, op[3], pad[3];
+};
+// what the entries that take an ffgp_ktree from the caller refuse about it (the tree itself is not null)
+static inline bool acq_tree_ok(const ffgp_ktree* t) {
+  if (!t->leaf || t->n_leaves < 2 || t->n_leaves > FFGP_TREE_LEAVES) return false;
+  if (t->n_leaves == 4 && t->shape != FFGP_TREE_CHAIN && t->shape != FFGP_TREE_BALANCED) return false;
+  for (int i = 0; i + 1 < t->n_leaves; ++i)
+    if (t->op[i] != FFGP_KOP_SUM && t->op[i] != FFGP_KOP_PRODUCT) return false;
+  for (int e = 0; e < t->n_leaves; ++e)
+    if (t->leaf[e].kfun < FFGP_KFUN_SE || t->leaf[e].kfun > FFGP_KFUN_LINEAR || !t->leaf[e].w_dev || !t->leaf[e].amp_dev) return false;
+  return true;
+}
+// what acq_run hands to `launch` beside the kernel's arguments
+struct AcqTrees {
+  const ffgp_ktree* const* host;      // [F] the members' trees as the caller gave them (null entry: a radial member), or null
+  const AcqMemberTree* table_dev;     // [F] in handle workspace, or null when the entry did not ask for it
+};
+
 // One driver (acq_run, acq_stack.hip) for every entry.
 // Checks the call, forms every member's L^-1 and the bias-correction table in handle workspace, launches through `launch` and waits.
-// `tree` (ffgp_acq_optimize_tree only, checked by that entry): the one member's kernel is this composition, so the member carries no
-// w_dev / amp_dev / kfun of its own and those three checks are skipped; it is handed on to `launch`.
+// `trees` (ffgp_acq_optimize_tree and ffgp_acq_optimize_stack_tree, which check the trees themselves): host array [F]; member f's kernel
+// is the composition trees[f], so the member carries no w_dev / amp_dev / kfun of its own and those three checks are skipped; a null
+// entry is a member with its own radial kernel.  It is handed on to `launch`.  `leaf_table`: the members' AcqMemberTree records are
+// uploaded behind the bias corrections and handed on as well.
 // `chain` (ffgp_acq_optimize_chain only): the per-member dimension rule is members[0].D = D <= FFGP_ACQ_MAX_D - 1 and D + 1 above it,
 // instead of one D for all; AcqLoop.D stays the D of the query points.
-typedef int (*acq_launch_fn)(ffgp_handle* h, const AcqStackArgs& a, int grid, const ffgp_ktree* tree);
+typedef int (*acq_launch_fn)(ffgp_handle* h, const AcqStackArgs& a, int grid, const AcqTrees& t);
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
-            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* tree = nullptr, bool chain = false);
+            long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* const* trees = nullptr, bool chain = false,
+            bool leaf_table = false);

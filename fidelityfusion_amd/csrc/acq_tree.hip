@@ -22,17 +22,10 @@
 
 #define ACQ_TREE_MAX FFGP_TREE_LEAVES
 
-struct AcqTreeLeaf {
-  const double* w;       // [D]
-  const double* amp;
-  const double* center;  // [D] or null (the origin); linear leaves only
-  double clamp, rinv;
-  int kfun, pad;
-};
 struct AcqTreeArgs {
   AcqStackMember m;      // X, Linv, alpha, n, np, var_add of the one posterior; its kernel is the tree below
   AcqLoop c;
-  AcqTreeLeaf k[ACQ_TREE_MAX];
+  AcqLeaf k[ACQ_TREE_MAX];
   int nl, shape, op[3];
 };
 
@@ -206,7 +199,8 @@ __global__ __launch_bounds__(ACQ_T) void ffgp_tree_acq_kernel(AcqTreeArgs a) {
 }
 
 // the leaf table travels by value in the kernel's arguments
-static int acq_tree_launch_by_d(ffgp_handle* h, const AcqStackArgs& s, int grid, const ffgp_ktree* t) {
+static int acq_tree_launch_by_d(ffgp_handle* h, const AcqStackArgs& s, int grid, const AcqTrees& trees) {
+  const ffgp_ktree* t = trees.host[0];
   AcqTreeArgs a = {};
   a.m = s.m[0];
   a.c = s.c;
@@ -226,12 +220,7 @@ int ffgp_acq_optimize_tree(ffgp_handle* h, const ffgp_acq_tree_problem* p, doubl
                            double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
   if (!p || (p->acq != FFGP_ACQ_UCB && p->acq != FFGP_ACQ_EI)) return FFGP_ERR_ARG;      // FFGP_ACQ_UCB_VAR: the stack entry only
   const ffgp_ktree* t = p->tree;
-  if (!t || !t->leaf || t->n_leaves < 2 || t->n_leaves > ACQ_TREE_MAX) return FFGP_ERR_ARG;
-  if (t->n_leaves == 4 && t->shape != FFGP_TREE_CHAIN && t->shape != FFGP_TREE_BALANCED) return FFGP_ERR_ARG;
-  for (int i = 0; i + 1 < t->n_leaves; ++i)
-    if (t->op[i] != FFGP_KOP_SUM && t->op[i] != FFGP_KOP_PRODUCT) return FFGP_ERR_ARG;
-  for (int e = 0; e < t->n_leaves; ++e)
-    if (t->leaf[e].kfun < FFGP_KFUN_SE || t->leaf[e].kfun > FFGP_KFUN_LINEAR || !t->leaf[e].w_dev || !t->leaf[e].amp_dev) return FFGP_ERR_ARG;
+  if (!t || !acq_tree_ok(t)) return FFGP_ERR_ARG;
   ffgp_acq_member m = {};
   m.n = p->n; m.D = p->D; m.d = p->d;
   m.X_dev = p->X_dev; m.L_dev = p->L_dev; m.ldl = p->ldl; m.alpha_dev = p->alpha_dev;
@@ -239,5 +228,5 @@ int ffgp_acq_optimize_tree(ffgp_handle* h, const ffgp_acq_tree_problem* p, doubl
   ffgp_acq_stack s = {};
   s.F = 1; s.members = &m; s.level_dev = nullptr;
   s.var_floor = p->var_floor; s.acq = p->acq; s.kappa = p->kappa; s.xi = p->xi; s.f_best = p->f_best; s.accumulate_grad = 0;
-  return acq_run(h, &s, acq_tree_launch_by_d, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev, t);
+  return acq_run(h, &s, acq_tree_launch_by_d, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev, &t);
 }

@@ -91,6 +91,49 @@ int main() {
     EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     mem[1].d = 1; mem[0].alpha_dev = nullptr;
     EXPECT(ffgp_acq_optimize_stack(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    // the stack entry for members with composed kernels: the trees are checked before the driver, nothing is dereferenced on refusal
+    {
+      mem[0].alpha_dev = &x;
+      ffgp_kdesc lf[4];
+      std::memset(lf, 0, sizeof lf);
+      for (ffgp_kdesc& k : lf) { k.kfun = FFGP_KFUN_SE; k.w_dev = &x; k.amp_dev = &x; k.kparam = 1.0; }
+      lf[1].kfun = FFGP_KFUN_LINEAR;
+      ffgp_ktree tr;
+      std::memset(&tr, 0, sizeof tr);
+      tr.n_leaves = 2; tr.op[0] = FFGP_KOP_SUM; tr.leaf = lf;
+      const ffgp_ktree* trees[2] = {&tr, nullptr};      // member 0 on the tree, member 1 on its own radial kernel
+      EXPECT(ffgp_acq_optimize_stack_tree(nullptr, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, nullptr, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, nullptr, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, nullptr, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, nullptr, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, nullptr, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, nullptr, nullptr, nullptr) == FFGP_ERR_ARG);
+      stk.F = FFGP_ACQ_MAX_MEMBERS + 1;      // (two trees, two members: the count is refused before any is read)
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      stk.F = 2; tr.n_leaves = 1;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.n_leaves = 5;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.n_leaves = 4; tr.shape = 2;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.shape = FFGP_TREE_BALANCED; tr.op[2] = 2;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.op[2] = FFGP_KOP_PRODUCT; lf[3].kfun = FFGP_KFUN_LINEAR + 1;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      lf[3].kfun = FFGP_KFUN_RQ; lf[2].w_dev = nullptr;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      lf[2].w_dev = &x; lf[0].amp_dev = nullptr;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      lf[0].amp_dev = &x; tr.leaf = nullptr;
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.leaf = lf; mem[1].w_dev = nullptr;      // the member without a tree needs its own kernel ...
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].w_dev = &x; mem[0].w_dev = nullptr; mem[0].amp_dev = nullptr; mem[0].n = 0;      // ... the one with a tree does not: refused for n
+      EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].w_dev = mem[0].amp_dev = &x; mem[0].n = 4;
+    }
     // the chain entry (NAR): the stack entry's driver with the D / D + 1 rule, and its own refusal of a coefficient other than 1
     mem[0].alpha_dev = &x; mem[1].D = 2;
     ffgp_acq_chain chn;

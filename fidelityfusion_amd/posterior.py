@@ -354,15 +354,24 @@ class PosteriorStack:
         """whether `optimize_acquisition` from X0 takes the one-launch call (ffgp_acq_optimize_stack)"""
         return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_fusable(X0) for m in self.members)
 
+    def acq_tree_fusable(self, X0):
+        """whether `optimize_acquisition(..., fuse_composed=True)` from X0 takes a one-launch call: at most 8 members, each of them
+        `acq_fusable` (one radial library kernel) or `acq_tree_fusable` (a descriptor tree of 2-4 library leaves)"""
+        return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_fusable(X0) or m.acq_tree_fusable(X0) for m in self.members)
+
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12, betas=(0.9, 0.999),
-                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None):
+                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None, fuse_composed=False):
         """`Posterior.optimize_acquisition` on the stack's posterior, with the same return tuple (X, trace, hist, state).
         acq = "ucb" / "ei" as there, or "ucb_var": mean + kappa var, the multi-fidelity drivers' form
         (MF_BayesianOptimization/Discrete/DMF_acq.py:49-63).  `level` (int or [Q]) gives every point its own `to_fidelity`, so one
         call optimises the acquisition at every fidelity; `accumulate_grad=True` runs the drivers' loop as it stands
         (DMF_acq.py:246-255: no zero_grad, Adam sees the running sum of the gradients; the sum travels as state["grad_sum"]).
         ONE kernel launch (csrc/acq_stack.hip) when every member is `acq_fusable` and there are at most 8 of them, otherwise the
-        per-step loop on `predict_diff` and torch.optim.Adam; state["fused"] says which."""
+        per-step loop on `predict_diff` and torch.optim.Adam; state["fused"] says which.
+        `fuse_composed=True` opts members with composed kernels in, as for a single posterior: a stack with at least one tree member
+        that is `acq_tree_fusable(X0)` is ONE launch as well (ffgp_acq_optimize_stack_tree, csrc/acq_stack_tree.hip: radial members
+        and Sum / Product trees of 2-4 leaves mixed freely), with the same return values and `state` contract.  A stack without a
+        tree member takes the call above whatever the keyword says; without the keyword nothing changes."""
         acq = str(acq).lower()
         if acq not in ("ucb", "ei", "ucb_var"):
             raise ValueError("acq must be 'ucb', 'ei' or 'ucb_var', got %r" % (acq,))
@@ -374,8 +383,11 @@ class PosteriorStack:
         va = self._var_adds(var_adds)
         lv = self._level(level, X0.shape[0])
         step0 = int(state["step"]) if state is not None else 0
-        if self.acq_fusable(X0) and steps <= _lib.FFGP_ACQ_MAX_STEPS:
-            return self._optimize_acq_fused(X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0)
+        if steps <= _lib.FFGP_ACQ_MAX_STEPS:
+            call = self._acq_call if self.acq_fusable(X0) else self._acq_call_trees if fuse_composed and self.acq_tree_fusable(X0) else None
+            if call is not None:
+                return self._optimize_acq_fused(X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0,
+                                                call)
         dev = self.dev
         X = X0.detach().to(device=dev, dtype=torch.float64).clone().requires_grad_(True)
         opt = torch.optim.Adam([X], lr=lr, betas=betas, eps=eps)
@@ -413,20 +425,32 @@ class PosteriorStack:
         return (X.detach().to(device=X0.device, dtype=X0.dtype), trace.to(X0.device), hist.to(X0.device), out)
 
     def _member_table(self, va, keep):
-        """the ctypes array of ffgp_acq_member; `keep` collects the tensors its pointers refer to"""
+        """the ctypes array of ffgp_acq_member; `keep` collects the tensors its pointers refer to.  A member on a descriptor tree
+        carries no kernel of its own (w_dev, amp_dev NULL, kfun 0): ffgp_acq_optimize_stack_tree reads its tree (`_tree_table`)"""
         tab = (_lib.AcqMember * self.F)()
         for f, m in enumerate(self.members):
             if m.alpha is None:
                 m._solve_alpha()
             alpha = m.alpha.reshape(-1).contiguous()
             keep.append(alpha)
+            own = m.tree is None
             tab[f] = _lib.AcqMember(n=m.n, D=m.D, d=1, X_dev=m.X.data_ptr(), L_dev=m.W.data_ptr(), ldl=m.ld, alpha_dev=alpha.data_ptr(),
-                                    w_dev=m.w.data_ptr(), amp_dev=m.amp.data_ptr(), clamp_min=float(m.clamp), kfun=int(m.kfun[0]),
-                                    kparam=float(m.kfun[1]), var_add_all=va[f], mean_coef=self.mean_coefs[f], var_coef=self.var_coefs[f])
+                                    w_dev=m.w.data_ptr() if own else None, amp_dev=m.amp.data_ptr() if own else None,
+                                    clamp_min=float(m.clamp) if own else 0.0, kfun=int(m.kfun[0]) if own else 0,
+                                    kparam=float(m.kfun[1]) if own else 1.0, var_add_all=va[f], mean_coef=self.mean_coefs[f],
+                                    var_coef=self.var_coefs[f])
         return tab
 
+    def _tree_table(self):
+        """the host array `trees` of ffgp_acq_optimize_stack_tree: each member's ffgp_ktree, NULL for a member with a kernel of its own"""
+        trees = (C.POINTER(_lib.KTree) * self.F)()
+        for f, m in enumerate(self.members):
+            if m.tree is not None:
+                trees[f] = C.pointer(m.tree[2])
+        return trees
+
     @torch.no_grad()
-    def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0):
+    def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0, call):
         dev, Q, D = self.dev, X0.shape[0], self.D
         X = X0.detach().clone().contiguous()
         buf = torch.zeros((3 if accumulate_grad else 2, Q, D), dtype=torch.float64, device=dev)
@@ -439,8 +463,8 @@ class PosteriorStack:
         hist = torch.empty((steps + 1, Q, D), dtype=torch.float64, device=dev)
         code = {"ucb": _lib.FFGP_ACQ_UCB, "ei": _lib.FFGP_ACQ_EI, "ucb_var": _lib.FFGP_ACQ_UCB_VAR}[acq]
         opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
-        self._acq_call(va, lv, dict(var_floor=float(var_floor), acq=code, kappa=float(kappa), xi=float(xi), f_best=float(f_best)), accumulate_grad,
-                       (_ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace), _ptr(hist), None))
+        call(va, lv, dict(var_floor=float(var_floor), acq=code, kappa=float(kappa), xi=float(xi), f_best=float(f_best)), accumulate_grad,
+             (_ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace), _ptr(hist), None))
         out = {"fused": True, "step": step0 + steps, "exp_avg": buf[0], "exp_avg_sq": buf[1]}
         if accumulate_grad:
             out["grad_sum"] = buf[2]
@@ -452,6 +476,13 @@ class PosteriorStack:
         s = _lib.AcqStack(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
                           accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
         check(lib.ffgp_acq_optimize_stack(self.members[0]._h(), C.byref(s), *call), "ffgp_acq_optimize_stack")
+
+    def _acq_call_trees(self, va, lv, acq_fields, accumulate_grad, call):
+        """the C entry of the fused call on a stack with tree members"""
+        keep = []
+        s = _lib.AcqStack(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
+                          accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
+        check(lib.ffgp_acq_optimize_stack_tree(self.members[0]._h(), C.byref(s), self._tree_table(), *call), "ffgp_acq_optimize_stack_tree")
 
 
 class _SinglePosterior(PosteriorStack):

@@ -900,6 +900,35 @@ typedef struct {
 int ffgp_acq_optimize_tree(ffgp_handle* h, const ffgp_acq_tree_problem* p, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
                            double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* ffgp_acq_optimize_stack on a stack whose members may carry COMPOSED kernels -- the reference's two-fidelity AR and ResGP are built
+   on SumKernel(LinearKernel(1), MaternKernel(1)) for both fidelities (two_fidelity_models/AR_autoRegression.py:31-34, ResGP.py:25-28),
+   and its multi-fidelity models take any kernel_list -- in ONE launch (csrc/acq_stack_tree.hip).  `s` is ffgp_acq_stack as it stands;
+   `trees` is a host array [s->F]:
+       trees[f] == NULL   member f is one radial library kernel, taken from the member's own w_dev / amp_dev / clamp_min / kfun / kparam
+                          exactly as ffgp_acq_optimize_stack reads them;
+       trees[f] != NULL   member f's kernel is that tree of 2-4 leaves, with the canonical forms and per-leaf rules of
+                          ffgp_acq_optimize_tree (FFGP_KFUN_LINEAR with optional center_dev, FFGP_KFUN_RQ); the member's own w_dev /
+                          amp_dev / kfun are then not read and may be NULL / 0.
+   Limits: F <= FFGP_ACQ_MAX_MEMBERS, every n <= FFGP_ACQ_MAX_N, one D <= FFGP_ACQ_MAX_D for all members, d = 1, steps <=
+   FFGP_ACQ_MAX_STEPS.  Per query point q, with on_f = (f <= min(level[q], F - 1)) (level_dev NULL: every member),
+       k_f,i = tree_f on the leaves' values at (X_f,i, x), its nodes rounded one by one as ffgp_assemble_tree rounds them,
+       mean = sum_f on_f mean_coef_f k_f^T alpha_f,    var = sum_f on_f var_coef_f (k_f(x, x) - |L_f^-1 k_f|^2 + var_add_all_f),
+       k_f(x, x) = tree_f on the self values amp_e phi_e(max(0, clamp_e)) | amp_e sum_k w_ek^2 (x_k - c_ek)^2;   a radial member: amp_f,
+   and FFGP_ACQ_UCB, FFGP_ACQ_EI or FFGP_ACQ_UCB_VAR on (mean, var) as ffgp_acq_optimize_stack defines them.  The loss is -sum a; its
+   gradient is the stack's -- the row sums with mean_coef_f alpha_f,i and var_coef_f B_f,i, combined as da/dmean Gm - 2 da/dvar Gv
+   after the last member -- with each row's dk_i/dx from the tree's reverse sweep times the leaf derivative (ffgp_acq_optimize_tree's
+   two forms, zero where s_e < clamp_e), plus the self term -da/dvar sum_f on_f var_coef_f dk_f(x, x)/dx, non-zero through linear
+   leaves only.  on_f is an exact 0 / 1 factor on both coefficients: a point's trajectory does not depend on its tile, its neighbours
+   or their levels, and level = k everywhere is the stack cut after member k, bit for bit.  accumulate_grad and state_dev [2 | 3, Q, D],
+   Xq, trace, hist, grad, step0, opt, evaluate mode (steps = 0), the workspace and the handle's inverted diagonal blocks keep
+   ffgp_acq_optimize_stack's contract (the members' leaf records travel in the same workspace, behind the bias corrections).
+   FFGP_ERR_ARG, before anything is enqueued (Xq, state, trace, hist and grad untouched): everything ffgp_acq_optimize_stack refuses --
+   its w_dev / amp_dev / kfun rules applying to the members with a NULL tree only --, trees NULL, and for a non-NULL tree what
+   ffgp_acq_optimize_tree refuses about a tree: its leaf array NULL, n_leaves outside 2..4, an unknown shape, op or leaf kfun, a
+   leaf's w_dev or amp_dev NULL.  Synchronous; returns 0.                                                                          */
+int ffgp_acq_optimize_stack_tree(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, double* Xq_dev, int Q, int steps,
+                                 const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another
