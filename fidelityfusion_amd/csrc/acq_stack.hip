@@ -205,11 +205,7 @@ int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, doubl
   }
   for (int f = F; f < FFGP_ACQ_MAX_MEMBERS; ++f) a.m[f] = a.m[0];      // never read: the member loop ends at F
   std::vector<double> bc(2 * (size_t)iters, 1.0);
-  for (int k = 0; k < steps; ++k) {
-    const double t = (double)(step0 + k + 1);
-    bc[2 * k] = 1.0 - std::pow(opt->beta1, t);
-    bc[2 * k + 1] = std::sqrt(1.0 - std::pow(opt->beta2, t));
-  }
+  ffgp_adam_bc_table(opt, step0, steps, bc.data());
   FFGP_HIP(hipMemcpyAsync(bc_dev, bc.data(), bc.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   std::vector<AcqMemberTree> table(leaf_table ? F : 0);      // (lives until the wait below, as bc does)
   AcqMemberTree* const table_dev = leaf_table ? reinterpret_cast<AcqMemberTree*>(bc_dev + bc.size()) : nullptr;

@@ -313,10 +313,7 @@ struct AcqMemberTree {
 };
 // what the entries that take an ffgp_ktree from the caller refuse about it (the tree itself is not null)
 static inline bool acq_tree_ok(const ffgp_ktree* t) {
-  if (!t->leaf || t->n_leaves < 2 || t->n_leaves > FFGP_TREE_LEAVES) return false;
-  if (t->n_leaves == 4 && t->shape != FFGP_TREE_CHAIN && t->shape != FFGP_TREE_BALANCED) return false;
-  for (int i = 0; i + 1 < t->n_leaves; ++i)
-    if (t->op[i] != FFGP_KOP_SUM && t->op[i] != FFGP_KOP_PRODUCT) return false;
+  if (!ffgp_tree_form_ok(t)) return false;
   for (int e = 0; e < t->n_leaves; ++e)
     if (t->leaf[e].kfun < FFGP_KFUN_SE || t->leaf[e].kfun > FFGP_KFUN_LINEAR || !t->leaf[e].w_dev || !t->leaf[e].amp_dev) return false;
   return true;

@@ -212,6 +212,44 @@ int main() {
       hr.l = 2; EXPECT(call(fake, 1, &hr, 2 * (2 + 2 + 2 * 2) - 1) == FFGP_ERR_ARG);
       hr.V_row_stride = -1; hr.V_col_stride = 1; EXPECT(call(fake, 1, &hr, 64) == FFGP_ERR_ARG);
     }
+    // the two tree trainers share the entry check, the tree-form check and the trainable-leaf check: every refusal of either comes
+    // before the handle is dereferenced
+    {
+      ffgp_kdesc lf[4];
+      std::memset(lf, 0, sizeof lf);
+      for (ffgp_kdesc& k : lf) { k.kfun = FFGP_KFUN_MATERN32; k.w_dev = &x; k.amp_dev = &x; k.kparam = 1.0; }
+      lf[0].kfun = FFGP_KFUN_LINEAR;
+      ffgp_ktree tr;
+      std::memset(&tr, 0, sizeof tr);
+      tr.n_leaves = 2; tr.op[0] = FFGP_KOP_SUM; tr.leaf = lf;
+      ffgp_problem tp;
+      std::memset(&tp, 0, sizeof tp);
+      tp.n = 4; tp.D = 1; tp.d = 1; tp.ll_variant = FFGP_LL_V1; tp.X_dev = tp.Y_dev = tp.diag_add_dev = &x; tp.tree = &tr;
+      ffgp_tree_links tl;
+      std::memset(&tl, 0, sizeof tl);
+      for (auto tt : {ffgp_train_tree_raw, ffgp_train_tree_lds_raw}) {
+        auto refused = [&](long stride = 64) { return tt(fake, 1, &tp, &tl, 3, &ad, &x, stride, 0, &x, 3) == FFGP_ERR_ARG; };
+        EXPECT(tt(nullptr, 1, &tp, &tl, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+        EXPECT(tt(fake, 1, nullptr, &tl, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+        EXPECT(tt(fake, 17, &tp, &tl, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+        EXPECT(tt(fake, 1, &tp, &tl, 0, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+        EXPECT(tt(fake, 1, &tp, &tl, 3, &ad, &x, 64, -1, &x, 3) == FFGP_ERR_ARG);
+        EXPECT(tt(fake, 1, &tp, &tl, 3, &ad, &x, 64, 0, &x, 2) == FFGP_ERR_ARG);      // trace_stride < steps
+        tr.n_leaves = 1; EXPECT(refused());
+        tr.n_leaves = 5; EXPECT(refused());
+        tr.n_leaves = 2; tr.leaf = nullptr; EXPECT(refused());
+        tr.leaf = lf; lf[1].kfun = FFGP_KFUN_RQ; EXPECT(refused());
+        lf[1].kfun = FFGP_KFUN_MATERN32; lf[1].w_dev = nullptr; EXPECT(refused());
+        lf[1].w_dev = &x; lf[0].amp_dev = nullptr; EXPECT(refused());
+        lf[0].amp_dev = &x; tl.leaf[1].center_train = 1; EXPECT(refused());      // a trained centre on a leaf that is not linear ...
+        tl.leaf[1].center_train = 0; tl.leaf[0].center_train = 1; EXPECT(refused());      // ... and on a linear leaf without center_dev
+        tl.leaf[0].center_train = 0; EXPECT(refused(2 * (2 + 2 + 1) - 1));      // state_stride < 2 P
+        tp.tree = nullptr; EXPECT(refused());
+        tp.tree = &tr;
+      }
+      tr.n_leaves = 4; tr.shape = 2;      // the one-launch form alone (the other leaves the shape to the assembly, behind the handle)
+      EXPECT(ffgp_train_tree_lds_raw(fake, 1, &tp, &tl, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+    }
     std::printf("asan_host_check: no device -- argument / no-device paths clean\n");
     return 0;
   }

@@ -1,5 +1,7 @@
 // What the host-driver translation units (handle.hip, nlml.hip, nlml_batch.hip, train_loop.hip, api.hip) need from each other.
 #pragma once
+#include <cmath>
+
 #include "ffgp_internal.h"
 
 // ---- handle.hip
@@ -17,6 +19,7 @@ struct RawGraph {          // the captured forward call (option "fwd_graph", ffg
 void ffgp_rawg_drop(RawGraph* r);      // forgets the captured call (null: nothing to do); the struct and its staging slot stay
 
 // ---- raw parameters: elementwise links around the fused call (kernels in nlml.hip / nlml_batch.hip, the Adam kernel of train_loop.hip)
+//      and inside the one-launch trainers (train.hip, train_tree_lds.hip)
 __device__ __forceinline__ double ffgp_link_val(int kind, double p, double c) {
   switch (kind) {
     case FFGP_LINK_INV_ABS_EPS: return 1.0 / (fabs(p) + c);
@@ -41,8 +44,9 @@ __device__ __forceinline__ double ffgp_link_der(int kind, double p, double c) {
 }
 
 // ---- torch.optim.Adam's update of ONE parameter with gradient g (no weight decay, no amsgrad), operation for operation; bc1 and
-// bc2_sqrt = 1 - beta1^t and sqrt(1 - beta2^t), computed on the host.  The one copy: ffgp_adam_kernel (train_loop.hip) and
-// ffgp_tree_adam_kernel (train_tree.hip) both call it.
+// bc2_sqrt = 1 - beta1^t and sqrt(1 - beta2^t), computed on the host (ffgp_adam_bc below).  The one copy; its callers: ffgp_adam_kernel and
+// ffgp_adam_car_kernel (train_loop.hip), ffgp_tree_adam_kernel (train_tree.hip), ffgp_hogp_adam_kernel (train_hogp.hip), tr_body
+// (train.hip), ffgp_train_tree_lds_kernel (train_tree_lds.hip) and acq_owner_step (acq_tile.h).
 __device__ __forceinline__ void ffgp_adam_update(double* par, double* m, double* v, double g, double lr, double b1, double b2, double eps,
                                                  double bc1, double bc2_sqrt) {
   const double m1 = m[0] + (g - m[0]) * (1.0 - b1);        // exp_avg.lerp_(grad, 1 - beta1)
@@ -51,6 +55,21 @@ __device__ __forceinline__ void ffgp_adam_update(double* par, double* m, double*
   v[0] = v1;
   const double denom = sqrt(v1) / bc2_sqrt + eps;
   par[0] = par[0] + (-(lr / bc1)) * (m1 / denom);          // param.addcdiv_(exp_avg, denom, value = -step_size)
+}
+// ... and its bias corrections at step t = step0 + k + 1, on the host with the C library's pow, as Python computes `1 - beta ** t`: the
+// trajectories are compared with torch's bit for bit, so every driver forms them here.  The table: [steps][2].
+static inline void ffgp_adam_bc(const ffgp_adam* opt, long step0, int k, double* bc1, double* bc2_sqrt) {
+  const double t = (double)(step0 + k + 1);
+  *bc1 = 1.0 - std::pow(opt->beta1, t);
+  *bc2_sqrt = std::sqrt(1.0 - std::pow(opt->beta2, t));
+}
+static inline void ffgp_adam_bc_table(const ffgp_adam* opt, long step0, int steps, double* bc) {
+  for (int k = 0; k < steps; ++k) ffgp_adam_bc(opt, step0, k, bc + 2 * k, bc + 2 * k + 1);
+}
+// what every K-steps-per-call trainer refuses about its own arguments (l: the members' links, of the entry's type)
+static inline bool ffgp_train_args_ok(const ffgp_handle* h, const void* p, const void* l, const ffgp_adam* opt, const double* state_dev,
+                                      const double* trace_dev, int F, int steps, long step0, long trace_stride) {
+  return h && p && l && opt && state_dev && trace_dev && F > 0 && F <= FFGP_TRAIN_MAXF && steps > 0 && step0 >= 0 && trace_stride >= steps;
 }
 
 // ---- nlml.hip: the pieces every likelihood driver shares

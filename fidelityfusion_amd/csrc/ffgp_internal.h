@@ -259,14 +259,11 @@ struct ffgp_handle {
   double* lane_skw[FFGP_GRAD_LANES];      // per-lane split-K workspaces (swapped into h->skw while a member is enqueued on the lane)
   size_t lane_skw_bytes[FFGP_GRAD_LANES];
   double* lane_scal;    // per-lane scalar scratch (64 doubles each; swapped into h->d_scal)
-  void* train_tab;      // ffgp_train_persist (train.hip): [models | bias corrections | status words] of the current call
-  size_t train_tab_bytes;
+  void* train_blk;      // the one-launch trainers' block of the current call (train_host.h; ffgp_train_persist and ffgp_train_tree_lds_raw
+  size_t train_blk_bytes;       // are synchronous, so one serves both): [tables | bias corrections | status words | per-model scratch]
+  void* train_blk_host; // pinned mirror of its head, everything before the scratch (staging of the tables, read-back of the status words)
+  size_t train_blk_host_bytes;
   double* small_kbuf;   // ffgp_small_mfma_enqueue: the evaluate-mode launches' parked kernel values (8 models x 36 x 256 doubles)
-  void* train_host;     // its pinned host mirror (staging of the table, read-back of the status words)
-  void* train_ttl;      // ffgp_train_tree_lds_raw (train_tree_lds.hip): [models | bias corrections | status words | the entries' per-leaf weights]
-  size_t train_ttl_bytes;
-  void* train_ttl_host; // pinned mirror of its first three parts
-  size_t train_ttl_host_bytes;
   int train_persist_off;  // option "train_persist" = 0: ffgp_train_raw never takes the one-launch trainer
   int* bt_info;         // [F] device status words (first non-positive pivot of each block)
   int* bt_info_host;    // pinned mirror

@@ -281,10 +281,8 @@ int ffgp_destroy(ffgp_handle* h) {
   }
   if (h->lane_scal) hipFree(h->lane_scal);
   if (h->small_kbuf) hipFree(h->small_kbuf);
-  if (h->train_tab) hipFree(h->train_tab);
-  if (h->train_host) hipHostFree(h->train_host);
-  if (h->train_ttl) hipFree(h->train_ttl);
-  if (h->train_ttl_host) hipHostFree(h->train_ttl_host);
+  if (h->train_blk) hipFree(h->train_blk);
+  if (h->train_blk_host) hipHostFree(h->train_blk_host);
   ffgp_assemble_collect_free(h);
   if (h->bt_info_host) hipHostFree(h->bt_info_host);
   if (h->d_scal) hipFree(h->d_scal);

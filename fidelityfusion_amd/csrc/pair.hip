@@ -12,10 +12,11 @@
 // The gradient tile reads G = d(value)/d(Sigma) once, rebuilds both parts from X, routes G to each part (Sum: G;
 // Product: G o K_other) and reduces g_w, g_amp, g_kparam and -- for the linear part -- g_center per descriptor.
 #include "ffgp_internal.h"
+#include "tree_ops.h"
 
 #define AT 64
 #define DC 16
-#define TREE_MAX 4
+#define TREE_MAX FFGP_TREE_LEAVES
 
 struct PairDesc {
   const double* w; const double* amp; const double* center;
@@ -467,10 +468,7 @@ __global__ __launch_bounds__(256) void ffgp_grad_pair_finish(const double* __res
 }
 
 static int pair_fill(PairArgs& a, const ffgp_ktree* t) {
-  if (!t || !t->leaf || t->n_leaves < 2 || t->n_leaves > TREE_MAX) return FFGP_ERR_ARG;
-  if (t->n_leaves == 4 && t->shape != FFGP_TREE_CHAIN && t->shape != FFGP_TREE_BALANCED) return FFGP_ERR_ARG;
-  for (int i = 0; i + 1 < t->n_leaves; ++i)
-    if (t->op[i] != FFGP_KOP_SUM && t->op[i] != FFGP_KOP_PRODUCT) return FFGP_ERR_ARG;
+  if (!t || !ffgp_tree_form_ok(t)) return FFGP_ERR_ARG;
   const ffgp_kdesc* k = t->leaf;
   for (int e = 0; e < t->n_leaves; ++e) {
     if (k[e].kfun < FFGP_KFUN_SE || k[e].kfun > FFGP_KFUN_LINEAR || !k[e].w_dev || !k[e].amp_dev) return FFGP_ERR_ARG;

@@ -35,8 +35,10 @@
 // moments, the samples and the partials of s behind the reduction's extra total (dloss/db needs sum dloss/dr .* y_low).  Launches of their own.
 // Covers: n <= 128, D <= 16, d <= 16, one radial-profile kernel, V1 likelihood (V2: plain and CAR members), diag_add and diag_vec (no matrix / all-entries /
 // mean(K) extras, no learnable profile parameter): what cigp_v10 produces.  Everything else keeps the paths it had.
-#include "ffgp_internal.h"
-#include "train_tile.h"
+// HOST side: the scaffold of train_host.h, shared with train_tree_lds.hip -- the call's block on the handle with its pinned mirror, the
+// bias corrections, the loop's arguments, the <8> / <16> dispatch, the launch, the status epilogue.  ffgp_train_persist adds what is its
+// own: the four classes of members, their tables, a launch per class.  The links and Adam's update are the copies of drivers.h.
+#include "train_host.h"
 
 #define TR_NRED 20        // values of the step's one workgroup reduction: ss, s_amp, tr G, log-det, tot[16]
 
@@ -74,12 +76,7 @@ struct TrainCar {
   const double* yl; const double* yh;    // [n, d]
   double* b_last;                        // optional [1]: b at the start of the last step taken
 };
-struct TrainCommon {
-  int steps;
-  double lr, b1, b2, eps;
-  const double* bc;                      // [steps][2]: 1 - beta1^t, sqrt(1 - beta2^t) -- computed on the host with the C library's pow, as Python does
-  int* info;                             // [models] status: 0, or the 1-based index of the first non-positive pivot of the step that failed
-  int* fail_step;                        // [models] the step at which it happened
+struct TrainCommon : TrainLoop {         // (the loop's arguments first: the layout the kernels were compiled against)
   int* shared_info;                      // evaluate mode: the handle's status word (batch: atomicMax of the failing pivot; single: plain store)
   int info_max;
   long* prof;                            // development (FFGP_TRAIN_TRACE=1): [12] wall_clock64 ticks per phase, summed over model 0's steps
@@ -93,37 +90,8 @@ struct TrainCommon {
     }                                                                \
   } while (0)
 
-__device__ __forceinline__ double tr_link_val(int kind, double p, double c) {
-  switch (kind) {
-    case FFGP_LINK_INV_ABS_EPS: return 1.0 / (fabs(p) + c);
-    case FFGP_LINK_EXP_NEG: return exp(-p) + c;
-    case FFGP_LINK_INV: return 1.0 / p + c;
-    case FFGP_LINK_ABS: return fabs(p);
-    case FFGP_LINK_EXP_SQ: { const double e = exp(p); return e * e; }
-    case FFGP_LINK_SQUARE: return p * p + c;
-    default: return p;
-  }
-}
-__device__ __forceinline__ double tr_link_der(int kind, double p, double c) {
-  switch (kind) {
-    case FFGP_LINK_INV_ABS_EPS: { const double a = fabs(p) + c; return ((p > 0.0) ? -1.0 : ((p < 0.0) ? 1.0 : 0.0)) / (a * a); }
-    case FFGP_LINK_EXP_NEG: return -exp(-p);
-    case FFGP_LINK_INV: return -1.0 / (p * p);
-    case FFGP_LINK_ABS: return (p > 0.0) ? 1.0 : ((p < 0.0) ? -1.0 : 0.0);
-    case FFGP_LINK_EXP_SQ: { const double e = exp(p); return 2.0 * e * e; }
-    case FFGP_LINK_SQUARE: return 2.0 * p;
-    default: return 1.0;
-  }
-}
-
-// LDS (doubles): S 36 * 272 | Xs [128][17] | Ym, Gam, Am [128][16] each | piv [128] | dvec [128] | small
-#define TR_OFF_XS (NBLK_LOWER * BLKSZ)
-#define TR_OFF_YM (TR_OFF_XS + TR_N * (TR_D + 1))
-#define TR_OFF_GAM (TR_OFF_YM + TR_N * TR_Y)
-#define TR_OFF_AM (TR_OFF_GAM + TR_N * TR_Y)
-#define TR_OFF_PIV (TR_OFF_AM + TR_N * TR_Y)
-#define TR_OFF_DVEC (TR_OFF_PIV + TR_N)
-#define TR_OFF_SMALL (TR_OFF_DVEC + TR_N)
+// LDS (doubles): the shared head of train_tile.h (S | Xs | Ym, Gam, Am | piv | dvec) | small
+#define TR_OFF_SMALL TR_OFF_TAIL
 #define TR_SMALL_DOUBLES (16 + 3 * 20 + 8 + 8 * TR_NRED + TR_NRED + 16)
 #define TR_LDS_DOUBLES (TR_OFF_SMALL + TR_SMALL_DOUBLES)
 // residual launches: the reduction has one more total (dloss/drho), then vl | vh | sgv = sgn(s) vl | diag G [128] each, rsum [8] (per-wave
@@ -270,9 +238,9 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   }
   __syncthreads();
   HELPER_ROLES(flags + 8, wave, hidx, nh);      // helpers of the factorisation's stage [A]
-  if (tid < D) wv[tid] = tr_link_val(M.l.w_link, raw[M.l.w_broadcast ? 0 : tid], M.l.w_c);
-  if (tid == 64) sc[0] = tr_link_val(M.l.amp_link, raw[nw], M.l.amp_c);
-  if (tid == 65) sc[1] = M.dadd ? tr_link_val(M.l.dadd_link, raw[nw + 1], M.l.dadd_c) : 0.0;
+  if (tid < D) wv[tid] = ffgp_link_val(M.l.w_link, raw[M.l.w_broadcast ? 0 : tid], M.l.w_c);
+  if (tid == 64) sc[0] = ffgp_link_val(M.l.amp_link, raw[nw], M.l.amp_c);
+  if (tid == 65) sc[1] = M.dadd ? ffgp_link_val(M.l.dadd_link, raw[nw + 1], M.l.dadd_c) : 0.0;
   __syncthreads();
 
   int failed = 0;
@@ -311,7 +279,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         if (lane == 0) {
           cs[0] = o[0]; cs[1] = o[1]; cs[2] = o[2]; cs[3] = o[3];
           cs[4] = craw[0];
-          sc[0] = tr_link_val(M.l.amp_link, raw[nw], M.l.amp_c) * o[0];
+          sc[0] = ffgp_link_val(M.l.amp_link, raw[nw], M.l.amp_c) * o[0];
         }
       }
     }
@@ -566,17 +534,17 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
           double gr;
           if (tid < nw) {
             if (!M.l.w_broadcast) {
-              gr = oscale * (-tot[4 + tid] / wv[tid]) * tr_link_der(M.l.w_link, raw[tid], M.l.w_c);
+              gr = oscale * (-tot[4 + tid] / wv[tid]) * ffgp_link_der(M.l.w_link, raw[tid], M.l.w_c);
             } else {
               double sg = 0.0;
               for (int k = 0; k < D; ++k) sg += -tot[4 + k] / wv[k];
-              gr = oscale * sg * tr_link_der(M.l.w_link, raw[0], M.l.w_c);
+              gr = oscale * sg * ffgp_link_der(M.l.w_link, raw[0], M.l.w_c);
             }
             if (M.g_w) M.g_w[tid] = gr;
           } else if (tid == nw) {
-            if (M.g_amp) M.g_amp[0] = oscale * tot[1] * tr_link_der(M.l.amp_link, raw[nw], M.l.amp_c);
+            if (M.g_amp) M.g_amp[0] = oscale * tot[1] * ffgp_link_der(M.l.amp_link, raw[nw], M.l.amp_c);
           } else if (M.g_dadd) {
-            M.g_dadd[0] = oscale * tot[2] * (M.dadd ? tr_link_der(M.l.dadd_link, raw[nw + 1], M.l.dadd_c) : 1.0);
+            M.g_dadd[0] = oscale * tot[2] * (M.dadd ? ffgp_link_der(M.l.dadd_link, raw[nw + 1], M.l.dadd_c) : 1.0);
           }
         }
         if (M.g_Y)
@@ -596,22 +564,22 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       double gr;
       if (tid < nw) {
         if (!M.l.w_broadcast) {
-          gr = oscale * (-tot[4 + tid] / wv[tid]) * tr_link_der(M.l.w_link, raw[tid], M.l.w_c);
+          gr = oscale * (-tot[4 + tid] / wv[tid]) * ffgp_link_der(M.l.w_link, raw[tid], M.l.w_c);
         } else {
           double sg = 0.0;
           for (int k = 0; k < D; ++k) sg += -tot[4 + k] / wv[k];
-          gr = oscale * sg * tr_link_der(M.l.w_link, raw[0], M.l.w_c);
+          gr = oscale * sg * ffgp_link_der(M.l.w_link, raw[0], M.l.w_c);
         }
       } else if (tid == nw) {
-        gr = oscale * tot[1] * tr_link_der(M.l.amp_link, raw[nw], M.l.amp_c);
+        gr = oscale * tot[1] * ffgp_link_der(M.l.amp_link, raw[nw], M.l.amp_c);
         if constexpr (CAR) gr *= cs[0];      // (tot[1] = T, with respect to the effective amplitude link(amp_raw) * s)
       } else if (CAR && slot_ > nw + 1) {      // b, l_z, sigma_z: dloss/ds = T link(amp_raw) times the partials of s; b's targets term
-        const double dls = tot[1] * tr_link_val(M.l.amp_link, raw[nw], M.l.amp_c);
+        const double dls = tot[1] * ffgp_link_val(M.l.amp_link, raw[nw], M.l.amp_c);
         const int k = slot_ - nw - 2;
         gr = oscale * dls * cs[1 + k];
         if (k == 0) gr = oscale * (dls * cs[1] - ceb[0] * tot[NRED - 1]);
       } else if (!isres || tid == nw + 1) {
-        gr = oscale * tot[2] * tr_link_der(M.l.dadd_link, raw[nw + 1], M.l.dadd_c);
+        gr = oscale * tot[2] * ffgp_link_der(M.l.dadd_link, raw[nw + 1], M.l.dadd_c);
       } else {
         gr = oscale * tot[NRED - 1];      // rho (raw = effective)
       }
@@ -620,26 +588,21 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       double* const pm_ = (CAR && slot_ > nw + 1) ? cmom + (slot_ - nw - 2) : mom + slot_;
       double* const pv_ = (CAR && slot_ > nw + 1) ? cmo2 + (slot_ - nw - 2) : mo2 + slot_;
       const double bc1 = cm.bc[2 * step], bc2s = cm.bc[2 * step + 1];
-      const double m1 = pm_[0] + (gr - pm_[0]) * (1.0 - cm.b1);              // exp_avg.lerp_(grad, 1 - beta1)
-      const double v1 = pv_[0] * cm.b2 + (1.0 - cm.b2) * gr * gr;             // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-      pm_[0] = m1;
-      pv_[0] = v1;
-      const double denom = sqrt(v1) / bc2s + cm.eps;
-      const double pnew = pr_[0] + (-(cm.lr / bc1)) * (m1 / denom);           // param.addcdiv_(exp_avg, denom, value = -step_size)
-      pr_[0] = pnew;
+      ffgp_adam_update(pr_, pm_, pv_, gr, cm.lr, cm.b1, cm.b2, cm.eps, bc1, bc2s);
+      const double pnew = pr_[0];
       if (CAR && tid == nw + 2) ceb[0] = exp(pnew);
       // the next step's effective value (nobody reads wv / sc between the reduction's barrier and the one below)
       if (tid < nw) {
         if (!M.l.w_broadcast) {
-          wv[tid] = tr_link_val(M.l.w_link, pnew, M.l.w_c);
+          wv[tid] = ffgp_link_val(M.l.w_link, pnew, M.l.w_c);
         } else {
-          const double e_ = tr_link_val(M.l.w_link, pnew, M.l.w_c);
+          const double e_ = ffgp_link_val(M.l.w_link, pnew, M.l.w_c);
           for (int k = 0; k < D; ++k) wv[k] = e_;
         }
       } else if (tid == nw) {
-        sc[0] = tr_link_val(M.l.amp_link, pnew, M.l.amp_c);
+        sc[0] = ffgp_link_val(M.l.amp_link, pnew, M.l.amp_c);
       } else if ((!isres && !(CAR && tid > nw + 1)) || tid == nw + 1) {      // (a CAR member's s is re-formed at the start of the step)
-        sc[1] = tr_link_val(M.l.dadd_link, pnew, M.l.dadd_c);
+        sc[1] = ffgp_link_val(M.l.dadd_link, pnew, M.l.dadd_c);
       }
     }
     LDS_BARRIER();
@@ -732,30 +695,6 @@ bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ff
 // model (in the caller's order) whose Sigma was not positive definite at some step.
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
                        long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r, const ffgp_car_link* cr) {
-  static bool attr_set[64] = {false};
-  if (h->device >= 0 && h->device < 64 && !attr_set[h->device]) {
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_persist_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_persist_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_resid_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES_RES * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_resid_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES_RES * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_v2_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_v2_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<8, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_car_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TR_LDS_DOUBLES_CAR * (int)sizeof(double)));
-    attr_set[h->device] = true;
-  }
   bool any_res = false, any_car = false;
   for (int f = 0; f < F && r; ++f) any_res = any_res || r[f].rho_dev != nullptr;
   for (int f = 0; f < F && cr; ++f) any_car = any_car || cr[f].b_dev != nullptr;
@@ -770,38 +709,17 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
       if (cls(f) == k) pos[f] = q++;
     cbeg[k + 1] = q;
   }
-  const int nv1 = cbeg[1];
-  // one device block: [F models | F residual links (residual launches) | 2 steps bias corrections | 2 F status ints | F x 36 x 256 kernel
-  // values]; its first four parts are staged in pinned host memory owned by the handle (an asynchronous copy from a temporary would have
-  // to be waited for)
-  const size_t tab_bytes = (size_t)F * sizeof(TrainModel);
-  const size_t res_off = (tab_bytes + 255) / 256 * 256;
-  const size_t car_off = any_res ? res_off + ((size_t)F * sizeof(TrainResid) + 255) / 256 * 256 : res_off;
-  const size_t bc_off = any_car ? car_off + ((size_t)F * sizeof(TrainCar) + 255) / 256 * 256 : car_off;
-  const size_t info_off = bc_off + ((size_t)2 * steps * sizeof(double) + 255) / 256 * 256;
-  const size_t head = info_off + (size_t)2 * F * sizeof(int);
-  const size_t k_off = (head + 255) / 256 * 256;
-  const size_t need = k_off + (size_t)F * NBLK_LOWER * 256 * sizeof(double);
-  if (need > h->train_tab_bytes) {
-    FFGP_HIP(hipStreamSynchronize(h->stream));
-    if (h->train_tab) hipFree(h->train_tab);
-    if (h->train_host) hipHostFree(h->train_host);
-    h->train_tab = nullptr;
-    h->train_host = nullptr;
-    h->train_tab_bytes = 0;
-    const size_t cap = need + need / 2;
-    if (hipMalloc(&h->train_tab, cap) != hipSuccess || hipHostMalloc(&h->train_host, cap, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      if (h->train_tab) hipFree(h->train_tab);
-      h->train_tab = nullptr;
-      return FFGP_ERR_ALLOC;
-    }
-    h->train_tab_bytes = cap;
-  }
-  char* host = reinterpret_cast<char*>(h->train_host);      // (the previous call on this handle was synchronous: the buffer is free)
-  memset(host, 0, head);
-  char* dev = reinterpret_cast<char*>(h->train_tab);
-  TrainModel* tm = reinterpret_cast<TrainModel*>(host);
+  // the call's block (train_host.h); the tables: [F models | F residual links (residual launches) | F CAR links (CAR launches)], the
+  // scratch: F x 36 x 256 kernel values
+  TrainLayout lay;
+  const size_t tab_off = lay.take((size_t)F * sizeof(TrainModel));
+  const size_t res_off = any_res ? lay.take((size_t)F * sizeof(TrainResid)) : 0;
+  const size_t car_off = any_car ? lay.take((size_t)F * sizeof(TrainCar)) : 0;
+  TrainBlock blk;
+  FFGP_CHECK(train_block_open(h, lay, F, steps, opt, step0, (size_t)F * NBLK_LOWER * 256 * sizeof(double), &blk));
+  char* const host = blk.host;
+  char* const dev = blk.dev;
+  TrainModel* tm = reinterpret_cast<TrainModel*>(host + tab_off);
   for (int f = 0; f < F; ++f) {
     const ffgp_problem& q = p[f];
     TrainModel& m = tm[pos[f]];
@@ -813,7 +731,7 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     m.clamp = q.clamp_min; m.rinv = (q.kparam != 0.0) ? 1.0 / q.kparam : 1.0; m.pi_const = q.pi_const; m.kfun = q.kfun;
     m.state = state_dev + (size_t)f * state_stride;
     m.trace = trace_dev + (size_t)f * trace_stride;
-    m.kbuf = reinterpret_cast<double*>(dev + k_off) + (size_t)pos[f] * NBLK_LOWER * 256;
+    m.kbuf = reinterpret_cast<double*>(dev + blk.scratch_off) + (size_t)pos[f] * NBLK_LOWER * 256;
     m.want_grad = 1;
   }
   if (any_res) {
@@ -842,18 +760,9 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
       t.b_last = q.b_last_dev;
     }
   }
-  double* bc = reinterpret_cast<double*>(host + bc_off);
-  for (int k = 0; k < steps; ++k) {
-    const double t = (double)(step0 + k + 1);
-    bc[2 * k] = 1.0 - std::pow(opt->beta1, t);
-    bc[2 * k + 1] = std::sqrt(1.0 - std::pow(opt->beta2, t));
-  }
-  FFGP_HIP(hipMemcpyAsync(dev, host, head, hipMemcpyHostToDevice, h->stream));
+  FFGP_HIP(hipMemcpyAsync(dev, host, blk.head, hipMemcpyHostToDevice, h->stream));
   TrainCommon cm;
-  cm.steps = steps; cm.lr = opt->lr; cm.b1 = opt->beta1; cm.b2 = opt->beta2; cm.eps = opt->eps;
-  cm.bc = reinterpret_cast<const double*>(dev + bc_off);
-  cm.info = reinterpret_cast<int*>(dev + info_off);
-  cm.fail_step = cm.info + F;
+  static_cast<TrainLoop&>(cm) = blk.loop;
   cm.shared_info = nullptr;
   cm.info_max = 0;
   cm.prof = nullptr;
@@ -864,48 +773,26 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
   }
   int Dm[4] = {0, 0, 0, 0};
   for (int f = 0; f < F; ++f) Dm[cls(f)] = std::max(Dm[cls(f)], p[f].D);
-  const int Dmax = Dm[0], Dmax2 = Dm[1];
-  const TrainResid* rtab = reinterpret_cast<const TrainResid*>(dev + res_off);
-  if (nv1 == 0) {
-  } else if (any_res && Dmax <= 8)
-    hipLaunchKernelGGL(ffgp_train_resid_kernel<8>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
-                       reinterpret_cast<const TrainModel*>(dev), rtab, cm);
-  else if (any_res)
-    hipLaunchKernelGGL(ffgp_train_resid_kernel<16>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES_RES * sizeof(double), h->stream,
-                       reinterpret_cast<const TrainModel*>(dev), rtab, cm);
-  else if (Dmax <= 8)
-    hipLaunchKernelGGL(ffgp_train_persist_kernel<8>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream,
-                       reinterpret_cast<const TrainModel*>(dev), cm);
-  else
-    hipLaunchKernelGGL(ffgp_train_persist_kernel<16>, dim3(nv1), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream,
-                       reinterpret_cast<const TrainModel*>(dev), cm);
-  for (int k = 1; k < 4; ++k) {      // the other classes: rows cbeg[k] .. cbeg[k + 1] - 1 of the tables and of the status words
+  for (int k = 0; k < 4; ++k) {      // class k: rows cbeg[k] .. cbeg[k + 1] - 1 of the tables and of the status words
     const int nk = cbeg[k + 1] - cbeg[k];
     if (nk == 0) continue;
     TrainCommon c2 = cm;
     c2.info = cm.info + cbeg[k];
     c2.fail_step = cm.fail_step + cbeg[k];
-    const TrainModel* tab2 = reinterpret_cast<const TrainModel*>(dev) + cbeg[k];
+    const TrainModel* tab = reinterpret_cast<const TrainModel*>(dev + tab_off) + cbeg[k];
+    const TrainResid* rtab = reinterpret_cast<const TrainResid*>(dev + res_off);      // (class 0 begins at row 0)
     const TrainCar* ctab = reinterpret_cast<const TrainCar*>(dev + car_off) + cbeg[k];
-    const size_t lds_car = TR_LDS_DOUBLES_CAR * sizeof(double);
-    if (k == 1 && Dmax2 <= 8)
-      hipLaunchKernelGGL(ffgp_train_v2_kernel<8>, dim3(nk), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream, tab2, c2);
-    else if (k == 1)
-      hipLaunchKernelGGL(ffgp_train_v2_kernel<16>, dim3(nk), dim3(TR_T), TR_LDS_DOUBLES * sizeof(double), h->stream, tab2, c2);
-    else if (k == 2 && Dm[2] <= 8)
-      hipLaunchKernelGGL((ffgp_train_car_kernel<8, false>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
-    else if (k == 2)
-      hipLaunchKernelGGL((ffgp_train_car_kernel<16, false>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
-    else if (Dm[3] <= 8)
-      hipLaunchKernelGGL((ffgp_train_car_kernel<8, true>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
-    else
-      hipLaunchKernelGGL((ffgp_train_car_kernel<16, true>), dim3(nk), dim3(TR_T), lds_car, h->stream, tab2, ctab, c2);
+    const size_t lds = TR_LDS_DOUBLES * sizeof(double), lds_res = TR_LDS_DOUBLES_RES * sizeof(double), lds_car = TR_LDS_DOUBLES_CAR * sizeof(double);
+    // (a lambda per kernel, in this order: the instantiations are emitted kernel by kernel, <8> then <16>, as they always were)
+    int rc;
+    if (k == 0 && !any_res) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_persist_kernel<dm()>, lds, nk, tab, c2); });
+    else if (k == 0) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_resid_kernel<dm()>, lds_res, nk, tab, rtab, c2); });
+    else if (k == 1) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_v2_kernel<dm()>, lds, nk, tab, c2); });
+    else if (k == 2) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_car_kernel<dm(), false>, lds_car, nk, tab, ctab, c2); });
+    else rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_car_kernel<dm(), true>, lds_car, nk, tab, ctab, c2); });
+    FFGP_CHECK(rc);
   }
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-  int* st = reinterpret_cast<int*>(host + info_off);
-  FFGP_HIP(hipMemcpyAsync(st, cm.info, (size_t)2 * F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  FFGP_HIP(hipStreamSynchronize(h->stream));
-  ffgp_invalidate(h);
+  const int rc = train_block_finish(h, blk, F, pos.data());
   if (cm.prof) {
     long pr[12];
     hipMemcpy(pr, cm.prof, sizeof(pr), hipMemcpyDeviceToHost);
@@ -919,9 +806,7 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     }
     fprintf(stderr, " | sum %.2f\n", tot);
   }
-  for (int f = 0; f < F; ++f)
-    if (st[pos[f]] != 0) return st[pos[f]];
-  return FFGP_OK;
+  return rc;
 }
 
 // ---- evaluate mode: one likelihood (+ gradients) of F small problems, ONE launch per eight of them ---------------------------------

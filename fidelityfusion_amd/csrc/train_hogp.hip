@@ -558,10 +558,8 @@ int ffgp_train_hogp_raw(ffgp_handle* h, int F, const ffgp_hogp_model* mo, const 
       aa.w_link = l[f].w_link; aa.amp_link = l[f].amp_link; aa.w_c = l[f].w_c; aa.amp_c = l[f].amp_c;
       aa.gk = w.gk; aa.gV = w.gV; aa.scal = w.scal; aa.info = w.info; aa.st = w.st; aa.nd = (double)w.nd;
       aa.state = state_dev + (size_t)f * state_stride;
-      const double t = (double)(step0[f] + k + 1);
       aa.lr = opt->lr; aa.b1 = opt->beta1; aa.b2 = opt->beta2; aa.eps = opt->eps;
-      aa.bc1 = 1.0 - std::pow(opt->beta1, t);
-      aa.bc2_sqrt = std::sqrt(1.0 - std::pow(opt->beta2, t));
+      ffgp_adam_bc(opt, step0[f], k, &aa.bc1, &aa.bc2_sqrt);
       aa.trace = trace_dev + (size_t)f * trace_stride; aa.step = k;
       hipLaunchKernelGGL(ffgp_hogp_adam_kernel, dim3(1), dim3(256), 0, h->stream, aa);
       HG_STAGE(hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP);

@@ -216,8 +216,7 @@ extern "C" __global__ void ffgp_adam_car_kernel(int F, ffgp_train_slot sl, ffgp_
 static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, int steps,
                       const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride,
                       const ffgp_car_link* cr = nullptr) {
-  if (!h || !p || !l || !opt || !state_dev || !trace_dev || F <= 0 || F > FFGP_TRAIN_MAXF || steps <= 0 || step0 < 0 || trace_stride < steps)
-    return FFGP_ERR_ARG;
+  if (!ffgp_train_args_ok(h, p, l, opt, state_dev, trace_dev, F, steps, step0, trace_stride)) return FFGP_ERR_ARG;
   ffgp_train_slot sl;
   bool all_small = true, any_res = false, any_car = false;
   for (int f = 0; f < F; ++f) {
@@ -347,16 +346,16 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
       if (lrc != FFGP_OK) break;
     }
     if (any_res) hipLaunchKernelGGL(ffgp_resid_grad, dim3(F), dim3(256), 0, h->stream, rs, gbuf);
-    const double t = (double)(step0 + k + 1);
-    const double bc1 = 1.0 - std::pow(opt->beta1, t), bc2 = 1.0 - std::pow(opt->beta2, t);
+    double bc1, bc2_sqrt;
+    ffgp_adam_bc(opt, step0, k, &bc1, &bc2_sqrt);
     if (any_car) {
       hipLaunchKernelGGL(ffgp_car_grad, dim3(F), dim3(256), 0, h->stream, cs, gbuf);
       hipLaunchKernelGGL(ffgp_adam_car_kernel, dim3(F), dim3(192), 0, h->stream, F, sl, cs, gbuf, state_dev, state_stride, opt->lr, opt->beta1,
-                         opt->beta2, opt->eps, bc1, std::sqrt(bc2), loss, trace_dev, trace_stride, k, h->d_info);
+                         opt->beta2, opt->eps, bc1, bc2_sqrt, loss, trace_dev, trace_stride, k, h->d_info);
       continue;
     }
     hipLaunchKernelGGL(ffgp_adam_kernel, dim3(F), dim3(192), 0, h->stream, F, sl, gbuf, state_dev, state_stride, opt->lr, opt->beta1,
-                       opt->beta2, opt->eps, bc1, std::sqrt(bc2), loss, trace_dev, trace_stride, k, h->d_info, h->fold_info,
+                       opt->beta2, opt->eps, bc1, bc2_sqrt, loss, trace_dev, trace_stride, k, h->d_info, h->fold_info,
                        (h->fold_info && !one_kernel) ? h->d_link + 256 : (const double*)nullptr, lk[0], p[0].D,
                        (lk[0].out_scale == 0.0) ? 1.0 : lk[0].out_scale);
   }

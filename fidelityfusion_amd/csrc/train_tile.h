@@ -1,7 +1,8 @@
 // The device pieces of the one-launch trainers, shared by train.hip (one radial kernel: tr_body) and train_tree_lds.hip (a SumKernel /
 // ProductKernel tree: ttl_body): the wave sum, the 16 x 16 block chains on the LDS block image of diag_block.h, the deal of the blocks to
 // the waves, and the phases of a step that do not depend on how Sigma was assembled -- the blocked Cholesky with its inverse, the last
-// row block of the inverse, Gamma = L^-1 Y and A = L^-T Gamma.  The arithmetic is train.hip's, moved here unchanged.
+// row block of the inverse, Gamma = L^-1 Y and A = L^-T Gamma.  The arithmetic is train.hip's, moved here unchanged.  Also what the two
+// kernels and their host drivers (train_host.h) agree on: the head of the LDS layout and the step loop's arguments.
 #pragma once
 #include "ffgp_internal.h"
 #include "diag_block.h"
@@ -10,6 +11,25 @@
 #define TR_N 128
 #define TR_D 16
 #define TR_Y 16
+
+// The head of both kernels' LDS (doubles), the layout the stage functions below assume: S 36 * 272 | Xs [128][17] | Ym, Gam, Am [128][16]
+// each | piv [128] | dvec [128]; a kernel's own tail begins at TR_OFF_TAIL.
+#define TR_OFF_XS (NBLK_LOWER * BLKSZ)
+#define TR_OFF_YM (TR_OFF_XS + TR_N * (TR_D + 1))
+#define TR_OFF_GAM (TR_OFF_YM + TR_N * TR_Y)
+#define TR_OFF_AM (TR_OFF_GAM + TR_N * TR_Y)
+#define TR_OFF_PIV (TR_OFF_AM + TR_N * TR_Y)
+#define TR_OFF_DVEC (TR_OFF_PIV + TR_N)
+#define TR_OFF_TAIL (TR_OFF_DVEC + TR_N)
+
+// The step loop's arguments, by value to every one-launch trainer's kernel; filled in one place (train_block_open, train_host.h).
+struct TrainLoop {
+  int steps;
+  double lr, b1, b2, eps;
+  const double* bc;                      // [steps][2]: 1 - beta1^t, sqrt(1 - beta2^t) (ffgp_adam_bc_table, drivers.h)
+  int* info;                             // [models] status: 0, or the 1-based index of the first non-positive pivot of the step that failed
+  int* fail_step;                        // [models] the step at which it happened
+};
 
 // sum over the 64 lanes of the wave, in all of them: four DPP steps inside the rows of 16 lanes, then the rows exchanged by gfx950's
 // row swaps (the shuffle form, ds_bpermute, is an LDS crossbar round trip per step: 6 dependent trips per value)

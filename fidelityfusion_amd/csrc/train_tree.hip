@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "drivers.h"
+#include "tree_ops.h"
 
 #define FFGP_TREE_MAXL 4
 // one member, as both kernels read it from device memory (F <= 16 of them: too large for a kernel argument)
@@ -107,8 +108,7 @@ extern "C" __global__ void ffgp_tree_adam_kernel(int F, int pmax, const ffgp_tre
 
 extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* l, int steps, const ffgp_adam* opt,
                                    double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
-  if (!h || !p || !l || !opt || !state_dev || !trace_dev || F <= 0 || F > FFGP_TRAIN_MAXF || steps <= 0 || step0 < 0 || trace_stride < steps)
-    return FFGP_ERR_ARG;
+  if (!ffgp_train_args_ok(h, p, l, opt, state_dev, trace_dev, F, steps, step0, trace_stride)) return FFGP_ERR_ARG;
   std::vector<ffgp_tree_member> tab(F);
   std::vector<ffgp_problem> pq(p, p + F);                        // the shadow problems: trees whose leaves read the effective parameters
   std::vector<ffgp_ktree> tq(F);
@@ -131,9 +131,7 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
     for (int e = 0; e < nl; ++e) {
       const ffgp_kdesc& k = t->leaf[e];
       const ffgp_leaf_links& ll = l[f].leaf[e];
-      const bool linear = (k.kfun == FFGP_KFUN_LINEAR);
-      if (!k.w_dev || !k.amp_dev || !(linear || (k.kfun >= FFGP_KFUN_SE && k.kfun <= FFGP_KFUN_MATERN52))) return FFGP_ERR_ARG;
-      if (ll.center_train && !(linear && k.center_dev)) return FFGP_ERR_ARG;
+      if (!ffgp_tree_leaf_trainable(k, ll)) return FFGP_ERR_ARG;
       M.w[e] = const_cast<double*>(k.w_dev);
       M.amp[e] = const_cast<double*>(k.amp_dev);
       M.cen[e] = ll.center_train ? const_cast<double*>(k.center_dev) : nullptr;
@@ -202,10 +200,10 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
     hipLaunchKernelGGL(ffgp_tree_link_fwd, dim3(F), dim3(256), 0, h->stream, tab_dev, scratch);
     for (int f = 0; f < F && lrc == FFGP_OK; ++f) lrc = ffgp_nlml_fused_async(h, &pq[f], loss + f, &g[f]);
     if (lrc != FFGP_OK) break;
-    const double t = (double)(step0 + k + 1);
-    const double bc1 = 1.0 - std::pow(opt->beta1, t), bc2 = 1.0 - std::pow(opt->beta2, t);
+    double bc1, bc2_sqrt;
+    ffgp_adam_bc(opt, step0, k, &bc1, &bc2_sqrt);
     hipLaunchKernelGGL(ffgp_tree_adam_kernel, dim3(1), dim3(256), 0, h->stream, F, pmax, tab_dev, scratch, state_dev, state_stride, opt->lr,
-                       opt->beta1, opt->beta2, opt->eps, bc1, std::sqrt(bc2), loss, trace_dev, trace_stride, k, h->d_info);
+                       opt->beta1, opt->beta2, opt->eps, bc1, bc2_sqrt, loss, trace_dev, trace_stride, k, h->d_info);
   }
   h->defer_info_copy = 0;
   h->fold_info = 0;

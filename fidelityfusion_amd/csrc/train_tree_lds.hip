@@ -30,11 +30,10 @@
 // A Sigma that is not positive definite stops THAT model at that step (its status word, NaN in its trace from there on, parameters
 // and moments as they were when the step began); the other models of the launch train on -- train.hip's rule.
 // Covers n <= 128, D <= 16, d <= 16, V1 likelihood, diag_add and diag_vec, leaves SE/ARD, Matern 1/2, 3/2, 5/2 and linear.
-#include <algorithm>
-#include <cmath>
-
-#include "drivers.h"
-#include "train_tile.h"
+// HOST side: the scaffold of train_host.h, shared with train.hip (block and pinned mirror on the handle, bias corrections, loop arguments,
+// dispatch, launch, status epilogue); this file adds the member description (ttl_describe) and its one table.  LDS: train_tile.h's head,
+// then this kernel's tail.
+#include "train_host.h"
 #include "tree_ops.h"
 
 #define TTL_L FFGP_TREE_LEAVES
@@ -63,27 +62,15 @@ struct TtlModel {
   double* wbuf;                          // [TTL_WBUF] the entries' per-leaf weights, pass 1 -> pass 2 of the same step
   TtlLeaf k[TTL_L];
 };
-struct TtlCommon {
-  int steps;
-  double lr, b1, b2, eps;
-  const double* bc;                      // [steps][2]: 1 - beta1^t, sqrt(1 - beta2^t), from the host's pow as Python computes them
-  int* info;                             // [models] 0, or the 1-based index of the first non-positive pivot of the step that failed
-  int* fail_step;                        // [models]
-};
+struct TtlCommon : TrainLoop {};         // (the loop's arguments under the name the kernel's symbol was built with)
 struct TtlTree {
   int nl, shape, op[3];
 };
 
-// LDS (doubles): S 36 * 272 | Xs [128][17] | Ym, Gam, Am [128][16] each | piv [128] | dvec [128] | per leaf wv, w2, cen [4][16] each and
+// LDS (doubles): the shared head of train_tile.h (S | Xs | Ym, Gam, Am | piv | dvec) | per leaf wv, w2, cen [4][16] each and
 // (amp, clamp, 1 / kparam, -) [4][4] | raw, exp_avg, exp_avg_sq, totals [136] each | dadd [8] | ints: parameter map [136], leaf kfun [4],
 // tree [5], pad, flags + SIMD words [16]
-#define TTL_OFF_XS (NBLK_LOWER * BLKSZ)
-#define TTL_OFF_YM (TTL_OFF_XS + TR_N * (TR_D + 1))
-#define TTL_OFF_GAM (TTL_OFF_YM + TR_N * TR_Y)
-#define TTL_OFF_AM (TTL_OFF_GAM + TR_N * TR_Y)
-#define TTL_OFF_PIV (TTL_OFF_AM + TR_N * TR_Y)
-#define TTL_OFF_DVEC (TTL_OFF_PIV + TR_N)
-#define TTL_OFF_LEAF (TTL_OFF_DVEC + TR_N)
+#define TTL_OFF_LEAF TR_OFF_TAIL
 #define TTL_OFF_PAR (TTL_OFF_LEAF + 3 * TTL_L * TR_D + 4 * TTL_L)
 #define TTL_OFF_SC (TTL_OFF_PAR + 4 * TTL_PPAD)
 #define TTL_OFF_INT (TTL_OFF_SC + 8)
@@ -126,12 +113,12 @@ __global__ __launch_bounds__(TR_T) void ffgp_train_tree_lds_kernel(const TtlMode
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const TtlModel* __restrict__ M = tab + blockIdx.x;
   double* S = lds;
-  double* Xs = lds + TTL_OFF_XS;
-  double* Ym = lds + TTL_OFF_YM;
-  double* Gam = lds + TTL_OFF_GAM;
-  double* Am = lds + TTL_OFF_AM;
-  double* piv = lds + TTL_OFF_PIV;
-  double* dvec = lds + TTL_OFF_DVEC;
+  double* Xs = lds + TR_OFF_XS;
+  double* Ym = lds + TR_OFF_YM;
+  double* Gam = lds + TR_OFF_GAM;
+  double* Am = lds + TR_OFF_AM;
+  double* piv = lds + TR_OFF_PIV;
+  double* dvec = lds + TR_OFF_DVEC;
   double* wv = lds + TTL_OFF_LEAF;         // [leaf][16] effective inverse length scales
   double* w2 = wv + TTL_L * TR_D;          // [leaf][16] their squares (zero past D)
   double* cen = w2 + TTL_L * TR_D;         // [leaf][16] a linear leaf's centre (zero past D, and for the origin)
@@ -504,10 +491,7 @@ static bool ttl_describe(const ffgp_problem& q, const ffgp_tree_links& l, long s
   const ffgp_ktree* t = q.tree;
   if (!t || q.pair || q.cov_dev || q.add_mat_dev || q.add_all != 0.0 || q.mean_jitter != 0.0 || q.ll_variant != FFGP_LL_V1) return false;
   if (q.n <= 0 || q.n > TR_N || q.D <= 0 || q.D > TR_D || q.d <= 0 || q.d > TR_Y || !q.X_dev || !q.Y_dev || !q.diag_add_dev) return false;
-  if (!t->leaf || t->n_leaves < 2 || t->n_leaves > TTL_L) return false;
-  if (t->n_leaves == 4 && t->shape != FFGP_TREE_CHAIN && t->shape != FFGP_TREE_BALANCED) return false;
-  for (int i = 0; i + 1 < t->n_leaves; ++i)
-    if (t->op[i] != FFGP_KOP_SUM && t->op[i] != FFGP_KOP_PRODUCT) return false;
+  if (!ffgp_tree_form_ok(t)) return false;
   memset(&m, 0, sizeof(m));
   m.n = q.n; m.D = q.D; m.d = q.d;
   m.nl = t->n_leaves; m.shape = (t->n_leaves == 4) ? t->shape : FFGP_TREE_CHAIN;
@@ -517,8 +501,7 @@ static bool ttl_describe(const ffgp_problem& q, const ffgp_tree_links& l, long s
     const ffgp_kdesc& k = t->leaf[e];
     const ffgp_leaf_links& ll = l.leaf[e];
     const bool linear = (k.kfun == FFGP_KFUN_LINEAR);
-    if (!k.w_dev || !k.amp_dev || !(linear || (k.kfun >= FFGP_KFUN_SE && k.kfun <= FFGP_KFUN_MATERN52))) return false;
-    if (ll.center_train && !(linear && k.center_dev)) return false;
+    if (!ffgp_tree_leaf_trainable(k, ll)) return false;
     TtlLeaf& lf = m.k[e];
     lf.w = const_cast<double*>(k.w_dev); lf.amp = const_cast<double*>(k.amp_dev);
     lf.cen = linear ? const_cast<double*>(k.center_dev) : nullptr;
@@ -538,8 +521,7 @@ static bool ttl_describe(const ffgp_problem& q, const ffgp_tree_links& l, long s
 
 extern "C" int ffgp_train_tree_lds_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* l, int steps, const ffgp_adam* opt,
                                        double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
-  if (!h || !p || !l || !opt || !state_dev || !trace_dev || F <= 0 || F > FFGP_TRAIN_MAXF || steps <= 0 || step0 < 0 || trace_stride < steps)
-    return FFGP_ERR_ARG;
+  if (!ffgp_train_args_ok(h, p, l, opt, state_dev, trace_dev, F, steps, step0, trace_stride)) return FFGP_ERR_ARG;
   TtlModel tm[FFGP_TRAIN_MAXF];
   int Dmax = 0;
   for (int f = 0; f < F; ++f) {      // (every member is checked before anything is allocated or enqueued)
@@ -547,71 +529,23 @@ extern "C" int ffgp_train_tree_lds_raw(ffgp_handle* h, int F, const ffgp_problem
     Dmax = std::max(Dmax, p[f].D);
   }
   FFGP_HIP(hipSetDevice(h->device));
-  static bool attr_set[64] = {false};
-  if (h->device >= 0 && h->device < 64 && !attr_set[h->device]) {
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_tree_lds_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TTL_LDS_DOUBLES * (int)sizeof(double)));
-    FFGP_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ffgp_train_tree_lds_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 TTL_LDS_DOUBLES * (int)sizeof(double)));
-    attr_set[h->device] = true;
-  }
-  // one device block: [F models | 2 steps bias corrections | 2 F status ints | F x TTL_WBUF weights]; its first three parts are staged
-  // in pinned host memory owned by the handle (the call is synchronous: the buffers are free when it returns)
-  const size_t bc_off = ((size_t)F * sizeof(TtlModel) + 255) / 256 * 256;
-  const size_t info_off = bc_off + ((size_t)2 * steps * sizeof(double) + 255) / 256 * 256;
-  const size_t head = info_off + (size_t)2 * F * sizeof(int);
-  const size_t w_off = (head + 255) / 256 * 256;
-  const size_t need = w_off + (size_t)F * TTL_WBUF * sizeof(double);
-  if (need > h->train_ttl_bytes || head > h->train_ttl_host_bytes) {
-    FFGP_HIP(hipStreamSynchronize(h->stream));
-    if (h->train_ttl) hipFree(h->train_ttl);
-    if (h->train_ttl_host) hipHostFree(h->train_ttl_host);
-    h->train_ttl = nullptr;
-    h->train_ttl_host = nullptr;
-    h->train_ttl_bytes = h->train_ttl_host_bytes = 0;
-    const size_t cap = need + need / 2, hcap = 2 * head;
-    if (hipMalloc(&h->train_ttl, cap) != hipSuccess || hipHostMalloc(&h->train_ttl_host, hcap, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      if (h->train_ttl) hipFree(h->train_ttl);
-      h->train_ttl = nullptr;
-      return FFGP_ERR_ALLOC;
-    }
-    h->train_ttl_bytes = cap;
-    h->train_ttl_host_bytes = hcap;
-  }
-  char* host = reinterpret_cast<char*>(h->train_ttl_host);
-  char* dev = reinterpret_cast<char*>(h->train_ttl);
-  memset(host, 0, head);
+  // the call's block (train_host.h); the table: F models, the scratch: F x TTL_WBUF weights
+  TrainLayout lay;
+  const size_t tab_off = lay.take((size_t)F * sizeof(TtlModel));
+  TrainBlock blk;
+  FFGP_CHECK(train_block_open(h, lay, F, steps, opt, step0, (size_t)F * TTL_WBUF * sizeof(double), &blk));
   for (int f = 0; f < F; ++f) {
     tm[f].state = state_dev + (size_t)f * state_stride;
     tm[f].trace = trace_dev + (size_t)f * trace_stride;
-    tm[f].wbuf = reinterpret_cast<double*>(dev + w_off) + (size_t)f * TTL_WBUF;
+    tm[f].wbuf = reinterpret_cast<double*>(blk.dev + blk.scratch_off) + (size_t)f * TTL_WBUF;
   }
-  memcpy(host, tm, (size_t)F * sizeof(TtlModel));
-  double* bc = reinterpret_cast<double*>(host + bc_off);
-  for (int k = 0; k < steps; ++k) {
-    const double t = (double)(step0 + k + 1);
-    bc[2 * k] = 1.0 - std::pow(opt->beta1, t);
-    bc[2 * k + 1] = std::sqrt(1.0 - std::pow(opt->beta2, t));
-  }
-  FFGP_HIP(hipMemcpyAsync(dev, host, head, hipMemcpyHostToDevice, h->stream));
+  memcpy(blk.host + tab_off, tm, (size_t)F * sizeof(TtlModel));
+  FFGP_HIP(hipMemcpyAsync(blk.dev, blk.host, blk.head, hipMemcpyHostToDevice, h->stream));
   TtlCommon cm;
-  cm.steps = steps; cm.lr = opt->lr; cm.b1 = opt->beta1; cm.b2 = opt->beta2; cm.eps = opt->eps;
-  cm.bc = reinterpret_cast<const double*>(dev + bc_off);
-  cm.info = reinterpret_cast<int*>(dev + info_off);
-  cm.fail_step = cm.info + F;
-  if (Dmax <= 8)
-    hipLaunchKernelGGL(ffgp_train_tree_lds_kernel<8>, dim3(F), dim3(TR_T), TTL_LDS_DOUBLES * sizeof(double), h->stream,
-                       reinterpret_cast<const TtlModel*>(dev), cm);
-  else
-    hipLaunchKernelGGL(ffgp_train_tree_lds_kernel<16>, dim3(F), dim3(TR_T), TTL_LDS_DOUBLES * sizeof(double), h->stream,
-                       reinterpret_cast<const TtlModel*>(dev), cm);
-  if (hipGetLastError() != hipSuccess) return FFGP_ERR_HIP;
-  int* st = reinterpret_cast<int*>(host + info_off);
-  FFGP_HIP(hipMemcpyAsync(st, cm.info, (size_t)2 * F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  FFGP_HIP(hipStreamSynchronize(h->stream));
-  ffgp_invalidate(h);
-  for (int f = 0; f < F; ++f)
-    if (st[f] != 0) return st[f];
-  return FFGP_OK;
+  static_cast<TrainLoop&>(cm) = blk.loop;
+  const TtlModel* tab = reinterpret_cast<const TtlModel*>(blk.dev + tab_off);
+  FFGP_CHECK(tr_by_dm(Dmax, [&](auto dm) {
+    return train_launch(h, ffgp_train_tree_lds_kernel<dm()>, TTL_LDS_DOUBLES * sizeof(double), F, tab, cm);
+  }));
+  return train_block_finish(h, blk, F, nullptr);      // (the table is in the caller's order)
 }

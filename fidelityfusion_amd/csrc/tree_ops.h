@@ -1,6 +1,6 @@
 // The canonical Sum / Product trees of include/ffgp.h (2-4 leaves) on the leaves' values, for the kernels that evaluate a composed kernel
 // entry by entry in registers: the acquisition loop (acq_tree.hip) and the one-launch trainer (train_tree_lds.hip).  A: any struct with
-// nl, shape and op[3] (FFGP_KOP_*; shape = FFGP_TREE_CHAIN | FFGP_TREE_BALANCED, read at nl = 4).
+// nl, shape and op[3] (FFGP_KOP_*; shape = FFGP_TREE_CHAIN | FFGP_TREE_BALANCED, read at nl = 4).  At the end, the hosts' checks of a tree.
 #pragma once
 #include "ffgp_internal.h"
 
@@ -52,4 +52,19 @@ __device__ __forceinline__ void ffgp_tree_back(const A& a, const double (&v)[FFG
   const bool p0 = a.op[0] == FFGP_KOP_PRODUCT;
   gv[0] = p0 ? gt0 * v[1] : gt0;
   gv[1] = p0 ? gt0 * v[0] : gt0;
+}
+
+// ---- the host side: what every entry that is handed an ffgp_ktree (not null) refuses about its form -- 2-4 leaves, one of the two
+//      shapes at four, Sum / Product nodes -- and what the tree trainers refuse about a leaf they are to train
+static inline bool ffgp_tree_form_ok(const ffgp_ktree* t) {
+  if (!t->leaf || t->n_leaves < 2 || t->n_leaves > FFGP_TREE_LEAVES) return false;
+  if (t->n_leaves == 4 && t->shape != FFGP_TREE_CHAIN && t->shape != FFGP_TREE_BALANCED) return false;
+  for (int i = 0; i + 1 < t->n_leaves; ++i)
+    if (t->op[i] != FFGP_KOP_SUM && t->op[i] != FFGP_KOP_PRODUCT) return false;
+  return true;
+}
+static inline bool ffgp_tree_leaf_trainable(const ffgp_kdesc& k, const ffgp_leaf_links& ll) {
+  const bool linear = (k.kfun == FFGP_KFUN_LINEAR);
+  if (!k.w_dev || !k.amp_dev || !(linear || (k.kfun >= FFGP_KFUN_SE && k.kfun <= FFGP_KFUN_MATERN52))) return false;
+  return !ll.center_train || (linear && k.center_dev);
 }

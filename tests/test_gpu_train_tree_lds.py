@@ -235,6 +235,55 @@ def test_sixteen_models_in_one_call_train_each_as_alone():
             assert np.array_equal(a, b), f
 
 
+def _on_a_handle_of_its_own(fn):
+    """fn() with this thread's library calls on a handle created here and destroyed behind it.  (The raw-parameter path lives on
+    slot 0 of its GPU, so the new handle takes that slot for the time being.)"""
+    from fidelityfusion_amd import _lib
+    with _lib._lock:
+        kept = _lib._handles.pop((0, 0), None)
+    try:
+        h = _lib.handle(0)
+        assert kept is None or h.value != kept.value
+        return fn()
+    finally:
+        torch.cuda.synchronize()
+        with _lib._lock:
+            h = _lib._handles.pop((0, 0), None)
+            if kept is not None:
+                _lib._handles[(0, 0)] = kept
+        if h is not None:
+            _lib.check(_lib.lib.ffgp_destroy(h), "ffgp_destroy")
+
+
+def test_the_two_one_launch_drivers_share_the_handles_block():
+    """ffgp_train_persist and ffgp_train_tree_lds_raw keep their tables, status words and scratch in ONE block of the handle.  Four calls
+    on one handle -- 2 ARD models (the block is made), 3 tree models (the tree driver grows it), 5 ARD models (the plain driver reuses it,
+    smaller), 1 tree model (the tree driver reuses it, smaller) -- against the same four calls each on a handle of its own, the first call
+    of that handle: traces, parameters and Adam state bit for bit (one workgroup per model, no atomics: the kernels are deterministic)"""
+    from fidelityfusion_amd.cigp_v10 import train_many
+    calls = [([(17, 2, 1, "ard", False)] * 2, False), ([(33, 2, 1, LM, False)] * 3, True), ([(80, 9, 3, "ard", False)] * 5, False),
+             ([(17, 2, 1, LM, False)], True)]
+    made = [make_models(members, 41 + 10 * z) for z, (members, _) in enumerate(calls)]
+
+    def run(z):
+        models, xs, ys = made[z]
+        models = [copy.deepcopy(m) for m in models]      # every run from the same initial parameters
+        trace, state = train_many(models, xs, ys, 6, lr=LR, tree_one_launch=calls[z][1])
+        n = len(models)
+        assert state["fused"] is True and state["tree_one_launch"] == (list(range(n)) if calls[z][1] else [])
+        assert list(state["chunks"]) == [tuple(range(n))] and bool(torch.isfinite(trace).all())
+        return trace.clone(), [params_of(m) for m in models], state["chunks"][tuple(range(n))].buf.clone()
+
+    alone = [_on_a_handle_of_its_own(lambda z=z: run(z)) for z in range(4)]
+    shared = _on_a_handle_of_its_own(lambda: [run(z) for z in range(4)])
+    for z in range(4):
+        assert torch.equal(shared[z][0], alone[z][0]), (z, rel(shared[z][0], alone[z][0]))
+        assert torch.equal(shared[z][2], alone[z][2]), z
+        for pa, pb in zip(shared[z][1], alone[z][1]):
+            assert all(np.array_equal(a, b) for a, b in zip(pa, pb)), z
+        assert any(np.abs(a - b).max() > 0 for pa, pb in zip(alone[z][1], [params_of(m) for m in made[z][0]]) for a, b in zip(pa, pb)), z
+
+
 def test_seventeen_models_make_two_chunks():
     from fidelityfusion_amd.cigp_v10 import train_many
     members = [(20 + 3 * f, 2, 1, LM, False) for f in range(17)]

@@ -46,13 +46,25 @@ def test_no_scratch_and_no_spilled_vector_register(kernels):
 
 
 def test_lds_fits_the_cu_and_the_launch_matches_the_bounds(kernels):
-    src = open(os.path.join(ROOT, "fidelityfusion_amd", "csrc", "train_tree_lds.hip")).read()
-    for piece in ("#define TTL_OFF_XS (NBLK_LOWER * BLKSZ)", "#define TTL_OFF_PAR (TTL_OFF_LEAF + 3 * TTL_L * TR_D + 4 * TTL_L)",
+    csrc = os.path.join(ROOT, "fidelityfusion_amd", "csrc")
+    src = open(os.path.join(csrc, "train_tree_lds.hip")).read()
+    tile = open(os.path.join(csrc, "train_tile.h")).read()
+    host = open(os.path.join(csrc, "train_host.h")).read()
+    # the formula restated above: the head both one-launch trainers share (train_tile.h), then this kernel's tail
+    for piece in ("#define TR_OFF_XS (NBLK_LOWER * BLKSZ)", "#define TR_OFF_YM (TR_OFF_XS + TR_N * (TR_D + 1))",
+                  "#define TR_OFF_GAM (TR_OFF_YM + TR_N * TR_Y)", "#define TR_OFF_AM (TR_OFF_GAM + TR_N * TR_Y)",
+                  "#define TR_OFF_PIV (TR_OFF_AM + TR_N * TR_Y)", "#define TR_OFF_DVEC (TR_OFF_PIV + TR_N)",
+                  "#define TR_OFF_TAIL (TR_OFF_DVEC + TR_N)", "#define TR_N 128", "#define TR_D 16", "#define TR_Y 16"):
+        assert piece in tile, piece
+    for piece in ("#define TTL_OFF_LEAF TR_OFF_TAIL", "#define TTL_OFF_PAR (TTL_OFF_LEAF + 3 * TTL_L * TR_D + 4 * TTL_L)",
                   "#define TTL_OFF_SC (TTL_OFF_PAR + 4 * TTL_PPAD)", "#define TTL_OFF_INT (TTL_OFF_SC + 8)",
                   "#define TTL_INTS (TTL_PPAD + 4 + 5 + 3 + 16)", "#define TTL_LDS_DOUBLES (TTL_OFF_INT + TTL_INTS / 2)", "#define TTL_PPAD 136"):
-        assert piece in src, piece      # the formula restated above
-    assert src.count("dim3(TR_T), TTL_LDS_DOUBLES * sizeof(double)") == 2      # both launches: 512 threads, this request
-    tile = open(os.path.join(ROOT, "fidelityfusion_amd", "csrc", "train_tile.h")).read()
+        assert piece in src, piece
+    # both launches: the one call below makes the <8> and the <16> instantiation (tr_by_dm), each with 512 threads and this request
+    assert src.count("train_launch(h, ffgp_train_tree_lds_kernel<dm()>, TTL_LDS_DOUBLES * sizeof(double), F, tab, cm)") == 1
+    assert "return f(std::integral_constant<int, 8>());\n  return f(std::integral_constant<int, 16>());" in host
+    assert "hipLaunchKernelGGL(kernel, dim3(grid), dim3(TR_T), lds_bytes, h->stream, a...);" in host
+    assert "hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)" in host
     assert "#define TR_T 512" in tile
     for name, meta in kernels.items():
         assert meta["max_flat_workgroup_size"] == 512, (name, meta)
