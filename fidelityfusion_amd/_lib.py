@@ -227,6 +227,10 @@ EXPORTS = {
                                      C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                       C.c_long, _dp, C.c_long]),
+    "ffgp_train_tree_res_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.POINTER(Residual), C.c_int,
+                                          C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
+    "ffgp_train_tree_lds_res_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.POINTER(Residual), C.c_int,
+                                              C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_lds_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,
                                           C.c_long, _dp, C.c_long]),
     "ffgp_train_hogp_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(HogpModel), C.POINTER(Links), C.POINTER(HogpResidual), C.c_int,

@@ -247,6 +247,25 @@ int main() {
         tp.tree = nullptr; EXPECT(refused());
         tp.tree = &tr;
       }
+      {   // ffgp_train_tree_res_raw: the residual member's own refusals, and r = NULL is ffgp_train_tree_raw's check
+        ffgp_residual rr;
+        std::memset(&rr, 0, sizeof rr);
+        auto refused = [&](const ffgp_residual* r, long stride = 64) {      // (both forms: launch per stage and one launch)
+          return ffgp_train_tree_res_raw(fake, 1, &tp, &tl, r, 3, &ad, &x, stride, 0, &x, 3) == FFGP_ERR_ARG &&
+                 ffgp_train_tree_lds_res_raw(fake, 1, &tp, &tl, r, 3, &ad, &x, stride, 0, &x, 3) == FFGP_ERR_ARG;
+        };
+        EXPECT(ffgp_train_tree_lds_res_raw(nullptr, 1, &tp, &tl, &rr, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+        tp.n = 129; EXPECT(ffgp_train_tree_lds_res_raw(fake, 1, &tp, &tl, nullptr, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+        tp.n = 4;
+        EXPECT(ffgp_train_tree_res_raw(nullptr, 1, &tp, &tl, &rr, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
+        EXPECT(refused(nullptr, 2 * (2 + 2 + 1) - 1));      // a plain member: state_stride < 2 P
+        rr.rho_dev = &x; EXPECT(refused(&rr));              // a residual member without y_low_dev / y_high_dev
+        rr.y_low_dev = rr.y_high_dev = &x; EXPECT(refused(&rr, 2 * (2 + 2 + 1)));      // state_stride < 2 (P + 1)
+        rr.v_low_dev = &x; EXPECT(refused(&rr));            // v_low_dev without v_high_dev
+        rr.v_high_dev = &x; rr.v_high_stride = -1; EXPECT(refused(&rr));
+        rr.v_high_stride = 1; lf[1].kfun = FFGP_KFUN_RQ; EXPECT(refused(&rr));
+        lf[1].kfun = FFGP_KFUN_MATERN32;
+      }
       tr.n_leaves = 4; tr.shape = 2;      // the one-launch form alone (the other leaves the shape to the assembly, behind the handle)
       EXPECT(ffgp_train_tree_lds_raw(fake, 1, &tp, &tl, 3, &ad, &x, 64, 0, &x, 3) == FFGP_ERR_ARG);
     }

@@ -6,24 +6,8 @@
 #include <cmath>
 #include <vector>
 
-#include "drivers.h"
+#include "train_tree.h"
 #include "tree_ops.h"
-
-#define FFGP_TREE_MAXL 4
-// one member, as both kernels read it from device memory (F <= 16 of them: too large for a kernel argument)
-struct ffgp_tree_member {
-  double* w[FFGP_TREE_MAXL];       // raw parameter storages, leaf by leaf
-  double* amp[FFGP_TREE_MAXL];
-  double* cen[FFGP_TREE_MAXL];     // a trained centre (linear leaf), else null
-  double* dadd;
-  double w_c[FFGP_TREE_MAXL], amp_c[FFGP_TREE_MAXL];
-  double dadd_c, sc;
-  long eff, geff;                  // where this member's effective parameters / their gradients start in the scratch (doubles)
-  int w_link[FFGP_TREE_MAXL], amp_link[FFGP_TREE_MAXL], nw[FFGP_TREE_MAXL];
-  int dadd_link, D, nl, P;
-};
-// effective parameters of a member: leaf e at e (D + 1) as [w (D) | amp], then diag_add at nl (D + 1);
-// their gradients: leaf e at e (2 D + 1) as [g_w (D) | g_amp | g_center (D)], then g_diag_add at nl (2 D + 1)
 
 // raw -> effective, one workgroup per member (ffgp_link_fwd's arithmetic for every leaf)
 extern "C" __global__ void ffgp_tree_link_fwd(const ffgp_tree_member* __restrict__ tab, double* __restrict__ scratch) {
@@ -67,47 +51,18 @@ extern "C" __global__ void ffgp_tree_adam_kernel(int F, int pmax, const ffgp_tre
     const ffgp_tree_member* M = tab + f;
     const int P = M->P;
     if (i >= P) continue;
-    const int D = M->D, gper = 2 * D + 1;
-    const double sc = M->sc;
-    const double* ge = scratch + M->geff;
     double* par;
-    double g;
-    if (i == P - 1) {
-      par = M->dadd;
-      g = sc * ge[M->nl * gper] * ffgp_link_der(M->dadd_link, par[0], M->dadd_c);
-    } else {
-      int e = 0, k = i;
-      for (; e < M->nl - 1; ++e) {
-        const int cnt = M->nw[e] + 1 + (M->cen[e] ? D : 0);
-        if (k < cnt) break;
-        k -= cnt;
-      }
-      const double* gl = ge + e * gper;
-      const int nw = M->nw[e];
-      if (k < nw) {
-        par = M->w[e] + k;
-        if (nw == D) {
-          g = sc * gl[k] * ffgp_link_der(M->w_link[e], par[0], M->w_c[e]);
-        } else {
-          double sg = 0.0;
-          for (int q = 0; q < D; ++q) sg += gl[q];
-          g = sc * sg * ffgp_link_der(M->w_link[e], par[0], M->w_c[e]);
-        }
-      } else if (k == nw) {
-        par = M->amp[e];
-        g = sc * gl[D] * ffgp_link_der(M->amp_link[e], par[0], M->amp_c[e]);
-      } else {
-        par = M->cen[e] + (k - nw - 1);
-        g = sc * gl[D + 1 + (k - nw - 1)];      // (identity link)
-      }
-    }
+    const double g = ffgp_tree_raw_grad(M, scratch, i, &par);
     double* m = state + (size_t)f * state_stride + i;
     ffgp_adam_update(par, m, m + P, g, lr, b1, b2, eps, bc1, bc2_sqrt);
   }
 }
 
-extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* l, int steps, const ffgp_adam* opt,
-                                   double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+// the loop of ffgp_train_tree_raw and ffgp_train_tree_res_raw (train_tree.h): with r, the members whose r[f].rho_dev is set train on
+// targets (and a diagonal extra) that ffgp_tree_resid_form_launch writes into the scratch before each step's likelihoods, the likelihood
+// delivers dloss/dr and dloss/ddvec beside them, and ffgp_tree_res_adam_launch takes the step in ffgp_tree_adam_kernel's place
+int ffgp_train_tree_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* l, const ffgp_residual* r, int steps,
+                         const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
   if (!ffgp_train_args_ok(h, p, l, opt, state_dev, trace_dev, F, steps, step0, trace_stride)) return FFGP_ERR_ARG;
   std::vector<ffgp_tree_member> tab(F);
   std::vector<ffgp_problem> pq(p, p + F);                        // the shadow problems: trees whose leaves read the effective parameters
@@ -122,7 +77,12 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
     const ffgp_problem& q = p[f];
     const ffgp_ktree* t = q.tree;
     if (!t || q.pair || q.cov_dev || !t->leaf || t->n_leaves < 2 || t->n_leaves > FFGP_TREE_MAXL || q.D <= 0 || q.D > 128 || q.n <= 0 ||
-        q.d <= 0 || !q.X_dev || !q.Y_dev || !q.diag_add_dev || (q.ll_variant != FFGP_LL_V1 && q.ll_variant != FFGP_LL_V2))
+        q.d <= 0 || !q.X_dev || !q.diag_add_dev || (q.ll_variant != FFGP_LL_V1 && q.ll_variant != FFGP_LL_V2))
+      return FFGP_ERR_ARG;
+    const bool resid = r && r[f].rho_dev;
+    if (resid ? (!r[f].y_low_dev || !r[f].y_high_dev || (!r[f].v_low_dev) != (!r[f].v_high_dev) ||
+                 (r[f].v_low_dev && (r[f].v_low_stride < 0 || r[f].v_high_stride < 0)))
+              : !q.Y_dev)
       return FFGP_ERR_ARG;
     const int D = q.D, nl = t->n_leaves;
     ffgp_tree_member& M = tab[f];
@@ -140,7 +100,7 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
       M.nw[e] = ll.w_broadcast ? 1 : D;
       P += M.nw[e] + 1 + (ll.center_train ? D : 0);
     }
-    if (state_stride < 2 * (long)P) return FFGP_ERR_ARG;
+    if (state_stride < 2 * (long)(P + (resid ? 1 : 0))) return FFGP_ERR_ARG;
     M.dadd = const_cast<double*>(q.diag_add_dev);
     M.dadd_link = l[f].dadd_link; M.dadd_c = l[f].dadd_c;
     M.sc = (l[f].out_scale == 0.0) ? 1.0 : l[f].out_scale;
@@ -148,6 +108,19 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
     M.eff = (long)off; off += (size_t)nl * (D + 1) + 1;
     M.geff = (long)off; off += (size_t)nl * (2 * D + 1) + 1;
     pmax = std::max(pmax, P);
+  }
+  // per residual member [r (n d) | dvec (n) | dloss/dr (n d) | dloss/ddvec (n)], behind the members' parameters
+  ffgp_tree_resid rs;
+  memset(&rs, 0, sizeof(rs));
+  long rmax = 0, res_off[FFGP_TRAIN_MAXF];
+  bool any_res = false;
+  for (int f = 0; f < F; ++f) {
+    if (!(r && r[f].rho_dev)) continue;
+    const long n = p[f].n, nd = n * p[f].d;
+    res_off[f] = (long)off;
+    off += 2 * (size_t)(nd + n);
+    rmax = std::max(rmax, std::max(nd, n));
+    any_res = true;
   }
   FFGP_HIP(hipSetDevice(h->device));
   if (h->train_tree_bytes < off * sizeof(double)) {      // (every earlier call on this handle has returned: nothing reads the old buffer)
@@ -186,6 +159,21 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
     memset(&g[f], 0, sizeof(ffgp_grads));
     g[f].g_diag_add_dev = ge + (size_t)M.nl * (2 * D + 1);
     g[f].g_pair = &gk[(size_t)f * FFGP_TREE_MAXL];
+    if (r && r[f].rho_dev) {
+      const long n = p[f].n, nd = n * p[f].d;
+      rs.rho[f] = r[f].rho_dev;
+      rs.yl[f] = r[f].y_low_dev; rs.yh[f] = r[f].y_high_dev;
+      rs.vl[f] = r[f].v_low_dev; rs.vh[f] = r[f].v_high_dev; rs.vls[f] = r[f].v_low_stride; rs.vhs[f] = r[f].v_high_stride;
+      rs.r[f] = scratch + res_off[f]; rs.dv[f] = rs.r[f] + nd;
+      rs.gY[f] = rs.dv[f] + n; rs.gdv[f] = rs.gY[f] + nd;
+      rs.rho_last[f] = r[f].rho_last_dev;
+      rs.nd[f] = nd; rs.n[f] = (int)n;
+      pq[f].Y_dev = rs.r[f];
+      pq[f].diag_vec_dev = rs.vl[f] ? rs.dv[f] : nullptr;
+      pq[f].diag_stride = 1;
+      g[f].g_Y_dev = rs.gY[f];
+      if (rs.vl[f]) g[f].g_diag_vec_dev = rs.gdv[f];
+    }
   }
   // (the table's host copy lives until the call's synchronisation below, on every way out)
   if (hipMemcpyAsync(scratch, tab.data(), (size_t)F * sizeof(ffgp_tree_member), hipMemcpyHostToDevice, h->stream) != hipSuccess) {
@@ -198,10 +186,16 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
   h->fold_info = 1;            // the Adam kernel clears / accumulates the status words; the factorisations of a step share info[0]
   for (int k = 0; k < steps && lrc == FFGP_OK; ++k) {
     hipLaunchKernelGGL(ffgp_tree_link_fwd, dim3(F), dim3(256), 0, h->stream, tab_dev, scratch);
+    if (any_res) ffgp_tree_resid_form_launch(h->stream, F, rs, rmax);
     for (int f = 0; f < F && lrc == FFGP_OK; ++f) lrc = ffgp_nlml_fused_async(h, &pq[f], loss + f, &g[f]);
     if (lrc != FFGP_OK) break;
     double bc1, bc2_sqrt;
     ffgp_adam_bc(opt, step0, k, &bc1, &bc2_sqrt);
+    if (any_res) {
+      ffgp_tree_res_adam_launch(h->stream, F, pmax, rs, tab_dev, scratch, state_dev, state_stride, opt, bc1, bc2_sqrt, loss, trace_dev,
+                                trace_stride, k, h->d_info);
+      continue;
+    }
     hipLaunchKernelGGL(ffgp_tree_adam_kernel, dim3(1), dim3(256), 0, h->stream, F, pmax, tab_dev, scratch, state_dev, state_stride, opt->lr,
                        opt->beta1, opt->beta2, opt->eps, bc1, bc2_sqrt, loss, trace_dev, trace_stride, k, h->d_info);
   }
@@ -218,4 +212,9 @@ extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p,
   FFGP_HIP(hipMemcpyAsync(h->h_info, h->d_info, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   ffgp_invalidate(h);
   return ffgp_wait(h);
+}
+
+extern "C" int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* l, int steps, const ffgp_adam* opt,
+                                   double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+  return ffgp_train_tree_impl(h, F, p, l, nullptr, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
 }

@@ -7,6 +7,8 @@ Python round trip, one autograd graph, one status read-back); here it costs its 
 Models whose kernel is a SumKernel / ProductKernel tree of up to four library kernels -- SumKernel(LinearKernel, MaternKernel) is the
 kernel of the reference's demos and two-fidelity models -- take the same route through ffgp_train_tree_raw (launch per stage, every size),
 or, with `tree_one_launch=True` and at most TREE_ONE_LAUNCH_MAX_N points, through ffgp_train_tree_lds_raw: one launch for all their steps.
+With `fuse_composed=True` train_AR's residual fidelities on such a kernel and `GP_basic` blocks over one are trained by the library too
+(ffgp_train_tree_res_raw; in one launch: ffgp_train_tree_lds_res_raw).
 """
 import ctypes as C
 
@@ -29,7 +31,8 @@ class AdamState:
     exp_avg_sq (nw + 5)] in the order length scales, signal variance, noise_variance, b, l_z, sigma_z); `step` = updates taken.
     A chunk of composed-kernel models (ffgp_train_tree_raw): buf[f] = [exp_avg (P) | exp_avg_sq (P)], P = sum over the leaves of
     (length scales + 1 + the centre's D for a LinearKernel) + 1, in the order leaf by leaf in the tree's canonical leaf order
-    (`kernel._Pair.tree_links`: length scales, signal variance, centre), then log_beta."""
+    (`kernel._Pair.tree_links`: length scales, signal variance, centre), then log_beta (a `GP_basic`: noise_variance); a residual member
+    of such a chunk (ffgp_train_tree_res_raw): [exp_avg (P + 1) | exp_avg_sq (P + 1)], rho last."""
 
     def __init__(self, buf, stride, step=0):
         self.buf, self.stride, self.step = buf, stride, step
@@ -40,7 +43,7 @@ def _jitter_and_pi():
     return JITTER, PI
 
 
-def _eligible(model, x, y):
+def _eligible(model, x, y, fuse_composed=False):
     """the model's links when ffgp_train_raw can train it: a `cigp` (or a `GP_basic`: `_eligible_gp_basic`) with a library kernel whose raw-parameter path applies (everything
     on one GPU in fp64, no learnable profile parameter, no gradient-carrying inputs), all three parameters trainable"""
     from . import functional as F
@@ -50,7 +53,7 @@ def _eligible(model, x, y):
         y_var = None
     from .gp_basic import GP_basic
     if isinstance(model, GP_basic):
-        return _eligible_gp_basic(model, x, y, y_var)
+        return _eligible_gp_basic(model, x, y, y_var, fuse_composed)
     if not (hasattr(model, "kernel") and hasattr(model, "log_beta")):
         return None
     if y_var is not None and not F.raw_ok(y_var):
@@ -68,15 +71,24 @@ def _eligible(model, x, y):
     return lk, y, y_var
 
 
-def _eligible_gp_basic(model, x, y, y_var):
+def _eligible_gp_basic(model, x, y, y_var, fuse_composed=False):
     """`_eligible` for a `GP_basic` (GaussianProcess/gp_basic.py): Sigma = K + noise_variance^2 I without jitter and the FFGP_LL_V2
     likelihood.  The links dict carries the two differences from a `cigp`: "diag" = (raw diagonal parameter, its link, its constant)
-    and "ll" = (variant, pi).  A list y (the FULL y_var matrix enters Sigma), a composed kernel or further parameters: the reference's loop."""
+    and "ll" = (variant, pi).  A list y (the FULL y_var matrix enters Sigma), a composed kernel or further parameters: the reference's loop.
+    Under `fuse_composed` a composed kernel goes by `_eligible_tree`'s rules, noise_variance in log_beta's place."""
     import math
     from . import functional as F
-    if y_var is not None or not isinstance(y, torch.Tensor) or hasattr(model.kernel, "tree_links"):
+    if y_var is not None or not isinstance(y, torch.Tensor):
         return None
     nv = model.noise_variance
+    if hasattr(model.kernel, "tree_links"):
+        if not fuse_composed:
+            return None
+        e = _eligible_tree(model, x, y, None, nv)
+        if e is not None:
+            e[0]["diag"] = (nv, _lib.LINK_SQUARE, 0.0)
+            e[0]["ll"] = (_lib.FFGP_LL_V2, math.pi)
+        return e
     with torch.enable_grad():
         lk = F.raw_path(model.kernel, x, y, nv)
     if lk is None or isinstance(lk.get("kparam"), torch.Tensor) or y.requires_grad or nv.numel() != 1:
@@ -145,18 +157,20 @@ def _loss(m, x, y):
     return (-m.log_likelihood(x, y)).sum()
 
 
-def _eligible_tree(model, x, y, y_var):
+def _eligible_tree(model, x, y, y_var, dpar=None):
     """`_eligible` for a composed kernel: ({"tree": (leaf modules, (shape, ops), leaf links)}, y, y_var) when ffgp_train_tree_raw can
     train the model -- `kernel.tree_links()` applies, everything fp64, contiguous and on one GPU, every leaf parameter (length scales,
-    signal variance, a linear leaf's centre) and log_beta trainable and together exactly the model's parameters, data without gradients"""
+    signal variance, a linear leaf's centre) and log_beta (`dpar`: a `GP_basic`'s noise_variance in its place) trainable and together
+    exactly the model's parameters, data without gradients"""
     from . import functional as F
+    dpar = model.log_beta if dpar is None else dpar
     tl = model.kernel.tree_links()
     if tl is None or not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor)):
         return None
-    pars = [t for lk in tl[2] for t in (lk["w"], lk["amp"], lk.get("center")) if t is not None] + [model.log_beta]
+    pars = [t for lk in tl[2] for t in (lk["w"], lk["amp"], lk.get("center")) if t is not None] + [dpar]
     if not F.raw_ok(x, y, y_var, *pars):
         return None
-    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0] or x.shape[1] > 128 or model.log_beta.numel() != 1:
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0] or x.shape[1] > 128 or dpar.numel() != 1:
         return None
     D = x.shape[1]
     for lk in tl[2]:
@@ -237,7 +251,8 @@ def _residual_ok(res, x):
     return True
 
 
-def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None, tree_one_launch=False, car=None):
+def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None, tree_one_launch=False, car=None,
+               fuse_composed=False):
     """`steps` Adam iterations on every model of `models` (independent `cigp` models, `xs[f]`, `ys[f]` their training data; y may be
     `[y, y_var]`), each exactly the reference's iteration (FidelityFusion_Models/ResGP.py:82-88): loss = -negative_log_likelihood,
     gradients of the three raw parameters, torch.optim.Adam(lr, betas, eps) update.  Returns `(trace, state)`:
@@ -252,7 +267,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     trained centre included; every leaf parameter and log_beta trainable, and nothing else) are trained by ffgp_train_tree_raw, launch
     per stage: those of at most 128 points up to 16 per call -- calls of their own, beside the plain and residual models' -- and every
     larger one in a call of its own, side by side with the other large models.  A not-PD Sigma in one model of such a call stops all
-    of that call's models at that step.  A composed-kernel model given a `residual=` link is NOT fused: it (and with it the whole
+    of that call's models at that step.  A composed-kernel model given a `residual=` link is NOT fused unless `fuse_composed` (below): it (and with it the whole
     `train_many` call, state["fused"] = False) keeps the reference's loop, as do compositions with a RationalQuadraticKernel leaf, a
     module used as two leaves, or kernel.FUSE_PAIRS = False.
     `tree_one_launch=True` sends the composed-kernel models of at most TREE_ONE_LAUNCH_MAX_N points with D <= 16 and d <= 16 through
@@ -261,6 +276,17 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     complete their steps.  The Adam state has the same layout on both routes, so a `state` may be continued with either value of the
     keyword; the two routes agree to rounding, not bit for bit.  Every other model is routed as without the keyword.
     state["tree_one_launch"] lists the indices of the models that took this route in the last call.
+    `fuse_composed=True` (off by default: without it nothing changes) fuses two kinds of model that otherwise keep the loop.  A
+    `cigp` over a composed kernel with a `residual=` link -- both forms, subset and non-subset with [n, n] variances -- is trained by
+    ffgp_train_tree_res_raw (csrc/train_tree_res.hip: launch per stage at every size; per step one launch forms the residual members'
+    targets, and the Adam launch reduces dloss/drho in a fixed order and moves P + 1 parameters), and a `GP_basic` over a composed
+    kernel goes through the tree entries with noise_variance under the square link, no jitter and the FFGP_LL_V2 likelihood --
+    `_eligible_tree`'s rules with noise_variance in log_beta's place; plain targets, or a residual link in the subset form (a list y or
+    residual variances would add a FULL matrix to Sigma: the reference's loop, as before).  Plain and residual tree members of at most
+    128 points may share a call; larger ones run side by side.  Under `tree_one_launch=True` the members of at most 128 points (D, d <= 16)
+    go to ffgp_train_tree_lds_res_raw instead -- ONE launch for all steps of a chunk's V1 members and one for its V2 members, a member
+    that is not positive definite stops alone -- and state["tree_one_launch"] lists them; the state is portable between the routes.  state["residual_targets"][f] and the parameters' version
+    counters behave as for residual members on a single radial kernel.
     A Sigma that is not positive definite raises torch.linalg.LinAlgError as the reference's loop would; the failing model's parameters
     then hold the values they had when that step began (the other small models of the same call have completed their steps; the
     optimiser state of a failed call is not advanced).
@@ -310,10 +336,12 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     res_of = (lambda f: residual[f]) if residual is not None else (lambda f: None)
     # a residual model's eligibility is judged on its y_high (same shape as its targets) and its link
     ys_e = [ys[f] if res_of(f) is None else _split_residual(res_of(f))[2] for f in range(nF)]
-    elig = [_eligible(m, x, y) if car_of(f) is None else _eligible_car(m, x, car_of(f)) for f, (m, x, y) in enumerate(zip(models, xs, ys_e))]
+    elig = [_eligible(m, x, y, fuse_composed) if car_of(f) is None else _eligible_car(m, x, car_of(f)) for f, (m, x, y) in enumerate(zip(models, xs, ys_e))]
     for f in range(nF):
-        if res_of(f) is not None and elig[f] is not None and (_is_tree(elig[f]) or not _residual_ok(res_of(f), xs[f])):
-            elig[f] = None      # (a composed kernel with a residual link: the reference's loop -- ffgp_train_tree_raw has no residual members)
+        if res_of(f) is not None and elig[f] is not None and ((_is_tree(elig[f]) and not fuse_composed) or not _residual_ok(res_of(f), xs[f])):
+            elig[f] = None      # (a composed kernel with a residual link: the reference's loop unless `fuse_composed` -- ffgp_train_tree_res_raw)
+        if res_of(f) is not None and _is_tree(elig[f]) and "diag" in elig[f][0] and _split_residual(res_of(f))[3] is not None:
+            elig[f] = None      # (a `GP_basic` over a tree: it adds the FULL residual variance matrix to Sigma -- the reference's loop)
     fused = all(e is not None for e in elig) and len({x.device for x in xs}) == 1
     if state is None:
         state = {"fused": fused, "chunks": {}, "opts": [None] * nF}
@@ -387,14 +415,24 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         shape, ops = form
         p = Problem()
         p.n, p.D, p.d = n, D, y.shape[1]
-        p.X_dev, p.Y_dev, p.diag_add_dev = x.data_ptr(), y.data_ptr(), m.log_beta.data_ptr()
+        dpar, dlink, dc = tl["diag"] if "diag" in tl else (m.log_beta, _lib.LINK_EXP_NEG, JITTER)
+        p.X_dev, p.Y_dev, p.diag_add_dev = x.data_ptr(), y.data_ptr(), dpar.data_ptr()
         if y_var is not None:
             p.diag_stride = y_var.shape[1] + 1 if y_var.dim() == 2 else 1
             p.diag_vec_dev = y_var.data_ptr()
-        p.ll_variant, p.pi_const = FFGP_LL_V1, PI
+        p.ll_variant, p.pi_const = tl["ll"] if "ll" in tl else (FFGP_LL_V1, PI)
+        rs = _lib.Residual()
+        if res_of(f) is not None:      # (only under `fuse_composed`: ffgp_train_tree_res_raw)
+            rho, yl, yh, vl, vh = _split_residual(res_of(f))
+            p.Y_dev, p.diag_vec_dev, p.diag_stride = None, None, 0
+            rs.rho_dev, rs.y_low_dev, rs.y_high_dev = rho.data_ptr(), yl.data_ptr(), yh.data_ptr()
+            if vl is not None:
+                rs.v_low_dev, rs.v_low_stride = vl.data_ptr(), vl.stride(0) + vl.stride(1)
+                rs.v_high_dev, rs.v_high_stride = vh.data_ptr(), vh.stride(0) + vh.stride(1)
+            rs.rho_last_dev = rho_last[f].data_ptr()
         arr = (_lib.KDesc * len(lks))()
         tree, tk = _lib.KTree(), _lib.TreeLinks()
-        P = 1
+        P = 1 + (1 if res_of(f) is not None else 0)
         for e, lk in enumerate(lks):
             arr[e].kfun, arr[e].clamp_min, arr[e].kparam = lk["kfun"], lk["clamp"], float(lk.get("kparam", 1.0))
             arr[e].w_dev, arr[e].amp_dev = lk["w"].data_ptr(), lk["amp"].data_ptr()
@@ -408,23 +446,33 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         for i, o in enumerate(ops):
             tree.op[i] = o
         p.tree = C.pointer(tree)
-        tk.dadd_link, tk.dadd_c, tk.out_scale = _lib.LINK_EXP_NEG, JITTER, 1.0
+        tk.dadd_link, tk.dadd_c, tk.out_scale = dlink, dc, 1.0
         keep += [arr, tree]
-        return p, tk, P
+        return p, tk, rs, P
 
     def run_tree(idx):
-        """one ffgp_train_tree_raw call -- ffgp_train_tree_lds_raw for a chunk of `one_launch` -- for the composed-kernel models `idx`
-        (<= 16); Adam state [exp_avg (P) | exp_avg_sq (P)] per model"""
-        name = "ffgp_train_tree_lds_raw" if idx[0] in one_launch else "ffgp_train_tree_raw"
+        """one ffgp_train_tree_raw call -- ffgp_train_tree_lds_raw for a chunk of `one_launch`, ffgp_train_tree_res_raw for a chunk with
+        residual members -- for the composed-kernel models `idx` (<= 16); Adam state [exp_avg (P) | exp_avg_sq (P)] per model, rho
+        the (P + 1)-th parameter of a residual one"""
+        anyres = any(res_of(f) is not None for f in idx)
+        anyv2 = any("ll" in elig[f][0] for f in idx)
+        if idx[0] in one_launch:      # (a chunk without a residual or V2 member keeps ffgp_train_tree_lds_raw: bit for bit the call it was)
+            name = "ffgp_train_tree_lds_res_raw" if anyres or anyv2 else "ffgp_train_tree_lds_raw"
+        else:
+            name = "ffgp_train_tree_res_raw" if anyres else "ffgp_train_tree_raw"
         fn = getattr(lib, name)
         h = _lib.handle(dev.index)
         _lib.bind_stream(h, dev.index)
         P = (Problem * len(idx))()
         L = (_lib.TreeLinks * len(idx))()
+        R = (_lib.Residual * len(idx))()
         keep, npar = [], []
         for j, f in enumerate(idx):
-            P[j], L[j], n_ = describe_tree(f, keep)
+            P[j], L[j], R[j], n_ = describe_tree(f, keep)
             npar.append(n_)
+        if name.endswith("res_raw"):
+            return launch(idx, 2 * max(npar), lambda st, tr: check(
+                fn(h, len(idx), P, L, R, int(steps), C.byref(opt), st.buf.data_ptr(), st.stride, int(st.step), tr.data_ptr(), tr.stride(0)), name))
         return launch(idx, 2 * max(npar), lambda st, tr: check(
             fn(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), st.stride, int(st.step), tr.data_ptr(), tr.stride(0)), name))
 
@@ -484,6 +532,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     small = [f for f in range(nF) if f not in trees and shapes[f][0] <= F.SMALL_BATCH_MAX_N and shapes[f][1] <= F.SMALL_BATCH_MAX_D
              and shapes[f][2] <= F.SMALL_BATCH_MAX_d]
     # ... and under `tree_one_launch` those the LDS trainer covers form calls of ffgp_train_tree_lds_raw, up to 16 per call.
+    # (residual and V2 members among them: ffgp_train_tree_lds_res_raw, plain and residual members sharing chunks)
     one_launch = {f for f in trees if tree_one_launch and shapes[f][0] <= TREE_ONE_LAUNCH_MAX_N and shapes[f][1] <= F.SMALL_BATCH_MAX_D
                   and shapes[f][2] <= F.SMALL_BATCH_MAX_d}
     lds_trees = sorted(one_launch)

@@ -668,6 +668,25 @@ typedef struct {
 int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, int steps, const ffgp_adam* opt,
                         double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 
+/* ffgp_train_tree_raw with RESIDUAL members -- train_AR's fidelities above 0 on a composed kernel (AR_autoRegression.py:123-137 with
+   SumKernel(LinearKernel, MaternKernel), the kernel of two_fidelity_models/AR_autoRegression.py:31-37) -- launch per stage, at every
+   size, both likelihood variants (csrc/train_tree_res.hip).  The arguments are ffgp_train_tree_raw's plus r, the struct and the member
+   rules ffgp_train_residual_raw's: r == NULL or r[f].rho_dev == NULL makes model f a plain member, trained exactly as
+   ffgp_train_tree_raw trains it (a call without any residual member IS ffgp_train_tree_raw's launches); for a residual member
+   p[f].Y_dev and p[f].diag_vec_dev are ignored, it trains on r = y_high - rho * y_low (a product, then a difference, rounded as torch
+   rounds it) and, in the non-subset form, on dvec_i = |v_high,ii - rho * v_low,ii|, both re-formed from the current rho at every step
+   by ONE launch for all residual members into handle-owned scratch.  rho is one more Adam parameter:
+       dloss/drho = -sum (dloss/dr) .* y_low - sum_i G_ii sgn(s_i) v_low,ii,      dloss/dr = A = Sigma^-1 r (V1), B = Sigma^-1 A (V2),
+   sgn(0) = 0, reduced member by member in a fixed order inside the Adam launch (a member's trajectory does not depend on its
+   companions), which then updates P + 1 parameters.  rho_last_dev receives the rho of the start of the last step taken.
+   Adam state of a residual member: [exp_avg (P + 1) | exp_avg_sq (P + 1)] in the tree's canonical leaf order, then diag_add, then rho;
+   state_stride >= 2 (P + 1), a plain member keeps 2 P.  FFGP_ERR_ARG, with nothing enqueued or written: what ffgp_train_tree_raw
+   refuses, a state_stride below that, a residual member without y_low_dev / y_high_dev, v_low_dev set without v_high_dev (or the
+   reverse), a negative variance stride.  Trace, status and failure semantics are ffgp_train_tree_raw's: the status is shared by the
+   call, and from the first step whose Sigma was not positive definite in ANY member on no parameter (no rho either) moves.      */
+int ffgp_train_tree_res_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, const ffgp_residual* r, int steps,
+                            const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
+
 /* ffgp_train_tree_raw's job for SMALL members in ONE launch (csrc/train_tree_lds.hip): a persistent workgroup per model keeps Sigma,
    its factor, the raw parameters of every leaf and their Adam moments in LDS and runs all `steps` iterations inside the kernel, as
    ffgp_train_raw's one-launch form does for a single radial kernel.  The parameter list, the ffgp_problem / ffgp_tree_links
@@ -685,6 +704,19 @@ int ffgp_train_tree_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp
    (in the caller's order), else 0.  Synchronous.                                                                              */
 int ffgp_train_tree_lds_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, int steps, const ffgp_adam* opt,
                             double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
+
+/* ffgp_train_tree_lds_raw extended to the FFGP_LL_V2 likelihood and to RESIDUAL members (csrc/train_tree_lds_res.hip): ONE launch for
+   all steps of the call's V1 members and one for its V2 members, a persistent workgroup per model.  Arguments and member rules are
+   ffgp_train_tree_res_raw's (r == NULL or r[f].rho_dev == NULL: a plain member -- with r == NULL this is the way in for plain V2 tree
+   models; ffgp_train_tree_lds_raw itself keeps its refusal of V2).  A residual member re-forms r = y_high - rho * y_low in the targets'
+   LDS image and dvec = |v_high,ii - rho * v_low,ii| (the variances: two [128] rows in LDS) at the top of every step, and rho is
+   parameter P of its Adam state [exp_avg (P + 1) | exp_avg_sq (P + 1)], interchangeable with ffgp_train_tree_res_raw's; rho_last_dev
+   receives the rho of the start of the last step taken.  Coverage and failure semantics are ffgp_train_tree_lds_raw's: n <= 128,
+   D <= 16, d <= 16, F <= 16, anything else FFGP_ERR_ARG with nothing enqueued or written; a member whose Sigma is not positive
+   definite stops alone -- NaN in its trace from that step on, its parameters, rho and every moment as they were when the step
+   began -- and the others complete.  Returns the pivot status of the first failing member in the caller's order, else 0.      */
+int ffgp_train_tree_lds_res_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, const ffgp_residual* r, int steps,
+                                const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 
 /* K Adam steps of F <= 16 independent HOGP blocks in ONE call (csrc/train_hogp.hip) -- train_GAR's loop
    (FidelityFusion_Models/GAR.py:76-126: per fidelity 100-1000 iterations of HOGP_simple.log_likelihood / backward / Adam at 4..100
