@@ -19,7 +19,7 @@ struct RawGraph {          // the captured forward call (option "fwd_graph", ffg
 void ffgp_rawg_drop(RawGraph* r);      // forgets the captured call (null: nothing to do); the struct and its staging slot stay
 
 // ---- raw parameters: elementwise links around the fused call (kernels in nlml.hip / nlml_batch.hip, the Adam kernel of train_loop.hip)
-//      and inside the one-launch trainers (train.hip, train_tree_lds.hip)
+//      and inside the one-launch trainers (train.hip; ttl_body of train_tree_lds.h)
 __device__ __forceinline__ double ffgp_link_val(int kind, double p, double c) {
   switch (kind) {
     case FFGP_LINK_INV_ABS_EPS: return 1.0 / (fabs(p) + c);
@@ -46,7 +46,7 @@ __device__ __forceinline__ double ffgp_link_der(int kind, double p, double c) {
 // ---- torch.optim.Adam's update of ONE parameter with gradient g (no weight decay, no amsgrad), operation for operation; bc1 and
 // bc2_sqrt = 1 - beta1^t and sqrt(1 - beta2^t), computed on the host (ffgp_adam_bc below).  The one copy; its callers: ffgp_adam_kernel and
 // ffgp_adam_car_kernel (train_loop.hip), ffgp_tree_adam_kernel (train_tree.hip), ffgp_hogp_adam_kernel (train_hogp.hip), tr_body
-// (train.hip), ffgp_train_tree_lds_kernel (train_tree_lds.hip) and acq_owner_step (acq_tile.h).
+// (train.hip), ttl_body (train_tree_lds.h) and acq_owner_step (acq_tile.h).
 __device__ __forceinline__ void ffgp_adam_update(double* par, double* m, double* v, double g, double lr, double b1, double b2, double eps,
                                                  double bc1, double bc2_sqrt) {
   const double m1 = m[0] + (g - m[0]) * (1.0 - b1);        // exp_avg.lerp_(grad, 1 - beta1)

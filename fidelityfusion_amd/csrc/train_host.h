@@ -1,4 +1,5 @@
-// The host side of the one-launch trainers, shared by ffgp_train_persist (train.hip) and ffgp_train_tree_lds_raw (train_tree_lds.hip).
+// The host side of the one-launch trainers, shared by ffgp_train_persist (train.hip) and the tree trainers ffgp_train_tree_lds_raw /
+// ffgp_train_tree_lds_res_raw (train_tree_lds.hip, train_tree_lds_res.hip; their one text: train_tree_lds.h).
 // A call of either is synchronous and works in ONE device block on the handle, every part at a 256-byte step:
 //   [ the driver's tables | 2 steps bias corrections | 2 F status ints ]  <- the head: staged in a pinned mirror, copied up in one piece
 //   [ the kernels' per-model scratch ]                                    <- never staged

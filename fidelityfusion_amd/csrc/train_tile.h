@@ -1,4 +1,4 @@
-// The device pieces of the one-launch trainers, shared by train.hip (one radial kernel: tr_body) and train_tree_lds.hip (a SumKernel /
+// The device pieces of the one-launch trainers, shared by train.hip (one radial kernel: tr_body) and train_tree_lds.h (a SumKernel /
 // ProductKernel tree: ttl_body): the wave sum, the 16 x 16 block chains on the LDS block image of diag_block.h, the deal of the blocks to
 // the waves, and the phases of a step that do not depend on how Sigma was assembled -- the blocked Cholesky with its inverse, the last
 // row block of the inverse, Gamma = L^-1 Y and A = L^-T Gamma.  The arithmetic is train.hip's, moved here unchanged.  Also what the two

@@ -1,14 +1,44 @@
-// ffgp_train_tree_lds_res_raw's device code and member description (train_tree_lds_res.hip): train_tree_lds.hip's persistent-workgroup step
-// loop as a template, ttl_body<DM, V2, RESID, MODEL>, with the V2 likelihood and residual members added under `if constexpr`.
-// train_tree_lds.hip itself does NOT include this file: instantiated from here its two kernels compiled to other code than from their
-// own text (another schedule of the first loop already; docs/experiments.md), and the project's rule for that case is to leave the measured
-// file as it is and share less.  So this is a second copy of the phases' text, in a namespace of its own; what the two share is
-// train_tile.h, train_host.h and tree_ops.h.  See train_tree_lds.hip for the phases.
+// K Adam steps of F composed-kernel models -- SumKernel / ProductKernel trees of 2-4 leaves (ffgp_ktree) -- in ONE launch: the step loop
+// ttl_body<DM, V2, RESID, MODEL>, its LDS layout and the member description (ttl_describe) of ffgp_train_tree_lds_raw (train_tree_lds.hip:
+// V1, plain members) and ffgp_train_tree_lds_res_raw (train_tree_lds_res.hip: V2 and residual members, added here under `if constexpr`).
+// Six instantiations in those two units; this is their one text.  The reference trains SumKernel(LinearKernel, MaternKernel) at N = 16 ... 128
+// (Bayesian_optimization/cigp.py:119-124: 300 Adam steps; con_mace_acq_demo.py:95-96: 100 per BO iteration; GaussianProcess/cigp_v10.py:81),
+// and ffgp_train_tree_raw (train_tree.hip) pays a launch chain per step at every size.  Here one PERSISTENT workgroup per model
+// (gridDim.x = models, 512 threads) runs every step inside the kernel, as tr_body<DM, true> of train.hip does for one radial kernel;
+// the phases between the assembly and the gradient pass ARE train.hip's (train_tile.h).  Per step:
+//
+//   Sigma  straight into the LDS block image (lower block triangle, identity beyond n).  X sits in LDS ONCE, as given (no per-leaf
+//          scaled copy: four do not fit, and a difference of given coordinates is formed exactly where a difference of scaled ones is
+//          not -- nor is it shifted by the first point as train.hip's scaled image is: that only protects scaled differences); each leaf
+//          keeps w_e^2 [16] and, a linear leaf, its centre [16].  Per entry and leaf the argument
+//              radial:  sum_k w_ek^2 (x_ik - x_jk)^2, clamped with the leaf's clamp_min        linear:  sum_k w_ek^2 (x_ik - c_k)(x_jk - c_k)
+//          then amp_e phi_e, then the tree, node by node as pair.hip rounds it (tree_ops.h); diag_add, then diag_vec, on the diagonal.
+//   ->     train_tile.h: blocked Cholesky and inverse, Gamma = L^-1 Y, A = L^-T Gamma.
+//   ->     gradient pass 1: Sigma^-1 block by block in the accumulators, G = d/2 Sigma^-1 - 1/2 A A^T; per entry the leaves are EVALUATED
+//          AGAIN and the tree's reverse sweep gives every leaf's upstream weight.  Out of it: tr G, every leaf's amplitude sum, and the
+//          entry's weight for each leaf's per-dimension sums, W_e = sym G dk/dv_e amp_e (-2 phi_e') (radial, 0 on the clamp) or
+//          sym G dk/dv_e amp_e (linear), parked in this model's global scratch [leaf][36][4][64] (L2-resident; written and read by the
+//          same lane).
+//          (Why the leaves are evaluated again instead of parked by the assembly as train.hip's kbuf parks them: the derivative
+//           -2 phi' needs the clamped argument and its own exponential whatever is parked -- train.hip's non-SE profiles evaluate it
+//           afresh too -- so parking would save one of two profile evaluations for two more global round trips per leaf and entry, and
+//           the scratch is wanted for the weights.)
+//   ->     gradient pass 2, LEAF BY LEAF: sum_entries W_e (x_ik - x_jk)^2 (radial), W_e (x_ik - c_k)(x_jk - c_k) and
+//          W_e ((x_ik - c_k) + (x_jk - c_k)) (linear: w and centre) -- one leaf's D (+ D) accumulators live at a time.
+//   ->     ONE workgroup reduction of all of it (the per-wave partial sums use Gamma's image: it is dead behind A), the links' chain rule
+//          (ffgp_link_der; a broadcast length scale: the D effective gradients summed in index order first) and torch.optim.Adam's
+//          update (ffgp_adam_update) on raw parameters and moments that live in LDS for the whole call; the loss before the update goes
+//          to the trace.  With p = (x - c) w these are pair.hip's gradients: g_w = (linear ? 2 : -1) w_k sum, g_c = -w_k^2 sum.
+// A Sigma that is not positive definite stops THAT model at that step (its status word, NaN in its trace from there on, parameters
+// and moments as they were when the step began); the other models of the launch train on -- train.hip's rule.
+// Covers n <= 128, D <= 16, d <= 16, diag_add and diag_vec, leaves SE/ARD, Matern 1/2, 3/2, 5/2 and linear; the V2 likelihood and
+// residual members (rho trained as one more parameter) where the template's V2 / RESID are set -- described at ttl_body.
+// HOST side: the scaffold of train_host.h, shared with train.hip (block and pinned mirror on the handle, bias corrections, loop arguments,
+// dispatch, launch, status epilogue); this file adds the member description (ttl_describe), each entry its one table.  LDS: train_tile.h's
+// head, then this kernel's tail.
 #pragma once
 #include "train_host.h"
 #include "tree_ops.h"
-
-namespace ttlr {
 
 #define TTL_L FFGP_TREE_LEAVES
 #define TTL_PMAX (TTL_L * (2 * TR_D + 1) + 1)      // raw parameters of a model at most: four linear leaves with D = 16 and trained centres
@@ -16,7 +46,6 @@ namespace ttlr {
 #define TTL_NSC 7                                  // scalars of the step's reduction: ss, tr G, log-det, s_amp[4]
 #define TTL_RW(DM) (TTL_NSC + TTL_L * 2 * (DM))    // ... then per leaf: w-sums [DM] | centre-sums [DM]
 #define TTL_WBUF (TTL_L * NBLK_LOWER * 256)        // doubles of global scratch per model
-
 
 struct TtlLeaf {
   double* w; double* amp;                // RAW parameters, updated in place when the kernel ends
@@ -71,10 +100,7 @@ struct TtlTree {
 static_assert(TTL_INTS % 2 == 0, "the int table ends on a double");
 static_assert(TTL_PMAX + 1 <= TTL_PPAD && TTL_RW(TR_D) + 1 <= TTL_PPAD, "rho and its total fit the rows as they are");
 static_assert(8 * (TTL_RW(TR_D) + 1) <= TR_N * TR_Y, "the waves' partial sums, dloss/drho included, fit Gamma's image");
-static_assert(TTL_RES_LDS_DOUBLES * sizeof(double) <= 160 * 1024, "the residual tree trainer's LDS exceeds a CU's 160 KiB");
-static_assert(TTL_PMAX <= TTL_PPAD && TTL_RW(TR_D) <= TTL_PPAD, "parameters and totals fit their rows");
-static_assert(8 * TTL_RW(TR_D) <= TR_N * TR_Y, "the waves' partial sums fit Gamma's image");
-static_assert(TTL_LDS_DOUBLES * sizeof(double) <= 160 * 1024, "the tree trainer's LDS exceeds a CU's 160 KiB");
+static_assert(TTL_RES_LDS_DOUBLES * sizeof(double) <= 160 * 1024, "the tree trainers' LDS (the larger, residual request) exceeds a CU's 160 KiB");
 
 // a leaf's bilinear form on rows xi, xj of X
 template <int DM>
@@ -104,8 +130,8 @@ __device__ __forceinline__ double ttl_form(bool lin, const double* xi, const dou
 // dimensions hold zeros and add nothing, so a model's arithmetic does not depend on which instantiation runs it)
 // V2: the FFGP_LL_V2 likelihood (B = Sigma^-1 A by the two block chains once more; the targets' image receives B, so the targets are
 // read again at the top of every step).  RESID: MODEL is TtlResModel and a member with rho set is a residual member (its targets and
-// diagonal extra re-formed from rho at the top of every step, rho its (P + 1)-th Adam parameter); the existing instantiations see
-// `if constexpr (false)` at every such place.
+// diagonal extra re-formed from rho at the top of every step, rho its (P + 1)-th Adam parameter); train_tree_lds.hip's instantiations
+// (V2 = RESID = false, MODEL = TtlModel) see `if constexpr (false)` at every such place.
 template <int DM, bool V2, bool RESID, class MODEL>
 __device__ __forceinline__ void ttl_body(const MODEL* __restrict__ tab, TtlCommon cm) {
   constexpr int RW = TTL_RW(DM) + (RESID ? 1 : 0);      // RESID: one more total, dloss/drho, behind the leaves' sums
@@ -608,5 +634,3 @@ static bool ttl_describe(const ffgp_problem& q, const ffgp_tree_links& l, long s
   m.oscale = (l.out_scale == 0.0) ? 1.0 : l.out_scale; m.pi_const = q.pi_const;
   return true;
 }
-
-}  // namespace ttlr

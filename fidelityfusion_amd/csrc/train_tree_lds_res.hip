@@ -2,12 +2,10 @@
 // blocks on a composed kernel, n <= 128 -- in ONE launch per likelihood class: ffgp_train_tree_lds_res_raw (include/ffgp.h).  The
 // persistent workgroup's step loop is train_tree_lds.h's ttl_body, instantiated here with RESID (a member whose rho is set re-forms its
 // targets r = y_high - rho y_low and its diagonal extra |v_high - rho v_low| at the top of every step, the variances as two [128] rows
-// in LDS behind train_tree_lds.hip's layout, and trains rho as parameter P) and with V2 (B = Sigma^-1 A by the two block chains once
+// in LDS behind the plain members' layout, and trains rho as parameter P) and with V2 (B = Sigma^-1 A by the two block chains once
 // more, G = d/2 Sigma^-1 - 1/2 (A B^T + B A^T)).  V1 and V2 members of one call get a launch each, class after class, as in
 // ffgp_train_persist; plain and residual members share a launch.  Host side: train_host.h's scaffold.
 #include "train_tree_lds.h"
-
-using namespace ttlr;
 
 template <int DM, bool V2>
 __global__ __launch_bounds__(TR_T) void ffgp_train_tree_lds_res_kernel(const TtlResModel* __restrict__ tab, TtlCommon cm) {

@@ -1,5 +1,5 @@
 // The canonical Sum / Product trees of include/ffgp.h (2-4 leaves) on the leaves' values, for the kernels that evaluate a composed kernel
-// entry by entry in registers: the acquisition loop (acq_tree.hip) and the one-launch trainer (train_tree_lds.hip).  A: any struct with
+// entry by entry in registers: the acquisition loop (acq_tree.hip) and the one-launch trainers (ttl_body, train_tree_lds.h).  A: any struct with
 // nl, shape and op[3] (FFGP_KOP_*; shape = FFGP_TREE_CHAIN | FFGP_TREE_BALANCED, read at nl = 4).  At the end, the hosts' checks of a tree.
 #pragma once
 #include "ffgp_internal.h"

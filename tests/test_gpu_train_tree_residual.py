@@ -401,19 +401,22 @@ def test_the_status_is_shared_by_the_call():
     assert bool(torch.isfinite(trace).all())
 
 
-def test_c_abi_refuses_and_accepts():
-    """ffgp_train_tree_res_raw through ctypes: FFGP_ERR_ARG with parameters, rho, state and trace untouched for state_stride = 2 P on a
-    residual member, v_low_dev without v_high_dev, an RQ leaf and a residual member without y_low_dev; the accepted call behind them
-    runs (P + 1 parameters move), with r = NULL it is ffgp_train_tree_raw, and ffgp_train_tree_lds_raw still refuses V2"""
+def _abi_case(D):
+    """one member through the C entries by ctypes: n = 20 (two 16-row strips, the second padded), d = 1, Sum(Linear with a trained centre,
+    leaf 1: Matern 5/2 unless `kfun1` says otherwise), the residual link with variances unless `resid` is off (None: r = NULL).
+    -> (call, raw, P): call(**kw) runs 3 Adam steps from zero moments and returns (rc, state, trace); raw: the parameters it moves"""
     from fidelityfusion_amd import _lib
     from fidelityfusion_amd._lib import KDesc, KTree, Problem, Residual, TreeLinks
-    n, D = 20, 2
+    n = 20
     rng = np.random.default_rng(2)
     x = T(rng.uniform(0, 1, (n, D)))
     yl = T(np.sin(3 * x.cpu().numpy()[:, :1]))
     yh = 1.2 * yl + 0.1 * T(rng.standard_normal((n, 1)))
     vl, vh = T(rng.uniform(0.01, 0.1, n)), T(rng.uniform(0.01, 0.1, n))
-    raw = {k: T(v) for k, v in {"w0": [1.0, 1.2], "a0": [1.0], "c0": [0.1, -0.1], "w1": [0.9, 1.1], "a1": [1.0], "lb": [0.7], "rho": [0.8]}.items()}
+    vnan_t = vh.clone()
+    vnan_t[0] = float("nan")
+    raw = {k: T(v) for k, v in {"w0": np.linspace(1.0, 1.2, D), "a0": [1.0], "c0": np.linspace(0.1, -0.1, D), "w1": np.linspace(0.9, 1.1, D),
+                                "a1": [1.0], "lb": [0.7], "rho": [0.8]}.items()}
     h = _lib.handle(0)
     _lib.bind_stream(h, 0)
     opt = _lib.Adam(1e-2, 0.9, 0.999, 1e-8)
@@ -455,8 +458,15 @@ def test_c_abi_refuses_and_accepts():
         torch.cuda.synchronize()
         return rc, state, trace
 
-    vnan_t = vh.clone()
-    vnan_t[0] = float("nan")
+    return call, raw, P
+
+
+def test_c_abi_refuses_and_accepts():
+    """ffgp_train_tree_res_raw through ctypes: FFGP_ERR_ARG with parameters, rho, state and trace untouched for state_stride = 2 P on a
+    residual member, v_low_dev without v_high_dev, an RQ leaf and a residual member without y_low_dev; the accepted call behind them
+    runs (P + 1 parameters move), with r = NULL it is ffgp_train_tree_raw, and ffgp_train_tree_lds_raw still refuses V2"""
+    from fidelityfusion_amd import _lib
+    call, raw, P = _abi_case(2)
     before = {k: v.clone() for k, v in raw.items()}
     LDS = "ffgp_train_tree_lds_res_raw"
     refused = {"lds_short_state_stride": dict(stride=2 * P, fn=LDS), "lds_v_low_without_v_high": dict(v_high=False, fn=LDS),
@@ -496,3 +506,23 @@ def test_c_abi_refuses_and_accepts():
         assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
         assert all(torch.equal(outs[0][2][k], outs[1][2][k]) for k in raw)
         assert torch.equal(raw["rho"], before["rho"])
+
+
+@pytest.mark.parametrize("D", [2, 9])
+def test_plain_member_through_the_lds_res_entry_is_the_lds_entry_bit_for_bit(D):
+    """one step loop (csrc/train_tree_lds.h's ttl_body), two units: a plain V1 member through ffgp_train_tree_lds_res_raw with r = NULL gives
+    the state, trace and raw parameters of ffgp_train_tree_lds_raw, bit for bit -- Sum(Linear with a trained centre, Matern 3/2), n = 20,
+    d = 1, three Adam steps; D = 2 runs the <8> instantiations, D = 9 the <16> ones"""
+    call, raw, P = _abi_case(D)
+    before = {k: v.clone() for k, v in raw.items()}
+    outs = []
+    for fn in ("ffgp_train_tree_lds_res_raw", "ffgp_train_tree_lds_raw"):
+        for k in raw:
+            raw[k].copy_(before[k])
+        rc, state, trace = call(kfun1=2, resid=None, fn=fn)
+        assert rc == 0 and bool(torch.isfinite(trace).all()), fn
+        outs.append((state.clone(), trace.clone(), {k: v.clone() for k, v in raw.items()}))
+    assert all(not torch.equal(outs[1][2][k], before[k]) for k in raw if k != "rho") and float(outs[1][0][:2 * P].abs().max()) > 0.0
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    assert all(torch.equal(outs[0][2][k], outs[1][2][k]) for k in raw)
+    assert torch.equal(raw["rho"], before["rho"])

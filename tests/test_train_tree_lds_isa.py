@@ -1,6 +1,6 @@
-"""Build-time check of the one-launch composed-kernel trainer (csrc/train_tree_lds.hip; no GPU needed: hipcc cross-compiles): each
-instantiation of its kernel runs entirely in registers and LDS -- no private (scratch) segment, no vector register spilled -- its
-dynamic LDS request fits the CU's 160 KiB, and it is compiled for the 512 threads it is launched with.  Metadata only, as
+"""Build-time check of the one-launch composed-kernel trainer (csrc/train_tree_lds.hip, its step loop and layout in
+csrc/train_tree_lds.h; no GPU needed: hipcc cross-compiles): each instantiation of its kernel runs entirely in registers and LDS -- no
+private (scratch) segment, no vector register spilled -- its dynamic LDS request fits the CU's 160 KiB, and it is compiled for the 512 threads it is launched with.  Metadata only, as
 test_eig_lds_isa.py."""
 import os
 import re
@@ -28,7 +28,7 @@ def kernels():
 
 
 def _dynamic_lds_bytes():
-    """the host's request, TTL_LDS_DOUBLES of train_tree_lds.hip restated: the block image, X [128][17], three [128][16] images, pivots
+    """the host's request, TTL_LDS_DOUBLES of train_tree_lds.h restated: the block image, X [128][17], three [128][16] images, pivots
     and the diagonal extra, the leaves' tables, four rows of 136 (raw parameters, two moments, totals), 8 scalars and the int table"""
     blocks, ints = 36 * 16 * 17, 136 + 4 + 5 + 3 + 16
     return (blocks + 128 * 17 + 3 * 128 * 16 + 2 * 128 + (3 * 4 * 16 + 4 * 4) + 4 * 136 + 8 + ints // 2) * 8
@@ -48,9 +48,10 @@ def test_no_scratch_and_no_spilled_vector_register(kernels):
 def test_lds_fits_the_cu_and_the_launch_matches_the_bounds(kernels):
     csrc = os.path.join(ROOT, "fidelityfusion_amd", "csrc")
     src = open(os.path.join(csrc, "train_tree_lds.hip")).read()
+    hdr = open(os.path.join(csrc, "train_tree_lds.h")).read()
     tile = open(os.path.join(csrc, "train_tile.h")).read()
     host = open(os.path.join(csrc, "train_host.h")).read()
-    # the formula restated above: the head both one-launch trainers share (train_tile.h), then this kernel's tail
+    # the formula restated above: the head both one-launch trainers share (train_tile.h), then this kernel's tail (train_tree_lds.h)
     for piece in ("#define TR_OFF_XS (NBLK_LOWER * BLKSZ)", "#define TR_OFF_YM (TR_OFF_XS + TR_N * (TR_D + 1))",
                   "#define TR_OFF_GAM (TR_OFF_YM + TR_N * TR_Y)", "#define TR_OFF_AM (TR_OFF_GAM + TR_N * TR_Y)",
                   "#define TR_OFF_PIV (TR_OFF_AM + TR_N * TR_Y)", "#define TR_OFF_DVEC (TR_OFF_PIV + TR_N)",
@@ -59,7 +60,7 @@ def test_lds_fits_the_cu_and_the_launch_matches_the_bounds(kernels):
     for piece in ("#define TTL_OFF_LEAF TR_OFF_TAIL", "#define TTL_OFF_PAR (TTL_OFF_LEAF + 3 * TTL_L * TR_D + 4 * TTL_L)",
                   "#define TTL_OFF_SC (TTL_OFF_PAR + 4 * TTL_PPAD)", "#define TTL_OFF_INT (TTL_OFF_SC + 8)",
                   "#define TTL_INTS (TTL_PPAD + 4 + 5 + 3 + 16)", "#define TTL_LDS_DOUBLES (TTL_OFF_INT + TTL_INTS / 2)", "#define TTL_PPAD 136"):
-        assert piece in src, piece
+        assert piece in hdr, piece
     # both launches: the one call below makes the <8> and the <16> instantiation (tr_by_dm), each with 512 threads and this request
     assert src.count("train_launch(h, ffgp_train_tree_lds_kernel<dm()>, TTL_LDS_DOUBLES * sizeof(double), F, tab, cm)") == 1
     assert "return f(std::integral_constant<int, 8>());\n  return f(std::integral_constant<int, 16>());" in host
