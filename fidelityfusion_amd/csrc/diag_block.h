@@ -54,24 +54,42 @@ __device__ __forceinline__ int simd_id() {
   return (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4) & 3;     // HW_REG_HW_ID (4), SIMD_ID = bits 5:4
 }
 
-// The helper waves of stage [A]: the waves that do not share wave 0's SIMD (fp64 MFMAs and the pivot loop's DP-ALU work share a pipe),
-// six with two waves per SIMD.  simd[w] = simd_id() of wave w, published behind a barrier.  Declares hidx (this wave's index among the
-// helpers, -1 for the others) and nh (their number).  The stage loops need nh >= 4 (the inverse's row blocks take two columns per helper
-// and have up to seven): a placement that leaves fewer makes all seven other waves helpers.  (A macro: as an inlined function the same
-// code compiled to a different instruction order, in wave 0's pivot loop of ffgp_small_mfma_kernel among other places.)
-#define HELPER_ROLES(simd, wave, hidx, nh)          \
-  int hidx = -1, nh = 0;                            \
-  {                                                 \
-    const int s0_ = (simd)[0];                      \
-    for (int w_ = 1; w_ < 8; ++w_) {                \
-      const bool is_h_ = (simd)[w_] != s0_;         \
-      if (is_h_ && w_ == (wave)) hidx = nh;         \
-      nh += is_h_ ? 1 : 0;                          \
-    }                                               \
-    if (nh < 4) {                                   \
-      nh = 7;                                       \
-      hidx = (wave) - 1;                            \
-    }                                               \
-    hidx = __builtin_amdgcn_readfirstlane(hidx);    \
-    nh = __builtin_amdgcn_readfirstlane(nh);        \
-  }
+// HELPER_ROLES(simd, wave, hidx, nh): the helper waves of stage [A] from the eight waves' SIMDs -- helper_roles.h, which the CPU test of
+// the hand-out (tests/test_helper_roles_host.py: all 4^8 tables) includes as well.  The kernels that expand it -- ffgp_potrf_diag128_v4
+// (potrf.hip), tr_body (train.hip), ttl_body (train_tree_lds.h) -- publish wave_simd(wave) per wave and call ROLES_SEEN behind it.
+#include "helper_roles.h"
+
+// The SIMD of wave `w` as HELPER_ROLES is to see it, and the roles it handed out.  Product build: the hardware's id, and nothing.
+// -DFFGP_TEST_ROLES (libffgp_roles.so, `make roles`; tests/test_gpu_helper_roles.py): the SIMD comes from a table the test sets, 2 bits
+// per wave, and lane 0 of every wave records the hidx and nh it got -- bits 3w..3w+2: hidx + 1 of wave w, bits 24..26: nh, bit 31: set
+// by every writer -- so that a test which forces a placement also sees that the stage loops ran under it.  One table and one record
+// per translation unit (FFGP_ROLES_TU names it in the two entry points below); the hardware hands out a placement like any of these
+// whenever other workgroups share the CU.
+#ifdef FFGP_TEST_ROLES
+static __device__ unsigned ffgp_roles_table = 0xE4E4u;      // 0 1 2 3 0 1 2 3: two waves per SIMD
+static __device__ unsigned ffgp_roles_seen = 0u;
+__device__ __forceinline__ int wave_simd(int w) { return (int)(ffgp_roles_table >> (2 * w)) & 3; }
+#define ROLES_SEEN(lane, wave, hidx, nh) \
+  if ((lane) == 0) atomicOr(&ffgp_roles_seen, 0x80000000u | ((unsigned)(nh) << 24) | ((unsigned)((hidx) + 1) << (3 * (wave))))
+#ifdef FFGP_ROLES_TU
+#define FFGP_ROLES_CAT2(a, b) a##b
+#define FFGP_ROLES_CAT(a, b) FFGP_ROLES_CAT2(a, b)
+// set the table (bits 2w..2w+1: the SIMD of wave w) for every later launch of this translation unit's kernels
+extern "C" __attribute__((visibility("default"))) int FFGP_ROLES_CAT(ffgp_test_roles_set_, FFGP_ROLES_TU)(unsigned table) {
+  if (hipDeviceSynchronize() != hipSuccess) return FFGP_ERR_HIP;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(ffgp_roles_table), &table, sizeof(table)) != hipSuccess) return FFGP_ERR_HIP;
+  return hipDeviceSynchronize() == hipSuccess ? 0 : FFGP_ERR_HIP;
+}
+// the record of the launches since the last call (0: none of this translation unit's kernels ran), which it clears
+extern "C" __attribute__((visibility("default"))) int FFGP_ROLES_CAT(ffgp_test_roles_seen_, FFGP_ROLES_TU)(unsigned* seen) {
+  const unsigned zero = 0u;
+  if (hipDeviceSynchronize() != hipSuccess) return FFGP_ERR_HIP;
+  if (hipMemcpyFromSymbol(seen, HIP_SYMBOL(ffgp_roles_seen), sizeof(*seen)) != hipSuccess) return FFGP_ERR_HIP;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(ffgp_roles_seen), &zero, sizeof(zero)) != hipSuccess) return FFGP_ERR_HIP;
+  return hipDeviceSynchronize() == hipSuccess ? 0 : FFGP_ERR_HIP;
+}
+#endif
+#else
+__device__ __forceinline__ int wave_simd(int) { return simd_id(); }
+#define ROLES_SEEN(lane, wave, hidx, nh)
+#endif

@@ -220,9 +220,10 @@ __global__ __launch_bounds__(512, 2) void ffgp_potrf_diag128_v4(double* __restri
   if (rag.pub && blockIdx.x == 0 && tid == 64) __hip_atomic_store(rag.pub, rag.pub_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (prio) __builtin_amdgcn_s_setprio(3);
   const int nst = (nb + 15) >> 4;
-  if (lane == 0) flags[wave] = simd_id();
+  if (lane == 0) flags[wave] = wave_simd(wave);
   LDS_BARRIER();
   HELPER_ROLES(flags, wave, hidx, nh);
+  ROLES_SEEN(lane, wave, hidx, nh);
   // ---- loads: wave 0 takes block (0, 0) straight into the factor's registers; the other waves bring every other lower block of the
   //      first nst block rows into LDS ([16][17] images; diagonal blocks mirrored to full), all loads of a wave in flight at once
   double v0[4];

@@ -225,7 +225,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     for (int r = 0; r < 4; ++r) S[blk_off(bi, bj) + (g + 4 * r) * BLD + c] = (bi == bj && g + 4 * r == c) ? 1.0 : 0.0;
   }
   if (tid == 0) flags[0] = 0;
-  if (lane == 0) flags[8 + wave] = simd_id();
+  if (lane == 0) flags[8 + wave] = wave_simd(wave);
   if (RESID && tid == 0) {
     rmode[0] = hasv ? 2 : (isres ? 1 : 0);
     const double* pv[4] = {isres ? Rp->yl : nullptr, isres ? Rp->yh : nullptr, Rp->rho, Rp->rho_last};
@@ -238,6 +238,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   }
   __syncthreads();
   HELPER_ROLES(flags + 8, wave, hidx, nh);      // helpers of the factorisation's stage [A]
+  ROLES_SEEN(lane, wave, hidx, nh);
   if (tid < D) wv[tid] = ffgp_link_val(M.l.w_link, raw[M.l.w_broadcast ? 0 : tid], M.l.w_c);
   if (tid == 64) sc[0] = ffgp_link_val(M.l.amp_link, raw[nw], M.l.amp_c);
   if (tid == 65) sc[1] = M.dadd ? ffgp_link_val(M.l.dadd_link, raw[nw + 1], M.l.dadd_c) : 0.0;

@@ -224,9 +224,10 @@ __device__ __forceinline__ void ttl_body(const MODEL* __restrict__ tab, TtlCommo
     tri[0] = M->nl; tri[1] = M->shape; tri[2] = M->op[0]; tri[3] = M->op[1]; tri[4] = M->op[2];
   }
   if (tid < TTL_L) kfi[tid] = (tid < M->nl) ? M->k[tid].kfun : FFGP_KFUN_SE;
-  if (lane == 0) flags[8 + wave] = simd_id();
+  if (lane == 0) flags[8 + wave] = wave_simd(wave);
   __syncthreads();
   HELPER_ROLES(flags + 8, wave, hidx, nh);      // helpers of the factorisation's stage [A]
+  ROLES_SEEN(lane, wave, hidx, nh);
   if (tid < TTL_L * TR_D) {      // the effective parameters of the first step (later ones: by the threads that update the raw ones)
     const int e = tid >> 4, k = tid & 15;
     double v = 0.0, cv = 0.0;
