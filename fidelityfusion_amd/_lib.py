@@ -223,6 +223,8 @@ EXPORTS = {
                                  _dp, C.c_long]),
     "ffgp_train_residual_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(Residual), C.c_int,
                                           C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
+    "ffgp_train_wide_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(Residual), C.POINTER(C.c_int),
+                                      C.c_int, C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long, C.POINTER(C.c_int)]),
     "ffgp_train_car_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(CarLink), C.c_int,
                                      C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,

@@ -45,6 +45,46 @@ int main() {
     ffgp_residual rs;
     std::memset(&rs, 0, sizeof rs);
     EXPECT(ffgp_train_residual_raw(nullptr, 1, &p, &lk, &rs, 3, &ad, &x, 8, 0, &x, 3) < 0);
+    // the wide-output one-launch trainer: every refusal comes before the handle is dereferenced or anything is enqueued
+    {
+      ffgp_handle* fk = reinterpret_cast<ffgp_handle*>(0x1);
+      ffgp_problem pw;
+      std::memset(&pw, 0, sizeof pw);
+      pw.n = 8; pw.D = 2; pw.d = 8; pw.X_dev = pw.Y_dev = pw.w_dev = pw.amp_dev = pw.diag_add_dev = &x;
+      pw.kfun = FFGP_KFUN_SE; pw.kparam = 1.0; pw.ll_variant = FFGP_LL_V1;
+      int dt = 40, inf = 7;
+      EXPECT(ffgp_train_wide_raw(nullptr, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, nullptr, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      EXPECT(ffgp_train_wide_raw(fk, 17, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 2, &inf) == FFGP_ERR_ARG);      // trace_stride < steps
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 7, 0, &x, 3, &inf) == FFGP_ERR_ARG);      // state_stride < 2 (D + 2)
+      dt = 16;      // not a wide model
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      dt = 40; pw.d = 41;      // more columns passed than the likelihood has
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      dt = 400; pw.d = 129;      // a plain member passes at most 128 columns
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      pw.d = 8; pw.n = 129;
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      pw.n = 8; pw.D = 17;
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 40, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      pw.D = 2; pw.ll_variant = FFGP_LL_V2;
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      pw.ll_variant = FFGP_LL_V1; pw.kfun = FFGP_KFUN_RQ;
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      pw.kfun = FFGP_KFUN_SE; pw.cov_dev = &x;
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, nullptr, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      pw.cov_dev = nullptr;
+      ffgp_residual rw;
+      std::memset(&rw, 0, sizeof rw);
+      rw.rho_dev = &x; rw.y_low_dev = &x;      // a residual member without y_high
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, &rw, &dt, 3, &ad, &x, 10, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      rw.y_high_dev = &x; rw.v_low_dev = &x;      // one variance diagonal without the other
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, &rw, &dt, 3, &ad, &x, 10, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      rw.v_low_dev = nullptr;      // rho is a fourth parameter: the state holds 2 (D + 3)
+      EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, &rw, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
+      EXPECT(inf == 7);      // (a refused call writes nothing)
+    }
     ffgp_kdesc kd[2];
     ffgp_kdesc_grads kg[2];
     std::memset(kd, 0, sizeof kd);

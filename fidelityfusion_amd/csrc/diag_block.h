@@ -93,3 +93,12 @@ extern "C" __attribute__((visibility("default"))) int FFGP_ROLES_CAT(ffgp_test_r
 __device__ __forceinline__ int wave_simd(int) { return simd_id(); }
 #define ROLES_SEEN(lane, wave, hidx, nh)
 #endif
+
+// The function form of the hand-out and its report, for a kernel that has no measured register allocation to keep (the macros above
+// are spelled out in the three kernels that were measured with them): simd[w] as HELPER_ROLES wants it, published behind a barrier.
+__device__ __forceinline__ void helper_roles(const int* simd, int lane, int wave, int& hidx_out, int& nh_out) {
+  HELPER_ROLES(simd, wave, hidx, nh);
+  ROLES_SEEN(lane, wave, hidx, nh);
+  hidx_out = hidx;
+  nh_out = nh;
+}

@@ -7,6 +7,9 @@ Python round trip, one autograd graph, one status read-back); here it costs its 
 Models whose kernel is a SumKernel / ProductKernel tree of up to four library kernels -- SumKernel(LinearKernel, MaternKernel) is the
 kernel of the reference's demos and two-fidelity models -- take the same route through ffgp_train_tree_raw (launch per stage, every size),
 or, with `tree_one_launch=True` and at most TREE_ONE_LAUNCH_MAX_N points, through ffgp_train_tree_lds_raw: one launch for all their steps.
+With `wide_one_launch=True` single-kernel `cigp` models of at most 128 points with MORE than 16 target columns -- CIGAR's fidelity 0 on a
+field, ResGP's and AR's residual fidelities -- are trained in one launch as well (ffgp_train_wide_raw), on targets compressed to at most
+n (a residual member: 2 n) columns by `compress_targets`.
 With `fuse_composed=True` train_AR's residual fidelities on such a kernel and `GP_basic` blocks over one are trained by the library too
 (ffgp_train_tree_res_raw; in one launch: ffgp_train_tree_lds_res_raw).
 """
@@ -22,6 +25,38 @@ TRAIN_MAX_MODELS = 16      # models per ffgp_train_raw call (include/ffgp.h); lo
 TRAIN_THREADS = 4          # host threads (handle + stream each) that train the larger models of one call side by side
 TREE_ONE_LAUNCH_MAX_N = 128   # composed-kernel models up to this size take ffgp_train_tree_lds_raw under `tree_one_launch=True`: the largest
                               # N at which it beat the launch-per-stage call by more than the run's spread (profiles/train_tree_lds_bench.txt)
+
+
+WIDE_KFUN_MAX = 3             # ffgp_train_wide_raw covers FFGP_KFUN_SE ... FFGP_KFUN_MATERN52
+
+
+def compress_targets(*mats):
+    """Row blocks of Z_eff with Z_eff Z_eff^T = Z Z^T, Z the matrices [n_i, d] stacked row-wise (m = sum n_i rows): the V1 likelihood
+    and its gradients -- a residual member's dloss/drho included -- depend on the targets only through inner products of their rows, so
+    training on the blocks of Z_eff [m, m] in place of the matrices gives the same loss and gradients whatever d is, as long as the
+    likelihood keeps the true d in its log-determinant term and constant (ffgp_train_wide_raw's d_true).  Z_eff = U sqrt(max(Lambda, 0))
+    from the eigendecomposition of the Gram Z Z^T: the Gram on the fp64 GEMM, the decomposition on the package's own solver (the
+    one-workgroup LDS solver up to 128 rows, the two-stage solver above: a residual member at n = 128 has m = 256), negative
+    eigenvalues -- rounding -- clamped to zero.  With d <= m there is nothing to gain and the inputs come back unchanged."""
+    from . import eigh as E
+    from . import functional as F
+    m, d = sum(t.shape[0] for t in mats), mats[0].shape[1]
+    if d <= m:
+        return mats
+    with torch.no_grad():
+        Z = torch.cat(mats, 0) if len(mats) > 1 else mats[0]
+        G = F.matmul_nt(Z, Z)
+        if m <= 128:
+            ev, U = F._syev_lds_checked(G[None])
+            ev, U = ev[0], U[0]
+        else:
+            ev, U = E.eigh(G)
+        Zeff = U * ev.clamp_min(0.0).sqrt()
+        out, r0 = [], 0
+        for t in mats:
+            out.append(Zeff[r0:r0 + t.shape[0]].contiguous())
+            r0 += t.shape[0]
+    return tuple(out)
 
 
 class AdamState:
@@ -252,7 +287,7 @@ def _residual_ok(res, x):
 
 
 def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, state=None, residual=None, tree_one_launch=False, car=None,
-               fuse_composed=False):
+               fuse_composed=False, wide_one_launch=False):
     """`steps` Adam iterations on every model of `models` (independent `cigp` models, `xs[f]`, `ys[f]` their training data; y may be
     `[y, y_var]`), each exactly the reference's iteration (FidelityFusion_Models/ResGP.py:82-88): loss = -negative_log_likelihood,
     gradients of the three raw parameters, torch.optim.Adam(lr, betas, eps) update.  Returns `(trace, state)`:
@@ -305,9 +340,23 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     drawn once per call, after `torch.manual_seed(105)`, which leaves the global generator as one reference step leaves it.
     state["residual_targets"][f] = [y_high - exp(b) * y_low, None] at the b of the start of the last step.  A tree or
     RationalQuadraticKernel base kernel, an l_z of several elements or CPU tensors: the reference's loop, same return values.
-    `car=` and `residual=` on one model raise ValueError."""
+    `car=` and `residual=` on one model raise ValueError.
+    `wide_one_launch=True` (off by default: without it nothing changes) sends the WIDE-output models of the call -- a `cigp` over one
+    library radial kernel (SE / ARD, Matern 1/2, 3/2, 5/2) on one GPU in fp64 with n <= 128, D <= 16 and d > 16 target columns, plain (y
+    or [y, y_var]) or with a `residual=` link in either form -- through ffgp_train_wide_raw, up to 16 per call: ONE kernel launch for
+    all their steps (csrc/train_wide.hip).  Their targets are compressed once per call by `compress_targets` -- Y to at most n columns,
+    a residual member's [y_high; y_low] to at most 2 n -- and the likelihood keeps the true d, so a step's cost does not depend on d.
+    Without the keyword these models run ffgp_train_raw's launch-per-stage form, 13 dependent launches per step at n = 128.  Every other
+    model of the call keeps its route.  Return values, in-place updates, state["residual_targets"], the failure rule (a not-PD Sigma
+    stops that model alone; LinAlgError) and the version counters are the one-launch route's; the Adam state of such a model is kept
+    per model under the key the launch-per-stage route uses, so a `state` may be continued with either value of the keyword (the
+    routes agree to rounding).  state["wide_one_launch"] lists the models that took the route in the last call, state["wide_status"]
+    their status words (0, or the failing pivot) and state["wide_trace"] their rows of the trace (NaN from a failing step on), which a
+    raising call does not return.  Without a GPU the keyword raises FFGPError: there is no other way to run this route."""
     models, xs, ys = list(models), list(xs), list(ys)
     nF = len(models)
+    if wide_one_launch and not torch.cuda.is_available():
+        raise _lib.FFGPError("train_many(wide_one_launch=True) needs an MI355X (gfx950) GPU: ffgp_train_wide_raw has no CPU path")
     if not (nF == len(xs) == len(ys)) or steps <= 0:
         raise ValueError("train_many: models, xs, ys must have one length and steps must be positive")
     if residual is not None:
@@ -347,6 +396,8 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         state = {"fused": fused, "chunks": {}, "opts": [None] * nF}
     state["residual_targets"] = [None] * nF
     state["tree_one_launch"] = []
+    if wide_one_launch or "wide_one_launch" in state:      # (a state that has been on the route: nothing of it took it in THIS call yet)
+        state["wide_one_launch"], state["wide_status"], state["wide_trace"] = [], {}, {}
     if not fused or not state["fused"]:
         if state["fused"]:
             raise ValueError("train_many: this state belongs to fused training; the models no longer qualify for it")
@@ -476,6 +527,58 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         return launch(idx, 2 * max(npar), lambda st, tr: check(
             fn(h, len(idx), P, L, int(steps), C.byref(opt), st.buf.data_ptr(), st.stride, int(st.step), tr.data_ptr(), tr.stride(0)), name))
 
+    def run_wide(idx, step0):
+        """one ffgp_train_wide_raw call for the wide models `idx` (<= 16, all at Adam step `step0`): targets compressed, the true d
+        apart.  Every model keeps an Adam state of its own under the key (f,) -- the launch-per-stage route's, which trains such a
+        model in a call of its own."""
+        h = _lib.handle(dev.index)
+        _lib.bind_stream(h, dev.index)
+        nm = len(idx)
+        P = (Problem * nm)()
+        L = (_lib.Links * nm)()
+        R = (_lib.Residual * nm)()
+        DT = (C.c_int * nm)()
+        INFO = (C.c_int * nm)()
+        keep, strides = [], []
+        for j, f in enumerate(idx):
+            P[j], L[j], R[j], _, nw = describe(f)
+            DT[j] = P[j].d
+            if res_of(f) is not None:
+                _, yl, yh, _, _ = _split_residual(res_of(f))
+                yhc, ylc = compress_targets(yh, yl)
+                R[j].y_high_dev, R[j].y_low_dev, P[j].d = yhc.data_ptr(), ylc.data_ptr(), yhc.shape[1]
+                keep += [yhc, ylc]
+            else:
+                yc, = compress_targets(elig[f][1])
+                P[j].Y_dev, P[j].d = yc.data_ptr(), yc.shape[1]
+                keep.append(yc)
+            strides.append(2 * (nw + 2))
+        # the models' states ([1, stride] each, the only copy kept between calls) are staged through a block of the call's: one short
+        # copy per model in, one out
+        smax = max(strides)
+        blk = torch.zeros((nm, smax), dtype=torch.float64, device=dev)
+        sts = []
+        for j, f in enumerate(idx):
+            st = state["chunks"].get((f,))
+            if st is None or st.stride != strides[j] or st.buf.device != dev:
+                st = state["chunks"][(f,)] = AdamState(torch.zeros((1, strides[j]), dtype=torch.float64, device=dev), strides[j], step0)
+            blk[j, :strides[j]].copy_(st.buf[0])
+            sts.append(st)
+        tr = torch.empty((nm, steps), dtype=torch.float64, device=dev)
+        rc = check(lib.ffgp_train_wide_raw(h, nm, P, L, R, DT, int(steps), C.byref(opt), blk.data_ptr(), smax, int(step0),
+                                           tr.data_ptr(), tr.stride(0), INFO), "ffgp_train_wide_raw")
+        for j, st in enumerate(sts):
+            st.buf[0].copy_(blk[j, :strides[j]])
+        if rc == 0:      # (a call that failed leaves its optimisers where they were: the caller sees LinAlgError)
+            for st in sts:
+                st.step += steps
+        trace[list(idx)] = tr
+        for j, f in enumerate(idx):
+            state["wide_status"][f] = int(INFO[j])
+            state["wide_trace"][f] = tr[j]
+        del keep
+        return rc
+
     def launch(idx, stride, call):
         """the chunk's Adam state and trace rows around one library call `call(state, trace rows)`; returns the status"""
         key = tuple(idx)
@@ -539,6 +642,15 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     small_trees = [f for f in sorted(trees) if shapes[f][0] <= F.SMALL_BATCH_MAX_N and f not in one_launch]
     large = [f for f in range(nF) if f not in set(small) and f not in set(small_trees) and f not in one_launch]      # (set(small): CAR ones too)
     state["tree_one_launch"] = lds_trees
+    # ... and under `wide_one_launch` the wide-output models ffgp_train_wide_raw covers leave `large` for calls of up to 16, models
+    # at one Adam step sharing a call (ffgp_train_wide_raw takes one step0)
+    wide = []
+    if wide_one_launch:
+        wide = [f for f in large if f not in trees and car_of(f) is None and shapes[f][0] <= F.SMALL_BATCH_MAX_N
+                and shapes[f][1] <= F.SMALL_BATCH_MAX_D and shapes[f][2] > F.SMALL_BATCH_MAX_d and "ll" not in elig[f][0]
+                and "diag" not in elig[f][0] and elig[f][0]["kfun"] <= WIDE_KFUN_MAX]
+        large = [f for f in large if f not in set(wide)]
+        state["wide_one_launch"] = wide
     # (CAR members have an entry point of their own: their small ones form chunks apart from the plain and residual models')
     small_car = [f for f in small if car_of(f) is not None]
     small = [f for f in small if car_of(f) is None]
@@ -550,6 +662,13 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     for group in (small, small_car, small_trees, lds_trees):
         for c0 in range(0, len(group), TRAIN_MAX_MODELS):
             rcs.append((group[c0:c0 + TRAIN_MAX_MODELS], run(group[c0:c0 + TRAIN_MAX_MODELS])))
+    by_step = {}
+    for f in wide:
+        st = state["chunks"].get((f,))
+        by_step.setdefault(st.step if st is not None else 0, []).append(f)
+    for step0, group in sorted(by_step.items()):
+        for c0 in range(0, len(group), TRAIN_MAX_MODELS):
+            rcs.append((group[c0:c0 + TRAIN_MAX_MODELS], run_wide(group[c0:c0 + TRAIN_MAX_MODELS], step0)))
     if len(large) >= 2 and _lib.current_slot() == 0:
         outs = threaded_blocks([(lambda f=f: run([f])) for f in large], nslots=min(TRAIN_THREADS, len(large)), device_index=dev.index)
         rcs += [([f], rc) for f, rc in zip(large, outs)]

@@ -592,6 +592,31 @@ int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const 
 int ffgp_nlml_fused_small_batch_async(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, double* nll_dev,
                                       const ffgp_grads* g);
 
+/* ffgp_train_raw's ONE-LAUNCH form for WIDE-output models -- more than 16 target columns at n <= 128 (csrc/train_wide.hip): CIGAR's
+   fidelity 0 on a field (FidelityFusion_Models/CIGAR.py:149-176: 128 points), ResGP and AR at Experiments/GAR_Aligned/exp_aligned.py's
+   sizes (100 low- against 4..32 high-fidelity points, hundreds to thousands of columns).  The V1 likelihood and all its gradients see
+   the targets only through inner products of their rows: with Z the stacked targets (Y of a plain member, [y_high; y_low] of a
+   residual one; m = n or 2 n rows) any Z_eff [m, c] with Z_eff Z_eff^T = Z Z^T trains the same model, as long as the d of
+   d sum log L_ii + n d / 2 log(2 pi) and of G = 1/2 (d Sigma^-1 - A A^T) stays the true one.  So the caller may pass the row blocks of
+   U sqrt(max(Lambda, 0)) from the eigendecomposition of Z Z^T (c = m columns whatever d is) in place of the targets:
+   p[f].d = the columns actually PASSED (Y_dev, or r[f].y_low_dev / y_high_dev: [n, p[f].d]), d_true[f] = the likelihood's d.
+   A persistent workgroup per model factors Sigma once per step and then streams ceil(p[f].d / 16) column blocks through
+   Gamma = L^-1 Y, A = L^-T Gamma, |Gamma|^2, sum A .* y_low and one MFMA group per owned block of A A^T; the gradient pass, the
+   reduction and Adam are ffgp_train_raw's.  r may be NULL; r[f].rho_dev = NULL is a plain member; the member rules, the Adam state
+   layout ([exp_avg (nw + 2) | exp_avg_sq (nw + 2)], a residual member nw + 3 with rho last), step0, the trace and rho_last_dev are
+   ffgp_train_residual_raw's, so a state moves freely between the two calls; the two agree to rounding, not bit for bit.
+   Covers F <= 16, n <= 128, D <= 16, d_true[f] > 16, p[f].d <= min(d_true[f], 128) for a plain member and min(d_true[f], 256) for a
+   residual one, FFGP_KFUN_SE ... FFGP_KFUN_MATERN52, the V1 likelihood, diag_add and diag_vec.  FFGP_ERR_ARG, with nothing enqueued
+   and nothing written, for anything else -- d_true[f] <= 16, n > 128, a tree, pair or caller-built covariance, the V2 likelihood,
+   FFGP_KFUN_RQ, add_mat_dev, add_all, mean_jitter, a state_stride below the member's 2 (nw + 2 (+ 1)) -- which is never trained
+   another way.  Failure semantics are the one-launch form's: a Sigma that is not positive definite stops that member alone at that
+   step -- NaN in its trace from there on, its parameters, rho and moments as they were when the step began -- the others complete,
+   and the call returns the pivot status of the first failing member in the caller's order, else 0.  info (host, may be NULL)
+   receives every member's own status [F].  Synchronous.                                                                        */
+int ffgp_train_wide_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, const ffgp_residual* r, const int* d_true,
+                        int steps, const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev,
+                        long trace_stride, int* info);
+
 /* ffgp_train_raw with CAR members -- train_CAR's fidelities above 0 (FidelityFusion_Models/CAR_ContinuousAutoRegression.py:116-142):
    model f trains on the targets r = y_high - exp(b) * y_low (a product, then a difference, rounded as ffgp_train_residual_raw rounds
    its own) under the kernel kernel1(x, x') * s(b, l_z, sigma_z), the Monte-Carlo fidelity integral of fidelity_kernel_MCMC (:14-67)
