@@ -91,6 +91,12 @@ class Residual(C.Structure):
                 ("v_high_dev", _dp), ("v_high_stride", C.c_long), ("rho_last_dev", _dp)]
 
 
+class TlinLink(C.Structure):
+    """ffgp_tlin_link: a tensor-linear member of ffgp_train_tlin_raw (V_dev NULL = a plain model)"""
+    _fields_ = [("V_dev", _dp), ("V_row_stride", C.c_long), ("V_col_stride", C.c_long), ("l", C.c_int), ("y_low_dev", _dp),
+                ("y_high_dev", _dp), ("V_last_dev", _dp)]
+
+
 class CarLink(C.Structure):
     """ffgp_car_link: a CAR member of ffgp_train_car_raw (b_dev NULL = a plain model)"""
     _fields_ = [("b_dev", _dp), ("zls_dev", _dp), ("zamp_dev", _dp), ("zeps", C.c_double), ("z1_dev", C.c_void_p), ("z2_dev", C.c_void_p),
@@ -225,6 +231,8 @@ EXPORTS = {
                                           C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_wide_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(Residual), C.POINTER(C.c_int),
                                       C.c_int, C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long, C.POINTER(C.c_int)]),
+    "ffgp_train_tlin_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(TlinLink), C.c_int,
+                                      C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_car_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(CarLink), C.c_int,
                                      C.POINTER(Adam), _dp, C.c_long, C.c_long, _dp, C.c_long]),
     "ffgp_train_tree_raw": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.c_int, C.POINTER(Adam), _dp, C.c_long,

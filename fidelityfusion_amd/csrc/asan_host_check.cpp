@@ -45,6 +45,28 @@ int main() {
     ffgp_residual rs;
     std::memset(&rs, 0, sizeof rs);
     EXPECT(ffgp_train_residual_raw(nullptr, 1, &p, &lk, &rs, 3, &ad, &x, 8, 0, &x, 3) < 0);
+    // the tensor-linear trainer: a NULL handle, and with a handle that must never be dereferenced the link's own refusals
+    {
+      ffgp_handle* fk = reinterpret_cast<ffgp_handle*>(0x1);
+      ffgp_problem pt;
+      std::memset(&pt, 0, sizeof pt);
+      pt.n = 8; pt.D = 2; pt.d = 3; pt.X_dev = pt.w_dev = pt.amp_dev = pt.diag_add_dev = &x;
+      pt.kfun = FFGP_KFUN_SE; pt.kparam = 1.0; pt.ll_variant = FFGP_LL_V1;
+      ffgp_tlin_link tk;
+      std::memset(&tk, 0, sizeof tk);
+      tk.V_dev = &x; tk.l = 2; tk.y_low_dev = tk.y_high_dev = &x;
+      EXPECT(ffgp_train_tlin_raw(nullptr, 1, &pt, &lk, &tk, 3, &ad, &x, 20, 0, &x, 3) < 0);
+      EXPECT(ffgp_train_tlin_raw(fk, 1, &pt, &lk, nullptr, 3, &ad, &x, 20, 0, &x, 3) == FFGP_ERR_ARG);
+      EXPECT(ffgp_train_tlin_raw(fk, 1, &pt, &lk, &tk, 3, &ad, &x, 19, 0, &x, 3) == FFGP_ERR_ARG);      // state_stride < 2 (D + 2 + h l)
+      tk.l = 4;      // l > h
+      EXPECT(ffgp_train_tlin_raw(fk, 1, &pt, &lk, &tk, 3, &ad, &x, 20, 0, &x, 3) == FFGP_ERR_ARG);
+      tk.l = 2; tk.y_low_dev = nullptr;
+      EXPECT(ffgp_train_tlin_raw(fk, 1, &pt, &lk, &tk, 3, &ad, &x, 20, 0, &x, 3) == FFGP_ERR_ARG);
+      tk.y_low_dev = &x; tk.V_row_stride = -1;
+      EXPECT(ffgp_train_tlin_raw(fk, 1, &pt, &lk, &tk, 3, &ad, &x, 20, 0, &x, 3) == FFGP_ERR_ARG);
+      tk.V_row_stride = 0; pt.ll_variant = FFGP_LL_V2;
+      EXPECT(ffgp_train_tlin_raw(fk, 1, &pt, &lk, &tk, 3, &ad, &x, 20, 0, &x, 3) == FFGP_ERR_ARG);
+    }
     // the wide-output one-launch trainer: every refusal comes before the handle is dereferenced or anything is enqueued
     {
       ffgp_handle* fk = reinterpret_cast<ffgp_handle*>(0x1);

@@ -265,6 +265,7 @@ struct ffgp_handle {
   size_t train_blk_host_bytes;
   double* small_kbuf;   // ffgp_small_mfma_enqueue: the evaluate-mode launches' parked kernel values (8 models x 36 x 256 doubles)
   int train_persist_off;  // option "train_persist" = 0: ffgp_train_raw never takes the one-launch trainer
+  int tlin_gemm_min;      // ffgp_train_tlin_raw: members with n l h >= this run their two products on the fp64 GEMM (0 = never)
   int* bt_info;         // [F] device status words (first non-positive pivot of each block)
   int* bt_info_host;    // pinned mirror
   int trtri_overlap;    // option (default 1)
@@ -390,12 +391,12 @@ bool ffgp_small2_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_grad
 bool ffgp_small_batch_ok(const ffgp_problem* p, const ffgp_grads* g);
 // train.hip: K Adam steps of F small models in ONE launch (one persistent workgroup per model)
 bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r = nullptr,
-                           const ffgp_car_link* cr = nullptr);
+                           const ffgp_car_link* cr = nullptr, const ffgp_tlin_link* tl = nullptr);
 bool ffgp_small_mfma_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_grads* g);      // one likelihood (+ gradients), n <= 128: same kernel, no Adam
 int ffgp_small_mfma_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g, int info_max);
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
                        long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r = nullptr,
-                       const ffgp_car_link* cr = nullptr);
+                       const ffgp_car_link* cr = nullptr, const ffgp_tlin_link* tl = nullptr);
 int ffgp_small_batch_enqueue(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, double* nll_dev, const ffgp_grads* g);
 // ---- assemble.hip, solve.hip, grad.hip, pair.hip, join.hip, eig.hip: the stages the host drivers string together
 int ffgp_assemble_impl(ffgp_handle* h, const double* X1, int n1, const double* X2, int n2, int D, const double* w,

@@ -203,6 +203,7 @@ int ffgp_create(int device, ffgp_handle** out) {
   h->syrk_light_tiles = 1;
   h->super_block = 1024;
   h->splitk_min_k = 1024;
+  h->tlin_gemm_min = 8192;      // (profiles/train_tlin_bench.txt: the plain kernels win up to n l h = 2048, the GEMM from 14400 on)
   h->skinny_max_n = 8;
   h->super_min_n = 2048;
   h->la_carry = 2;
@@ -355,6 +356,7 @@ static const ffgp_option k_options[] = {
     {"chase_xl_max_n", &ffgp_handle::chase_xl_max_n, OPT_INT},
     {"grad_lanes", &ffgp_handle::grad_lanes, OPT_INT, 1.0, 3.0},
     {"train_persist", &ffgp_handle::train_persist_off, OPT_NOT},
+    {"tlin_gemm_min", &ffgp_handle::tlin_gemm_min, OPT_INT, 0.0, 2147483647.0},
     {"chase_xcc", &ffgp_handle::chase_xcc, OPT_INT, 0.0, 15.0},
     {"la_carry", &ffgp_handle::la_carry, OPT_INT},
     {"la_carry_n", &ffgp_handle::la_carry_n, OPT_INT, 0.0},

@@ -33,6 +33,11 @@
 // 116-142): the targets r = y_high - exp(b) y_low and the effective amplitude link(amp_raw) * s(b, l_z, sigma_z) -- the Monte-Carlo fidelity
 // integral, car_scale_wave in train_tile.h -- are re-formed at every step; b, l_z, sigma_z are three more Adam parameters, kept with their
 // moments, the samples and the partials of s behind the reduction's extra total (dloss/db needs sum dloss/dr .* y_low).  Launches of their own.
+// TENSOR-LINEAR members (tr_body<DM, true, false, false, false, true>, ffgp_train_tlin_kernel; train_CIGAR's fidelities above 0, CIGAR.py:116-133):
+// the targets are R = y_high - y_low V^T with V [h, l] (h = d <= 16, l <= h) the map's matrix, re-formed at every step into the zero-padded
+// target image; V, its two moments, dloss/dV = -A^T y_low and V as the step began stay in LDS for the whole call (5 x 256 doubles) and V's
+// h l entries are Adam parameters nw + 2 ... of the member.  The diagonal extra |diag(v_high) - diag(v_low)| is constant -- the member's
+// diag_vec -- so none of the residual class's four [128] arrays is needed; y_low / y_high are read from global memory.  Launches of their own.
 // Covers: n <= 128, D <= 16, d <= 16, one radial-profile kernel, V1 likelihood (V2: plain and CAR members), diag_add and diag_vec (no matrix / all-entries /
 // mean(K) extras, no learnable profile parameter): what cigp_v10 produces.  Everything else keeps the paths it had.
 // HOST side: the scaffold of train_host.h, shared with train_tree_lds.hip -- the call's block on the handle with its pinned mirror, the
@@ -76,6 +81,13 @@ struct TrainCar {
   const double* yl; const double* yh;    // [n, d]
   double* b_last;                        // optional [1]: b at the start of the last step taken
 };
+// a tensor-linear member's link (ffgp_tlin_link): every member of a tensor-linear launch has one
+struct TrainTlin {
+  double* V; long rs, cs;                // [h, l] RAW, element (a, b) at V[a * rs + b * cs], updated in place when the kernel ends
+  int l;
+  const double* yl; const double* yh;    // [n, l], [n, h]
+  double* V_last;                        // optional [h, l] row-major: V at the start of the last step taken
+};
 struct TrainCommon : TrainLoop {         // (the loop's arguments first: the layout the kernels were compiled against)
   int* shared_info;                      // evaluate mode: the handle's status word (batch: atomicMax of the failing pivot; single: plain store)
   int info_max;
@@ -107,13 +119,22 @@ static_assert(TR_LDS_DOUBLES_RES * sizeof(double) <= 160 * 1024, "the residual l
 #define TR_LDS_DOUBLES_CAR (TR_OFF_CAR + 2 * TR_N + 12 + 8 + 8 + 8)
 static_assert(TR_LDS_DOUBLES_CAR * sizeof(double) <= 160 * 1024, "the CAR launch's LDS exceeds a CU's 160 KiB");
 
+// tensor-linear launches: V | exp_avg | exp_avg_sq | dV | V at the start of the step, [16 x 16] each, row-major [h][l]; the parked words [8]:
+// y_low, y_high (read through tr_lds_ptr), l
+#define TR_OFF_TLIN TR_OFF_RES
+#define TR_LDS_DOUBLES_TLIN (TR_OFF_TLIN + 5 * TR_Y * TR_Y + 8)
+static_assert(TR_LDS_DOUBLES_TLIN * sizeof(double) <= 160 * 1024, "the tensor-linear launch's LDS exceeds a CU's 160 KiB");
+
 // DM: the input dimensions the per-entry loops are unrolled for (8 or 16: every model of the launch has D <= DM)
 // TRAIN: every step of the loop with Adam inside; !TRAIN ("evaluate"): ONE pass that writes the value and the gradients out
 // RESID (with TRAIN only): members with R.rho set are residual models (see the head of this file)
 // V2 (with TRAIN, without RESID): the FFGP_LL_V2 likelihood of GP_basic (see the head of this file)
 // CAR (with TRAIN, without RESID): every member is a CAR member (see the head of this file)
-template <int DM, bool TRAIN, bool RESID = false, bool V2 = false, bool CAR = false>
-__device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& cm, const TrainResid* Rp = nullptr, const TrainCar* Cp = nullptr) {
+// TLIN (with TRAIN alone): every member is a tensor-linear member (see the head of this file)
+template <int DM, bool TRAIN, bool RESID = false, bool V2 = false, bool CAR = false, bool TLIN = false>
+__device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& cm, const TrainResid* Rp = nullptr, const TrainCar* Cp = nullptr,
+                                        const TrainTlin* Tp = nullptr) {
+  static_assert(!TLIN || (TRAIN && !RESID && !V2 && !CAR), "tensor-linear members train on the V1 likelihood, in launches of their own");
   static_assert(TRAIN || !RESID, "residual members train");
   static_assert(!V2 || (TRAIN && !RESID), "the V2 likelihood: plain and CAR members of the training loop");
   static_assert(!CAR || (TRAIN && !RESID), "CAR members train, in launches of their own");
@@ -151,6 +172,12 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   double* csum = cs + 8;                   // [8] per-wave sums of dloss/dr .* y_low
   int* cptr = reinterpret_cast<int*>(csum + 8);       // [0..11] y_low, y_high, b, l_z, sigma_z, b_last (read through tr_lds_ptr); [12] nz,
                                                       // [13] 1: fp32 draws (the link is not read again after the set-up)
+  double* tV = lds + TR_OFF_TLIN;          // tensor-linear members: [h][l] V
+  double* tmV = tV + TR_Y * TR_Y;          // its exp_avg
+  double* tvV = tmV + TR_Y * TR_Y;         // its exp_avg_sq
+  double* tdV = tvV + TR_Y * TR_Y;         // dloss/dV of the current step (before the output scale)
+  double* tV0 = tdV + TR_Y * TR_Y;         // V at the start of the current step
+  int* tptr = reinterpret_cast<int*>(tV0 + TR_Y * TR_Y);      // [0..3] y_low, y_high (read through tr_lds_ptr); [4] l
   bool isres = RESID && Rp->rho != nullptr;           // (for the set-up only: the step loop reads rmode)
   bool hasv = isres && Rp->vl != nullptr;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -166,7 +193,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
   // targets, Gamma and A live as [128][16] images, zero beyond (n, d): the matrix-core products read them without guards
   for (int idx = tid; idx < TR_N * TR_Y; idx += TR_T) {
     const int i = idx >> 4, q = idx & 15;
-    Ym[idx] = (!CAR && !isres && i < n && q < d) ? M.Y[i * d + q] : 0.0;      // (a residual or CAR member's are formed at every step)
+    Ym[idx] = (!CAR && !TLIN && !isres && i < n && q < d) ? M.Y[i * d + q] : 0.0;      // (a residual, CAR or tensor-linear member's are formed at every step)
     Gam[idx] = 0.0;
     Am[idx] = 0.0;
   }
@@ -194,8 +221,26 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       else raw[tid] = (tid < nw) ? M.w[tid] : (tid == nw ? M.amp[0] : (M.dadd ? M.dadd[0] : 0.0));
       if (TRAIN) {
         mom[tid] = M.state[tid];
-        mo2[tid] = M.state[npar + tid];
+        mo2[tid] = M.state[npar + (TLIN ? d * Tp->l : 0) + tid];      // (a tensor-linear member: [exp_avg (P) | exp_avg_sq (P)], P = nw + 2 + h l)
       }
+    }
+  }
+  if constexpr (TLIN) {
+    const int tl_ = Tp->l, hl = d * tl_;
+    if (tid < hl) {      // V through its strides into the row-major image; its moments behind the three parameters'
+      tV[tid] = Tp->V[(tid / tl_) * Tp->rs + (tid % tl_) * Tp->cs];
+      tmV[tid] = M.state[nw + 2 + tid];
+      tvV[tid] = M.state[nw + 2 + hl + nw + 2 + tid];
+    }
+    if (tid == 0) {
+      const double* pv[2] = {Tp->yl, Tp->yh};
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const unsigned long long u = reinterpret_cast<unsigned long long>(pv[k]);
+        tptr[2 * k] = (int)(unsigned)u;
+        tptr[2 * k + 1] = (int)(unsigned)(u >> 32);
+      }
+      tptr[4] = tl_;
     }
   }
   if constexpr (CAR) {
@@ -284,6 +329,23 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         }
       }
     }
+    if constexpr (TLIN) {      // this step's targets R = y_high - y_low V^T: per entry one chain of fused multiply-adds over l, then the difference
+      const double* yl = tr_lds_ptr(tptr);
+      const double* yh = tr_lds_ptr(tptr + 2);
+      const int tl_ = tr_lds_int(tptr + 4);
+      int t0_ = tid;      // (opaque per step: the loop's offsets into y_low, y_high and V are otherwise hoisted out of the step loop and spilled across it)
+      asm volatile("" : "+v"(t0_));
+      for (int idx = t0_; idx < n * TR_Y; idx += TR_T) {
+        const int i = idx >> 4, q = idx & 15;
+        if (q < d) {
+          double s_ = 0.0;
+#pragma unroll 4
+          for (int b = 0; b < tl_; ++b) s_ = __builtin_fma(yl[i * tl_ + b], tV[q * tl_ + b], s_);
+          Ym[idx] = __dsub_rn(yh[i * d + q], s_);
+        }
+      }
+      if (t0_ < d * tl_) tV0[t0_] = tV[t0_];
+    }
     isres = RESID && tr_lds_int(rmode) != 0;
     if (isres) {      // this step's targets r = y_high - rho y_low and diagonal extra |s|, s = v_high - rho v_low, rounded as torch's
                       // `y_high - rho * y_low` (a product, then a difference: never contracted)
@@ -370,6 +432,16 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     {
       tr_gamma_rows(S, Ym, Gam, nst, lane, wave, g, c);
       LDS_BARRIER();
+      if constexpr (TLIN) {      // the targets' image is dead until the next step: y_low takes it, [n][16] zero beyond l, for dloss/dV below
+        const double* yl = tr_lds_ptr(tptr);
+        const int tl_ = tr_lds_int(tptr + 4);
+        int t0_ = tid;
+        asm volatile("" : "+v"(t0_));
+        for (int idx = t0_; idx < n * TR_Y; idx += TR_T) {
+          const int i = idx >> 4, q = idx & 15;
+          Ym[idx] = (q < tl_) ? yl[i * tl_ + q] : 0.0;
+        }
+      }
       double ay = 0.0;      // residual members: this lane's part of sum A .* y_low
       isres = RESID && tr_lds_int(rmode) != 0;
       d4_t acc = {0.0, 0.0, 0.0, 0.0};
@@ -390,6 +462,18 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         if (lane == 0) rsum[wave] = ay;
       }
       LDS_BARRIER();
+    }
+    if constexpr (TLIN) {      // dloss/dV[a][b] = -sum_i A[i][a] y_low[i][b], i ascending: one thread per entry, both operands in LDS
+      const int tl_ = tr_lds_int(tptr + 4);
+      int t0_ = tid;
+      asm volatile("" : "+v"(t0_));
+      if (t0_ < d * tl_) {
+        const int a_ = t0_ / tl_, b_ = t0_ - a_ * tl_;
+        double s_ = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < n; ++i) s_ = __builtin_fma(Am[i * TR_Y + a_], Ym[i * TR_Y + b_], s_);
+        tdV[t0_] = -s_;
+      }
     }
     if constexpr (V2) {      // B = Sigma^-1 A: the same two chains once more -- W A over Gamma (dead once A exists), B over the targets' image
       tr_gamma_rows(S, Am, Gam, nst, lane, wave, g, c);
@@ -557,11 +641,11 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
     }
     if (tid == 0) M.trace[step] = value;
     isres = RESID && tr_lds_int(rmode) != 0;
-    if (tid < nw + 2 + (isres ? 1 : 0) + (CAR ? 3 : 0)) {
+    if (tid < nw + 2 + (isres ? 1 : 0) + (CAR ? 3 : 0) + (TLIN ? d * tr_lds_int(tptr + 4) : 0)) {
       // (CAR: the slot opaque per step -- the loop-invariant addresses of a member's last three parameters, their moments and partials are
       //  otherwise hoisted out of the step loop and spilled across it)
       int slot_ = tid;
-      if constexpr (CAR) asm volatile("" : "+v"(slot_));
+      if constexpr (CAR || TLIN) asm volatile("" : "+v"(slot_));
       double gr;
       if (tid < nw) {
         if (!M.l.w_broadcast) {
@@ -579,15 +663,18 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         const int k = slot_ - nw - 2;
         gr = oscale * dls * cs[1 + k];
         if (k == 0) gr = oscale * (dls * cs[1] - ceb[0] * tot[NRED - 1]);
+      } else if (TLIN && slot_ > nw + 1) {     // V's entry slot - nw - 2 (raw = effective; tdV was written before the reduction's barriers)
+        gr = oscale * tdV[slot_ - nw - 2];
       } else if (!isres || tid == nw + 1) {
         gr = oscale * tot[2] * ffgp_link_der(M.l.dadd_link, raw[nw + 1], M.l.dadd_c);
       } else {
         gr = oscale * tot[NRED - 1];      // rho (raw = effective)
       }
       // (a CAR member's last three parameters and their moments live in craw / cmom / cmo2)
-      double* const pr_ = (CAR && slot_ > nw + 1) ? craw + (slot_ - nw - 2) : raw + slot_;
-      double* const pm_ = (CAR && slot_ > nw + 1) ? cmom + (slot_ - nw - 2) : mom + slot_;
-      double* const pv_ = (CAR && slot_ > nw + 1) ? cmo2 + (slot_ - nw - 2) : mo2 + slot_;
+      // (... a tensor-linear member's V entries and theirs in tV / tmV / tvV)
+      double* const pr_ = ((CAR || TLIN) && slot_ > nw + 1) ? (TLIN ? tV : craw) + (slot_ - nw - 2) : raw + slot_;
+      double* const pm_ = ((CAR || TLIN) && slot_ > nw + 1) ? (TLIN ? tmV : cmom) + (slot_ - nw - 2) : mom + slot_;
+      double* const pv_ = ((CAR || TLIN) && slot_ > nw + 1) ? (TLIN ? tvV : cmo2) + (slot_ - nw - 2) : mo2 + slot_;
       const double bc1 = cm.bc[2 * step], bc2s = cm.bc[2 * step + 1];
       ffgp_adam_update(pr_, pm_, pv_, gr, cm.lr, cm.b1, cm.b2, cm.eps, bc1, bc2s);
       const double pnew = pr_[0];
@@ -602,7 +689,7 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
         }
       } else if (tid == nw) {
         sc[0] = ffgp_link_val(M.l.amp_link, pnew, M.l.amp_c);
-      } else if ((!isres && !(CAR && tid > nw + 1)) || tid == nw + 1) {      // (a CAR member's s is re-formed at the start of the step)
+      } else if ((!isres && !((CAR || TLIN) && tid > nw + 1)) || tid == nw + 1) {      // (a CAR member's s is re-formed at the start of the step)
         sc[1] = ffgp_link_val(M.l.dadd_link, pnew, M.l.dadd_c);
       }
     }
@@ -635,7 +722,16 @@ __device__ __forceinline__ void tr_body(const TrainModel& M, const TrainCommon& 
       if (rl) rl[0] = rho0[0];
     }
     M.state[tid] = mom[tid];
-    M.state[npe + tid] = mo2[tid];
+    M.state[npe + (TLIN ? d * Tp->l : 0) + tid] = mo2[tid];
+  }
+  if constexpr (TLIN) {      // V through its strides, its moments, and V as the last step taken began (a failed step left all of them as they were)
+    const int tl_ = Tp->l, hl = d * tl_;
+    if (tid < hl) {
+      Tp->V[(tid / tl_) * Tp->rs + (tid % tl_) * Tp->cs] = tV[tid];
+      M.state[nw + 2 + tid] = tmV[tid];
+      M.state[nw + 2 + hl + nw + 2 + tid] = tvV[tid];
+      if (Tp->V_last) Tp->V_last[tid] = tV0[tid];
+    }
   }
   (void)failed;
 }
@@ -665,6 +761,13 @@ __global__ __launch_bounds__(TR_T) void ffgp_train_car_kernel(const TrainModel* 
   const TrainModel M = tab[blockIdx.x];
   tr_body<DM, true, false, V2, true>(M, cm, nullptr, ctab + blockIdx.x);
 }
+// tensor-linear members (ffgp_train_tlin_raw); ttab[f] is member f's link
+template <int DM>
+__global__ __launch_bounds__(TR_T) void ffgp_train_tlin_kernel(const TrainModel* __restrict__ tab, const TrainTlin* __restrict__ ttab,
+                                                               TrainCommon cm) {
+  const TrainModel M = tab[blockIdx.x];
+  tr_body<DM, true, false, false, false, true>(M, cm, nullptr, nullptr, ttab + blockIdx.x);
+}
 // evaluate mode: up to eight models per launch, their descriptions by value (the enqueue-only entry points must not stage anything in
 // host memory that a later call could overwrite)
 #define TR_EVAL_BATCH 8
@@ -677,13 +780,16 @@ __global__ __launch_bounds__(TR_T) void ffgp_small_mfma_kernel(TrainEvalBatch b,
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, const ffgp_car_link* cr) {
+bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, const ffgp_car_link* cr,
+                           const ffgp_tlin_link* tl) {
   if (h->train_persist_off || h->use_naive || h->timing) return false;
   if (p->n <= 0 || p->n > TR_N || p->D <= 0 || p->D > TR_D || p->d <= 0 || p->d > TR_Y) return false;
   if (p->cov_dev || p->pair || p->tree || p->add_mat_dev || p->add_all != 0.0 || p->mean_jitter != 0.0) return false;
   const bool car = cr && cr->b_dev;
   if (car && (r || cr->nz <= 0 || cr->nz > TR_N)) return false;
-  const bool res = (r && r->rho_dev) || car;      // (a residual or CAR member's targets come from its link: its Y_dev is ignored)
+  const bool lin = tl && tl->V_dev;      // (l <= h = d <= 16: train_impl has checked the link)
+  if (lin && p->ll_variant != FFGP_LL_V1) return false;
+  const bool res = (r && r->rho_dev) || car || lin;      // (a residual, CAR or tensor-linear member's targets come from its link: its Y_dev is ignored)
   if (!p->X_dev || (!res && !p->Y_dev) || !p->w_dev || !p->amp_dev || !p->diag_add_dev) return false;
   if (p->kfun < FFGP_KFUN_SE || p->kfun > FFGP_KFUN_RQ) return false;
   if (p->ll_variant == FFGP_LL_V2) return !res || car;      // (ffgp_train_v2_kernel: plain members, diag_add under any link; CAR members)
@@ -695,16 +801,18 @@ bool ffgp_train_persist_ok(const ffgp_handle* h, const ffgp_problem* p, const ff
 // steps of F models (each must pass ffgp_train_persist_ok), one launch; synchronous.  Returns 0 or the pivot status of the first
 // model (in the caller's order) whose Sigma was not positive definite at some step.
 int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, int steps, const ffgp_adam* opt, double* state_dev,
-                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r, const ffgp_car_link* cr) {
-  bool any_res = false, any_car = false;
+                       long state_stride, long step0, double* trace_dev, long trace_stride, const ffgp_residual* r, const ffgp_car_link* cr,
+                       const ffgp_tlin_link* tl) {
+  bool any_res = false, any_car = false, any_lin = false;
+  for (int f = 0; f < F && tl; ++f) any_lin = any_lin || tl[f].V_dev != nullptr;
   for (int f = 0; f < F && r; ++f) any_res = any_res || r[f].rho_dev != nullptr;
   for (int f = 0; f < F && cr; ++f) any_car = any_car || cr[f].b_dev != nullptr;
-  // four classes of members, a launch each: V1 (plain and residual), V2, CAR on V1, CAR on V2.  pos[f] = model f's row of the tables and
+  // five classes of members, a launch each: V1 (plain and residual), V2, CAR on V1, CAR on V2, tensor-linear.  pos[f] = model f's row of the tables and
   // of the status words: class after class, the caller's order inside a class; cbeg[k] = the first row of class k
-  auto cls = [&](int f) { return ((cr && cr[f].b_dev) ? 2 : 0) + (p[f].ll_variant == FFGP_LL_V2 ? 1 : 0); };
+  auto cls = [&](int f) { return (tl && tl[f].V_dev) ? 4 : ((cr && cr[f].b_dev) ? 2 : 0) + (p[f].ll_variant == FFGP_LL_V2 ? 1 : 0); };
   std::vector<int> pos(F);
-  int cbeg[5] = {0, 0, 0, 0, 0};
-  for (int k = 0, q = 0; k < 4; ++k) {
+  int cbeg[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = 0, q = 0; k < 5; ++k) {
     cbeg[k] = q;
     for (int f = 0; f < F; ++f)
       if (cls(f) == k) pos[f] = q++;
@@ -716,6 +824,7 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
   const size_t tab_off = lay.take((size_t)F * sizeof(TrainModel));
   const size_t res_off = any_res ? lay.take((size_t)F * sizeof(TrainResid)) : 0;
   const size_t car_off = any_car ? lay.take((size_t)F * sizeof(TrainCar)) : 0;
+  const size_t lin_off = any_lin ? lay.take((size_t)F * sizeof(TrainTlin)) : 0;
   TrainBlock blk;
   FFGP_CHECK(train_block_open(h, lay, F, steps, opt, step0, (size_t)F * NBLK_LOWER * 256 * sizeof(double), &blk));
   char* const host = blk.host;
@@ -761,6 +870,18 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
       t.b_last = q.b_last_dev;
     }
   }
+  if (any_lin) {
+    TrainTlin* tt = reinterpret_cast<TrainTlin*>(host + lin_off);
+    for (int f = 0; f < F; ++f) {
+      const ffgp_tlin_link& q = tl[f];
+      if (!q.V_dev) continue;
+      TrainTlin& t = tt[pos[f]];
+      t.V = q.V_dev; t.rs = q.V_row_stride; t.cs = q.V_col_stride; t.l = q.l;
+      if (t.rs == 0 && t.cs == 0) { t.rs = q.l; t.cs = 1; }
+      t.yl = q.y_low_dev; t.yh = q.y_high_dev;
+      t.V_last = q.V_last_dev;
+    }
+  }
   FFGP_HIP(hipMemcpyAsync(dev, host, blk.head, hipMemcpyHostToDevice, h->stream));
   TrainCommon cm;
   static_cast<TrainLoop&>(cm) = blk.loop;
@@ -772,9 +893,9 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     FFGP_HIP(hipMalloc(&cm.prof, 12 * sizeof(long)));
     FFGP_HIP(hipMemset(cm.prof, 0, 12 * sizeof(long)));
   }
-  int Dm[4] = {0, 0, 0, 0};
+  int Dm[5] = {0, 0, 0, 0, 0};
   for (int f = 0; f < F; ++f) Dm[cls(f)] = std::max(Dm[cls(f)], p[f].D);
-  for (int k = 0; k < 4; ++k) {      // class k: rows cbeg[k] .. cbeg[k + 1] - 1 of the tables and of the status words
+  for (int k = 0; k < 5; ++k) {      // class k: rows cbeg[k] .. cbeg[k + 1] - 1 of the tables and of the status words
     const int nk = cbeg[k + 1] - cbeg[k];
     if (nk == 0) continue;
     TrainCommon c2 = cm;
@@ -783,14 +904,17 @@ int ffgp_train_persist(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_
     const TrainModel* tab = reinterpret_cast<const TrainModel*>(dev + tab_off) + cbeg[k];
     const TrainResid* rtab = reinterpret_cast<const TrainResid*>(dev + res_off);      // (class 0 begins at row 0)
     const TrainCar* ctab = reinterpret_cast<const TrainCar*>(dev + car_off) + cbeg[k];
+    const TrainTlin* ttab = reinterpret_cast<const TrainTlin*>(dev + lin_off) + cbeg[k];
     const size_t lds = TR_LDS_DOUBLES * sizeof(double), lds_res = TR_LDS_DOUBLES_RES * sizeof(double), lds_car = TR_LDS_DOUBLES_CAR * sizeof(double);
+    const size_t lds_lin = TR_LDS_DOUBLES_TLIN * sizeof(double);
     // (a lambda per kernel, in this order: the instantiations are emitted kernel by kernel, <8> then <16>, as they always were)
     int rc;
     if (k == 0 && !any_res) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_persist_kernel<dm()>, lds, nk, tab, c2); });
     else if (k == 0) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_resid_kernel<dm()>, lds_res, nk, tab, rtab, c2); });
     else if (k == 1) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_v2_kernel<dm()>, lds, nk, tab, c2); });
     else if (k == 2) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_car_kernel<dm(), false>, lds_car, nk, tab, ctab, c2); });
-    else rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_car_kernel<dm(), true>, lds_car, nk, tab, ctab, c2); });
+    else if (k == 3) rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_car_kernel<dm(), true>, lds_car, nk, tab, ctab, c2); });
+    else rc = tr_by_dm(Dm[k], [&](auto dm) { return train_launch(h, ffgp_train_tlin_kernel<dm()>, lds_lin, nk, tab, ttab, c2); });
     FFGP_CHECK(rc);
   }
   const int rc = train_block_finish(h, blk, F, pos.data());

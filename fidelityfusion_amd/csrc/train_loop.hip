@@ -1,5 +1,6 @@
 // K training steps in one call, launch per stage: the loop around the likelihood drivers with Adam on the device, and the residual
 // members' kernels.  (train.hip is the one-launch trainer this falls through to when every model is small.)  See include/ffgp.h.
+#include <climits>
 #include <cmath>
 #include <memory>
 
@@ -213,12 +214,91 @@ extern "C" __global__ void ffgp_adam_car_kernel(int F, ffgp_train_slot sl, ffgp_
   ffgp_adam_update(par, m, m + npar, gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + i], lr, b1, b2, eps, bc1, bc2_sqrt);
 }
 
+// tensor-linear members of the launch-per-stage loop (ffgp_train_tlin_raw; train_CIGAR's fidelities above 0, CIGAR.py:116-133): per step
+// their targets R = y_high - y_low V^T are formed before the likelihood call and dloss/dV = -(dloss/dR)^T y_low after it; V's h l entries
+// are Adam parameters nw + 2 ... of the member.  Members with gemm[f] set run both products on the fp64 GEMM (train_impl enqueues them:
+// T = y_low V^T into the gY buffer, which is dead until the likelihood writes it), the others in the plain kernels below.
+struct ffgp_tlin_slot {
+  double* V[FFGP_TRAIN_MAXF];            // null: a plain member
+  long rs[FFGP_TRAIN_MAXF], cs[FFGP_TRAIN_MAXF];
+  const double* yl[FFGP_TRAIN_MAXF];     // [n, l]
+  const double* yh[FFGP_TRAIN_MAXF];     // [n, h]
+  double* r[FFGP_TRAIN_MAXF];            // [n, h] targets
+  double* gY[FFGP_TRAIN_MAXF];           // [n, h] dloss/dR (GEMM members: y_low V^T before the likelihood call)
+  double* dV[FFGP_TRAIN_MAXF];           // [h, l] row-major
+  double* V_last[FFGP_TRAIN_MAXF];       // optional [h, l] row-major
+  int n[FFGP_TRAIN_MAXF], l[FFGP_TRAIN_MAXF], h[FFGP_TRAIN_MAXF], gemm[FFGP_TRAIN_MAXF];
+};
+// R[i, a] = y_high[i, a] - sum_b y_low[i, b] V[a, b] (b ascending, one chain of fused multiply-adds, then the difference); V_last = V
+extern "C" __global__ void ffgp_tlin_form(ffgp_tlin_slot ts) {
+  const int f = blockIdx.y;
+  if (!ts.V[f]) return;
+  const int l = ts.l[f], h = ts.h[f];
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t < (long)ts.n[f] * h) {
+    if (ts.gemm[f]) {
+      ts.r[f][t] = __dsub_rn(ts.yh[f][t], ts.gY[f][t]);
+    } else {
+      const long i = t / h;
+      const double* yl = ts.yl[f] + i * l;
+      const double* v = ts.V[f] + (t - i * h) * ts.rs[f];
+      double s = 0.0;
+      for (int b = 0; b < l; ++b) s = __builtin_fma(yl[b], v[b * ts.cs[f]], s);
+      ts.r[f][t] = __dsub_rn(ts.yh[f][t], s);
+    }
+  }
+  if (ts.V_last[f] && t < (long)h * l) ts.V_last[f][t] = ts.V[f][(t / l) * ts.rs[f] + (t % l) * ts.cs[f]];
+}
+// dV[a, b] = -sum_i gY[i, a] y_low[i, b], i ascending: one thread per entry (the members below the GEMM switch)
+extern "C" __global__ void ffgp_tlin_grad(ffgp_tlin_slot ts) {
+  const int f = blockIdx.y;
+  if (!ts.V[f] || ts.gemm[f]) return;
+  const int l = ts.l[f], h = ts.h[f], n = ts.n[f];
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= h * l) return;
+  const double* g = ts.gY[f] + t / l;
+  const double* yl = ts.yl[f] + t % l;
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s = __builtin_fma(g[(long)i * h], yl[(long)i * l], s);
+  ts.dV[f][t] = -s;
+}
+// Adam for a call with tensor-linear members: block x = 0 of member f moves w, amp, diag_add (raw gradients from gbuf) and stores the loss,
+// blocks x >= 1 move V's entries 256 each through V's strides; the moments of parameter q at state[q] and state[P + q], P = nw + 2 + h l.
+// The status words are kept by the likelihood's own epilogue.
+extern "C" __global__ void ffgp_adam_tlin_kernel(ffgp_train_slot sl, ffgp_tlin_slot ts, const double* __restrict__ gbuf, double* __restrict__ state,
+                                                 long state_stride, double lr, double b1, double b2, double eps, double bc1, double bc2_sqrt,
+                                                 const double* __restrict__ loss, double* __restrict__ trace, long trace_stride, int step,
+                                                 const int* __restrict__ info) {
+  const int f = blockIdx.y;
+  const int bad = info[0] | info[1];
+  const int nw = sl.nw[f];
+  const long hl = ts.V[f] ? (long)ts.h[f] * ts.l[f] : 0;
+  const long npar = nw + 2 + hl;
+  double* m0 = state + (size_t)f * state_stride;
+  if (blockIdx.x == 0) {
+    if (threadIdx.x == 0) trace[(size_t)f * trace_stride + step] = bad ? __builtin_nan("") : loss[f];
+    if (bad) return;
+    const int i = threadIdx.x;
+    if (i >= nw + 2) return;
+    double* par = (i < nw) ? sl.w[f] + i : (i == nw ? sl.amp[f] : sl.dadd[f]);
+    ffgp_adam_update(par, m0 + i, m0 + npar + i, gbuf[(size_t)f * FFGP_TRAIN_GSTRIDE + i], lr, b1, b2, eps, bc1, bc2_sqrt);
+    return;
+  }
+  if (bad) return;
+  const long e = (long)(blockIdx.x - 1) * 256 + threadIdx.x;
+  if (e >= hl) return;
+  const int l = ts.l[f];
+  double* par = ts.V[f] + (e / l) * ts.rs[f] + (e % l) * ts.cs[f];
+  double* m = m0 + nw + 2 + e;
+  ffgp_adam_update(par, m, m + npar, ts.dV[f][e], lr, b1, b2, eps, bc1, bc2_sqrt);
+}
+
 static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_residual* r, int steps,
                       const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride,
-                      const ffgp_car_link* cr = nullptr) {
+                      const ffgp_car_link* cr = nullptr, const ffgp_tlin_link* tl = nullptr) {
   if (!ffgp_train_args_ok(h, p, l, opt, state_dev, trace_dev, F, steps, step0, trace_stride)) return FFGP_ERR_ARG;
   ffgp_train_slot sl;
-  bool all_small = true, any_res = false, any_car = false;
+  bool all_small = true, any_res = false, any_car = false, any_lin = false;
   for (int f = 0; f < F; ++f) {
     const ffgp_problem& q = p[f];
     if (!q.w_dev || !q.amp_dev || !q.diag_add_dev || q.cov_dev || q.pair || q.tree || q.D <= 0 || q.D > 128 || q.n <= 0 || q.d <= 0) return FFGP_ERR_ARG;
@@ -232,8 +312,13 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
                 !cr[f].y_low_dev || !cr[f].y_high_dev || !q.X_dev))
       return FFGP_ERR_ARG;
     any_car = any_car || car;
+    const bool lin = tl && tl[f].V_dev;
+    if (lin && (r || cr || !tl[f].y_low_dev || !tl[f].y_high_dev || !q.X_dev || tl[f].l < 1 || tl[f].l > q.d || tl[f].V_row_stride < 0 ||
+                tl[f].V_col_stride < 0 || q.ll_variant != FFGP_LL_V1))
+      return FFGP_ERR_ARG;
+    any_lin = any_lin || lin;
     const int nw = l[f].w_broadcast ? 1 : q.D;
-    if (state_stride < 2 * (nw + 2 + (res ? 1 : 0) + (car ? 3 : 0))) return FFGP_ERR_ARG;
+    if (state_stride < 2 * (nw + 2 + (res ? 1 : 0) + (car ? 3 : 0) + (lin ? (long)q.d * tl[f].l : 0L))) return FFGP_ERR_ARG;
     sl.w[f] = const_cast<double*>(q.w_dev);
     sl.amp[f] = const_cast<double*>(q.amp_dev);
     sl.dadd[f] = const_cast<double*>(q.diag_add_dev);
@@ -244,8 +329,9 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
   FFGP_HIP(hipSetDevice(h->device));
   {   // every model small enough for one workgroup: the whole loop is ONE launch (train.hip)
     bool persist = true;
-    for (int f = 0; f < F && persist; ++f) persist = ffgp_train_persist_ok(h, p + f, l + f, r ? r + f : nullptr, cr ? cr + f : nullptr);
-    if (persist) return ffgp_train_persist(h, F, p, l, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, r, cr);
+    for (int f = 0; f < F && persist; ++f)
+      persist = ffgp_train_persist_ok(h, p + f, l + f, r ? r + f : nullptr, cr ? cr + f : nullptr, tl ? tl + f : nullptr);
+    if (persist) return ffgp_train_persist(h, F, p, l, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, r, cr, tl);
   }
   if (!h->train_g) {
     FFGP_HIP(hipMalloc(&h->train_g, (size_t)FFGP_TRAIN_MAXF * (FFGP_TRAIN_GSTRIDE + 1) * sizeof(double)));
@@ -313,6 +399,38 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
       lk[f].amp_c = 0.0;
     }
   }
+  ffgp_tlin_slot ts;
+  memset(&ts, 0, sizeof(ts));
+  long vmax = 0;
+  bool lin_plain = false;
+  if (any_lin) {      // per tensor-linear member [R (n h) | dloss/dR (n h) | dV (h l)], each on a 16-byte boundary, freed when the call returns
+    auto even = [](size_t x) { return (x + 1) & ~(size_t)1; };
+    size_t tot = 0;
+    for (int f = 0; f < F; ++f)
+      if (tl[f].V_dev) tot += 2 * even((size_t)p[f].n * p[f].d) + even((size_t)p[f].d * tl[f].l);
+    FFGP_HIP(hipMalloc(&rbuf, tot * sizeof(double)));
+    rbuf_owner.reset(rbuf);
+    size_t off = 0;
+    for (int f = 0; f < F; ++f) {
+      if (!tl[f].V_dev) continue;
+      const long n = p[f].n, hh = p[f].d, ll = tl[f].l, nh = n * hh;
+      ts.V[f] = tl[f].V_dev;
+      ts.rs[f] = tl[f].V_row_stride; ts.cs[f] = tl[f].V_col_stride;
+      if (ts.rs[f] == 0 && ts.cs[f] == 0) { ts.rs[f] = ll; ts.cs[f] = 1; }
+      ts.yl[f] = tl[f].y_low_dev; ts.yh[f] = tl[f].y_high_dev;
+      ts.r[f] = rbuf + off; ts.gY[f] = ts.r[f] + even(nh); ts.dV[f] = ts.gY[f] + even(nh);
+      ts.V_last[f] = tl[f].V_last_dev;
+      ts.n[f] = (int)n; ts.l[f] = (int)ll; ts.h[f] = (int)hh;
+      // the fp64 GEMM reads V K-major (unit column stride) or MN-major (unit row stride: the bilinear initialisation's transposed view)
+      ts.gemm[f] = (h->tlin_gemm_min > 0 && (double)n * ll * hh >= (double)h->tlin_gemm_min && (ts.cs[f] == 1 || ts.rs[f] == 1) &&
+                    std::max(ts.rs[f], ts.cs[f]) <= INT_MAX) ? 1 : 0;
+      lin_plain = lin_plain || !ts.gemm[f];
+      off += 2 * even(nh) + even(hh * ll);
+      rmax = std::max(rmax, std::max(nh, hh * ll));
+      vmax = std::max(vmax, hh * ll);
+      pq[f].Y_dev = ts.r[f];
+    }
+  }
   for (int f = 0; f < F; ++f) {
     memset(&g[f], 0, sizeof(ffgp_grads));
     g[f].g_w_dev = gbuf + (size_t)f * FFGP_TRAIN_GSTRIDE;
@@ -323,6 +441,7 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
       if (rs.vl[f]) g[f].g_diag_vec_dev = const_cast<double*>(rs.gdv[f]);
     }
     if (cs.b[f]) g[f].g_Y_dev = const_cast<double*>(cs.gY[f]);
+    if (ts.V[f]) g[f].g_Y_dev = ts.gY[f];
     all_small = all_small && ffgp_small_batch_ok(&pq[f], &g[f]);
   }
   p = pq.data();
@@ -331,12 +450,20 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
   // (the one-kernel paths -- n <= 40, or option small_finish -- apply the links inside their kernel and write raw gradients)
   const bool one_kernel = ffgp_small_ok(h, p, &g[0]) || ffgp_small2_ok(h, p, &g[0]);
   h->defer_info_copy = 1;      // (the per-call read-back of the status word: once, after the loop)
-  h->fold_info = (F == 1 && !any_car) ? 1 : 0;   // one model: the Adam kernel clears / accumulates the status words (see ffgp_adam_kernel;
+  h->fold_info = (F == 1 && !any_car && !any_lin) ? 1 : 0;   // one model: the Adam kernel clears / accumulates the status words (see ffgp_adam_kernel;
                                                   // a call with CAR members leaves them to the likelihood's epilogue)
   int lrc = FFGP_OK;
   for (int k = 0; k < steps && lrc == FFGP_OK; ++k) {
     if (any_res) hipLaunchKernelGGL(ffgp_resid_form, dim3((unsigned)((rmax + 255) / 256), F), dim3(256), 0, h->stream, rs);
     if (any_car) hipLaunchKernelGGL(ffgp_car_form, dim3((unsigned)((rmax + 255) / 256), F), dim3(256), 0, h->stream, cs);
+    if (any_lin) {
+      for (int f = 0; f < F && lrc == FFGP_OK; ++f)      // T = y_low V^T [n, h] into the gY buffer
+        if (ts.gemm[f])
+          lrc = ffgp_gemm_launch(h, OP_KMAJOR, ts.cs[f] == 1 ? OP_KMAJOR : OP_MNMAJOR, TILES_FULL, 0, ts.yl[f], ts.l[f], ts.V[f],
+                                 (int)(ts.cs[f] == 1 ? ts.rs[f] : ts.cs[f]), ts.gY[f], ts.h[f], ts.n[f], ts.h[f], ts.l[f], 1.0, 0.0);
+      if (lrc != FFGP_OK) break;
+      hipLaunchKernelGGL(ffgp_tlin_form, dim3((unsigned)((rmax + 255) / 256), F), dim3(256), 0, h->stream, ts);
+    }
     if (all_small && F > 1) {
       if ((lrc = ffgp_zero_async(h, h->d_info, sizeof(int))) != FFGP_OK) break;
       if ((lrc = ffgp_small_batch_enqueue(h, F, p, lk.data(), loss, g.data())) != FFGP_OK) break;
@@ -348,6 +475,17 @@ static int train_impl(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_l
     if (any_res) hipLaunchKernelGGL(ffgp_resid_grad, dim3(F), dim3(256), 0, h->stream, rs, gbuf);
     double bc1, bc2_sqrt;
     ffgp_adam_bc(opt, step0, k, &bc1, &bc2_sqrt);
+    if (any_lin) {
+      for (int f = 0; f < F && lrc == FFGP_OK; ++f)      // dV = -gY^T y_low [h, l]
+        if (ts.gemm[f])
+          lrc = ffgp_gemm_launch(h, OP_MNMAJOR, OP_MNMAJOR, TILES_FULL, 0, ts.gY[f], ts.h[f], ts.yl[f], ts.l[f], ts.dV[f], ts.l[f], ts.h[f],
+                                 ts.l[f], ts.n[f], -1.0, 0.0);
+      if (lrc != FFGP_OK) break;
+      if (lin_plain) hipLaunchKernelGGL(ffgp_tlin_grad, dim3((unsigned)((vmax + 255) / 256), F), dim3(256), 0, h->stream, ts);
+      hipLaunchKernelGGL(ffgp_adam_tlin_kernel, dim3((unsigned)(1 + (vmax + 255) / 256), F), dim3(256), 0, h->stream, sl, ts, gbuf, state_dev,
+                         state_stride, opt->lr, opt->beta1, opt->beta2, opt->eps, bc1, bc2_sqrt, loss, trace_dev, trace_stride, k, h->d_info);
+      continue;
+    }
     if (any_car) {
       hipLaunchKernelGGL(ffgp_car_grad, dim3(F), dim3(256), 0, h->stream, cs, gbuf);
       hipLaunchKernelGGL(ffgp_adam_car_kernel, dim3(F), dim3(192), 0, h->stream, F, sl, cs, gbuf, state_dev, state_stride, opt->lr, opt->beta1,
@@ -385,6 +523,12 @@ int ffgp_train_residual_raw(ffgp_handle* h, int F, const ffgp_problem* p, const 
                             const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
   if (!r) return FFGP_ERR_ARG;
   return train_impl(h, F, p, l, r, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride);
+}
+
+int ffgp_train_tlin_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_tlin_link* t, int steps,
+                        const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride) {
+  if (!t) return FFGP_ERR_ARG;
+  return train_impl(h, F, p, l, nullptr, steps, opt, state_dev, state_stride, step0, trace_dev, trace_stride, nullptr, t);
 }
 
 int ffgp_train_car_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_car_link* c, int steps,

@@ -12,6 +12,9 @@ field, ResGP's and AR's residual fidelities -- are trained in one launch as well
 n (a residual member: 2 n) columns by `compress_targets`.
 With `fuse_composed=True` train_AR's residual fidelities on such a kernel and `GP_basic` blocks over one are trained by the library too
 (ffgp_train_tree_res_raw; in one launch: ffgp_train_tree_lds_res_raw).
+`residual[f]` = (tensor_linear, y_low, y_high) makes model f one of train_CIGAR's fidelities above 0 (FidelityFusion_Models/CIGAR.py:110-134):
+a `cigp` on y_high - Tensor_linear(y_low) with the map's matrix under the same Adam (ffgp_train_tlin_raw: one launch for all steps up to
+128 points with D, h <= 16, launch per stage above).
 """
 import ctypes as C
 
@@ -63,7 +66,9 @@ class AdamState:
     """torch.optim.Adam's per-parameter state of the models of one `train_many` chunk, kept on the device between calls:
     buf[f] = [exp_avg (nw + 2) | exp_avg_sq (nw + 2)] in the order length scales, signal variance, log_beta (a residual model:
     [exp_avg (nw + 3) | exp_avg_sq (nw + 3)], rho last; a `GP_basic`: noise_variance in log_beta's place; a CAR model: [exp_avg (nw + 5) |
-    exp_avg_sq (nw + 5)] in the order length scales, signal variance, noise_variance, b, l_z, sigma_z); `step` = updates taken.
+    exp_avg_sq (nw + 5)] in the order length scales, signal variance, noise_variance, b, l_z, sigma_z; a model with a `Tensor_linear`
+    link: [exp_avg (P) | exp_avg_sq (P)], P = nw + 2 + h l, in the order length scales, signal variance, log_beta, the map's matrix V [h, l]
+    row-major -- whatever V's strides are); `step` = updates taken.
     A chunk of composed-kernel models (ffgp_train_tree_raw): buf[f] = [exp_avg (P) | exp_avg_sq (P)], P = sum over the leaves of
     (length scales + 1 + the centre's D for a LinearKernel) + 1, in the order leaf by leaf in the tree's canonical leaf order
     (`kernel._Pair.tree_links`: length scales, signal variance, centre), then log_beta (a `GP_basic`: noise_variance); a residual member
@@ -230,6 +235,47 @@ def _split_residual(res):
     return rho, yl, yh, None, None
 
 
+def _is_tlin(res):
+    """a residual link whose first entry is a `Tensor_linear` module (train_CIGAR's form) instead of a scalar rho (train_AR's)"""
+    return res is not None and isinstance(res[0], torch.nn.Module)
+
+
+def _tlin_ok(res, x, e):
+    """a `Tensor_linear` link the fused call can train on a model with links `e`: a one-mode map whose matrix V = vectors[-1] [h, l] is
+    an fp64 leaf that requires grad on x's device (contiguous, or the transposed view of the bilinear initialisation), y_low [n, l] and
+    y_high [n, h] fp64, contiguous, without gradient, variances [n, n] on both sides or on neither; the model a plain `cigp` over one
+    radial library kernel"""
+    from . import functional as F
+    from .kdesc import FFGP_KFUN_LINEAR
+    tl, yl, yh, vl, vh = _split_residual(res)
+    vecs = getattr(tl, "vectors", None)
+    if vecs is None or len(vecs) != 1 or _is_tree(e) or "diag" in e[0] or e[0]["kfun"] == FFGP_KFUN_LINEAR:
+        return False
+    V = vecs[0]
+    if not (isinstance(V, torch.Tensor) and V.dim() == 2 and V.dtype == torch.float64 and V.device == x.device and V.requires_grad and V.is_leaf
+            and (V.is_contiguous() or V.T.is_contiguous()) and {id(q) for q in tl.parameters()} == {id(V)}):
+        return False
+    n, (h, l) = x.shape[0], V.shape
+    for t, c in ((yl, l), (yh, h)):
+        if not (isinstance(t, torch.Tensor) and tuple(t.shape) == (n, c) and t.dtype == torch.float64 and t.device == x.device
+                and t.is_contiguous() and not t.requires_grad):
+            return False
+    if (vl is None) != (vh is None) or not 1 <= l <= h:
+        return False
+    for v in (vl, vh):
+        if v is not None and not (isinstance(v, torch.Tensor) and tuple(v.shape) == (n, n) and v.device == x.device and not v.requires_grad
+                                  and F.raw_ok(v)):
+            return False
+    return True
+
+
+def _tlin_targets(res, V):
+    """train_CIGAR's residual at this V (CIGAR.py:119-123): [y_high - y_low V^T, |v_high - v_low| or None]"""
+    _, yl, yh, vl, vh = _split_residual(res)
+    with torch.no_grad():
+        return [yh - yl @ V.T, None if vl is None else (vh - vl).abs()]
+
+
 def _residual_targets(res, rho):
     """train_AR's residual at this rho (AR_autoRegression.py:125-126,131-132): [y_high - rho * y_low, |v_high - rho * v_low| or None]"""
     _, yl, yh, vl, vh = _split_residual(res)
@@ -245,10 +291,16 @@ def _reference_loop(models, xs, ys, steps, lr, betas, eps, opts, residual=None, 
         res = residual[f] if residual is not None else None
         cr = car[f] if car is not None else None
         if opts[f] is None:
-            opts[f] = torch.optim.Adam(list(m.parameters()) + ([res[0]] if res is not None else []), lr=lr, betas=betas, eps=eps)
+            extra = [] if res is None else (list(res[0].parameters()) if _is_tlin(res) else [res[0]])
+            opts[f] = torch.optim.Adam(list(m.parameters()) + extra, lr=lr, betas=betas, eps=eps)
         for k in range(steps):
             opts[f].zero_grad()
-            if res is not None:      # the residual at the current rho, with its graph (AR_autoRegression.py:123-137)
+            if _is_tlin(res):        # train_CIGAR's residual at the current map, with its graph (CIGAR.py:116-133)
+                tl, yl, yh, vl, vh = _split_residual(res)
+                y = [yh - tl(yl), (vh - vl).abs()] if vl is not None else yh - tl(yl)
+                if k == steps - 1:
+                    targets[f] = [y[0].detach(), y[1].detach()] if vl is not None else [y.detach(), None]
+            elif res is not None:    # the residual at the current rho, with its graph (AR_autoRegression.py:123-137)
                 rho, yl, yh, vl, vh = _split_residual(res)
                 y = [yh - rho * yl, (vh - rho * vl).abs()] if vl is not None else yh - rho * yl
                 if k == steps - 1:
@@ -333,6 +385,21 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     (then |v_high - rho * v_low| is the y_var whose diagonal enters Sigma) -- and rho (a one-element fp64 parameter) is a fourth Adam
     parameter, updated in place like the others.  state["residual_targets"][f] = [res_mean, res_var] (res_var None in the subset form)
     is that residual at the rho of the start of the last step, computed with torch: what train_AR hands to add_data.
+    `residual[f]` = (tensor_linear, y_low, y_high) -- a `gp_computation_pack.Tensor_linear` in rho's place, the form `hogp_simple.train_many`
+    takes -- makes model f one of train_CIGAR's fidelities above 0 (CIGAR.py:110-134; `ys[f]` is then None): every step trains it on
+    y_high - tensor_linear(y_low) -- y_low [n, l], y_high [n, h] tensors (subset form) or [mean, var] lists with var [n, n] (then
+    |v_high - v_low|, which does not depend on the map, is the y_var whose diagonal enters Sigma) -- and the map's matrix V = vectors[-1]
+    [h, l] is h l further Adam parameters, updated in place through its strides (the bilinear initialisation for l < h is a transposed
+    view) with its version counter bumped like the others.  Fused (ffgp_train_tlin_raw) when the map has one mode, V is an fp64 leaf that
+    requires grad on the model's GPU, y_low / y_high are fp64, contiguous and carry no gradient, variances are [n, n] on both sides or on
+    neither, and the model is eligible as a plain `cigp` over one radial library kernel; a multi-mode map, a composed kernel, a `GP_basic` or
+    CPU tensors run the reference's loop instead (Adam over the model's parameters plus the map's; state["fused"] = False; same return
+    values).  Link members form chunks of their own -- those with n <= 128, D <= 16, h <= 16 up to 16 per call, trained in ONE launch for
+    all steps (csrc/train.hip: V, its moments and its gradient in LDS; a member that is not positive definite stops alone), every larger
+    one a call of its own, launch per stage, the two products y_low V^T and dloss/dV = -A^T y_low on the fp64 GEMM from n l h = 8192 on --
+    and share a `train_many` call freely with plain, rho, CAR and tree members.  state["residual_targets"][f] = [y_high -
+    tensor_linear(y_low), |v_high - v_low| or None] at the V of the start of the last step, computed with torch: what train_CIGAR hands
+    to add_data.  A link together with `ys[f]` or with `car[f]` raises ValueError.
     `car[f]` = (b, y_low, y_high) makes model f one of train_CAR's fidelities above 0 (CAR_ContinuousAutoRegression.py:116-142; `ys[f]`
     is then None): a `GP_basic` over a `kernel.FidelityKernelMCMC` whose `b` is that very tensor, trained on y_high - exp(b) * y_low
     under kernel1 * s(b, l_z, sigma_z); six groups of parameters move per step -- the base kernel's two, l_z, sigma_z, b and
@@ -365,7 +432,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
             raise ValueError("train_many: residual must have one entry per model")
         for f, res in enumerate(residual):
             if res is not None and (ys[f] is not None or len(res) != 3):
-                raise ValueError("train_many: a residual model takes (rho, y_low, y_high) and ys[f] = None")
+                raise ValueError("train_many: a residual model takes (rho or a Tensor_linear, y_low, y_high) and ys[f] = None")
             if res is None and ys[f] is None and (car is None or car[f] is None):
                 raise ValueError("train_many: model %d has neither targets nor a residual link" % f)
     if car is not None:
@@ -386,7 +453,12 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     # a residual model's eligibility is judged on its y_high (same shape as its targets) and its link
     ys_e = [ys[f] if res_of(f) is None else _split_residual(res_of(f))[2] for f in range(nF)]
     elig = [_eligible(m, x, y, fuse_composed) if car_of(f) is None else _eligible_car(m, x, car_of(f)) for f, (m, x, y) in enumerate(zip(models, xs, ys_e))]
+    tlin = {f for f in range(nF) if _is_tlin(res_of(f))}
     for f in range(nF):
+        if f in tlin:      # (a Tensor_linear link: ffgp_train_tlin_raw, or the reference's loop)
+            if elig[f] is not None and not _tlin_ok(res_of(f), xs[f], elig[f]):
+                elig[f] = None
+            continue
         if res_of(f) is not None and elig[f] is not None and ((_is_tree(elig[f]) and not fuse_composed) or not _residual_ok(res_of(f), xs[f])):
             elig[f] = None      # (a composed kernel with a residual link: the reference's loop unless `fuse_composed` -- ffgp_train_tree_res_raw)
         if res_of(f) is not None and _is_tree(elig[f]) and "diag" in elig[f][0] and _split_residual(res_of(f))[3] is not None:
@@ -409,7 +481,16 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     dev = xs[0].device
     trace = torch.empty((nF, steps), dtype=torch.float64, device=dev)
     opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
-    rho_last = {f: torch.empty_like(res_of(f)[0].detach()) for f in range(nF) if res_of(f) is not None}
+    rho_last = {f: torch.empty_like(res_of(f)[0].detach()) for f in range(nF) if res_of(f) is not None and f not in tlin}
+    # a Tensor_linear member's matrix, V at the start of the last step (row-major) and its constant diagonal extra |diag(v_high) - diag(v_low)|
+    tl_V = {f: res_of(f)[0].vectors[0] for f in tlin}
+    V_last = {f: torch.empty(tuple(tl_V[f].shape), dtype=torch.float64, device=dev) for f in tlin}
+    tl_dvec = {}
+    for f in tlin:
+        _, _, _, vl, vh = _split_residual(res_of(f))
+        if vl is not None:
+            with torch.no_grad():
+                tl_dvec[f] = (vh.diagonal() - vl.diagonal()).abs().contiguous()
     b_last = {f: torch.empty_like(car_of(f)[0].detach()) for f in range(nF) if car_of(f) is not None}
     zdev = {}      # the CAR members' samples on the device (alive until the calls have returned)
 
@@ -434,8 +515,16 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         ll.amp_link, ll.amp_c = lk["amp_link"], 0.0
         ll.dadd_link, ll.dadd_c = dlink, dc
         ll.out_scale = 1.0          # the value is the loss the reference minimises: -negative_log_likelihood = +nll
-        rs = _lib.Residual()
-        if res_of(f) is not None:
+        rs, tk = _lib.Residual(), _lib.TlinLink()
+        if f in tlin:
+            _, yl, yh, _, _ = _split_residual(res_of(f))
+            V = tl_V[f]
+            p.Y_dev, p.diag_vec_dev, p.diag_stride = None, None, 0
+            if f in tl_dvec:
+                p.diag_vec_dev, p.diag_stride = tl_dvec[f].data_ptr(), 1
+            tk.V_dev, tk.V_row_stride, tk.V_col_stride, tk.l = V.data_ptr(), V.stride(0), V.stride(1), V.shape[1]
+            tk.y_low_dev, tk.y_high_dev, tk.V_last_dev = yl.data_ptr(), yh.data_ptr(), V_last[f].data_ptr()
+        elif res_of(f) is not None:
             rho, yl, yh, vl, vh = _split_residual(res_of(f))
             p.diag_vec_dev, p.diag_stride = None, 0
             rs.rho_dev, rs.y_low_dev, rs.y_high_dev = rho.data_ptr(), yl.data_ptr(), yh.data_ptr()
@@ -455,7 +544,9 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
                 cl.z1_dev, cl.z2_dev = z1.data_ptr(), z2.data_ptr()
             cl.nz, cl.lf, cl.hf = z1.numel(), c["lf"], c["hf"]
             cl.y_low_dev, cl.y_high_dev, cl.b_last_dev = yl.data_ptr(), yh.data_ptr(), b_last[f].data_ptr()
-        return p, ll, rs, cl, lk["w"].numel() + (1 if res_of(f) is not None else 0) + (3 if car_of(f) is not None else 0)
+        if f in tlin:
+            return p, ll, rs, cl, tk, lk["w"].numel() + tl_V[f].numel()
+        return p, ll, rs, cl, tk, lk["w"].numel() + (1 if res_of(f) is not None else 0) + (3 if car_of(f) is not None else 0)
 
     def describe_tree(f, keep):
         """model f with a composed kernel: its problem (the tree's leaves on their RAW parameters) and ffgp_tree_links; P = its number
@@ -541,7 +632,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         INFO = (C.c_int * nm)()
         keep, strides = [], []
         for j, f in enumerate(idx):
-            P[j], L[j], R[j], _, nw = describe(f)
+            P[j], L[j], R[j], _, _, nw = describe(f)
             DT[j] = P[j].d
             if res_of(f) is not None:
                 _, yl, yh, _, _ = _split_residual(res_of(f))
@@ -606,12 +697,17 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
         L = (_lib.Links * len(idx))()
         R = (_lib.Residual * len(idx))()
         Cl = (_lib.CarLink * len(idx))()
+        Tl = (_lib.TlinLink * len(idx))()
         nws = []
         for j, f in enumerate(idx):
-            P[j], L[j], R[j], Cl[j], nw = describe(f)
+            P[j], L[j], R[j], Cl[j], Tl[j], nw = describe(f)
             nws.append(nw)
         anyres = any(res_of(f) is not None for f in idx)
         stride = 2 * (max(nws) + 2)
+        if idx[0] in tlin:      # (chunks of their own: `groups` below; Adam state [exp_avg (P) | exp_avg_sq (P)], P = nw + 2 + h l, V row-major last)
+            return launch(idx, stride, lambda st, tr: check(
+                lib.ffgp_train_tlin_raw(h, len(idx), P, L, Tl, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
+                                        tr.data_ptr(), tr.stride(0)), "ffgp_train_tlin_raw"))
         if any(car_of(f) is not None for f in idx):      # (never in one chunk with residual members: `groups` below)
             return launch(idx, stride, lambda st, tr: check(
                 lib.ffgp_train_car_raw(h, len(idx), P, L, Cl, int(steps), C.byref(opt), st.buf.data_ptr(), stride, int(st.step),
@@ -646,20 +742,24 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     # at one Adam step sharing a call (ffgp_train_wide_raw takes one step0)
     wide = []
     if wide_one_launch:
-        wide = [f for f in large if f not in trees and car_of(f) is None and shapes[f][0] <= F.SMALL_BATCH_MAX_N
+        wide = [f for f in large if f not in trees and f not in tlin and car_of(f) is None and shapes[f][0] <= F.SMALL_BATCH_MAX_N
                 and shapes[f][1] <= F.SMALL_BATCH_MAX_D and shapes[f][2] > F.SMALL_BATCH_MAX_d and "ll" not in elig[f][0]
                 and "diag" not in elig[f][0] and elig[f][0]["kfun"] <= WIDE_KFUN_MAX]
         large = [f for f in large if f not in set(wide)]
         state["wide_one_launch"] = wide
     # (CAR members have an entry point of their own: their small ones form chunks apart from the plain and residual models')
     small_car = [f for f in small if car_of(f) is not None]
-    small = [f for f in small if car_of(f) is None]
+    # ... and so have Tensor_linear members: the small ones (n <= 128, D, h <= 16) up to 16 per call, every larger one a call of its own
+    small_tlin = [f for f in small if f in tlin]
+    small = [f for f in small if car_of(f) is None and f not in tlin]
     if len(small) == 1:      # (a lone small model gains nothing from the batch kernel: its own call folds the tail launches)
         large, small = sorted(large + small), []
     if len(small_car) == 1:
         large, small_car = sorted(large + small_car), []
+    if len(small_tlin) == 1:
+        large, small_tlin = sorted(large + small_tlin), []
     rcs = []
-    for group in (small, small_car, small_trees, lds_trees):
+    for group in (small, small_car, small_tlin, small_trees, lds_trees):
         for c0 in range(0, len(group), TRAIN_MAX_MODELS):
             rcs.append((group[c0:c0 + TRAIN_MAX_MODELS], run(group[c0:c0 + TRAIN_MAX_MODELS])))
     by_step = {}
@@ -678,7 +778,7 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
     bump = getattr(torch.autograd.graph, "increment_version", None)      # (torch >= 2.1: no kernel; else an in-place no-op add)
     with torch.no_grad():
         for f, m in enumerate(models):
-            for q in list(m.parameters()) + ([res_of(f)[0]] if res_of(f) is not None else []):
+            for q in list(m.parameters()) + ([] if res_of(f) is None else ([tl_V[f]] if f in tlin else [res_of(f)[0]])):
                 if bump is not None:
                     bump(q)
                 else:
@@ -688,6 +788,8 @@ def train_many(models, xs, ys, steps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, sta
             _raise_not_pd(rc, "linalg.cholesky (train_many, model%s %s)" % ("s" if len(idx) > 1 else "", ", ".join(map(str, idx))))
     for f, rl in rho_last.items():      # train_AR's data for the fidelity: the residual at the rho of the start of the last step
         state["residual_targets"][f] = _residual_targets(res_of(f), rl.reshape(res_of(f)[0].shape))
+    for f, vl_ in V_last.items():       # train_CIGAR's data for the fidelity: the residual at the V of the start of the last step
+        state["residual_targets"][f] = _tlin_targets(res_of(f), vl_)
     for f, bl in b_last.items():        # train_CAR's data for the fidelity: the residual at the b of the start of the last step
         state["residual_targets"][f] = _car_targets(car_of(f), bl.reshape(car_of(f)[0].shape))
     return trace, state

@@ -263,6 +263,9 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
                         sequence is its single call's, so are its bits; 1 = member after member.  Measured -3 ... -6 %),
             "train_persist" (default 1: ffgp_train_raw runs sets of small models -- n <= 128, D, d <= 16 -- as ONE persistent kernel launch,
                         see ffgp_train_raw; 0 = one launch per stage and step, the round-5 form),
+            "tlin_gemm_min" (default 8192: tensor-linear members of ffgp_train_tlin_raw with n l h >= this form y_low V^T and dloss/dV on
+                        the fp64 MFMA GEMM, smaller ones in a plain fixed-order kernel -- faster up to n l h = 2048, slower from 14400 on,
+                        profiles/train_tlin_bench.txt; 0 = never the GEMM),
             "chase_xcc" (0..15; default: handles of one process take XCDs 0..7 in turn -- the XCD whose wavefronts run the XCD-local
                         chase; a value no wave of the launch reports leaves the whole chase to the chip-wide launch behind it: a test mode),
             "batch_grad_ob" (default 1: the shared chain's gradient stage inverts all blocks in one outer-batched sequence of launches),
@@ -659,6 +662,50 @@ typedef struct {
 } ffgp_car_link;
 int ffgp_train_car_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, const ffgp_car_link* c, int steps,
                        const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
+
+/* ffgp_train_raw with TENSOR-LINEAR members -- train_CIGAR's fidelities above 0 (FidelityFusion_Models/CIGAR.py:116-133): model f is a
+   cigp trained on y_high - Tensor_linear(y_low), and the Tensor_linear's matrix sits under the same Adam as the three GP parameters.
+   Only the LAST mode's matrix V [h, l] of a Tensor_linear acts (gp_computation_pack.py:155-158); with y_low [n, l], y_high [n, h = p.d]:
+       targets     R = y_high - y_low V^T                       every entry one dot product over l in a fixed order, then one subtraction
+       diag extra  |diag(v_high) - diag(v_low)|                  constant: the caller forms it once and passes it as p[f].diag_vec_dev;
+                                                                 it does not depend on V and contributes nothing to V's gradient
+       gradient    dloss/dV[a, b] = -sum_i (dloss/dR)[i, a] y_low[i, b],     dloss/dR = A = Sigma^-1 R (the V1 likelihood's g_Y_dev)
+                                                                 every sum in a fixed order, no floating-point atomics
+       Adam        V's h l entries are further Adam parameters (same lr, betas, eps, bias corrections): per member
+                   [exp_avg (P) | exp_avg_sq (P)], P = nw + 2 + h l, in the order w, amp, diag_add, V row-major
+   V is updated in place through its strides (Tensor_linear's bilinear initialisation for l < h is a transposed view).  t[f].V_dev =
+   NULL is a plain model, trained exactly as ffgp_train_raw trains it; plain and tensor-linear members may share a call.  For a
+   tensor-linear member p[f].Y_dev is ignored.  V_last_dev, when set, receives V (row-major) as it was at the start of the last step
+   taken: train_CIGAR keeps y_high - Tensor_linear(y_low) at that V as the fidelity's data.
+   ONE LAUNCH FOR THE WHOLE LOOP (csrc/train.hip, a class of members launched on its own as the CAR class is) when every member of the
+   call has n <= 128, D <= 16, h <= 16 (so l <= 16) and what ffgp_train_raw's one-launch form asks besides: V, its two moments, dV and
+   V as the step began stay in LDS for the whole call, R goes into the zero-padded target image and dV comes from A and y_low, both
+   read from global memory at every step; everything else is ffgp_train_raw's step.  There a member whose Sigma is not positive
+   definite stops alone: its trace holds NaN from that step on, and V, the moments and the three parameters keep the values they had
+   when the step began (the factorisation comes first in the step: nothing of V has moved); the others complete.  Option
+   "train_persist" = 0 restores the launch-per-stage loop.  Members with h > 16 always run launch per stage: V differs from column
+   block to column block, so ffgp_train_wide_raw's Gram identity does not apply.
+   LAUNCH PER STAGE at every other size: per step one launch forms every member's R into the call's buffer, the likelihood / gradient
+   launches of ffgp_train_raw run with g_Y_dev set, one launch forms dV into a buffer of its own, and one launch -- a grid over the
+   h l entries -- takes Adam's step (ffgp_train_raw's update function) on nw + 2 + h l values per member.  Members with
+   n l h >= option "tlin_gemm_min" run both products on the fp64 MFMA GEMM (one launch each per member), smaller ones -- and a V with
+   neither stride 1 -- in a plain fixed-order kernel.  No host synchronisation inside the loop.  There the status is shared by the
+   call's members: from the first step whose Sigma was not positive definite in any member on nothing of the call moves (V and its
+   moments included) and the trace holds NaN.  Trace, step0 and the return value are ffgp_train_raw's.
+   FFGP_ERR_ARG, with nothing enqueued and nothing written: t == NULL, what ffgp_train_raw refuses, a tensor-linear member without
+   y_low_dev / y_high_dev / X_dev, l outside 1..h (the reference only maps to an equal or finer output), a negative stride, the V2
+   likelihood on such a member, state_stride < 2 P.  Synchronous.                                                               */
+typedef struct {
+  double* V_dev;              /* [h, l] raw, updated in place; NULL = a plain model */
+  long V_row_stride;          /* element (a, b) of V at V_dev[a * V_row_stride + b * V_col_stride]; both 0 = row-major (l, 1) */
+  long V_col_stride;
+  int l;                      /* 1 .. h (h = p[f].d) */
+  const double* y_low_dev;    /* [n, l] */
+  const double* y_high_dev;   /* [n, h] */
+  double* V_last_dev;         /* optional [h, l] row-major */
+} ffgp_tlin_link;
+int ffgp_train_tlin_raw(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, const ffgp_tlin_link* t, int steps,
+                        const ffgp_adam* opt, double* state_dev, long state_stride, long step0, double* trace_dev, long trace_stride);
 
 /* ffgp_train_raw for models whose kernel is a COMPOSITION -- SumKernel / ProductKernel trees of 2-4 leaves (ffgp_ktree), the kernel of
    the reference's own demos and of every two-fidelity model (SumKernel(LinearKernel, MaternKernel): GaussianProcess/cigp_v10.py:81,111,
