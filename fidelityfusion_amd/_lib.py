@@ -159,6 +159,7 @@ FFGP_ACQ_UCB, FFGP_ACQ_EI = 0, 1
 FFGP_ACQ_UCB_VAR = 2             # ffgp_acq_optimize_stack only
 FFGP_ACQ_MAX_MEMBERS = 8
 FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D, FFGP_ACQ_MAX_STEPS = 256, 16, 4096      # include/ffgp.h
+FFGP_ACQ_STAGED_MAX_N = 2048     # ffgp_acq_optimize_stack_staged: images in handle workspace, not in LDS
 
 LINK_ID, LINK_INV_ABS_EPS, LINK_EXP_NEG, LINK_INV, LINK_ABS, LINK_EXP_SQ, LINK_SQUARE = range(7)
 
@@ -249,6 +250,7 @@ EXPORTS = {
     "ffgp_acq_optimize": (C.c_int, [C.c_void_p, C.POINTER(AcqProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_tree": (C.c_int, [C.c_void_p, C.POINTER(AcqTreeProblem), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_stack": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
+    "ffgp_acq_optimize_stack_staged": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_stack_tree": (C.c_int, [C.c_void_p, C.POINTER(AcqStack), C.POINTER(C.POINTER(KTree)), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp,
                                                C.c_long, _dp, _dp, _dp]),
     "ffgp_acq_optimize_chain": (C.c_int, [C.c_void_p, C.POINTER(AcqChain), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),

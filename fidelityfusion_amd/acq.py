@@ -11,7 +11,9 @@ drivers' MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 -- every fidelity l
 with `fuse_composed=True` also when fidelities run on SumKernel / ProductKernel trees, the reference's own
 SumKernel(LinearKernel, MaternKernel) of its two-fidelity AR and ResGP (csrc/acq_stack_tree.hip).
 `optimize_acqf_nar` is that loop on NAR (FidelityFusion_Models/NAR.py:30-61), whose upper fidelities take the lower fidelity's predicted
-mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip)."""
+mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip).
+Past the one-launch kernels' 256 training points, `staged=True` on `optimize_acqf` / `optimize_acqf_mf` keeps the loop on the device:
+launch per stage, every step enqueued by one library call (csrc/acq_staged.hip), for radial-kernel models of up to 2048 points."""
 import inspect
 import math
 
@@ -88,13 +90,15 @@ def _generic_loop(acq, X0, f_best, steps, lr):
 
 
 def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0,
-                  var_floor=1e-12, return_best_only=True, fuse_composed=False):
+                  var_floor=1e-12, return_best_only=True, fuse_composed=False, staged=False):
     """The reference's `optimize_acqf` from the start points X0 [Q, D] (untouched): `steps` (its `num_restarts`) Adam iterations at
     `lr` on loss = -acq(X).sum(), then its selection rule (`select_best`); `return_best_only=False` returns the final points.
       * model = a `cigp`: the posterior of (x_train, y_train) the model caches, with the noise `cigp.forward` adds to the variance
         (1 / beta); model = a `functional.Posterior`: as it stands (no noise added).  acq = "ucb" (kappa, var_floor) or "ei" (f_best, xi);
         `fuse_composed=True` runs a composed kernel's loop (SumKernel / ProductKernel trees, the reference's own
         SumKernel(LinearKernel, MaternKernel)) in one launch as well (`Posterior.optimize_acquisition`, csrc/acq_tree.hip);
+        `staged=True` runs a radial-kernel model of 257 ... 2048 points launch per stage inside one library call
+        (csrc/acq_staged.hip) instead of the per-step loop; models of up to 256 points keep the one-launch call;
       * model = an acquisition object (`UCB`, `EI`, anything with forward(X) or forward(X, f_best)): the step-by-step torch loop."""
     if X0 is None:
         raise ValueError("optimize_acqf needs the start points X0 [Q, D]")
@@ -106,14 +110,14 @@ def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, 
             post = model._cached_posterior(x_train, y)[0]
             noise = float(model.log_beta.detach().exp().pow(-1))
         X, trace, hist, _ = post.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
-                                                      var_add_all=noise, var_floor=var_floor, fuse_composed=fuse_composed)
+                                                      var_add_all=noise, var_floor=var_floor, fuse_composed=fuse_composed, staged=staged)
     else:
         X, trace, hist = _generic_loop(model, X0, f_best, steps, lr)
     return select_best(X0, trace, hist) if return_best_only else X
 
 
 def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12,
-                     accumulate_grad=False, return_best_only=True, fuse_composed=False):
+                     accumulate_grad=False, return_best_only=True, fuse_composed=False, staged=False):
     """The multi-fidelity drivers' acquisition optimiser (DMF_acq.py:226-262) on the posterior of AR / ResGP
     (FidelityFusion_Models/AR_autoRegression.py:56-89): `models` is the trainers' `gpr_list` (frozen `cigp`), data[f] = (x_f, y_f) the
     data model f was trained on (for f > 0 the residuals), rho = (rho_0, ...) AR's scale factors -- None: all ones, ResGP.  Member f
@@ -122,7 +126,9 @@ def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001,
     drivers' loop over the fidelities is ONE call; acq = "ucb", "ei" or "ucb_var" (mean + kappa var, the drivers' UCB_MF with
     kappa = 0.2 D); `accumulate_grad=True` omits zero_grad as the drivers' loop does.  `fuse_composed=True` runs the loop in one launch
     also when models carry composed kernels (`PosteriorStack.optimize_acquisition`, csrc/acq_stack_tree.hip); by default such a stack
-    takes the per-step loop.  Returns `select_best` on the trace, or the final points with `return_best_only=False`."""
+    takes the per-step loop.  `staged=True` runs a stack of radial-kernel models with a fidelity of 257 ... 2048 points -- the
+    reference's demo trains on 300 / 300 / 250 -- launch per stage inside one library call (csrc/acq_staged.hip) instead of the per-step
+    loop; composed kernels and `fuse_composed=True` are out of its scope.  Returns `select_best` on the trace, or the final points with `return_best_only=False`."""
     if X0 is None:
         raise ValueError("optimize_acqf_mf needs the start points X0 [Q, D]")
     models = list(models)
@@ -138,7 +144,8 @@ def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001,
         noise.append(float(m.log_beta.detach().exp().pow(-1)))
     stack = PosteriorStack(members, coefs)
     X, trace, hist, _ = stack.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
-                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad, fuse_composed=fuse_composed)
+                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad, fuse_composed=fuse_composed,
+                                                   staged=staged)
     return select_best(X0, trace, hist) if return_best_only else X
 
 

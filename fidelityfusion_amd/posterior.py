@@ -221,6 +221,14 @@ class Posterior:
                 and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D and isinstance(X0, torch.Tensor) and X0.is_cuda and X0.device == self.dev
                 and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1 and X0.shape[1] == self.D)
 
+    def acq_staged_ok(self, X0):
+        """whether `optimize_acquisition(..., staged=True)` from X0 may take the launch-per-stage call (ffgp_acq_optimize_stack_staged):
+        `acq_fusable`'s conditions with n up to FFGP_ACQ_STAGED_MAX_N = 2048 in place of 256 -- ONE radial library kernel (no descriptor
+        tree, no LinearKernel), one output, D <= 16, the start points fp64 on this posterior's GPU"""
+        return (self.tree is None and 0 <= int(self.kfun[0]) < FFGP_KFUN_LINEAR and self.d == 1 and 1 <= self.n <= _lib.FFGP_ACQ_STAGED_MAX_N
+                and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D and isinstance(X0, torch.Tensor) and X0.is_cuda and X0.device == self.dev
+                and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1 and X0.shape[1] == self.D)
+
     def acq_tree_fusable(self, X0):
         """whether `optimize_acquisition(..., fuse_composed=True)` from X0 takes the one-launch call for composed kernels
         (ffgp_acq_optimize_tree): a descriptor tree of 2-4 library leaves (radial profiles and LinearKernel), one output, n and D
@@ -231,7 +239,7 @@ class Posterior:
                 and X0.device == self.dev and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1 and X0.shape[1] == self.D)
 
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_add_all=0.0, var_floor=1e-12,
-                             betas=(0.9, 0.999), eps=1e-8, state=None, fuse_composed=False):
+                             betas=(0.9, 0.999), eps=1e-8, state=None, fuse_composed=False, staged=False):
         """`steps` Adam iterations of the reference's acquisition optimiser on this frozen posterior
         (Bayesian_optimization/acq.py:48-68: zero_grad(); loss = -acq(X).sum(); loss.backward(); Adam.step()), from the start points
         X0 [Q, D] (left untouched).  acq = "ucb": mean + kappa sqrt(max(var, var_floor)); "ei": acq.py:161-181 with f_best, xi.
@@ -244,14 +252,20 @@ class Posterior:
         depends on the factor alone; later `predict` / `predict_diff` calls then solve with those blocks (see `predict_diff`).
         `fuse_composed=True` opts a composed kernel in: when `acq_tree_fusable(X0)` and steps <= 4096 the loop is ONE launch as well
         (ffgp_acq_optimize_tree, csrc/acq_tree.hip: Sum / Product trees of 2-4 leaves, LinearKernel included), with the same return
-        values, `state` contract and state["fused"] = True; otherwise, and by default, such a posterior takes the per-step loop."""
+        values, `state` contract and state["fused"] = True; otherwise, and by default, such a posterior takes the per-step loop.
+        `staged=True` opts larger models in: a posterior that is not `acq_fusable(X0)` but `acq_staged_ok(X0)` (n up to 2048) runs the
+        loop launch per stage inside ONE library call (ffgp_acq_optimize_stack_staged, csrc/acq_staged.hip) -- same return values and
+        `state` contract, state["staged"] = True and state["fused"] = False; an `acq_fusable` problem takes the one-launch call exactly
+        as without the keyword, and `staged="force"` sends it to the staged call as well (tests, tools/acq_staged_bench.py).  Composed
+        kernels are out of the staged call's scope, and with `fuse_composed=True` the keyword is ignored."""
         acq = str(acq).lower()
         if acq not in ("ucb", "ei"):
             raise ValueError("acq must be 'ucb' or 'ei', got %r" % (acq,))
         # one posterior is the stack of one member with coefficient 1: the checks, the per-step loop and the fused call live there
         single = _TreePosterior if fuse_composed and self.tree is not None else _SinglePosterior
         return single([self], [1.0]).optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
-                                                          var_floor=var_floor, betas=betas, eps=eps, var_adds=[var_add_all], state=state)
+                                                          var_floor=var_floor, betas=betas, eps=eps, var_adds=[var_add_all], state=state,
+                                                          staged=False if fuse_composed else staged)
 
     @torch.no_grad()
     def append(self, X_new, Y_new):
@@ -354,13 +368,18 @@ class PosteriorStack:
         """whether `optimize_acquisition` from X0 takes the one-launch call (ffgp_acq_optimize_stack)"""
         return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_fusable(X0) for m in self.members)
 
+    def acq_staged_ok(self, X0):
+        """whether `optimize_acquisition(..., staged=True)` from X0 may take the launch-per-stage call (ffgp_acq_optimize_stack_staged):
+        at most 8 members, each of them `Posterior.acq_staged_ok` (one radial library kernel, d = 1, D <= 16, n <= 2048)"""
+        return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_staged_ok(X0) for m in self.members)
+
     def acq_tree_fusable(self, X0):
         """whether `optimize_acquisition(..., fuse_composed=True)` from X0 takes a one-launch call: at most 8 members, each of them
         `acq_fusable` (one radial library kernel) or `acq_tree_fusable` (a descriptor tree of 2-4 library leaves)"""
         return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_fusable(X0) or m.acq_tree_fusable(X0) for m in self.members)
 
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12, betas=(0.9, 0.999),
-                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None, fuse_composed=False):
+                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None, fuse_composed=False, staged=False):
         """`Posterior.optimize_acquisition` on the stack's posterior, with the same return tuple (X, trace, hist, state).
         acq = "ucb" / "ei" as there, or "ucb_var": mean + kappa var, the multi-fidelity drivers' form
         (MF_BayesianOptimization/Discrete/DMF_acq.py:49-63).  `level` (int or [Q]) gives every point its own `to_fidelity`, so one
@@ -371,7 +390,17 @@ class PosteriorStack:
         `fuse_composed=True` opts members with composed kernels in, as for a single posterior: a stack with at least one tree member
         that is `acq_tree_fusable(X0)` is ONE launch as well (ffgp_acq_optimize_stack_tree, csrc/acq_stack_tree.hip: radial members
         and Sum / Product trees of 2-4 leaves mixed freely), with the same return values and `state` contract.  A stack without a
-        tree member takes the call above whatever the keyword says; without the keyword nothing changes."""
+        tree member takes the call above whatever the keyword says; without the keyword nothing changes.
+        `staged=True` opts members beyond the one-launch kernels' n <= 256 in: a stack that is not `acq_fusable(X0)` but
+        `acq_staged_ok(X0)` (radial members of up to 2048 points) runs the loop launch per stage inside ONE library call
+        (ffgp_acq_optimize_stack_staged, csrc/acq_staged.hip: levels, coefficients, `var_adds`, all three acquisitions and
+        `accumulate_grad` as in the one-launch call, whose `state` it continues and hands on); state["staged"] = True and
+        state["fused"] = False then.  An `acq_fusable` stack takes the one-launch call exactly as without the keyword;
+        `staged="force"` sends it to the staged call too (tests, tools/acq_staged_bench.py).  Out of the staged call's scope, with
+        their routing unchanged: members with composed kernels, the NAR chain (`PosteriorChain`), and `fuse_composed=True`, which
+        makes this keyword a no-op."""
+        if staged not in (False, True, "force"):
+            raise ValueError("staged must be False, True or 'force', got %r" % (staged,))
         acq = str(acq).lower()
         if acq not in ("ucb", "ei", "ucb_var"):
             raise ValueError("acq must be 'ucb', 'ei' or 'ucb_var', got %r" % (acq,))
@@ -384,10 +413,15 @@ class PosteriorStack:
         lv = self._level(level, X0.shape[0])
         step0 = int(state["step"]) if state is not None else 0
         if steps <= _lib.FFGP_ACQ_MAX_STEPS:
-            call = self._acq_call if self.acq_fusable(X0) else self._acq_call_trees if fuse_composed and self.acq_tree_fusable(X0) else None
+            stage = bool(staged) and not fuse_composed and self.acq_staged_ok(X0)
+            if stage and (staged == "force" or not self.acq_fusable(X0)):
+                call = self._acq_call_staged
+            else:
+                stage = False
+                call = self._acq_call if self.acq_fusable(X0) else self._acq_call_trees if fuse_composed and self.acq_tree_fusable(X0) else None
             if call is not None:
                 return self._optimize_acq_fused(X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0,
-                                                call)
+                                                call, stage)
         dev = self.dev
         X = X0.detach().to(device=dev, dtype=torch.float64).clone().requires_grad_(True)
         opt = torch.optim.Adam([X], lr=lr, betas=betas, eps=eps)
@@ -450,7 +484,9 @@ class PosteriorStack:
         return trees
 
     @torch.no_grad()
-    def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0, call):
+    def _optimize_acq_fused(self, X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0, call,
+                            staged=False):
+        """the buffers of a C-side loop and its returned state; `staged`: the launch-per-stage call took it, not a one-launch kernel"""
         dev, Q, D = self.dev, X0.shape[0], self.D
         X = X0.detach().clone().contiguous()
         buf = torch.zeros((3 if accumulate_grad else 2, Q, D), dtype=torch.float64, device=dev)
@@ -465,7 +501,9 @@ class PosteriorStack:
         opt = _lib.Adam(float(lr), float(betas[0]), float(betas[1]), float(eps))
         call(va, lv, dict(var_floor=float(var_floor), acq=code, kappa=float(kappa), xi=float(xi), f_best=float(f_best)), accumulate_grad,
              (_ptr(X), Q, steps, C.byref(opt), _ptr(buf), step0, _ptr(trace), _ptr(hist), None))
-        out = {"fused": True, "step": step0 + steps, "exp_avg": buf[0], "exp_avg_sq": buf[1]}
+        out = {"fused": not staged, "step": step0 + steps, "exp_avg": buf[0], "exp_avg_sq": buf[1]}
+        if staged:
+            out["staged"] = True
         if accumulate_grad:
             out["grad_sum"] = buf[2]
         return X, trace, hist, out
@@ -476,6 +514,13 @@ class PosteriorStack:
         s = _lib.AcqStack(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
                           accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
         check(lib.ffgp_acq_optimize_stack(self.members[0]._h(), C.byref(s), *call), "ffgp_acq_optimize_stack")
+
+    def _acq_call_staged(self, va, lv, acq_fields, accumulate_grad, call):
+        """the C entry of the launch-per-stage call: ffgp_acq_optimize_stack's arguments, a single posterior as the stack of one"""
+        keep = []
+        s = _lib.AcqStack(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
+                          accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
+        check(lib.ffgp_acq_optimize_stack_staged(self.members[0]._h(), C.byref(s), *call), "ffgp_acq_optimize_stack_staged")
 
     def _acq_call_trees(self, va, lv, acq_fields, accumulate_grad, call):
         """the C entry of the fused call on a stack with tree members"""
@@ -557,6 +602,10 @@ class PosteriorChain(PosteriorStack):
                 mean = m * on.unsqueeze(1) if mean is None else mean + m * on.unsqueeze(1)
                 var = v * on if var is None else var + v * on
         return mean, var
+
+    def acq_staged_ok(self, X0):
+        """never: the launch-per-stage call serves stacks, not the chain"""
+        return False
 
     def acq_fusable(self, X0):
         """whether `optimize_acquisition` from X0 takes the one-launch call (ffgp_acq_optimize_chain): at most 8 members, each ONE

@@ -945,6 +945,29 @@ typedef struct {
 int ffgp_acq_optimize_stack(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
                             double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* ffgp_acq_optimize_stack past FFGP_ACQ_MAX_N training points: the same loop LAUNCH PER STAGE (csrc/acq_staged.hip), every step
+   enqueued by this one call -- no host synchronisation and no Python inside the loop.  `s`, Xq, state, trace, hist, grad, step0, opt,
+   evaluate mode (steps = 0), level, the coefficients, var_add_all, FFGP_ACQ_UCB / FFGP_ACQ_EI / FFGP_ACQ_UCB_VAR and accumulate_grad
+   are ffgp_acq_optimize_stack's, field for field and layout for layout: an Adam state moves between the two entries, and a single
+   posterior is the stack of one member with both coefficients 1.  Limits: every n in 1..FFGP_ACQ_STAGED_MAX_N; F, D, d = 1, steps and
+   kfun as there.  Per call L_f^-1 of every member is formed in handle workspace (the handle's inverted diagonal blocks rebuilt from
+   L_dev before each, left keyed on the LAST member's factor; only L's lower triangle within n columns is read) -- nothing is factored
+   inside the loop.  Per step 5 + 2 F launches, whatever Q and n: K_s of all members, V_f = L_f^-1 K_s,f and B_f = L_f^-T V_f on the
+   fp64 MFMA GEMM, column sums, the acquisition value, the input-gradient tiles, the owners' Adam update.  No atomics and no order of
+   summation that depends on timing or on the grid: 12 + 18 steps through state_dev equal 30 steps bit for bit; cutting Q into several
+   calls can change the GEMM's tile choice and with it the last bits.  The loop stops enqueueing at the first refused launch and
+   returns that status.  FFGP_ERR_ARG, before anything is enqueued (Xq, state and trace untouched): everything
+   ffgp_acq_optimize_stack refuses, with n outside 1..FFGP_ACQ_STAGED_MAX_N in place of its rule on n, and Q D beyond INT_MAX.
+   Synchronous.
+   Workspace, in doubles, with np_f = n_f rounded up to 16, Qp = Q rounded up to 64, C = the largest ceil(n_f / 128) and DM = 2, 8 or
+   16 (the first that holds D):
+       sum_f [ np_f^2  (L_f^-1)  +  4 n_f Qp  (K_s, its derivative factors, V, B)  +  n_f^2 / 4 + 128 n_f + 16  (triangular inverse) ]
+       + F C Qp (2 + DM) + 3 Qp      (the chunk sums and the per-point values)
+   -- 75 MiB for one member of 2048 points and Q = 500, 0.6 GiB for eight of them; a request the device cannot serve is FFGP_ERR_HIP.  */
+#define FFGP_ACQ_STAGED_MAX_N 2048
+int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                                   double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* The same loop on a CHAIN of frozen posteriors -- the drivers' acquisition optimiser on NAR (FidelityFusion_Models/NAR.py:30-61), whose
    upper fidelities take the lower fidelity's predicted MEAN as one more input column -- in ONE launch (csrc/acq_chain.hip).
    members[0] is a posterior on x [D], 1 <= D <= FFGP_ACQ_MAX_D - 1; members[f > 0] are posteriors on z = [x, m_{f-1}], D + 1 inputs;
