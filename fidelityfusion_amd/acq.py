@@ -13,7 +13,9 @@ SumKernel(LinearKernel, MaternKernel) of its two-fidelity AR and ResGP (csrc/acq
 `optimize_acqf_nar` is that loop on NAR (FidelityFusion_Models/NAR.py:30-61), whose upper fidelities take the lower fidelity's predicted
 mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip).
 Past the one-launch kernels' 256 training points, `staged=True` on `optimize_acqf` / `optimize_acqf_mf` keeps the loop on the device:
-launch per stage, every step enqueued by one library call (csrc/acq_staged.hip), for radial-kernel models of up to 2048 points."""
+launch per stage, every step enqueued by one library call (csrc/acq_staged.hip), for radial-kernel models of up to 2048 points; with
+`fuse_composed=True` as well, the same holds for SumKernel / ProductKernel models and stacks with such fidelities
+(csrc/acq_staged_tree.hip) -- the reference's cigp and AR on SumKernel(LinearKernel, MaternKernel) once a run has passed 256 points."""
 import inspect
 import math
 
@@ -98,7 +100,8 @@ def optimize_acqf(model, x_train=None, y_train=None, X0=None, steps=30, lr=0.1, 
         `fuse_composed=True` runs a composed kernel's loop (SumKernel / ProductKernel trees, the reference's own
         SumKernel(LinearKernel, MaternKernel)) in one launch as well (`Posterior.optimize_acquisition`, csrc/acq_tree.hip);
         `staged=True` runs a radial-kernel model of 257 ... 2048 points launch per stage inside one library call
-        (csrc/acq_staged.hip) instead of the per-step loop; models of up to 256 points keep the one-launch call;
+        (csrc/acq_staged.hip) instead of the per-step loop; models of up to 256 points keep the one-launch call; both keywords
+        together do the same for a composed-kernel model of 257 ... 2048 points (csrc/acq_staged_tree.hip);
       * model = an acquisition object (`UCB`, `EI`, anything with forward(X) or forward(X, f_best)): the step-by-step torch loop."""
     if X0 is None:
         raise ValueError("optimize_acqf needs the start points X0 [Q, D]")
@@ -128,7 +131,8 @@ def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001,
     also when models carry composed kernels (`PosteriorStack.optimize_acquisition`, csrc/acq_stack_tree.hip); by default such a stack
     takes the per-step loop.  `staged=True` runs a stack of radial-kernel models with a fidelity of 257 ... 2048 points -- the
     reference's demo trains on 300 / 300 / 250 -- launch per stage inside one library call (csrc/acq_staged.hip) instead of the per-step
-    loop; composed kernels and `fuse_composed=True` are out of its scope.  Returns `select_best` on the trace, or the final points with `return_best_only=False`."""
+    loop; with `fuse_composed=True` as well, so does a stack whose models carry composed kernels (csrc/acq_staged_tree.hip), while
+    `staged=True` alone leaves such a stack on the per-step loop.  Returns `select_best` on the trace, or the final points with `return_best_only=False`."""
     if X0 is None:
         raise ValueError("optimize_acqf_mf needs the start points X0 [Q, D]")
     models = list(models)

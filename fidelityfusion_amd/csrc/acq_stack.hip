@@ -135,7 +135,7 @@ static int acq_stack_launch_by_d(ffgp_handle* h, const AcqStackArgs& a, int grid
 }
 
 // member p's kernel as a leaf record: its tree (checked by the entry), or the one leaf of its own radial kernel
-static AcqMemberTree acq_member_tree(const ffgp_acq_member& p, const ffgp_ktree* t) {
+AcqMemberTree acq_member_tree(const ffgp_acq_member& p, const ffgp_ktree* t) {
   AcqMemberTree r = {};
   r.nl = t ? t->n_leaves : 1;
   r.shape = (t && t->n_leaves == 4) ? t->shape : FFGP_TREE_CHAIN;

@@ -19,35 +19,13 @@
 // four lanes' sums are added through LDS in the order 0..3.  The chunking is a function of n alone, no sum is taken in an order that
 // depends on Q, on the grid or on timing, and there are no atomics: what can differ between two ways of cutting Q is the GEMM's
 // tile choice alone.
+// The host driver, the column-sum kernel and the owner kernel also serve the entry for composed kernels (acq_staged_tree.hip) through
+// acq_staged_run (acq_staged.h), which brings its own stages 1, 4 and 5.
 #include <climits>
 #include <cmath>
 #include <vector>
 
-#include "acq_tile.h"
-
-#define AS_T 256
-#define AS_COLS 64
-#define AS_LANES 4
-#define AS_ROWS 128
-
-struct AcqStagedMember {
-  const double *X, *alpha, *w, *amp;
-  double *Ks, *DK, *V, *B;      // [n][Qp] each
-  double clamp, rinv, var_add, mean_coef, var_coef;
-  int n, kfun;
-};
-struct AcqStagedArgs {
-  AcqStagedMember m[FFGP_ACQ_MAX_MEMBERS];
-  const int* level;      // [Q] or null
-  double *Xq, *state, *trace, *hist, *grad;
-  double *pm, *pv;       // [F][nch][Qp] chunk sums of K_s^T alpha and |V|^2
-  double *av, *gm, *gv;  // [Qp] the acquisition value, da/dmean, da/dvar
-  double* part;          // [F][nch][Qp][DM] chunk sums of d(-a)/dx
-  int F, D, DM, Q, Qp, nch, steps, acq, accumulate;
-  double var_floor, kappa, xi, f_best, lr, b1, b2, eps;
-};
-
-__device__ __forceinline__ int as_chunks(int n) { return (n + AS_ROWS - 1) / AS_ROWS; }
+#include "acq_staged.h"
 
 // ---- 1. K_s and the derivative factors; the columns Q..Qp-1 are written as zeros
 template <int DM>
@@ -106,9 +84,6 @@ __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_col_kernel(AcqStagedArgs
     (which ? a.pv : a.pm)[((size_t)blockIdx.z * a.nch + blockIdx.y) * a.Qp + q] = s;
   }
 }
-
-// this point's weights of member f: an exact 0 / 1 factor on its two coefficients (acq_stack.hip, Levels)
-__device__ __forceinline__ int as_level(const AcqStagedArgs& a, int q) { return a.level ? min(a.level[q], a.F - 1) : a.F - 1; }
 
 // ---- 4. mean, variance, the acquisition value and its two derivatives, per point
 __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_value_kernel(AcqStagedArgs a) {
@@ -199,6 +174,7 @@ __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_owner_kernel(AcqStagedAr
     const int nch = as_chunks(a.m[f].n);
     for (int ch = 0; ch < nch; ++ch) gx += a.part[(((size_t)f * a.nch + ch) * a.Qp + q) * a.DM + dd];
   }
+  if (a.self) gx -= a.gv[q] * a.self[e];      // the tree entry: -(da/dvar) sum_f c'_f dk_f(x, x)/dx, non-zero through linear leaves
   double x = a.Xq[e];
   if (dd == 0) a.trace[(size_t)k * a.Q + q] = a.av[q];
   if (a.hist) a.hist[(size_t)k * plane + e] = x;
@@ -217,11 +193,6 @@ __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_owner_kernel(AcqStagedAr
   }
 }
 
-// one stage of the step loop: a refused launch ends the call there, before a later stage reads what it did not write
-#define AS_STAGE(call) \
-  if ((rc = (call)) != FFGP_OK) break
-static inline int as_launched() { return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP; }
-
 template <int DM>
 static int as_ks_launch(ffgp_handle* h, const AcqStagedArgs& a, dim3 grid) {
   hipLaunchKernelGGL(ffgp_acq_staged_ks_kernel<DM>, grid, dim3(AS_T), 0, h->stream, a);
@@ -232,10 +203,21 @@ static int as_grad_launch(ffgp_handle* h, const AcqStagedArgs& a, dim3 grid) {
   hipLaunchKernelGGL(ffgp_acq_staged_grad_kernel<DM>, grid, dim3(AS_T), 0, h->stream, a);
   return as_launched();
 }
+static int as_ks_stage(ffgp_handle* h, const AcqStagedArgs& a, dim3 tiles) {
+  return acq_by_dm(a.D, [&](auto dm) { return as_ks_launch<dm()>(h, a, tiles); });
+}
+static int as_value_stage(ffgp_handle* h, const AcqStagedArgs& a) {
+  hipLaunchKernelGGL(ffgp_acq_staged_value_kernel, dim3((a.Q + AS_T - 1) / AS_T), dim3(AS_T), 0, h->stream, a);
+  return as_launched();
+}
+static int as_grad_stage(ffgp_handle* h, const AcqStagedArgs& a, dim3 tiles) {
+  return acq_by_dm(a.D, [&](auto dm) { return as_grad_launch<dm()>(h, a, tiles); });
+}
 
-int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
-                                   double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
-  // the argument classes acq_run refuses (acq_stack.hip), with this entry's own limit on n
+// The driver of both staged entries (acq_staged.h).
+int acq_staged_run(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, const AcqStagedStages& st, double* Xq_dev, int Q,
+                   int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+  // the argument classes acq_run refuses (acq_stack.hip), with these entries' own limit on n
   if (!h || !s || !Xq_dev || !trace_dev || Q <= 0 || steps < 0 || steps > FFGP_ACQ_MAX_STEPS || step0 < 0) return FFGP_ERR_ARG;
   if (steps > 0 && (!opt || !state_dev)) return FFGP_ERR_ARG;
   if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members) return FFGP_ERR_ARG;
@@ -243,34 +225,40 @@ int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, doub
   const int F = s->F, D = s->members[0].D;
   for (int f = 0; f < F; ++f) {
     const ffgp_acq_member& p = s->members[f];
-    if (!p.X_dev || !p.L_dev || !p.alpha_dev || !p.w_dev || !p.amp_dev) return FFGP_ERR_ARG;
+    const bool tree = trees && trees[f];      // such a member carries no w_dev / amp_dev / kfun of its own
+    if (!p.X_dev || !p.L_dev || !p.alpha_dev || (!tree && (!p.w_dev || !p.amp_dev))) return FFGP_ERR_ARG;
     if (p.n < 1 || p.n > FFGP_ACQ_STAGED_MAX_N || p.D < 1 || p.D > FFGP_ACQ_MAX_D || p.D != D || p.d != 1) return FFGP_ERR_ARG;
     if (p.ldl < p.n || p.ldl > INT_MAX) return FFGP_ERR_ARG;
-    if (p.kfun < FFGP_KFUN_SE || p.kfun > FFGP_KFUN_RQ) return FFGP_ERR_ARG;      // (the linear kernel's k(x, x) depends on x)
+    if (!tree && (p.kfun < FFGP_KFUN_SE || p.kfun > FFGP_KFUN_RQ)) return FFGP_ERR_ARG;      // (the linear kernel's k(x, x) depends on x)
   }
   if ((size_t)Q * D > (size_t)INT_MAX || Q > INT_MAX - AS_COLS) return FFGP_ERR_ARG;
   FFGP_HIP(hipSetDevice(h->device));
   const int iters = steps > 0 ? steps : 1;
   const int DM = acq_by_dm(D, [](auto dm) { return (int)dm(); });
   const int Qp = ffgp_round_up(Q, AS_COLS), qt = Qp / AS_COLS;
+  const size_t imgs = (size_t)st.images;
   // workspace, in doubles (the arithmetic beside FFGP_ACQ_STAGED_MAX_N in ffgp.h):
-  //   [L_f^-1 (np_f x np_f) | K_s, DK, V, B of member f (4 n_f Qp), f = 0..F-1 | TRTRI scratch per member | pm, pv | av, gm, gv | part]
+  //   [L_f^-1 (np_f x np_f) | the images of member f (K_s, DK, V, B: 4 n_f Qp; without DK 3 n_f Qp), f = 0..F-1 | TRTRI scratch per member
+  //    | pm, pv | av, gm, gv | part | trees: self (Qp DM), the leaf records]
   size_t xd = 0, md = 0, td = 0;
   int nch = 0;
   for (int f = 0; f < F; ++f) {
     const size_t n = (size_t)s->members[f].n, np = (size_t)ffgp_round_up((int)n, 16);
     xd += np * np;
-    md += 4 * n * Qp;
+    md += imgs * n * Qp;
     td += n * n / 4 + n * FFGP_NB + 16;
     nch = max(nch, (int)((n + AS_ROWS - 1) / AS_ROWS));
   }
-  const size_t pd = (size_t)F * nch * Qp;
-  FFGP_CHECK(ffgp_ensure_ws(h, (xd + md + td + 2 * pd + 3 * (size_t)Qp + pd * DM) * sizeof(double)));
+  const size_t pd = (size_t)F * nch * Qp, sd = trees ? (size_t)Qp * DM : 0;
+  FFGP_CHECK(ffgp_ensure_ws(h, (xd + md + td + 2 * pd + 3 * (size_t)Qp + pd * DM + sd) * sizeof(double) + (trees ? F * sizeof(AcqMemberTree) : 0)));
   double* X = h->ws;
   double* M = X + xd;
   double* T = M + md;
   AcqStagedArgs a;
   a.pm = T + td; a.pv = a.pm + pd; a.av = a.pv + pd; a.gm = a.av + Qp; a.gv = a.gm + Qp; a.part = a.gv + Qp;
+  a.self = trees ? a.part + pd * DM : nullptr;
+  AcqMemberTree* const table_dev = trees ? reinterpret_cast<AcqMemberTree*>(a.part + pd * DM + sd) : nullptr;
+  a.tab = table_dev;
   // zeros: L^-1 above the diagonal and in its padding, and the columns Q..Qp-1 of V and B, which no GEMM writes
   FFGP_CHECK(ffgp_zero_async(h, X, (xd + md) * sizeof(double)));
   const double* Linv[FFGP_ACQ_MAX_MEMBERS];
@@ -281,7 +269,12 @@ int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, doub
     const size_t img = (size_t)n * Qp;
     AcqStagedMember& m = a.m[f];
     m.X = p.X_dev; m.alpha = p.alpha_dev; m.w = p.w_dev; m.amp = p.amp_dev;
-    m.Ks = M; m.DK = M + img; m.V = M + 2 * img; m.B = M + 3 * img;
+    m.Ks = M;
+    if (imgs == 4) {
+      m.DK = M + img; m.V = M + 2 * img; m.B = M + 3 * img;
+    } else {
+      m.DK = nullptr; m.V = M + img; m.B = M + 2 * img;
+    }
     m.clamp = p.clamp_min; m.rinv = (p.kparam != 0.0) ? 1.0 / p.kparam : 1.0; m.var_add = p.var_add_all;
     m.mean_coef = p.mean_coef; m.var_coef = p.var_coef; m.n = n; m.kfun = p.kfun;
     Linv[f] = X; np_of[f] = np;
@@ -289,12 +282,17 @@ int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, doub
     ffgp_invalidate(h);
     FFGP_CHECK(ffgp_trtri_impl(h, p.L_dev, n, (int)p.ldl, X, np, T));
     X += (size_t)np * np;
-    M += 4 * img;
+    M += imgs * img;
     T += (size_t)n * n / 4 + (size_t)n * FFGP_NB + 16;
   }
   for (int f = F; f < FFGP_ACQ_MAX_MEMBERS; ++f) a.m[f] = a.m[0];      // never read: every member loop ends at F
   std::vector<double> bc(2 * (size_t)iters, 1.0);
   ffgp_adam_bc_table(opt, step0, steps, bc.data());
+  std::vector<AcqMemberTree> table(trees ? F : 0);      // (lives until the wait below)
+  if (trees) {
+    for (int f = 0; f < F; ++f) table[f] = acq_member_tree(s->members[f], trees[f]);
+    FFGP_HIP(hipMemcpyAsync(table_dev, table.data(), table.size() * sizeof(AcqMemberTree), hipMemcpyHostToDevice, h->stream));
+  }
   a.level = s->level_dev;
   a.Xq = Xq_dev; a.state = state_dev; a.trace = trace_dev; a.hist = hist_dev; a.grad = grad_dev;
   a.F = F; a.D = D; a.DM = DM; a.Q = Q; a.Qp = Qp; a.nch = nch; a.steps = steps; a.acq = s->acq; a.accumulate = s->accumulate_grad ? 1 : 0;
@@ -305,7 +303,7 @@ int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, doub
   const size_t plane = (size_t)Q * D;
   int rc = FFGP_OK;
   for (int k = 0; k < iters; ++k) {
-    AS_STAGE(acq_by_dm(D, [&](auto dm) { return as_ks_launch<dm()>(h, a, tiles); }));
+    AS_STAGE(st.ks(h, a, tiles));
     for (int f = 0; f < F && rc == FFGP_OK; ++f) {
       const AcqStagedMember& m = a.m[f];
       // V = L^-1 K_s (L^-1 lower: k ends at the tile row), B = L^-T V (k starts at it)
@@ -316,9 +314,8 @@ int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, doub
     if (rc != FFGP_OK) break;
     hipLaunchKernelGGL(ffgp_acq_staged_col_kernel, tiles, dim3(AS_T), 0, h->stream, a);
     AS_STAGE(as_launched());
-    hipLaunchKernelGGL(ffgp_acq_staged_value_kernel, dim3((Q + AS_T - 1) / AS_T), dim3(AS_T), 0, h->stream, a);
-    AS_STAGE(as_launched());
-    AS_STAGE(acq_by_dm(D, [&](auto dm) { return as_grad_launch<dm()>(h, a, tiles); }));
+    AS_STAGE(st.value(h, a));
+    AS_STAGE(st.grad(h, a, tiles));
     hipLaunchKernelGGL(ffgp_acq_staged_owner_kernel, dim3((unsigned)((plane + AS_T - 1) / AS_T)), dim3(AS_T), 0, h->stream, a, k, k == iters - 1 ? 1 : 0,
                        bc[2 * k], bc[2 * k + 1]);
     AS_STAGE(as_launched());
@@ -328,3 +325,10 @@ int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, doub
   if (rc != FFGP_OK) return rc;
   return e == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
 }
+
+int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                                   double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+  static const AcqStagedStages stages = {4, as_ks_stage, as_value_stage, as_grad_stage};
+  return acq_staged_run(h, s, nullptr, stages, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev);
+}
+

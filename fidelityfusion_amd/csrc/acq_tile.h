@@ -318,6 +318,8 @@ static inline bool acq_tree_ok(const ffgp_ktree* t) {
     if (t->leaf[e].kfun < FFGP_KFUN_SE || t->leaf[e].kfun > FFGP_KFUN_LINEAR || !t->leaf[e].w_dev || !t->leaf[e].amp_dev) return false;
   return true;
 }
+// member p's kernel as a leaf record (acq_stack.hip): its tree, checked by the entry, or the one leaf of its own radial kernel
+AcqMemberTree acq_member_tree(const ffgp_acq_member& p, const ffgp_ktree* t);
 // what acq_run hands to `launch` beside the kernel's arguments
 struct AcqTrees {
   const ffgp_ktree* const* host;      // [F] the members' trees as the caller gave them (null entry: a radial member), or null

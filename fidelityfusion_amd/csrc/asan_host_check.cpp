@@ -2,6 +2,7 @@
 // Without a GPU every entry point must fail cleanly: ffgp_create reports FFGP_ERR_NODEVICE and leaves *out untouched,
 // a NULL handle is FFGP_ERR_ARG everywhere, ffgp_destroy(NULL) is a no-op.  With a GPU visible the same binary also
 // runs one small fused NLML so that the workspace bookkeeping (grow, reuse, destroy) is walked under ASAN's allocator.
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -195,6 +196,22 @@ int main() {
       mem[1].w_dev = &x; mem[0].w_dev = nullptr; mem[0].amp_dev = nullptr; mem[0].n = 0;      // ... the one with a tree does not: refused for n
       EXPECT(ffgp_acq_optimize_stack_tree(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
       mem[0].w_dev = mem[0].amp_dev = &x; mem[0].n = 4;
+      // the two launch-per-stage entries share one driver (acq_staged_run): its refusals, with the staged rule on n and the one on Q D
+      EXPECT(ffgp_acq_optimize_stack_staged(nullptr, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_staged(fake, &stk, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_staged(fake, &stk, &x, INT_MAX, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(nullptr, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(fake, nullptr, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(fake, &stk, nullptr, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(fake, &stk, trees, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(fake, &stk, trees, &x, INT_MAX, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, nullptr, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].n = FFGP_ACQ_STAGED_MAX_N + 1; mem[1].ldl = 4096;
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_stack_staged(fake, &stk, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].n = 4; mem[1].ldl = 4; tr.n_leaves = 5;
+      EXPECT(ffgp_acq_optimize_stack_tree_staged(fake, &stk, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.n_leaves = 4;
     }
     // the chain entry (NAR): the stack entry's driver with the D / D + 1 rule, and its own refusal of a coefficient other than 1
     mem[0].alpha_dev = &x; mem[1].D = 2;

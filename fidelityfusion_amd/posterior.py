@@ -238,6 +238,16 @@ class Posterior:
                 and 1 <= self.n <= _lib.FFGP_ACQ_MAX_N and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D and isinstance(X0, torch.Tensor) and X0.is_cuda
                 and X0.device == self.dev and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1 and X0.shape[1] == self.D)
 
+    def acq_tree_staged_ok(self, X0):
+        """whether `optimize_acquisition(..., fuse_composed=True, staged=True)` from X0 may take the launch-per-stage call for composed
+        kernels (ffgp_acq_optimize_stack_tree_staged): `acq_tree_fusable`'s conditions with n up to FFGP_ACQ_STAGED_MAX_N = 2048 in
+        place of 256 -- a descriptor tree of 2-4 library leaves, one output, D <= 16, the start points fp64 on this posterior's GPU"""
+        return (self.tree is not None and 2 <= len(self.tree[0]) <= 4
+                and all(0 <= int(dsc["kfun"]) <= FFGP_KFUN_LINEAR for dsc in self.tree[0]) and self.d == 1
+                and 1 <= self.n <= _lib.FFGP_ACQ_STAGED_MAX_N and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D and isinstance(X0, torch.Tensor)
+                and X0.is_cuda and X0.device == self.dev and X0.dtype == torch.float64 and X0.dim() == 2 and X0.shape[0] >= 1
+                and X0.shape[1] == self.D)
+
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_add_all=0.0, var_floor=1e-12,
                              betas=(0.9, 0.999), eps=1e-8, state=None, fuse_composed=False, staged=False):
         """`steps` Adam iterations of the reference's acquisition optimiser on this frozen posterior
@@ -256,8 +266,12 @@ class Posterior:
         `staged=True` opts larger models in: a posterior that is not `acq_fusable(X0)` but `acq_staged_ok(X0)` (n up to 2048) runs the
         loop launch per stage inside ONE library call (ffgp_acq_optimize_stack_staged, csrc/acq_staged.hip) -- same return values and
         `state` contract, state["staged"] = True and state["fused"] = False; an `acq_fusable` problem takes the one-launch call exactly
-        as without the keyword, and `staged="force"` sends it to the staged call as well (tests, tools/acq_staged_bench.py).  Composed
-        kernels are out of the staged call's scope, and with `fuse_composed=True` the keyword is ignored."""
+        as without the keyword, and `staged="force"` sends it to the staged call as well (tests, tools/acq_staged_bench.py).
+        `fuse_composed=True` together with `staged=True` opts a large composed-kernel model in: a posterior that is not
+        `acq_tree_fusable(X0)` but `acq_tree_staged_ok(X0)` (2-4 leaves, n up to 2048) runs the staged loop for composed kernels
+        (ffgp_acq_optimize_stack_tree_staged, csrc/acq_staged_tree.hip), with state["staged"] = True and state["fused"] = False; one of
+        up to 256 points keeps its one-launch call bit for bit unless `staged="force"`.  `staged=True` alone leaves a composed kernel
+        on the per-step loop: composed kernels stay opt-in through `fuse_composed`."""
         acq = str(acq).lower()
         if acq not in ("ucb", "ei"):
             raise ValueError("acq must be 'ucb' or 'ei', got %r" % (acq,))
@@ -265,7 +279,7 @@ class Posterior:
         single = _TreePosterior if fuse_composed and self.tree is not None else _SinglePosterior
         return single([self], [1.0]).optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best,
                                                           var_floor=var_floor, betas=betas, eps=eps, var_adds=[var_add_all], state=state,
-                                                          staged=False if fuse_composed else staged)
+                                                          fuse_composed=fuse_composed, staged=staged)
 
     @torch.no_grad()
     def append(self, X_new, Y_new):
@@ -378,6 +392,22 @@ class PosteriorStack:
         `acq_fusable` (one radial library kernel) or `acq_tree_fusable` (a descriptor tree of 2-4 library leaves)"""
         return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_fusable(X0) or m.acq_tree_fusable(X0) for m in self.members)
 
+    def acq_tree_staged_ok(self, X0):
+        """whether `optimize_acquisition(..., fuse_composed=True, staged=True)` from X0 may take the launch-per-stage call for stacks
+        with composed members (ffgp_acq_optimize_stack_tree_staged): at most 8 members, each of them `acq_staged_ok` (one radial
+        library kernel) or `acq_tree_staged_ok` (a descriptor tree of 2-4 library leaves), n <= 2048"""
+        return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and all(m.acq_staged_ok(X0) or m.acq_tree_staged_ok(X0) for m in self.members)
+
+    def _acq_route(self, X0, fuse_composed, staged):
+        """(the C entry's caller or None for the per-step loop, whether it is a launch-per-stage call)"""
+        one = self._acq_call if self.acq_fusable(X0) else self._acq_call_trees if fuse_composed and self.acq_tree_fusable(X0) else None
+        if staged and (staged == "force" or one is None):
+            if self.acq_staged_ok(X0):      # no composed member
+                return self._acq_call_staged, True
+            if fuse_composed and self.acq_tree_staged_ok(X0):
+                return self._acq_call_trees_staged, True
+        return one, False
+
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12, betas=(0.9, 0.999),
                              eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None, fuse_composed=False, staged=False):
         """`Posterior.optimize_acquisition` on the stack's posterior, with the same return tuple (X, trace, hist, state).
@@ -396,9 +426,14 @@ class PosteriorStack:
         (ffgp_acq_optimize_stack_staged, csrc/acq_staged.hip: levels, coefficients, `var_adds`, all three acquisitions and
         `accumulate_grad` as in the one-launch call, whose `state` it continues and hands on); state["staged"] = True and
         state["fused"] = False then.  An `acq_fusable` stack takes the one-launch call exactly as without the keyword;
-        `staged="force"` sends it to the staged call too (tests, tools/acq_staged_bench.py).  Out of the staged call's scope, with
-        their routing unchanged: members with composed kernels, the NAR chain (`PosteriorChain`), and `fuse_composed=True`, which
-        makes this keyword a no-op."""
+        `staged="force"` sends it to the staged call too (tests, tools/acq_staged_bench.py).
+        `fuse_composed=True` together with `staged=True` opts large stacks with composed members in: a stack that takes no one-launch
+        call and has a composed member, but is `acq_tree_staged_ok(X0)` (radial members and trees of 2-4 leaves mixed freely, every
+        n <= 2048), runs the staged loop for composed kernels (ffgp_acq_optimize_stack_tree_staged, csrc/acq_staged_tree.hip), with
+        the same return values, `state` contract and state["staged"] = True; a stack without a composed member takes the radial
+        staged call, and one that takes a one-launch call keeps it bit for bit unless `staged="force"`.  `staged=True` alone leaves
+        a stack with a composed member on the per-step loop.  Out of the staged calls' scope, with its routing unchanged: the NAR
+        chain (`PosteriorChain`)."""
         if staged not in (False, True, "force"):
             raise ValueError("staged must be False, True or 'force', got %r" % (staged,))
         acq = str(acq).lower()
@@ -413,12 +448,7 @@ class PosteriorStack:
         lv = self._level(level, X0.shape[0])
         step0 = int(state["step"]) if state is not None else 0
         if steps <= _lib.FFGP_ACQ_MAX_STEPS:
-            stage = bool(staged) and not fuse_composed and self.acq_staged_ok(X0)
-            if stage and (staged == "force" or not self.acq_fusable(X0)):
-                call = self._acq_call_staged
-            else:
-                stage = False
-                call = self._acq_call if self.acq_fusable(X0) else self._acq_call_trees if fuse_composed and self.acq_tree_fusable(X0) else None
+            call, stage = self._acq_route(X0, fuse_composed, staged)
             if call is not None:
                 return self._optimize_acq_fused(X0, steps, lr, acq, kappa, xi, f_best, var_floor, betas, eps, lv, va, accumulate_grad, state, step0,
                                                 call, stage)
@@ -530,6 +560,15 @@ class PosteriorStack:
         check(lib.ffgp_acq_optimize_stack_tree(self.members[0]._h(), C.byref(s), self._tree_table(), *call), "ffgp_acq_optimize_stack_tree")
 
 
+    def _acq_call_trees_staged(self, va, lv, acq_fields, accumulate_grad, call):
+        """the C entry of the launch-per-stage call on a stack with tree members, a single tree posterior as the stack of one"""
+        keep = []
+        s = _lib.AcqStack(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
+                          accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
+        check(lib.ffgp_acq_optimize_stack_tree_staged(self.members[0]._h(), C.byref(s), self._tree_table(), *call),
+              "ffgp_acq_optimize_stack_tree_staged")
+
+
 class _SinglePosterior(PosteriorStack):
     """`Posterior.optimize_acquisition`: the stack of that one member with coefficient 1, whose fused call is the single-posterior
     entry (ffgp_acq_optimize, its own kernel in csrc/acq.hip)"""
@@ -605,6 +644,10 @@ class PosteriorChain(PosteriorStack):
 
     def acq_staged_ok(self, X0):
         """never: the launch-per-stage call serves stacks, not the chain"""
+        return False
+
+    def acq_tree_staged_ok(self, X0):
+        """never, for the same reason"""
         return False
 
     def acq_fusable(self, X0):

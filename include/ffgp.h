@@ -1056,6 +1056,32 @@ int ffgp_acq_optimize_tree(ffgp_handle* h, const ffgp_acq_tree_problem* p, doubl
 int ffgp_acq_optimize_stack_tree(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, double* Xq_dev, int Q, int steps,
                                  const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* ffgp_acq_optimize_stack_tree past FFGP_ACQ_MAX_N training points: the same loop LAUNCH PER STAGE (csrc/acq_staged_tree.hip on the
+   driver of csrc/acq_staged.hip), every step enqueued by this one call.  The arguments are ffgp_acq_optimize_stack_tree's, one for one
+   (trees[f] == NULL: member f is one radial library kernel, read from the member's own fields), and so are the semantics, field for
+   field and layout for layout: the per-point level, the coefficients, var_add_all, FFGP_ACQ_UCB / FFGP_ACQ_EI / FFGP_ACQ_UCB_VAR,
+   accumulate_grad, evaluate mode (steps = 0), state_dev [2 | 3, Q, D], trace, hist and grad; k_f(x, x) is taken through the tree (a
+   radial member: amp_f), and the loss gradient is da/dmean Gm - 2 da/dvar Gv - da/dvar S with S = sum_f on_f var_coef_f dk_f(x, x)/dx,
+   non-zero through linear leaves only.  An Adam state moves between this entry, ffgp_acq_optimize_stack_tree, ffgp_acq_optimize_tree
+   and ffgp_acq_optimize_stack_staged.  Limits: every n in 1..FFGP_ACQ_STAGED_MAX_N; F <= FFGP_ACQ_MAX_MEMBERS, one D <= FFGP_ACQ_MAX_D
+   for all members, d = 1, steps <= FFGP_ACQ_MAX_STEPS.  Per call L_f^-1 of every member is formed in handle workspace and the leaf
+   records are uploaded there, as ffgp_acq_optimize_stack_staged and ffgp_acq_optimize_stack_tree do.  Per step 5 + 2 F launches,
+   whatever Q, n and the leaf counts: K_s of all members through their trees, V_f = L_f^-1 K_s,f and B_f = L_f^-T V_f on the fp64 MFMA
+   GEMM, the column sums, the value (k_f(x, x), S and the acquisition), the input-gradient tiles -- which keep no derivative image: the
+   leaves of a row are evaluated again and the tree's reverse sweep runs per row -- and the owners' Adam update.  No atomics and no
+   order of summation that depends on timing or on the grid: a + b steps through state_dev equal a + b steps in one call bit for bit;
+   cutting Q into several calls can change the GEMM's tile choice and with it the last bits.  The loop stops enqueueing at the first
+   refused launch and returns that status.  FFGP_ERR_ARG, before anything is enqueued (Xq, state, trace, hist and grad untouched):
+   everything ffgp_acq_optimize_stack_tree refuses, with n outside 1..FFGP_ACQ_STAGED_MAX_N in place of its rule on n, and Q D beyond
+   INT_MAX.  Synchronous.
+   Workspace, in doubles, with np_f, Qp, C and DM as beside FFGP_ACQ_STAGED_MAX_N:
+       sum_f [ np_f^2  (L_f^-1)  +  3 n_f Qp  (K_s, V, B)  +  n_f^2 / 4 + 128 n_f + 16  (triangular inverse) ]
+       + F C Qp (2 + DM) + 3 Qp  (the chunk sums and the per-point values)  + Qp DM  (S)  + 28 F  (the leaf records, 224 bytes each)
+   -- 67 MiB for one member of 2048 points and Q = 500, 0.5 GiB for eight of them.                                              */
+int ffgp_acq_optimize_stack_tree_staged(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, double* Xq_dev, int Q,
+                                        int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev,
+                                        double* grad_dev);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another
