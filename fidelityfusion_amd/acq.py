@@ -15,7 +15,9 @@ mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip).
 Past the one-launch kernels' 256 training points, `staged=True` on `optimize_acqf` / `optimize_acqf_mf` keeps the loop on the device:
 launch per stage, every step enqueued by one library call (csrc/acq_staged.hip), for radial-kernel models of up to 2048 points; with
 `fuse_composed=True` as well, the same holds for SumKernel / ProductKernel models and stacks with such fidelities
-(csrc/acq_staged_tree.hip) -- the reference's cigp and AR on SumKernel(LinearKernel, MaternKernel) once a run has passed 256 points."""
+(csrc/acq_staged_tree.hip) -- the reference's cigp and AR on SumKernel(LinearKernel, MaternKernel) once a run has passed 256 points.
+`staged=True` on `optimize_acqf_nar` does the same for a NAR chain of radial-kernel models of up to 2048 points per fidelity
+(csrc/acq_staged_chain.hip)."""
 import inspect
 import math
 
@@ -154,14 +156,16 @@ def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001,
 
 
 def optimize_acqf_nar(models, data, X0, level=None, steps=10, lr=0.001, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12,
-                      accumulate_grad=False, return_best_only=True):
+                      accumulate_grad=False, return_best_only=True, staged=False):
     """The multi-fidelity drivers' acquisition optimiser (DMF_acq.py:226-262) on the posterior of NAR (FidelityFusion_Models/NAR.py:30-61):
     `models` is the NAR trainer's `gpr_list` (frozen `cigp`), data[0] = (x_0, y_0), data[f > 0] = the 'concat-f' set the trainer stored:
     inputs [x, y_low_mean] and y, possibly as the list [y, y_var] (`cigp.forward` ignores y_var; y[0] is used, as `optimize_acqf_mf`
     does).  Member f is model f's cached posterior with that model's 1 / beta added to its variance; member f > 0 is queried at
     [x, mean of member f - 1] and the model reports the mean and variance of the member a point stops at.  `level` (int or [Q]) is each
     start point's `to_fidelity` (None: the top level), so the drivers' loop over the fidelities is ONE call; acq, `accumulate_grad` and
-    the return value as in `optimize_acqf_mf`."""
+    the return value as in `optimize_acqf_mf`.  `staged=True` runs a chain of radial-kernel models with a fidelity of 257 ... 2048
+    points -- NAR's demo trains on 300 / 300 / 250 -- launch per stage inside one library call (`PosteriorChain.optimize_acquisition`,
+    csrc/acq_staged_chain.hip) instead of the per-step loop; a chain of up to 256 points per fidelity keeps the one-launch call."""
     if X0 is None:
         raise ValueError("optimize_acqf_nar needs the start points X0 [Q, D]")
     models = list(models)
@@ -174,5 +178,5 @@ def optimize_acqf_nar(models, data, X0, level=None, steps=10, lr=0.001, acq="ucb
         noise.append(float(m.log_beta.detach().exp().pow(-1)))
     chain = PosteriorChain(members)
     X, trace, hist, _ = chain.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
-                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad)
+                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad, staged=staged)
     return select_best(X0, trace, hist) if return_best_only else X

@@ -1,9 +1,12 @@
-// What the two launch-per-stage acquisition entries share (acq_staged.hip: members with one radial kernel; acq_staged_tree.hip: members
-// that may carry composed kernels): the tile shape, the argument structs, the chunk and level rules, and ONE host driver
-// (acq_staged_run, acq_staged.hip) -- the argument checks, the workspace carve-up, the zero-fill, the per-member ffgp_invalidate +
-// ffgp_trtri_impl prologue, the bias-correction table, the step loop with its two GEMMs per member, the column-sum kernel and the owner
-// kernel.  What an entry brings is its three stage launches: K_s, the value and the gradient tiles.
+// What the launch-per-stage acquisition entries share (acq_staged.hip: stacks of members with one radial kernel; acq_staged_tree.hip:
+// stacks whose members may carry composed kernels; acq_staged_chain.hip: the NAR chain): the tile shape, the argument structs, the chunk
+// and level rules, ONE host prologue (acq_staged_prepare, acq_staged.hip) -- the argument checks, the workspace carve-up, the zero-fill,
+// the per-member ffgp_invalidate + ffgp_trtri_impl, the bias-correction table --, the two GEMMs per member, the column-sum kernel and the
+// owner kernel.  The two stack entries also share their step loop (acq_staged_run) and bring its three stage launches: K_s, the value
+// and the gradient tiles.  The chain's members run in sequence, so it has a step loop of its own on the same prologue and stages.
 #pragma once
+#include <vector>
+
 #include "acq_tile.h"
 
 #define AS_T 256
@@ -46,6 +49,34 @@ struct AcqStagedStages {
   int (*value)(ffgp_handle* h, const AcqStagedArgs& a);
   int (*grad)(ffgp_handle* h, const AcqStagedArgs& a, dim3 tiles);
 };
+
+// What acq_staged_prepare leaves for a step loop: the kernels' arguments, each member's L^-1 in handle workspace, the Adam bias
+// corrections per step, and the host copy of the leaf records, which has to outlive the upload (acq_staged_finish waits).
+struct AcqStagedPlan {
+  AcqStagedArgs a;
+  const double* Linv[FFGP_ACQ_MAX_MEMBERS];
+  int np_of[FFGP_ACQ_MAX_MEMBERS];
+  std::vector<double> bc;      // [2 iters]
+  std::vector<AcqMemberTree> table;
+  double* extra;               // the entry's own `extra_doubles` behind everything else, or null
+  int iters, qt;               // max(steps, 1); Qp / AS_COLS
+};
+// The prologue of every staged loop: the argument checks (`chain`: the dimension rule is ffgp_acq_optimize_chain's -- members[0].D = D <=
+// FFGP_ACQ_MAX_D - 1 and D + 1 above it, the kernels' DM then holds D + 1 -- instead of one D for all), the workspace carve-up with
+// `images` [n][Qp] matrices per member, the zero-fill of L^-1 and the images, ffgp_invalidate + ffgp_trtri_impl per member, the
+// bias-correction table, the upload of the leaf records (`trees` non-null) and the filling of AcqStagedArgs.  FFGP_ERR_ARG is returned
+// before anything is enqueued.
+int acq_staged_prepare(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, int images, bool chain, size_t extra_doubles,
+                       double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev,
+                       double* grad_dev, AcqStagedPlan& pl);
+// the stages that are the same in every loop: V_f = L_f^-1 K_s,f and B_f = L_f^-T V_f (two clipped GEMMs), the column sums of members
+// f0 .. f0 + tiles.z - 1, step k's owner launch; and the wait that ends the call, which returns `rc` if that is a failure
+int as_solve_stage(ffgp_handle* h, const AcqStagedPlan& pl, int f);
+int as_col_stage(ffgp_handle* h, const AcqStagedArgs& a, dim3 tiles, int f0);
+int as_owner_stage(ffgp_handle* h, const AcqStagedPlan& pl, int k);
+int acq_staged_finish(ffgp_handle* h, int rc);
+
+// The step loop of the two stack entries: one launch per stage over all members (blockIdx.z is the member).
 // `trees` (the tree entry, which checks the trees itself): host array [F] as acq_run takes it -- member f's kernel is trees[f], a null
 // entry is a member with its own radial kernel -- and the members' leaf records are uploaded behind the rest of the workspace.
 int acq_staged_run(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, const AcqStagedStages& st, double* Xq_dev, int Q,

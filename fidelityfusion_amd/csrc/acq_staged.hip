@@ -19,8 +19,9 @@
 // four lanes' sums are added through LDS in the order 0..3.  The chunking is a function of n alone, no sum is taken in an order that
 // depends on Q, on the grid or on timing, and there are no atomics: what can differ between two ways of cutting Q is the GEMM's
 // tile choice alone.
-// The host driver, the column-sum kernel and the owner kernel also serve the entry for composed kernels (acq_staged_tree.hip) through
-// acq_staged_run (acq_staged.h), which brings its own stages 1, 4 and 5.
+// The step loop (acq_staged_run, acq_staged.h), the column-sum kernel and the owner kernel also serve the entry for composed kernels
+// (acq_staged_tree.hip), which brings its own stages 1, 4 and 5.  The host prologue (acq_staged_prepare), the GEMM stage, the column-sum
+// kernel and the owner kernel serve the chain's loop too (acq_staged_chain.hip), which runs its members in sequence.
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -58,10 +59,12 @@ __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_ks_kernel(AcqStagedArgs 
   }
 }
 
-// ---- 3. chunk sums of K_s^T alpha and |V|^2, per column
-__global__ __launch_bounds__(AS_T) void ffgp_acq_staged_col_kernel(AcqStagedArgs a) {
+// ---- 3. chunk sums of K_s^T alpha and |V|^2, per column, of member f0 + blockIdx.z (the stack loops: every member in one launch; the
+// chain loop: one member per launch)
+__global__ __launch_bounds__(AS_T) void ffgp_acq_staged_col_kernel(AcqStagedArgs a, int f0) {
   __shared__ double red[2][AS_LANES][AS_COLS];
-  const AcqStagedMember& mb = a.m[blockIdx.z];
+  const int f = f0 + blockIdx.z;
+  const AcqStagedMember& mb = a.m[f];
   const int n = mb.n, r0 = blockIdx.y * AS_ROWS;
   if (r0 >= n) return;
   const int rows = min(AS_ROWS, n - r0), tid = threadIdx.x, c = tid & 63, lane = tid >> 6;
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_col_kernel(AcqStagedArgs
     double s = 0.0;
 #pragma unroll
     for (int l = 0; l < AS_LANES; ++l) s += red[which][l][c];
-    (which ? a.pv : a.pm)[((size_t)blockIdx.z * a.nch + blockIdx.y) * a.Qp + q] = s;
+    (which ? a.pv : a.pm)[((size_t)f * a.nch + blockIdx.y) * a.Qp + q] = s;
   }
 }
 
@@ -214,32 +217,57 @@ static int as_grad_stage(ffgp_handle* h, const AcqStagedArgs& a, dim3 tiles) {
   return acq_by_dm(a.D, [&](auto dm) { return as_grad_launch<dm()>(h, a, tiles); });
 }
 
-// The driver of both staged entries (acq_staged.h).
-int acq_staged_run(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, const AcqStagedStages& st, double* Xq_dev, int Q,
-                   int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+// ---- the host side that every staged loop shares (acq_staged.h)
+int as_col_stage(ffgp_handle* h, const AcqStagedArgs& a, dim3 tiles, int f0) {
+  hipLaunchKernelGGL(ffgp_acq_staged_col_kernel, tiles, dim3(AS_T), 0, h->stream, a, f0);
+  return as_launched();
+}
+int as_owner_stage(ffgp_handle* h, const AcqStagedPlan& pl, int k) {
+  const size_t plane = (size_t)pl.a.Q * pl.a.D;
+  hipLaunchKernelGGL(ffgp_acq_staged_owner_kernel, dim3((unsigned)((plane + AS_T - 1) / AS_T)), dim3(AS_T), 0, h->stream, pl.a, k,
+                     k == pl.iters - 1 ? 1 : 0, pl.bc[2 * k], pl.bc[2 * k + 1]);
+  return as_launched();
+}
+int as_solve_stage(ffgp_handle* h, const AcqStagedPlan& pl, int f) {
+  const AcqStagedMember& m = pl.a.m[f];
+  const int Q = pl.a.Q, Qp = pl.a.Qp;
+  // V = L^-1 K_s (L^-1 lower: k ends at the tile row), B = L^-T V (k starts at it)
+  int rc = ffgp_gemm_launch(h, OP_KMAJOR, OP_MNMAJOR, TILES_FULL, 0, pl.Linv[f], pl.np_of[f], m.Ks, Qp, m.V, Qp, m.n, Q, m.n, 1.0, 0.0, TRI_HI_I);
+  if (rc == FFGP_OK)
+    rc = ffgp_gemm_launch(h, OP_MNMAJOR, OP_MNMAJOR, TILES_FULL, 0, pl.Linv[f], pl.np_of[f], m.V, Qp, m.B, Qp, m.n, Q, m.n, 1.0, 0.0, TRI_LO_I);
+  return rc;
+}
+
+int acq_staged_prepare(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, int images, bool chain, size_t extra_doubles,
+                       double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev,
+                       double* grad_dev, AcqStagedPlan& pl) {
   // the argument classes acq_run refuses (acq_stack.hip), with these entries' own limit on n
   if (!h || !s || !Xq_dev || !trace_dev || Q <= 0 || steps < 0 || steps > FFGP_ACQ_MAX_STEPS || step0 < 0) return FFGP_ERR_ARG;
   if (steps > 0 && (!opt || !state_dev)) return FFGP_ERR_ARG;
   if (s->F < 1 || s->F > FFGP_ACQ_MAX_MEMBERS || !s->members) return FFGP_ERR_ARG;
   if (s->acq != FFGP_ACQ_UCB && s->acq != FFGP_ACQ_EI && s->acq != FFGP_ACQ_UCB_VAR) return FFGP_ERR_ARG;
   const int F = s->F, D = s->members[0].D;
+  if (chain && D > FFGP_ACQ_MAX_D - 1) return FFGP_ERR_ARG;      // the members above the first take [x, mean below]: D + 1 inputs
   for (int f = 0; f < F; ++f) {
     const ffgp_acq_member& p = s->members[f];
     const bool tree = trees && trees[f];      // such a member carries no w_dev / amp_dev / kfun of its own
     if (!p.X_dev || !p.L_dev || !p.alpha_dev || (!tree && (!p.w_dev || !p.amp_dev))) return FFGP_ERR_ARG;
-    if (p.n < 1 || p.n > FFGP_ACQ_STAGED_MAX_N || p.D < 1 || p.D > FFGP_ACQ_MAX_D || p.D != D || p.d != 1) return FFGP_ERR_ARG;
+    if (p.n < 1 || p.n > FFGP_ACQ_STAGED_MAX_N || p.D < 1 || p.D > FFGP_ACQ_MAX_D || p.D != ((chain && f > 0) ? D + 1 : D) || p.d != 1)
+      return FFGP_ERR_ARG;
     if (p.ldl < p.n || p.ldl > INT_MAX) return FFGP_ERR_ARG;
     if (!tree && (p.kfun < FFGP_KFUN_SE || p.kfun > FFGP_KFUN_RQ)) return FFGP_ERR_ARG;      // (the linear kernel's k(x, x) depends on x)
   }
   if ((size_t)Q * D > (size_t)INT_MAX || Q > INT_MAX - AS_COLS) return FFGP_ERR_ARG;
   FFGP_HIP(hipSetDevice(h->device));
-  const int iters = steps > 0 ? steps : 1;
-  const int DM = acq_by_dm(D, [](auto dm) { return (int)dm(); });
-  const int Qp = ffgp_round_up(Q, AS_COLS), qt = Qp / AS_COLS;
-  const size_t imgs = (size_t)st.images;
+  AcqStagedArgs& a = pl.a;
+  pl.iters = steps > 0 ? steps : 1;
+  const int DM = acq_by_dm(chain ? D + 1 : D, [](auto dm) { return (int)dm(); });
+  const int Qp = ffgp_round_up(Q, AS_COLS);
+  pl.qt = Qp / AS_COLS;
+  const size_t imgs = (size_t)images;
   // workspace, in doubles (the arithmetic beside FFGP_ACQ_STAGED_MAX_N in ffgp.h):
   //   [L_f^-1 (np_f x np_f) | the images of member f (K_s, DK, V, B: 4 n_f Qp; without DK 3 n_f Qp), f = 0..F-1 | TRTRI scratch per member
-  //    | pm, pv | av, gm, gv | part | trees: self (Qp DM), the leaf records]
+  //    | pm, pv | av, gm, gv | part | trees: self (Qp DM), the leaf records | the entry's own extra doubles]
   size_t xd = 0, md = 0, td = 0;
   int nch = 0;
   for (int f = 0; f < F; ++f) {
@@ -250,19 +278,20 @@ int acq_staged_run(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* co
     nch = max(nch, (int)((n + AS_ROWS - 1) / AS_ROWS));
   }
   const size_t pd = (size_t)F * nch * Qp, sd = trees ? (size_t)Qp * DM : 0;
-  FFGP_CHECK(ffgp_ensure_ws(h, (xd + md + td + 2 * pd + 3 * (size_t)Qp + pd * DM + sd) * sizeof(double) + (trees ? F * sizeof(AcqMemberTree) : 0)));
+  // (the leaf records are 224 bytes each: a multiple of a double, so what follows them stays aligned)
+  static_assert(sizeof(AcqMemberTree) % sizeof(double) == 0, "the leaf records end on a double");
+  FFGP_CHECK(ffgp_ensure_ws(h, (xd + md + td + 2 * pd + 3 * (size_t)Qp + pd * DM + sd + extra_doubles) * sizeof(double) +
+                                   (trees ? F * sizeof(AcqMemberTree) : 0)));
   double* X = h->ws;
   double* M = X + xd;
   double* T = M + md;
-  AcqStagedArgs a;
   a.pm = T + td; a.pv = a.pm + pd; a.av = a.pv + pd; a.gm = a.av + Qp; a.gv = a.gm + Qp; a.part = a.gv + Qp;
   a.self = trees ? a.part + pd * DM : nullptr;
   AcqMemberTree* const table_dev = trees ? reinterpret_cast<AcqMemberTree*>(a.part + pd * DM + sd) : nullptr;
   a.tab = table_dev;
+  pl.extra = extra_doubles ? reinterpret_cast<double*>(reinterpret_cast<char*>(a.part + pd * DM + sd) + (trees ? F * sizeof(AcqMemberTree) : 0)) : nullptr;
   // zeros: L^-1 above the diagonal and in its padding, and the columns Q..Qp-1 of V and B, which no GEMM writes
   FFGP_CHECK(ffgp_zero_async(h, X, (xd + md) * sizeof(double)));
-  const double* Linv[FFGP_ACQ_MAX_MEMBERS];
-  int np_of[FFGP_ACQ_MAX_MEMBERS];
   for (int f = 0; f < F; ++f) {
     const ffgp_acq_member& p = s->members[f];
     const int n = p.n, np = ffgp_round_up(n, 16);
@@ -277,7 +306,7 @@ int acq_staged_run(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* co
     }
     m.clamp = p.clamp_min; m.rinv = (p.kparam != 0.0) ? 1.0 / p.kparam : 1.0; m.var_add = p.var_add_all;
     m.mean_coef = p.mean_coef; m.var_coef = p.var_coef; m.n = n; m.kfun = p.kfun;
-    Linv[f] = X; np_of[f] = np;
+    pl.Linv[f] = X; pl.np_of[f] = np;
     // the handle's inverted diagonal blocks are rebuilt from each factor, for acq_run's reason: a trajectory depends on the factors alone
     ffgp_invalidate(h);
     FFGP_CHECK(ffgp_trtri_impl(h, p.L_dev, n, (int)p.ldl, X, np, T));
@@ -286,44 +315,46 @@ int acq_staged_run(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* co
     T += (size_t)n * n / 4 + (size_t)n * FFGP_NB + 16;
   }
   for (int f = F; f < FFGP_ACQ_MAX_MEMBERS; ++f) a.m[f] = a.m[0];      // never read: every member loop ends at F
-  std::vector<double> bc(2 * (size_t)iters, 1.0);
-  ffgp_adam_bc_table(opt, step0, steps, bc.data());
-  std::vector<AcqMemberTree> table(trees ? F : 0);      // (lives until the wait below)
+  pl.bc.assign(2 * (size_t)pl.iters, 1.0);
+  ffgp_adam_bc_table(opt, step0, steps, pl.bc.data());
+  pl.table.resize(trees ? F : 0);      // (lives until the caller's wait)
   if (trees) {
-    for (int f = 0; f < F; ++f) table[f] = acq_member_tree(s->members[f], trees[f]);
-    FFGP_HIP(hipMemcpyAsync(table_dev, table.data(), table.size() * sizeof(AcqMemberTree), hipMemcpyHostToDevice, h->stream));
+    for (int f = 0; f < F; ++f) pl.table[f] = acq_member_tree(s->members[f], trees[f]);
+    FFGP_HIP(hipMemcpyAsync(table_dev, pl.table.data(), pl.table.size() * sizeof(AcqMemberTree), hipMemcpyHostToDevice, h->stream));
   }
   a.level = s->level_dev;
   a.Xq = Xq_dev; a.state = state_dev; a.trace = trace_dev; a.hist = hist_dev; a.grad = grad_dev;
   a.F = F; a.D = D; a.DM = DM; a.Q = Q; a.Qp = Qp; a.nch = nch; a.steps = steps; a.acq = s->acq; a.accumulate = s->accumulate_grad ? 1 : 0;
   a.var_floor = s->var_floor; a.kappa = s->kappa; a.xi = s->xi; a.f_best = s->f_best;
   a.lr = opt ? opt->lr : 0.0; a.b1 = opt ? opt->beta1 : 0.0; a.b2 = opt ? opt->beta2 : 0.0; a.eps = opt ? opt->eps : 0.0;
+  return FFGP_OK;
+}
 
-  const dim3 tiles(qt, nch, F);
-  const size_t plane = (size_t)Q * D;
-  int rc = FFGP_OK;
-  for (int k = 0; k < iters; ++k) {
-    AS_STAGE(st.ks(h, a, tiles));
-    for (int f = 0; f < F && rc == FFGP_OK; ++f) {
-      const AcqStagedMember& m = a.m[f];
-      // V = L^-1 K_s (L^-1 lower: k ends at the tile row), B = L^-T V (k starts at it)
-      rc = ffgp_gemm_launch(h, OP_KMAJOR, OP_MNMAJOR, TILES_FULL, 0, Linv[f], np_of[f], m.Ks, Qp, m.V, Qp, m.n, Q, m.n, 1.0, 0.0, TRI_HI_I);
-      if (rc == FFGP_OK)
-        rc = ffgp_gemm_launch(h, OP_MNMAJOR, OP_MNMAJOR, TILES_FULL, 0, Linv[f], np_of[f], m.V, Qp, m.B, Qp, m.n, Q, m.n, 1.0, 0.0, TRI_LO_I);
-    }
-    if (rc != FFGP_OK) break;
-    hipLaunchKernelGGL(ffgp_acq_staged_col_kernel, tiles, dim3(AS_T), 0, h->stream, a);
-    AS_STAGE(as_launched());
-    AS_STAGE(st.value(h, a));
-    AS_STAGE(st.grad(h, a, tiles));
-    hipLaunchKernelGGL(ffgp_acq_staged_owner_kernel, dim3((unsigned)((plane + AS_T - 1) / AS_T)), dim3(AS_T), 0, h->stream, a, k, k == iters - 1 ? 1 : 0,
-                       bc[2 * k], bc[2 * k + 1]);
-    AS_STAGE(as_launched());
-  }
+int acq_staged_finish(ffgp_handle* h, int rc) {
   // nothing waited inside the loop; the call itself is synchronous, as the one-launch entries are
   const hipError_t e = hipStreamSynchronize(h->stream);
   if (rc != FFGP_OK) return rc;
   return e == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
+}
+
+// The step loop of the two stack entries (acq_staged.h).
+int acq_staged_run(ffgp_handle* h, const ffgp_acq_stack* s, const ffgp_ktree* const* trees, const AcqStagedStages& st, double* Xq_dev, int Q,
+                   int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev) {
+  AcqStagedPlan pl;
+  FFGP_CHECK(acq_staged_prepare(h, s, trees, st.images, false, 0, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev, pl));
+  const AcqStagedArgs& a = pl.a;
+  const dim3 tiles(pl.qt, a.nch, a.F);
+  int rc = FFGP_OK;
+  for (int k = 0; k < pl.iters; ++k) {
+    AS_STAGE(st.ks(h, a, tiles));
+    for (int f = 0; f < a.F && rc == FFGP_OK; ++f) rc = as_solve_stage(h, pl, f);
+    if (rc != FFGP_OK) break;
+    AS_STAGE(as_col_stage(h, a, tiles, 0));
+    AS_STAGE(st.value(h, a));
+    AS_STAGE(st.grad(h, a, tiles));
+    AS_STAGE(as_owner_stage(h, pl, k));
+  }
+  return acq_staged_finish(h, rc);
 }
 
 int ffgp_acq_optimize_stack_staged(ffgp_handle* h, const ffgp_acq_stack* s, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,

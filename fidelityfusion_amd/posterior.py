@@ -432,8 +432,8 @@ class PosteriorStack:
         n <= 2048), runs the staged loop for composed kernels (ffgp_acq_optimize_stack_tree_staged, csrc/acq_staged_tree.hip), with
         the same return values, `state` contract and state["staged"] = True; a stack without a composed member takes the radial
         staged call, and one that takes a one-launch call keeps it bit for bit unless `staged="force"`.  `staged=True` alone leaves
-        a stack with a composed member on the per-step loop.  Out of the staged calls' scope, with its routing unchanged: the NAR
-        chain (`PosteriorChain`)."""
+        a stack with a composed member on the per-step loop.  The NAR chain (`PosteriorChain`) has a staged call of its own
+        (ffgp_acq_optimize_chain_staged), behind the same keyword."""
         if staged not in (False, True, "force"):
             raise ValueError("staged must be False, True or 'force', got %r" % (staged,))
         acq = str(acq).lower()
@@ -643,36 +643,67 @@ class PosteriorChain(PosteriorStack):
         return mean, var
 
     def acq_staged_ok(self, X0):
-        """never: the launch-per-stage call serves stacks, not the chain"""
+        """never: the stacks' launch-per-stage calls do not serve the chain, which has its own (`acq_chain_staged_ok`)"""
         return False
 
     def acq_tree_staged_ok(self, X0):
         """never, for the same reason"""
         return False
 
+    def _acq_starts_ok(self, X0):
+        return (isinstance(X0, torch.Tensor) and X0.is_cuda and X0.device == self.dev and X0.dtype == torch.float64 and X0.dim() == 2
+                and X0.shape[0] >= 1 and X0.shape[1] == self.D)
+
+    def _acq_members_ok(self, nmax):
+        def member_ok(m):
+            return (m.tree is None and 0 <= int(m.kfun[0]) < FFGP_KFUN_LINEAR and m.d == 1 and 1 <= m.n <= nmax)
+        return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D - 1 and all(member_ok(m) for m in self.members)
+
     def acq_fusable(self, X0):
         """whether `optimize_acquisition` from X0 takes the one-launch call (ffgp_acq_optimize_chain): at most 8 members, each ONE
         radial library kernel with one output and n <= 256, D + 1 <= 16, the start points fp64 [Q, D] on the chain's GPU"""
-        def member_ok(m):
-            return (m.tree is None and 0 <= int(m.kfun[0]) < FFGP_KFUN_LINEAR and m.d == 1 and 1 <= m.n <= _lib.FFGP_ACQ_MAX_N)
-        return (self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D - 1 and all(member_ok(m) for m in self.members)
-                and isinstance(X0, torch.Tensor) and X0.is_cuda and X0.device == self.dev and X0.dtype == torch.float64 and X0.dim() == 2
-                and X0.shape[0] >= 1 and X0.shape[1] == self.D)
+        return self._acq_members_ok(_lib.FFGP_ACQ_MAX_N) and self._acq_starts_ok(X0)
+
+    def acq_chain_staged_ok(self, X0):
+        """whether `optimize_acquisition(..., staged=True)` from X0 may take the launch-per-stage call (ffgp_acq_optimize_chain_staged):
+        `acq_fusable`'s conditions with n up to FFGP_ACQ_STAGED_MAX_N = 2048 in place of 256"""
+        return self._acq_members_ok(_lib.FFGP_ACQ_STAGED_MAX_N) and self._acq_starts_ok(X0)
+
+    def _acq_route(self, X0, fuse_composed, staged):
+        """(the C entry's caller or None for the per-step loop, whether it is the launch-per-stage call)"""
+        one = self._acq_call if self.acq_fusable(X0) else None
+        if staged and (staged == "force" or one is None) and self.acq_chain_staged_ok(X0):
+            return self._acq_call_chain_staged, True
+        return one, False
 
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12, betas=(0.9, 0.999),
-                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None):
+                             eps=1e-8, level=None, var_adds=None, accumulate_grad=False, state=None, staged=False):
         """`PosteriorStack.optimize_acquisition` on the chain's posterior: the same arguments, the same return tuple
         (X, trace, hist, state).  ONE kernel launch (ffgp_acq_optimize_chain, csrc/acq_chain.hip) when `acq_fusable(X0)` and
         steps <= 4096 -- only the member a point stops at pays for the triangular solves -- otherwise the per-step loop on
-        `predict_diff` and torch.optim.Adam (composed kernels, n > 256, D + 1 > 16, more than 8 members); state["fused"] says which."""
+        `predict_diff` and torch.optim.Adam (composed kernels, n > 256, D + 1 > 16, more than 8 members); state["fused"] says which.
+        `staged=True` opts members beyond n <= 256 in: a chain that is not `acq_fusable(X0)` but `acq_chain_staged_ok(X0)` (radial
+        members of up to 2048 points) runs the loop launch per stage inside ONE library call (ffgp_acq_optimize_chain_staged,
+        csrc/acq_staged_chain.hip: levels, `var_adds`, all three acquisitions and `accumulate_grad` as in the one-launch call, whose
+        `state` it continues and hands on); state["staged"] = True and state["fused"] = False then.  An `acq_fusable` chain takes the
+        one-launch call exactly as without the keyword; `staged="force"` sends it to the staged call too (tests,
+        tools/acq_chain_staged_bench.py).  Composed-kernel members, more than 8 members, D + 1 > 16 and n > 2048 keep the per-step loop."""
         return super().optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
-                                            betas=betas, eps=eps, level=level, var_adds=var_adds, accumulate_grad=accumulate_grad, state=state)
+                                            betas=betas, eps=eps, level=level, var_adds=var_adds, accumulate_grad=accumulate_grad, state=state,
+                                            staged=staged)
 
     def _acq_call(self, va, lv, acq_fields, accumulate_grad, call):
         keep = []
         c = _lib.AcqChain(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
                           accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
         check(lib.ffgp_acq_optimize_chain(self.members[0]._h(), C.byref(c), *call), "ffgp_acq_optimize_chain")
+
+    def _acq_call_chain_staged(self, va, lv, acq_fields, accumulate_grad, call):
+        """the C entry of the chain's launch-per-stage call: ffgp_acq_optimize_chain's arguments"""
+        keep = []
+        c = _lib.AcqChain(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
+                          accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
+        check(lib.ffgp_acq_optimize_chain_staged(self.members[0]._h(), C.byref(c), *call), "ffgp_acq_optimize_chain_staged")
 
 
 class PosteriorCache:

@@ -994,6 +994,38 @@ typedef struct {
 int ffgp_acq_optimize_chain(ffgp_handle* h, const ffgp_acq_chain* c, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
                             double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* ffgp_acq_optimize_chain past FFGP_ACQ_MAX_N training points: the same loop LAUNCH PER STAGE (csrc/acq_staged_chain.hip on the
+   prologue and the shared stages of csrc/acq_staged.hip), every step enqueued by this one call -- NAR's own demo trains on 300 / 300 /
+   250 points (FidelityFusion_Models/NAR.py:119-128).  The arguments are ffgp_acq_optimize_chain's, one for one, and so are the model,
+   the outputs, the state layout [2 | 3, Q, D], accumulate_grad, the Adam arithmetic, evaluate mode (steps = 0) and the handling of
+   level_dev (read as min(level, F - 1); a negative level stops at no member: value 0, gradient 0, the point does not move): an Adam
+   state moves between the two entries.  Limits: every n in 1..FFGP_ACQ_STAGED_MAX_N; F <= FFGP_ACQ_MAX_MEMBERS, members[0].D in
+   1..FFGP_ACQ_MAX_D - 1, members[f > 0].D = members[0].D + 1, d = 1, radial kfun, both coefficients 1.0, steps <= FFGP_ACQ_MAX_STEPS.
+   Per call L_f^-1 of every member is formed in handle workspace as ffgp_acq_optimize_stack_staged forms it, and one small kernel over
+   level_dev takes the census of the levels -- tops = the set of members at which some point stops, top = the highest of them --,
+   read back once (4 bytes) before the step loop; with level_dev NULL tops = {F - 1} and nothing is read back.  Nothing is waited for
+   inside the step loop.  The members of a chain run in sequence, so a step is, with the member index an argument of each launch:
+       forward, f = 0..top:  K_s,f and its derivative factors on z_f = [x, m_{f-1}(x)] (the mean fed forward is the chunk sums added in
+                             chunk order, the expression that reports it);  only for f in tops, V_f = L_f^-1 K_s,f and
+                             B_f = L_f^-T V_f on the fp64 MFMA GEMM;  the column sums of K_s,f^T alpha_f and |V_f|^2
+       the acquisition value on the mean and the variance amp_f - |V_f|^2 + var_add_all_f of the member each point stops at
+       reverse, f = top..0:  the input-gradient tiles of member f -- upstream da/dmean alpha_i - 2 da/dvar B_iq for the points that stop
+                             at f, -gu alpha_i for those that stop above it (gu = d(-a)/dm_f, member f + 1's partials of its last
+                             input summed in chunk order), an exact 0 for the others
+       the owners' sum over (member, chunk) of the D coordinates of x, the outputs and the Adam update
+   -- 3 (top + 1) + 2 |tops| + 2 launches per step whatever Q and n: 13 for one level of a three-member chain.  No atomics and no
+   order of summation that depends on Q, on timing or on the grid: a + b steps through state_dev equal a + b steps in one call bit for
+   bit, and level = k everywhere is the chain cut after member k, bit for bit; cutting Q into several calls can change the GEMM's tile
+   choice and with it the last bits.  The loop stops enqueueing at the first refused launch and returns that status.  FFGP_ERR_ARG,
+   before anything is enqueued (Xq, state, trace, hist and grad untouched): everything ffgp_acq_optimize_chain refuses, with n outside
+   1..FFGP_ACQ_STAGED_MAX_N in place of its rule on n, and Q D beyond INT_MAX.  Synchronous.
+   Workspace, in doubles, with np_f, Qp and C as beside FFGP_ACQ_STAGED_MAX_N and DM = 2, 8 or 16 (the first that holds D + 1):
+       sum_f [ np_f^2  (L_f^-1)  +  4 n_f Qp  (K_s, its derivative factors, V, B)  +  n_f^2 / 4 + 128 n_f + 16  (triangular inverse) ]
+       + F C Qp (2 + DM) + 3 Qp  (the chunk sums and the per-point values)  + 1  (the census word)
+   -- ffgp_acq_optimize_stack_staged's figure for the same members: 75 MiB for one member of 2048 points and Q = 500.               */
+int ffgp_acq_optimize_chain_staged(ffgp_handle* h, const ffgp_acq_chain* c, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
+                                   double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* The single-posterior loop of ffgp_acq_optimize on a posterior whose kernel is a COMPOSITION -- the reference's own
    Bayesian-optimisation model runs on SumKernel(LinearKernel(1), MaternKernel(1)) (Bayesian_optimization/cigp.py:119; cigp_v10.py:81;
    two_fidelity_models/ResGP.py:25, AR_autoRegression.py:31) -- in ONE launch (csrc/acq_tree.hip).  `tree`: 2-4 leaves in the canonical

@@ -101,6 +101,26 @@ def _check_diag_barriers_one(asm, name):
     return bars
 
 
+def private_segments(src, name_substr):
+    """{kernel: .private_segment_fixed_size} of the kernels of translation unit `src` whose name contains `name_substr`, from the
+    code-object metadata in the assembly: 0 means the kernel keeps no scratch (no spilled register, no array left in private memory)"""
+    asm = device_asm(src)
+    sizes = {}
+    for m in re.finditer(r"\.name:\s+(\S+)\n(?:\s+\.\w+:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", asm):
+        if name_substr in m.group(1) and not m.group(1).endswith(".kd"):
+            sizes[m.group(1)] = int(m.group(2))
+    return sizes
+
+
+def check_acq_staged_chain_no_scratch():
+    """the chain's staged kernels (census, K_s x 3, value, gradient x 3): every one without a private segment"""
+    sizes = private_segments("acq_staged_chain.hip", "ffgp_acq_staged_chain_")
+    assert len(sizes) == 8, sorted(sizes)
+    assert all(v == 0 for v in sizes.values()), sizes
+    return sizes
+
+
 if __name__ == "__main__":
     print("ffgp_potrf_diag128_v4: barriers behind an LDS drain:", check_diag_barriers())
     print("sb2st_chase: counter stores behind an explicit vmcnt(0):", check_chase_publish())
+    print("acq_staged_chain.hip: private segment sizes:", check_acq_staged_chain_no_scratch())
