@@ -11,7 +11,9 @@ drivers' MF_BayesianOptimization/Discrete/DMF_acq.py:226-262 -- every fidelity l
 with `fuse_composed=True` also when fidelities run on SumKernel / ProductKernel trees, the reference's own
 SumKernel(LinearKernel, MaternKernel) of its two-fidelity AR and ResGP (csrc/acq_stack_tree.hip).
 `optimize_acqf_nar` is that loop on NAR (FidelityFusion_Models/NAR.py:30-61), whose upper fidelities take the lower fidelity's predicted
-mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip).
+mean as an input -- one launch as well (`PosteriorChain`, csrc/acq_chain.hip); with `fuse_composed=True` also when fidelities run on
+SumKernel / ProductKernel trees, the reference's own SumKernel(LinearKernel, MaternKernel) of its two-fidelity NAR
+(csrc/acq_chain_tree.hip; up to 256 points per fidelity).
 Past the one-launch kernels' 256 training points, `staged=True` on `optimize_acqf` / `optimize_acqf_mf` keeps the loop on the device:
 launch per stage, every step enqueued by one library call (csrc/acq_staged.hip), for radial-kernel models of up to 2048 points; with
 `fuse_composed=True` as well, the same holds for SumKernel / ProductKernel models and stacks with such fidelities
@@ -156,7 +158,7 @@ def optimize_acqf_mf(models, data, X0, rho=None, level=None, steps=10, lr=0.001,
 
 
 def optimize_acqf_nar(models, data, X0, level=None, steps=10, lr=0.001, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12,
-                      accumulate_grad=False, return_best_only=True, staged=False):
+                      accumulate_grad=False, return_best_only=True, staged=False, fuse_composed=False):
     """The multi-fidelity drivers' acquisition optimiser (DMF_acq.py:226-262) on the posterior of NAR (FidelityFusion_Models/NAR.py:30-61):
     `models` is the NAR trainer's `gpr_list` (frozen `cigp`), data[0] = (x_0, y_0), data[f > 0] = the 'concat-f' set the trainer stored:
     inputs [x, y_low_mean] and y, possibly as the list [y, y_var] (`cigp.forward` ignores y_var; y[0] is used, as `optimize_acqf_mf`
@@ -165,7 +167,10 @@ def optimize_acqf_nar(models, data, X0, level=None, steps=10, lr=0.001, acq="ucb
     start point's `to_fidelity` (None: the top level), so the drivers' loop over the fidelities is ONE call; acq, `accumulate_grad` and
     the return value as in `optimize_acqf_mf`.  `staged=True` runs a chain of radial-kernel models with a fidelity of 257 ... 2048
     points -- NAR's demo trains on 300 / 300 / 250 -- launch per stage inside one library call (`PosteriorChain.optimize_acquisition`,
-    csrc/acq_staged_chain.hip) instead of the per-step loop; a chain of up to 256 points per fidelity keeps the one-launch call."""
+    csrc/acq_staged_chain.hip) instead of the per-step loop; a chain of up to 256 points per fidelity keeps the one-launch call.
+    `fuse_composed=True` runs the loop in one launch also when models carry composed kernels (SumKernel / ProductKernel trees of 2-4
+    library kernels, LinearKernel included; csrc/acq_chain_tree.hip) and every fidelity has at most 256 points; by default such a chain
+    takes the per-step loop, and so it does past 256 points whatever the keywords say (the staged call serves radial chains only)."""
     if X0 is None:
         raise ValueError("optimize_acqf_nar needs the start points X0 [Q, D]")
     models = list(models)
@@ -178,5 +183,6 @@ def optimize_acqf_nar(models, data, X0, level=None, steps=10, lr=0.001, acq="ucb
         noise.append(float(m.log_beta.detach().exp().pow(-1)))
     chain = PosteriorChain(members)
     X, trace, hist, _ = chain.optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
-                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad, staged=staged)
+                                                   level=level, var_adds=noise, accumulate_grad=accumulate_grad, staged=staged,
+                                                   fuse_composed=fuse_composed)
     return select_best(X0, trace, hist) if return_best_only else X

@@ -1,12 +1,12 @@
 // What the acquisition optimisers' kernels share (acq.hip: one frozen posterior; acq_stack.hip: a stack of them; acq_tree.hip: one
 // posterior on a composed kernel; acq_chain.hip: a chain of them, each fed the mean of the one below; acq_stack_tree.hip: a stack whose
-// members may carry composed kernels): a 256-thread
+// members may carry composed kernels; acq_chain_tree.hip: such a chain): a 256-thread
 // workgroup owns 16 query points, K_s / V / B live in LDS as [np][16] images, and V = L^-1 K_s, B = L^-T V are v_mfma_f64_16x16x4_f64
 // block chains whose A operand, L^-1, is read from global memory / L2 with one block of prefetch.  Every stage that is the same in its
 // callers stands here once, as a __device__ __forceinline__ function of thread (rg = tid >> 4, j = tid & 15) on query column j: the
 // member load, the squared distance, the row-group reduction, the two chain passes, the acquisition value, the owner thread's
 // prologue, step and write-back, and the launch.  What differs in substance -- the K_s row loop, the gradient pass, the loop over
-// members or leaves -- stays in the five files.  The host side exists once too: acq_run (acq_stack.hip) serves every entry, a single
+// members or leaves -- stays in the six files.  The host side exists once too: acq_run (acq_stack.hip) serves every entry, a single
 // posterior as the stack of one member.
 #pragma once
 #include <type_traits>
@@ -328,12 +328,14 @@ struct AcqTrees {
 
 // One driver (acq_run, acq_stack.hip) for every entry.
 // Checks the call, forms every member's L^-1 and the bias-correction table in handle workspace, launches through `launch` and waits.
-// `trees` (ffgp_acq_optimize_tree and ffgp_acq_optimize_stack_tree, which check the trees themselves): host array [F]; member f's kernel
+// `trees` (ffgp_acq_optimize_tree, ffgp_acq_optimize_stack_tree and ffgp_acq_optimize_chain_tree, which check the trees themselves): host array [F]; member f's kernel
 // is the composition trees[f], so the member carries no w_dev / amp_dev / kfun of its own and those three checks are skipped; a null
 // entry is a member with its own radial kernel.  It is handed on to `launch`.  `leaf_table`: the members' AcqMemberTree records are
 // uploaded behind the bias corrections and handed on as well.
-// `chain` (ffgp_acq_optimize_chain only): the per-member dimension rule is members[0].D = D <= FFGP_ACQ_MAX_D - 1 and D + 1 above it,
-// instead of one D for all; AcqLoop.D stays the D of the query points.
+// `chain` (ffgp_acq_optimize_chain and ffgp_acq_optimize_chain_tree): the per-member dimension rule is members[0].D = D <=
+// FFGP_ACQ_MAX_D - 1 and D + 1 above it, instead of one D for all; AcqLoop.D stays the D of the query points.  The three compose
+// (ffgp_acq_optimize_chain_tree passes all of them): the dimension rule applies to a member with a tree as to any other, the radial
+// checks are skipped for it, and a leaf record holds pointers only -- the row length D_f of w and centre is the kernel's to apply.
 typedef int (*acq_launch_fn)(ffgp_handle* h, const AcqStackArgs& a, int grid, const AcqTrees& t);
 int acq_run(ffgp_handle* h, const ffgp_acq_stack* s, acq_launch_fn launch, double* Xq_dev, int Q, int steps, const ffgp_adam* opt, double* state_dev,
             long step0, double* trace_dev, double* hist_dev, double* grad_dev, const ffgp_ktree* const* trees = nullptr, bool chain = false,

@@ -229,6 +229,62 @@ int main() {
     EXPECT(ffgp_acq_optimize_chain(fake, &chn, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     chn.members = nullptr;
     EXPECT(ffgp_acq_optimize_chain(fake, &chn, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    // the chain entry for members with composed kernels: the coefficients and the trees are checked before the driver, which then
+    // applies the chain's D / D + 1 rule and skips the radial checks of the members that have a tree
+    {
+      chn.members = mem; mem[0].D = 1; mem[1].D = 2;
+      ffgp_kdesc lf[4];
+      std::memset(lf, 0, sizeof lf);
+      for (ffgp_kdesc& k : lf) { k.kfun = FFGP_KFUN_SE; k.w_dev = &x; k.amp_dev = &x; k.kparam = 1.0; }
+      lf[0].kfun = FFGP_KFUN_LINEAR;
+      ffgp_ktree tr;
+      std::memset(&tr, 0, sizeof tr);
+      tr.n_leaves = 2; tr.op[0] = FFGP_KOP_SUM; tr.leaf = lf;
+      const ffgp_ktree* trees[2] = {nullptr, &tr};      // member 0 on its own radial kernel, member 1 on the tree
+      EXPECT(ffgp_acq_optimize_chain_tree(nullptr, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, nullptr, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, nullptr, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, nullptr, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, nullptr, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, nullptr, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, nullptr, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, -1, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      chn.F = FFGP_ACQ_MAX_MEMBERS + 1;      // (two trees, two members: the count is refused before any is read)
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      chn.F = 0;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      chn.F = 2; mem[1].var_coef = 0.5;      // a chain member has no weight
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].var_coef = 1.0; mem[1].D = 1;   // the second member, tree or not, must take D + 1 inputs
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].D = FFGP_ACQ_MAX_D; mem[1].D = FFGP_ACQ_MAX_D + 1;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].D = 1; mem[1].D = 2; tr.n_leaves = 1;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.n_leaves = 5;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.n_leaves = 4; tr.shape = 2;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.shape = FFGP_TREE_BALANCED; tr.op[2] = 2;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.op[2] = FFGP_KOP_PRODUCT; lf[3].kfun = FFGP_KFUN_LINEAR + 1;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      lf[3].kfun = FFGP_KFUN_RQ; lf[2].w_dev = nullptr;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      lf[2].w_dev = &x; lf[0].amp_dev = nullptr;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      lf[0].amp_dev = &x; tr.leaf = nullptr;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.leaf = lf; mem[0].w_dev = nullptr;      // the member without a tree needs its own kernel ...
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].w_dev = &x; mem[0].kfun = FFGP_KFUN_LINEAR;      // ... a radial one
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].kfun = FFGP_KFUN_SE; mem[1].w_dev = nullptr; mem[1].amp_dev = nullptr; mem[1].n = 0;      // the one with a tree does not: refused for n
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].w_dev = mem[1].amp_dev = &x; mem[1].n = 4; chn.members = nullptr;
+      EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+    }
     mem[0].D = 1; mem[1].D = 1; mem[0].alpha_dev = nullptr;
     // the single-posterior entry builds its one-member stack on the host and forwards: its refusals, next to the stack entry's
     ffgp_acq_problem ap;

@@ -1114,6 +1114,46 @@ int ffgp_acq_optimize_stack_tree_staged(ffgp_handle* h, const ffgp_acq_stack* s,
                                         int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev,
                                         double* grad_dev);
 
+/* ffgp_acq_optimize_chain on a chain whose members may carry COMPOSED kernels -- the reference's two-fidelity NAR is built on
+   SumKernel(LinearKernel(1), MaternKernel(1)) below and SumKernel(LinearKernel(2), MaternKernel(2)) above
+   (two_fidelity_models/NAR_NonlinearAR.py:23-26), and NAR(fidelity_num, kernel_list) takes any kernel list -- in ONE launch
+   (csrc/acq_chain_tree.hip).  `c` is ffgp_acq_chain as it stands; `trees` is a host array [c->F]:
+       trees[f] == NULL   member f is one radial library kernel, taken from the member's own w_dev / amp_dev / clamp_min / kfun / kparam
+                          exactly as ffgp_acq_optimize_chain reads them;
+       trees[f] != NULL   member f's kernel is that tree of 2-4 leaves, with the canonical forms and per-leaf rules of
+                          ffgp_acq_optimize_tree (FFGP_KFUN_LINEAR with optional center_dev, FFGP_KFUN_RQ); the member's own w_dev /
+                          amp_dev / kfun are then not read and may be NULL / 0.  Every leaf of member f carries D_f = members[f].D
+                          weights -- D for f = 0, D + 1 above it, the last one on the mean fed forward -- and a centre of the same length.
+   Limits, ffgp_acq_optimize_chain's: F <= FFGP_ACQ_MAX_MEMBERS, every n <= FFGP_ACQ_MAX_N, members[0].D = D in 1..FFGP_ACQ_MAX_D - 1,
+   members[f > 0].D = D + 1, d = 1, both coefficients 1.0, steps <= FFGP_ACQ_MAX_STEPS.  Per query point x with
+   s = min(level[q], F - 1) (level_dev NULL: F - 1), z_0 = x and z_f = [x, u], u = m_{f-1}:
+       k_f,i = tree_f on the leaves' values at (Z_f,i, z_f), its nodes rounded one by one as ffgp_assemble_tree rounds them,
+       m_f = sum_i alpha_f,i k_f,i   for f = 0..s,        mean = m_s,    var = k_s(z_s, z_s) - |L_s^-1 k_s|^2 + var_add_all_s,
+       k_f(z, z) = tree_f on the self values amp_e phi_e(max(0, clamp_e)) | amp_e sum_k w_ek^2 (z_k - c_ek)^2;   a radial member: amp_f,
+   and FFGP_ACQ_UCB, FFGP_ACQ_EI or FFGP_ACQ_UCB_VAR on (mean, var) as ffgp_acq_optimize_stack defines them; the lower members
+   contribute no variance.  The loss is -sum a.  With t_i = -dk_f(Z_i, z)/dz over all D_f coordinates (the tree's reverse sweep times
+   the leaf derivative, ffgp_acq_optimize_tree's two forms, zero where s_e < clamp_e), gm = da/dmean and gv = da/dvar:
+       member s:       c_i = gm alpha_s,i - 2 gv B_i  (B = Sigma_s^-1 k_s),    G = sum_i c_i t_i[0..D),
+                       gu = sum_i c_i t_i[D] - gv dk_s(z, z)/du,   dk_s(z, z)/du = sum over the linear leaves of
+                            (dk_s(z, z)/dv_e) 2 amp_e w_e^2[D] (u - c_e[D])
+       member f < s:   c_i = -gu alpha_f,i  (gu = d(-a)/dm_f),   G += sum_i c_i t_i[0..D),   the next gu = sum_i c_i t_i[D]
+       d(-a)/dx = G - gv dk_s(z, z)/dx      (the self term: non-zero through linear leaves only, along x AND along u)
+   -- in a chain a linear leaf sees the lower member's mean as an input coordinate, so the variance's self term feeds the chain as well.
+   Adam acts on the D coordinates of x only.  Only the member a point stops at pays for the triangular chains and for k_f(z, z).  A
+   chain without a linear leaf has both self terms exactly 0 and follows ffgp_acq_optimize_chain to rounding.  Switched-off members
+   are selects that add exact zeros: a point's trajectory does not depend on its tile, its neighbours or their levels, and level = k
+   everywhere is the chain cut after member k, bit for bit.  level values are read as min(level, F - 1); a point with a negative
+   level stops at no member: its value is 0, its gradient 0 and it does not move.  Xq [Q, D], trace, hist, grad, step0, opt, evaluate
+   mode (steps = 0), state_dev [2 | 3, Q, D] and accumulate_grad keep ffgp_acq_optimize_chain's contract -- an Adam state moves between
+   this entry, ffgp_acq_optimize_chain and ffgp_acq_optimize_chain_staged --, the workspace and the handle's inverted diagonal blocks
+   likewise (the members' leaf records travel in the same workspace, behind the bias corrections).
+   FFGP_ERR_ARG, before anything is enqueued (Xq, state, trace, hist and grad untouched): everything ffgp_acq_optimize_chain refuses --
+   its w_dev / amp_dev / kfun rules applying to the members with a NULL tree only --, trees NULL, and for a non-NULL tree what
+   ffgp_acq_optimize_tree refuses about a tree: its leaf array NULL, n_leaves outside 2..4, an unknown shape, op or leaf kfun, a
+   leaf's w_dev or amp_dev NULL.  Synchronous; returns 0.                                                                          */
+int ffgp_acq_optimize_chain_tree(ffgp_handle* h, const ffgp_acq_chain* c, const ffgp_ktree* const* trees, double* Xq_dev, int Q, int steps,
+                                 const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another

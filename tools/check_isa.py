@@ -120,7 +120,16 @@ def check_acq_staged_chain_no_scratch():
     return sizes
 
 
+def check_acq_chain_tree_no_scratch():
+    """the one-launch kernel for chains with composed-kernel members (D + 1 <= 2, 8, 16): every instantiation without a private segment"""
+    sizes = private_segments("acq_chain_tree.hip", "ffgp_chain_tree_acq_kernel")
+    assert len(sizes) == 3, sorted(sizes)
+    assert all(v == 0 for v in sizes.values()), sizes
+    return sizes
+
+
 if __name__ == "__main__":
     print("ffgp_potrf_diag128_v4: barriers behind an LDS drain:", check_diag_barriers())
     print("sb2st_chase: counter stores behind an explicit vmcnt(0):", check_chase_publish())
     print("acq_staged_chain.hip: private segment sizes:", check_acq_staged_chain_no_scratch())
+    print("acq_chain_tree.hip: private segment sizes:", check_acq_chain_tree_no_scratch())
