@@ -7,7 +7,8 @@
 // Geometry: 128x128 output tile per 256-thread workgroup (4 waves as 2x2, each wave 64x64 = 4x4 MFMA tiles,
 // 16 accumulators x 4 fp64 = 128 VGPRs), BK = 16 (4 MFMA k-steps), double-buffered LDS, one barrier per
 // k-tile, global->register->LDS staging issued a full compute phase ahead (the 64-cycle fp64 MFMA leaves
-// the load/LDS pipes almost idle, so a deeper pipeline buys nothing).  2 workgroups per CU (2 x 72 KiB LDS,
+// the load/LDS pipes almost idle, so a deeper pipeline buys nothing; the 128 x 128 fast tile of K-major operands stages
+// global->LDS directly, see gemm_tile_fast128).  2 workgroups per CU (2 x 72 KiB LDS,
 // <= 256 VGPRs) so one workgroup's C epilogue overlaps the other's MFMA stream.
 //
 // LDS images (both bank-conflict-free for the ds_read_b64 operand fetch, see MI355X guide "LDS"):
@@ -349,6 +350,21 @@ __device__ __forceinline__ void gemm_tile_fast(const char* __restrict__ baseA, c
 //       comes behind barrier t+1, which every wave reaches with its reads of s^1 returned.
 //   I3  per accumulator the MFMAs keep gemm_tile_fast's order (kt ascending, kq ascending inside it, the same negate-A modifier, C
 //       loaded into the accumulators first): the values are the unrotated loop's bit for bit.
+// K-major x K-major operands (the SYRK, the passenger-row GEMMs, most factorisation launches) are staged by direct-to-LDS loads
+// instead: no staging registers, no LDS store pass, no wait for memory inside the MFMA stream.  Per k-tile t (the reads and MFMAs as above):
+//     kq = 0 .. 2  as above, without loads and stores
+//                  s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier       (DMA_BARRIER: this wave's pieces of k-tile t+1 have landed in stage s^1)
+//     kq = 3       X <- kq 0 of stage s^1 ; 16 MFMAs on Y, the 8 pieces of k-tile t+2 INTO STAGE s one behind each of the first eight
+// so a piece has a whole k-tile period to land, not half of one.  The prologue issues k-tiles 0 and 1 (both stages are free), then the
+// C loads, and waits for all of them at its barrier ("barrier -1"); k-tile nkt-2 has the barrier and nothing left to fetch; the last
+// k-tile is peeled as before.  I1 and I3 hold as they stand (the barrier's wait covers the reads of stage s); in place of I2:
+//   I2' a stage receives pieces only behind the barrier that ends its last read: the pieces of k-tile t+2 are issued behind barrier t,
+//       and every wave reached barrier t with its reads of stage s returned (I1).
+//   I4  a stage is read only behind a barrier that follows every wave's vmcnt(0): an LDS-DMA is a VMEM operation, nothing but the
+//       issuing wave's vmcnt orders a later LDS read behind it, and other waves' reads need the barrier on top.  Stage s^1 is read
+//       behind barrier t; its pieces (k-tile t+1) were issued behind barrier t-1 and every wave waited vmcnt(0) in front of barrier t.
+//       The compiler's own bookkeeping adds no wait between a piece and the LDS reads that follow it (tests/test_gemm_dma_loop_isa.py).
+// The raw barrier matters: __syncthreads() would be the same instructions here, but says nothing about the pieces by contract.
 // The compiler's scheduler would undo the rotation (it sinks the next-stage reads below the 64th MFMA, which puts a full LDS round trip
 // in front of the loop's first MFMA again), so the phase order is pinned with sched_barrier.
 // ------------------------------------------------------------------------------------------------------------
@@ -361,6 +377,26 @@ __device__ __forceinline__ void gload_buf(__amdgpu_buffer_rsrc_t r, const unsign
 #pragma unroll
   for (int i = 0; i < Geo<TS>::NLD; ++i) v[i] = __builtin_bit_cast(d2_t, (gemm_v4u)__builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[i], 0, 0));
 }
+
+// Direct-to-LDS staging (K-major x K-major operands).  One `buffer_load_dwordx4 ... offen lds` writes 64 lanes x 16 bytes to
+// consecutive LDS addresses from a wave-uniform base (M0), so lane idx = tid + 256 i lands at row idx >> 3, slot idx & 7 of the
+// [row][16] image; the image's XOR swizzle therefore goes on the SOURCE side: the lane fetches chunk slot ^ ((row >> 1) & 7) of its
+// row, where sstore puts chunk ch into slot ch ^ ((row >> 1) & 7) -- the same image, the same 128-byte line per 8 lanes.
+typedef __attribute__((address_space(3))) char gemm_lds_t;
+__device__ __forceinline__ void dma_lane_offsets(int tid, const unsigned (&voff)[4], unsigned (&dv)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int idx = tid + 256 * i;
+    const int row = idx >> 3, slot = idx & 7;
+    dv[i] = voff[i] + (unsigned)(((slot ^ ((row >> 1) & 7)) - slot) * 16);      // voff[i] is row * ld * 8 + slot * 16
+  }
+}
+__device__ __forceinline__ void gemm_dma16(__amdgpu_buffer_rsrc_t r, gemm_lds_t* dst, unsigned voff, int soff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, soff, 0, 0);
+}
+// the barrier of the DMA form: this wave's pieces have landed (an LDS-DMA is a VMEM operation: nothing but the issuing wave's vmcnt
+// orders a later ds_read behind it), its LDS reads have returned
+#define DMA_BARRIER() asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 //
 // DIAG = true is the diagonal tile of a lower-mode launch (ti == tj) on the same loop.  Its values must be the general tile's, which
@@ -396,9 +432,57 @@ __device__ __forceinline__ void gemm_tile_fast128(const char* __restrict__ baseA
     }                                                                   \
     GEMM_PIN();                                                         \
   } while (0)
-  d2_t ra[4], rb[4];
-  gload_buf<TS>(gemm_rsrc(baseA), voffA, ra);
-  gload_buf<TS>(gemm_rsrc(baseB), voffB, rb);
+  constexpr bool DMA = (OPA == OP_KMAJOR && OPB == OP_KMAJOR);
+  // DMA form: piece p of a k-tile (p < 4: operand A, else B; 1 KiB per wave) -- destination stage + operand + (256 (p & 3) + 64 wave) * 16
+  // bytes through M0, source this lane's swizzled chunk + k offset kt * 128 in an SGPR
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rsA = gemm_rsrc(baseA), rsB = gemm_rsrc(baseB);
+  [[maybe_unused]] unsigned dvA[4], dvB[4];
+  [[maybe_unused]] gemm_lds_t* ldsw = nullptr;
+  if constexpr (DMA) {
+    dma_lane_offsets(tid, voffA, dvA);
+    dma_lane_offsets(tid, voffB, dvB);
+    ldsw = (gemm_lds_t*)smem + __builtin_amdgcn_readfirstlane(tid >> 6) * 1024;
+  }
+#define GEMM_DMA(p, stage, kt)                                          \
+  gemm_dma16((p) < 4 ? rsA : rsB, ldsw + (stage) * (STAGE * 8) + ((p) < 4 ? 0 : BUFA * 8) + ((p) & 3) * 4096, \
+             (p) < 4 ? dvA[(p) & 3] : dvB[(p) & 3], (kt) * (BK * 8))
+#define GEMM_DMA_ALL(stage, kt)                                         \
+  do {                                                                  \
+    _Pragma("unroll") for (int p_ = 0; p_ < 8; ++p_) GEMM_DMA(p_, stage, kt); \
+    GEMM_PIN();                                                         \
+  } while (0)
+  // the 16 MFMAs of kq = 3 with the eight pieces of a k-tile dealt out, one behind each of the first eight (each piece is an M0 write,
+  // an s_nop and the load: as one burst behind the barrier they take longer to issue than the MFMA the pipe holds meanwhile.  Trace
+  // build, k = 512, k-loop cycles lone / pair: burst 157 420 / 264 750, behind every second MFMA 149 184 / 255 780, this 149 184 / 254 140)
+#define GEMM_MFMA_DMA(a, b, stage, kt)                                  \
+  do {                                                                  \
+    if constexpr (DIAG) {      /* (one wave issues no MFMA: every wave's pieces go out first, the MFMAs stay one conditional block) */ \
+      GEMM_DMA_ALL(stage, kt);                                          \
+      GEMM_MFMA(a, b);                                                  \
+    } else {                                                            \
+      _Pragma("unroll") for (int i = 0; i < W; ++i)                     \
+        _Pragma("unroll") for (int j = 0; j < W; ++j) {                 \
+          acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, NEG ? 1 : 0); \
+          if (i * W + j < 8) {                                          \
+            GEMM_PIN();                                                 \
+            GEMM_DMA(i * W + j, stage, kt);                             \
+            GEMM_PIN();                                                 \
+          }                                                             \
+        }                                                               \
+      GEMM_PIN();                                                       \
+    }                                                                   \
+  } while (0)
+  [[maybe_unused]] d2_t ra[4], rb[4];
+  if constexpr (DMA) {
+    // k-tiles 0 and 1 go out together, in front of the C tile.  (k-tile 1 behind "barrier -1", where the loop issues k-tile kt + 2
+    // behind barrier kt, was built first: the compiler, which cannot see the wait inside DMA_BARRIER, then drains the pieces with a
+    // vmcnt(0) of its own in the loop's preheader, one exposed memory round trip per tile.  Stage 1 has no reader yet.)
+    GEMM_DMA_ALL(0, 0);
+    if (nkt > 1) GEMM_DMA_ALL(1, 1);
+  } else {
+    gload_buf<TS>(rsA, voffA, ra);
+    gload_buf<TS>(rsB, voffB, rb);
+  }
   d4_t acc[W][W];
   if (load_c) {
 #pragma unroll
@@ -415,36 +499,73 @@ __device__ __forceinline__ void gemm_tile_fast128(const char* __restrict__ baseA
 #pragma unroll
       for (int j = 0; j < W; ++j) acc[i][j] = (d4_t){0.0, 0.0, 0.0, 0.0};
   }
-  sstore<OPA, TS>(smem, tid, ra);
-  sstore<OPB, TS>(smem + BUFA, tid, rb);
-  LDS_BARRIER();      // (the C loads stay in flight: the first MFMA waits for them)
+  if constexpr (DMA) {
+    GEMM_PIN();
+    DMA_BARRIER();      // "barrier -1": k-tiles 0 and 1 and, issued behind them, the C tile have landed -- one plain wait covers all
+  } else {
+    sstore<OPA, TS>(smem, tid, ra);
+    sstore<OPB, TS>(smem + BUFA, tid, rb);
+    LDS_BARRIER();      // (the C loads stay in flight: the first MFMA waits for them)
+  }
 #ifdef FFGP_GEMM_TRACE
   if (tid == 0 && ffgp_trace_buf) ffgp_trace_buf[(size_t)trace_bid * 8 + 1] = __builtin_readcyclecounter();
 #endif
   double xa[W], xb[W], ya[W], yb[W];
   GEMM_PIN();
-  GEMM_READ(smem, 0, xa, xb);
-  for (int kt = 0; kt + 1 < nkt; ++kt) {
-    const double* sS = smem + (kt & 1) * STAGE;          // stage s
-    double* sN = smem + ((kt & 1) ^ 1) * STAGE;          // stage s^1
-    baseA += stepA;
-    baseB += stepB;
-    gload_buf<TS>(gemm_rsrc(baseA), voffA, ra);
-    gload_buf<TS>(gemm_rsrc(baseB), voffB, rb);
-    GEMM_PIN();
-    GEMM_READ(sS, 1, ya, yb);
-    GEMM_MFMA(xa, xb);
-    GEMM_READ(sS, 2, xa, xb);
-    GEMM_MFMA(ya, yb);
-    sstore<OPA, TS>(sN, tid, ra);
-    sstore<OPB, TS>(sN + BUFA, tid, rb);
-    GEMM_PIN();
-    GEMM_READ(sS, 3, ya, yb);
-    GEMM_MFMA(xa, xb);
-    LDS_BARRIER();
-    GEMM_PIN();
-    GEMM_READ(sN, 0, xa, xb);
-    GEMM_MFMA(ya, yb);
+  if constexpr (DMA) {
+    GEMM_READ(smem, 0, xa, xb);
+    for (int kt = 0; kt + 2 < nkt; ++kt) {
+      const double* sS = smem + (kt & 1) * STAGE;          // stage s: read by this k-tile, refilled with k-tile kt + 2 behind its barrier
+      const double* sN = smem + ((kt & 1) ^ 1) * STAGE;    // stage s^1: k-tile kt + 1, in flight since barrier kt - 1
+      GEMM_READ(sS, 1, ya, yb);
+      GEMM_MFMA(xa, xb);
+      GEMM_READ(sS, 2, xa, xb);
+      GEMM_MFMA(ya, yb);
+      GEMM_READ(sS, 3, ya, yb);
+      GEMM_MFMA(xa, xb);
+      DMA_BARRIER();
+      GEMM_PIN();
+      GEMM_READ(sN, 0, xa, xb);
+      GEMM_MFMA_DMA(ya, yb, kt & 1, kt + 2);
+    }
+    if (nkt > 1) {      // k-tile nkt - 2: its barrier opens the last k-tile's stage; nothing is left to fetch
+      const double* sS = smem + (nkt & 1) * STAGE;
+      const double* sN = smem + ((nkt & 1) ^ 1) * STAGE;
+      GEMM_READ(sS, 1, ya, yb);
+      GEMM_MFMA(xa, xb);
+      GEMM_READ(sS, 2, xa, xb);
+      GEMM_MFMA(ya, yb);
+      GEMM_READ(sS, 3, ya, yb);
+      GEMM_MFMA(xa, xb);
+      DMA_BARRIER();
+      GEMM_PIN();
+      GEMM_READ(sN, 0, xa, xb);
+      GEMM_MFMA(ya, yb);
+    }
+  } else {
+    GEMM_READ(smem, 0, xa, xb);
+    for (int kt = 0; kt + 1 < nkt; ++kt) {
+      const double* sS = smem + (kt & 1) * STAGE;          // stage s
+      double* sN = smem + ((kt & 1) ^ 1) * STAGE;          // stage s^1
+      baseA += stepA;
+      baseB += stepB;
+      gload_buf<TS>(gemm_rsrc(baseA), voffA, ra);
+      gload_buf<TS>(gemm_rsrc(baseB), voffB, rb);
+      GEMM_PIN();
+      GEMM_READ(sS, 1, ya, yb);
+      GEMM_MFMA(xa, xb);
+      GEMM_READ(sS, 2, xa, xb);
+      GEMM_MFMA(ya, yb);
+      sstore<OPA, TS>(sN, tid, ra);
+      sstore<OPB, TS>(sN + BUFA, tid, rb);
+      GEMM_PIN();
+      GEMM_READ(sS, 3, ya, yb);
+      GEMM_MFMA(xa, xb);
+      LDS_BARRIER();
+      GEMM_PIN();
+      GEMM_READ(sN, 0, xa, xb);
+      GEMM_MFMA(ya, yb);
+    }
   }
   {
     const double* sS = smem + ((nkt - 1) & 1) * STAGE;
@@ -459,6 +580,9 @@ __device__ __forceinline__ void gemm_tile_fast128(const char* __restrict__ baseA
 #undef GEMM_PIN
 #undef GEMM_READ
 #undef GEMM_MFMA
+#undef GEMM_DMA
+#undef GEMM_DMA_ALL
+#undef GEMM_MFMA_DMA
 #ifdef FFGP_GEMM_TRACE
   if (tid == 0 && ffgp_trace_buf) ffgp_trace_buf[(size_t)trace_bid * 8 + 2] = __builtin_readcyclecounter();
 #endif
@@ -1188,7 +1312,7 @@ static int gemm_plan(ffgp_handle* h, int opa, int opb, int mode, int syrk_tag, c
   }
   // "Polite" trailing update: once the factorisation is bound by its dependency chain (trailing matrix below polite_m
   // rows) the 128-tile SYRK is launched with LDS padding so that only one of its workgroups fits a CU.  Alone it still
-  // runs the MFMA pipe at ~70 %, and the other half of every CU -- VGPRs, LDS, issue slots -- is free for the chain's
+  // runs the MFMA pipe at 88 % (70 % when polite_m was first set, at 6144; 8192 since the direct-to-LDS staging), and the other half of every CU -- VGPRs, LDS, issue slots -- is free for the chain's
   // kernels at all times instead of only when a SYRK workgroup happens to exit.
   a.pad_lds = 0;
   if (syrk_tag && tsm == 128 && h->lookahead && h->polite_m > 0 && m < h->polite_m && h->stream != h->aux) a.pad_lds = POLITE_PAD_KB * 1024;

@@ -198,7 +198,7 @@ int ffgp_create(int device, ffgp_handle** out) {
   h->small_tile_threshold = 640;
   h->batch_grad_ob = 1;
   h->tile32_threshold = 1024;
-  h->polite_m = 6144;
+  h->polite_m = 8192;
   h->split_rem_max = 180;
   h->syrk_light_tiles = 1;
   h->super_block = 1024;

@@ -200,8 +200,9 @@ int ffgp_set_stream(ffgp_handle* h, void* hip_stream); /* hipStream_t; NULL rest
             "gemm_tile" (0 = automatic; 32 / 64 / 128 force the GEMM tile shape -- tests and benchmarks),
             "small_tile_threshold" (default 640: launches with fewer 128-tiles use 64-tiles),
             "tile32_threshold" (default 1024: K-major launches with fewer 64-tiles use 32-row tiles),
-            "polite_m" (default 6144: trailing updates with fewer rows run one workgroup per CU so that the side
-                        stream's kernels always find free registers and LDS),
+            "polite_m" (default 8192: trailing updates with fewer rows run one workgroup per CU so that the side
+                        stream's kernels always find free registers and LDS; 6144 until the 128-tile staged its operands
+                        directly into LDS -- a lone workgroup then ran at 0.82 of the MFMA cadence, now 0.88),
             "split_rem_max" (default 180: a 128-tile launch whose tile count leaves a remainder <= this modulo the 256 CUs
                         hands those last tiles out as 64 x 64 quarters -- same bits, a shorter last round; 0 = never),
             "syrk_light_tiles" (default 1: in the 128-tile symmetric updates a last tile row of at most 32 rows -- the passenger

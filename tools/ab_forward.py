@@ -22,7 +22,7 @@ amp = torch.ones(1, dtype=torch.float64, device=dev)
 dadd = torch.tensor([np.exp(-1.0) + 1e-6], dtype=torch.float64, device=dev)
 configs = [dict(kv.split("=") for kv in c.split(",") if kv) for c in sys.argv[1:]]
 keys = sorted({k for c in configs for k in c})
-defaults = {"polite_m": 6144, "split_rem_max": 180, "nb_outer": 512,
+defaults = {"polite_m": 8192, "split_rem_max": 180, "nb_outer": 512,
             "tile32_threshold": 1024, "small_tile_threshold": 640, "aux_prio": 1, "la_carry": 2, "lookahead": 1, "la_min_n": 1024, "trsm128": 1, "polite64_pad_kb": 60, "polite32_pad_kb": 46, "ho_values": 1, "ho_defer": 2, "la_carry_rows": 8192, "diag_excl_rows": 4096, "la_carry_n": 12288}
 res = {i: [] for i in range(len(configs))}
 for rnd in range(4):

@@ -2,7 +2,8 @@
 
 kernel_meta(asm, name)   the .amdhsa metadata entries of one kernel (.vgpr_count, .vgpr_spill_count, .group_segment_fixed_size ...)
 k_loop(asm, name)        the instructions of the innermost loop that holds 64 negate-A MFMAs (one k-tile of the alpha = -1 fast form)
-loop_report(loop)        what tests/test_gemm_loop_isa.py asserts on: barriers, MFMAs / LDS reads behind the barrier, 64-bit vector adds
+loop_report(loop)        what tests/test_gemm_loop_isa.py asserts on: barriers, MFMAs / LDS reads behind the barrier, 64-bit vector adds;
+                         and tests/test_gemm_dma_loop_isa.py: direct-to-LDS loads, LDS stores, where the vmcnt waits sit
 
 `python tools/gemm_loop_isa.py` prints the report for the trailing update's instantiation.
 """
@@ -67,7 +68,26 @@ def k_loop(asm, name=SYRK, mfmas=64, marker="neg:[1,0,0]"):
 def loop_report(loop):
     bars = [i for i, l in enumerate(loop) if l.startswith("s_barrier")]
     after = loop[bars[-1] + 1:] if bars else []
+    vmem = [i for i, l in enumerate(loop) if re.match(r"(global|buffer)_load", l)]
+    dma = [i for i in vmem if re.search(r"\blds$", loop[i])]                # direct-to-LDS: the register load's mnemonic + `lds`
+    vmw = [i for i, l in enumerate(loop) if l.startswith("s_waitcnt") and "vmcnt" in l]
+    last_mfma_before_bar = max([i for i, l in enumerate(loop[:bars[0]]) if l.startswith("v_mfma")], default=-1) if bars else -1
+    # a DMA followed (cyclically: the loop's top follows its back edge) by a vmcnt wait before the next LDS read
+    ring = loop + loop
+    drained = 0
+    for i in dma:
+        for l in ring[i + 1:i + 1 + len(loop)]:
+            if l.startswith("ds_read"):
+                break
+            if l.startswith("s_waitcnt") and "vmcnt" in l:
+                drained += 1
+                break
     return {
+        "lds_dma_loads": len(dma),
+        "ds_write": sum(1 for l in loop if l.startswith("ds_write")),
+        "vmcnt_waits": len(vmw),
+        "vmcnt_wait_in_front_of_barrier": bool(bars) and len(vmw) == 1 and last_mfma_before_bar < vmw[0] < bars[0],
+        "vmcnt_wait_between_dma_and_ds_read": drained,
         "instructions": len(loop),
         "barriers": len(bars),
         "mfma_before_barrier": sum(1 for l in (loop[:bars[0]] if bars else []) if l.startswith("v_mfma")),
