@@ -260,6 +260,8 @@ EXPORTS = {
                                                   _dp]),
     "ffgp_acq_optimize_chain_tree": (C.c_int, [C.c_void_p, C.POINTER(AcqChain), C.POINTER(C.POINTER(KTree)), _dp, C.c_int, C.c_int, C.POINTER(Adam), _dp,
                                                C.c_long, _dp, _dp, _dp]),
+    "ffgp_acq_optimize_chain_tree_staged": (C.c_int, [C.c_void_p, C.POINTER(AcqChain), C.POINTER(C.POINTER(KTree)), _dp, C.c_int, C.c_int,
+                                                      C.POINTER(Adam), _dp, C.c_long, _dp, _dp, _dp]),
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),

@@ -19,7 +19,8 @@ launch per stage, every step enqueued by one library call (csrc/acq_staged.hip),
 `fuse_composed=True` as well, the same holds for SumKernel / ProductKernel models and stacks with such fidelities
 (csrc/acq_staged_tree.hip) -- the reference's cigp and AR on SumKernel(LinearKernel, MaternKernel) once a run has passed 256 points.
 `staged=True` on `optimize_acqf_nar` does the same for a NAR chain of radial-kernel models of up to 2048 points per fidelity
-(csrc/acq_staged_chain.hip)."""
+(csrc/acq_staged_chain.hip), and with `fuse_composed="staged"` for a chain whose fidelities run on SumKernel / ProductKernel trees
+(csrc/acq_staged_chain_tree.hip)."""
 import inspect
 import math
 
@@ -170,7 +171,10 @@ def optimize_acqf_nar(models, data, X0, level=None, steps=10, lr=0.001, acq="ucb
     csrc/acq_staged_chain.hip) instead of the per-step loop; a chain of up to 256 points per fidelity keeps the one-launch call.
     `fuse_composed=True` runs the loop in one launch also when models carry composed kernels (SumKernel / ProductKernel trees of 2-4
     library kernels, LinearKernel included; csrc/acq_chain_tree.hip) and every fidelity has at most 256 points; by default such a chain
-    takes the per-step loop, and so it does past 256 points whatever the keywords say (the staged call serves radial chains only)."""
+    takes the per-step loop, and with `fuse_composed=True` it keeps that loop past 256 points.  `fuse_composed="staged"` means what
+    True means and, together with `staged=True`, runs a chain with composed-kernel fidelities of 257 ... 2048 points -- the
+    reference's NAR on SumKernel(LinearKernel, MaternKernel) at its demo's 300 / 300 / 250 -- launch per stage inside one library call
+    as well (csrc/acq_staged_chain_tree.hip); the value is passed through to `PosteriorChain.optimize_acquisition`."""
     if X0 is None:
         raise ValueError("optimize_acqf_nar needs the start points X0 [Q, D]")
     models = list(models)

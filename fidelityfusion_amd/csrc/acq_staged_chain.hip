@@ -35,30 +35,6 @@
 
 #include "acq_staged.h"
 
-// the chunk sums p[f][0 .. chunks(n_f) - 1][q] added in chunk order: a member's mean (p = pm) or |V|^2 (p = pv)
-__device__ __forceinline__ double asc_chunk_sum(const double* p, const AcqStagedArgs& a, int f, int q) {
-  const int nch = as_chunks(a.m[f].n);
-  double s = 0.0;
-  for (int ch = 0; ch < nch; ++ch) s += p[((size_t)f * a.nch + ch) * a.Qp + q];
-  return s;
-}
-// member f's rows r0 .. r0 + rows - 1 into LDS, row length Df padded to DM with zeros
-template <int DM>
-__device__ __forceinline__ void asc_load_rows(double* Xs, const double* X, int r0, int rows, int Df, int tid) {
-  for (int idx = tid; idx < rows * DM; idx += AS_T) {
-    const int i = idx / DM, dd = idx % DM;
-    Xs[idx] = (dd < Df) ? X[(size_t)(r0 + i) * Df + dd] : 0.0;
-  }
-}
-// z_f = [x_q, u_q] of a live column, zeros beyond; u_q = m_{f-1}(x_q), and for f = 0 the coordinate D stays 0 under w^2 = 0
-template <int DM>
-__device__ __forceinline__ void asc_load_z(double (&xj)[DM], const AcqStagedArgs& a, int f, int q, bool live) {
-  const int D = a.D;
-  const double u = (live && f > 0) ? asc_chunk_sum(a.pm, a, f - 1, q) : 0.0;
-#pragma unroll
-  for (int dd = 0; dd < DM; ++dd) xj[dd] = (live && dd < D) ? a.Xq[(size_t)q * D + dd] : (dd == D ? u : 0.0);
-}
-
 // ---- the census of the levels: bit l of *out = some point stops at member l (levels clipped to F - 1, negative ones match no member)
 __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_chain_census_kernel(const int* level, int Q, int F, unsigned* out) {
   __shared__ unsigned bits[AS_T];
@@ -213,6 +189,32 @@ static int asc_step(ffgp_handle* h, const AcqStagedPlan& pl, int top, unsigned t
   return as_owner_stage(h, pl, k);
 }
 
+// The census of a call (acq_staged.h): `tops`, `top`, and the zero-fill of the gradient partials above `top`.  The census word is the
+// first of the entry's extra doubles.  A refused launch or copy is returned for the caller's acq_staged_finish.
+int acq_staged_chain_census(ffgp_handle* h, const AcqStagedPlan& pl, unsigned& tops, int& top) {
+  const AcqStagedArgs& a = pl.a;
+  const int F = a.F;
+  tops = 1u << (F - 1);
+  top = F - 1;
+  if (a.level) {
+    unsigned* const census = reinterpret_cast<unsigned*>(pl.extra);
+    hipLaunchKernelGGL(ffgp_acq_staged_chain_census_kernel, dim3(1), dim3(AS_T), 0, h->stream, a.level, a.Q, F, census);
+    int rc = as_launched();
+    if (rc == FFGP_OK && hipMemcpyAsync(&tops, census, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = FFGP_ERR_HIP;
+    if (rc != FFGP_OK) return rc;
+    FFGP_HIP(hipStreamSynchronize(h->stream));      // the one wait before the step loop
+    tops &= (1u << F) - 1u;
+  }
+  top = -1;
+  for (int f = 0; f < F; ++f)
+    if ((tops >> f) & 1u) top = f;
+  if (top < F - 1) {      // no launch writes these members' partials, and the owner kernel sums over every member
+    const size_t per_member = (size_t)a.nch * a.Qp * a.DM;
+    return ffgp_zero_async(h, a.part + (size_t)(top + 1) * per_member, (size_t)(F - 1 - top) * per_member * sizeof(double));
+  }
+  return FFGP_OK;
+}
+
 // The coefficients are checked here, as ffgp_acq_optimize_chain checks them (reserved: a chain member has no weight of its own);
 // everything else the staged prologue refuses, told that the members above the first take one more input.
 int ffgp_acq_optimize_chain_staged(ffgp_handle* h, const ffgp_acq_chain* c, double* Xq_dev, int Q, int steps, const ffgp_adam* opt,
@@ -226,26 +228,9 @@ int ffgp_acq_optimize_chain_staged(ffgp_handle* h, const ffgp_acq_chain* c, doub
   s.var_floor = c->var_floor; s.acq = c->acq; s.kappa = c->kappa; s.xi = c->xi; s.f_best = c->f_best; s.accumulate_grad = c->accumulate_grad;
   AcqStagedPlan pl;
   FFGP_CHECK(acq_staged_prepare(h, &s, nullptr, 4, true, 1, Xq_dev, Q, steps, opt, state_dev, step0, trace_dev, hist_dev, grad_dev, pl));
-  const AcqStagedArgs& a = pl.a;
-  const int F = a.F;
-  unsigned tops = 1u << (F - 1);
-  if (a.level) {
-    unsigned* const census = reinterpret_cast<unsigned*>(pl.extra);
-    hipLaunchKernelGGL(ffgp_acq_staged_chain_census_kernel, dim3(1), dim3(AS_T), 0, h->stream, a.level, Q, F, census);
-    int rc = as_launched();
-    if (rc == FFGP_OK && hipMemcpyAsync(&tops, census, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = FFGP_ERR_HIP;
-    if (rc != FFGP_OK) return acq_staged_finish(h, rc);
-    FFGP_HIP(hipStreamSynchronize(h->stream));      // the one wait before the step loop
-    tops &= (1u << F) - 1u;
-  }
-  int top = -1;
-  for (int f = 0; f < F; ++f)
-    if ((tops >> f) & 1u) top = f;
-  int rc = FFGP_OK;
-  if (top < F - 1) {      // no launch writes these members' partials, and the owner kernel sums over every member
-    const size_t per_member = (size_t)a.nch * a.Qp * a.DM;
-    rc = ffgp_zero_async(h, a.part + (size_t)(top + 1) * per_member, (size_t)(F - 1 - top) * per_member * sizeof(double));
-  }
+  unsigned tops;
+  int top;
+  int rc = acq_staged_chain_census(h, pl, tops, top);
   for (int k = 0; k < pl.iters && rc == FFGP_OK; ++k) rc = asc_step(h, pl, top, tops, k);
   return acq_staged_finish(h, rc);
 }

@@ -23,51 +23,6 @@
 
 #include "acq_staged.h"
 
-#define AST_NL FFGP_TREE_LEAVES
-
-// the tree that tree_ops.h evaluates: a one-leaf record as the sum of its leaf and 0.0 (exact)
-struct AstTree {
-  int nl, shape, op[3];
-};
-__device__ __forceinline__ AstTree ast_tree(const AcqMemberTree& mt) {
-  AstTree tr;
-  tr.nl = max(mt.nl, 2); tr.shape = mt.shape; tr.op[0] = mt.op[0]; tr.op[1] = mt.op[1]; tr.op[2] = mt.op[2];
-  return tr;
-}
-
-// An offset of zero the compiler cannot see through.  The leaf record in LDS is workgroup-uniform and loop-invariant, and hoisting its
-// 2 x 4 x DM doubles out of the row loop into registers is what the compiler does when it can: at DM = 16 that is 256 registers beside
-// x_q and the running sums, and a private segment.  Each use of a leaf's w^2 and centre goes through its own opaque offset, so the
-// values are read from LDS (a broadcast read) where they are used and live no longer than one leaf's term.
-__device__ __forceinline__ int ast_opaque0() {
-  int o = 0;
-  asm volatile("" : "+v"(o));
-  return o;
-}
-
-// member's leaf record into LDS: per leaf w^2 [DM] and centre [DM] (zero from D on, zero past nl, the centre zero unless linear and
-// given) and lp = (amp, clamp, 1 / kparam, 0.0: padding); all four leaf slots are written.  The caller's barrier publishes it.
-template <int DM>
-__device__ __forceinline__ void ast_load_record(const AcqMemberTree& mt, int D, int tid, double* w2, double* cen, double* lp) {
-  const int nl = mt.nl;
-#pragma unroll
-  for (int e = 0; e < AST_NL; ++e) {
-    const bool live = e < nl;
-    const bool lin = live && mt.k[e].kfun == FFGP_KFUN_LINEAR;
-    if (tid < DM) {
-      const double wv = (live && tid < D) ? mt.k[e].w[tid] : 0.0;
-      w2[e * DM + tid] = wv * wv;
-      cen[e * DM + tid] = (lin && tid < D && mt.k[e].center) ? mt.k[e].center[tid] : 0.0;
-    }
-    if (tid == 0) {
-      lp[4 * e] = live ? mt.k[e].amp[0] : 0.0;
-      lp[4 * e + 1] = live ? mt.k[e].clamp : 0.0;
-      lp[4 * e + 2] = live ? mt.k[e].rinv : 1.0;
-      lp[4 * e + 3] = 0.0;
-    }
-  }
-}
-
 // ---- 1. K_s through the tree; the columns Q..Qp-1 are written as zeros
 template <int DM>
 __global__ __launch_bounds__(AS_T) void ffgp_acq_staged_tree_ks_kernel(AcqStagedArgs a) {

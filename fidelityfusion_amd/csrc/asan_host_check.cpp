@@ -284,6 +284,43 @@ int main() {
       EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
       mem[1].w_dev = mem[1].amp_dev = &x; mem[1].n = 4; chn.members = nullptr;
       EXPECT(ffgp_acq_optimize_chain_tree(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      // the launch-per-stage entry for such chains: the coefficients and the trees are checked before the staged prologue, which
+      // applies the chain's D / D + 1 rule, the staged rule on n and the one on Q D
+      chn.members = mem;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(nullptr, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, nullptr, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, nullptr, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, nullptr, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 0, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, INT_MAX, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, nullptr, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, nullptr, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, nullptr, nullptr, nullptr) == FFGP_ERR_ARG);
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, -1, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      chn.F = FFGP_ACQ_MAX_MEMBERS + 1;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      chn.F = 0;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      chn.F = 2; mem[1].mean_coef = 0.8;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].mean_coef = 1.0; mem[1].D = 1;   // the member on the tree must take D + 1 inputs
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].D = FFGP_ACQ_MAX_D; mem[1].D = FFGP_ACQ_MAX_D + 1;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].D = 1; mem[1].D = 2; mem[1].n = FFGP_ACQ_STAGED_MAX_N + 1; mem[1].ldl = 4096;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].n = 4; mem[1].ldl = 4; mem[1].d = 2;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[1].d = 1; tr.n_leaves = 5;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      tr.n_leaves = 4; lf[3].kfun = FFGP_KFUN_LINEAR + 1;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      lf[3].kfun = FFGP_KFUN_RQ; mem[0].kfun = FFGP_KFUN_LINEAR;      // the member without a tree needs a radial kernel of its own
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      mem[0].kfun = FFGP_KFUN_SE; chn.acq = 7;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
+      chn.acq = FFGP_ACQ_UCB_VAR; chn.members = nullptr;
+      EXPECT(ffgp_acq_optimize_chain_tree_staged(fake, &chn, trees, &x, 1, 1, &ad, &x, 0, &x, nullptr, nullptr) == FFGP_ERR_ARG);
     }
     mem[0].D = 1; mem[1].D = 1; mem[0].alpha_dev = nullptr;
     // the single-posterior entry builds its one-member stack on the host and forwards: its refusals, next to the stack entry's

@@ -674,20 +674,31 @@ class PosteriorChain(PosteriorStack):
         some member is composed): `acq_fusable`'s size rules -- at most 8 members, one output, n <= 256, D + 1 <= 16, the start points
         fp64 [Q, D] on the chain's GPU -- with every member ONE radial library kernel or a descriptor tree of 2-4 library leaves
         (radial profiles and LinearKernel) on its own D_f inputs"""
+        return self._acq_tree_members_ok(_lib.FFGP_ACQ_MAX_N) and self._acq_starts_ok(X0)
+
+    def _acq_tree_members_ok(self, nmax):
         def member_ok(m):
-            if m.d != 1 or not 1 <= m.n <= _lib.FFGP_ACQ_MAX_N:
+            if m.d != 1 or not 1 <= m.n <= nmax:
                 return False
             if m.tree is None:
                 return 0 <= int(m.kfun[0]) < FFGP_KFUN_LINEAR
             return 2 <= len(m.tree[0]) <= 4 and all(0 <= int(dsc["kfun"]) <= FFGP_KFUN_LINEAR for dsc in m.tree[0])
-        return (self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D - 1 and all(member_ok(m) for m in self.members)
-                and self._acq_starts_ok(X0))
+        return self.F <= _lib.FFGP_ACQ_MAX_MEMBERS and 1 <= self.D <= _lib.FFGP_ACQ_MAX_D - 1 and all(member_ok(m) for m in self.members)
+
+    def acq_chain_tree_staged_ok(self, X0):
+        """whether `optimize_acquisition(..., fuse_composed="staged", staged=True)` from X0 may take the launch-per-stage call for
+        chains with composed members (ffgp_acq_optimize_chain_tree_staged): `acq_tree_fusable`'s conditions with n up to
+        FFGP_ACQ_STAGED_MAX_N = 2048 in place of 256"""
+        return self._acq_tree_members_ok(_lib.FFGP_ACQ_STAGED_MAX_N) and self._acq_starts_ok(X0)
 
     def _acq_route(self, X0, fuse_composed, staged):
-        """(the C entry's caller or None for the per-step loop, whether it is the launch-per-stage call)"""
+        """(the C entry's caller or None for the per-step loop, whether it is a launch-per-stage call)"""
         one = self._acq_call if self.acq_fusable(X0) else self._acq_call_trees if fuse_composed and self.acq_tree_fusable(X0) else None
-        if staged and (staged == "force" or one is None) and self.acq_chain_staged_ok(X0):
-            return self._acq_call_chain_staged, True
+        if staged and (staged == "force" or one is None):
+            if self.acq_chain_staged_ok(X0):      # no composed member
+                return self._acq_call_chain_staged, True
+            if fuse_composed == "staged" and self.acq_chain_tree_staged_ok(X0):
+                return self._acq_call_chain_trees_staged, True
         return one, False
 
     def optimize_acquisition(self, X0, steps=30, lr=0.1, acq="ucb", kappa=2.0, xi=0.01, f_best=0.0, var_floor=1e-12, betas=(0.9, 0.999),
@@ -706,13 +717,22 @@ class PosteriorChain(PosteriorStack):
         `acq_tree_fusable(X0)` (radial members and Sum / Product trees of 2-4 leaves mixed freely, LinearKernel included, every
         n <= 256) is ONE launch as well (ffgp_acq_optimize_chain_tree, csrc/acq_chain_tree.hip), with the same return values, `state`
         contract and state["fused"] = True.  An all-radial chain takes ffgp_acq_optimize_chain whatever the keyword says; without the
-        keyword nothing changes: a chain with a composed member runs the per-step loop.  Past 256 points there is no call for a
-        composed chain yet: with `fuse_composed=True` and `staged=True` together a radial chain goes staged and a chain with a
-        composed member keeps the per-step loop.  The keyword travels in `**opt_in`, which takes `fuse_composed` (default False)
-        and nothing else: the chain's explicit signature is the radial call's and stays as tests/test_acq_stack_tree_host.py holds it."""
+        keyword nothing changes: a chain with a composed member runs the per-step loop.  With `fuse_composed=True` and `staged=True`
+        together a radial chain goes staged and a chain with a composed member past 256 points keeps the per-step loop.
+        `fuse_composed="staged"` (the chain only) means what True means and also permits the staged call for composed chains: with
+        `staged=True` a chain that takes no one-launch call but is `acq_chain_tree_staged_ok(X0)` (radial members and trees of 2-4
+        leaves mixed freely, every n <= 2048) runs the loop launch per stage inside ONE library call
+        (ffgp_acq_optimize_chain_tree_staged, csrc/acq_staged_chain_tree.hip), with the same return values and `state` contract --
+        a state moves between it, the one-launch calls and the radial staged call -- and state["staged"] = True,
+        state["fused"] = False.  A chain of up to 256 points per member keeps its one-launch call unless `staged="force"`.  Any
+        other value of `fuse_composed` raises ValueError.  The keyword travels in `**opt_in`, which takes `fuse_composed` (default
+        False) and nothing else: the chain's explicit signature is the radial call's and stays as tests/test_acq_stack_tree_host.py
+        holds it."""
         fuse_composed = opt_in.pop("fuse_composed", False)
         if opt_in:
             raise TypeError("optimize_acquisition() got an unexpected keyword argument %r" % sorted(opt_in)[0])
+        if fuse_composed not in (False, True, "staged"):
+            raise ValueError("fuse_composed must be False, True or 'staged', got %r" % (fuse_composed,))
         return super().optimize_acquisition(X0, steps=steps, lr=lr, acq=acq, kappa=kappa, xi=xi, f_best=f_best, var_floor=var_floor,
                                             betas=betas, eps=eps, level=level, var_adds=var_adds, accumulate_grad=accumulate_grad, state=state,
                                             fuse_composed=fuse_composed, staged=staged)
@@ -736,6 +756,14 @@ class PosteriorChain(PosteriorStack):
         c = _lib.AcqChain(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
                           accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
         check(lib.ffgp_acq_optimize_chain_staged(self.members[0]._h(), C.byref(c), *call), "ffgp_acq_optimize_chain_staged")
+
+    def _acq_call_chain_trees_staged(self, va, lv, acq_fields, accumulate_grad, call):
+        """the C entry of the launch-per-stage call on a chain with tree members: ffgp_acq_optimize_chain_tree's arguments"""
+        keep = []
+        c = _lib.AcqChain(F=self.F, members=self._member_table(va, keep), level_dev=lv.data_ptr() if lv is not None else None,
+                          accumulate_grad=1 if accumulate_grad else 0, **acq_fields)
+        check(lib.ffgp_acq_optimize_chain_tree_staged(self.members[0]._h(), C.byref(c), self._tree_table(), *call),
+              "ffgp_acq_optimize_chain_tree_staged")
 
 
 class PosteriorCache:

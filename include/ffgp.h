@@ -1155,6 +1155,45 @@ int ffgp_acq_optimize_stack_tree_staged(ffgp_handle* h, const ffgp_acq_stack* s,
 int ffgp_acq_optimize_chain_tree(ffgp_handle* h, const ffgp_acq_chain* c, const ffgp_ktree* const* trees, double* Xq_dev, int Q, int steps,
                                  const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev, double* grad_dev);
 
+/* ffgp_acq_optimize_chain_tree past FFGP_ACQ_MAX_N training points: the same loop LAUNCH PER STAGE (csrc/acq_staged_chain_tree.hip on
+   the prologue and the shared stages of csrc/acq_staged.hip), every step enqueued by this one call -- the reference's NAR stands on
+   SumKernel(LinearKernel, MaternKernel) fidelities (two_fidelity_models/NAR_NonlinearAR.py:23-26) and its demo trains on 300 / 300 /
+   250 points (FidelityFusion_Models/NAR.py:119-128).  The arguments are ffgp_acq_optimize_chain_tree's, one for one (trees[f] == NULL:
+   member f is one radial library kernel, read from the member's own fields), and so are the model, the outputs, the state layout
+   [2 | 3, Q, D], accumulate_grad, the Adam arithmetic, evaluate mode (steps = 0) and the handling of level_dev (read as
+   min(level, F - 1); a negative level stops at no member: value 0, gradient 0, the point does not move): an Adam state moves between
+   this entry, ffgp_acq_optimize_chain_tree and ffgp_acq_optimize_chain_staged.  Limits, ffgp_acq_optimize_chain_staged's: every n in
+   1..FFGP_ACQ_STAGED_MAX_N; F <= FFGP_ACQ_MAX_MEMBERS, members[0].D in 1..FFGP_ACQ_MAX_D - 1, members[f > 0].D = members[0].D + 1,
+   d = 1, both coefficients 1.0, steps <= FFGP_ACQ_MAX_STEPS; a non-NULL tree as ffgp_acq_optimize_chain_tree accepts it.
+   The step is ffgp_acq_optimize_chain_staged's -- the census of the levels once per call, the members in sequence,
+   3 (top + 1) + 2 |tops| + 2 launches per step whatever Q and n -- with the stages of a composed kernel:
+       forward, f = 0..top:  K_s,f = tree_f on the leaves' values at (Z_f,i, z_f), z_f = [x, m_{f-1}(x)] (the mean fed forward is the
+                             chunk sums added in chunk order, the expression that reports it); only for f in tops the two GEMMs; the
+                             column sums
+       the value, per point with s = level:  k_s(z_s, z_s) through the tree on the self values, var = k_s(z, z) - |V_s|^2 +
+                             var_add_all_s, the acquisition, and the self term's two shares S = dk_s(z, z)/dx and
+                             su = dk_s(z, z)/du = sum over the linear leaves of (dk_s(z, z)/dv_e) 2 amp_e w_e^2[D] (u - c_e[D])
+       reverse, f = top..0:  the input-gradient tiles of member f, which keep no derivative image (the leaves of a row are evaluated
+                             again and the tree's reverse sweep runs per row); upstream gm alpha_i - 2 gv B_iq for the points that
+                             stop at f, -gu alpha_i for those that stop above it, an exact 0 for the others;
+                             gu = (member f + 1's partials of its last input summed in chunk order) - gv su when level = f + 1,
+                             in that order
+       the owners' sum over (member, chunk) of the D coordinates of x, minus gv S, the outputs and the Adam update.
+   No atomics and no order of summation that depends on Q, on timing or on the grid: a + b steps through state_dev equal a + b steps
+   in one call bit for bit, and level = k everywhere is the chain cut after member k, bit for bit; cutting Q into several calls can
+   change the GEMM's tile choice and with it the last bits.  The loop stops enqueueing at the first refused launch and returns that
+   status.  FFGP_ERR_ARG, before anything is enqueued (Xq, state, trace, hist and grad untouched): everything
+   ffgp_acq_optimize_chain_tree refuses, with n outside 1..FFGP_ACQ_STAGED_MAX_N in place of its rule on n, and Q D beyond INT_MAX.
+   Synchronous.
+   Workspace, in doubles, with np_f, Qp and C as beside FFGP_ACQ_STAGED_MAX_N and DM = 2, 8 or 16 (the first that holds D + 1):
+       sum_f [ np_f^2  (L_f^-1)  +  3 n_f Qp  (K_s, V, B)  +  n_f^2 / 4 + 128 n_f + 16  (triangular inverse) ]
+       + F C Qp (2 + DM) + 3 Qp  (the chunk sums and the per-point values)  + Qp DM  (S)  + 28 F  (the leaf records, 224 bytes each)
+       + 1 + Qp  (the census word, su)
+   -- ffgp_acq_optimize_chain_staged's figure with three images per member instead of four.                                       */
+int ffgp_acq_optimize_chain_tree_staged(ffgp_handle* h, const ffgp_acq_chain* c, const ffgp_ktree* const* trees, double* Xq_dev, int Q,
+                                        int steps, const ffgp_adam* opt, double* state_dev, long step0, double* trace_dev, double* hist_dev,
+                                        double* grad_dev);
+
 /* Same, enqueue only: returns as soon as the work is on the handle's stream (nll/gradients are valid after
    ffgp_wait).  With one handle + stream per block, independent GP blocks (the fidelities of one model, the seeds
    of an experiment sweep) overlap on one GPU: one block's latency-bound factorisation tail runs under another

@@ -120,6 +120,15 @@ def check_acq_staged_chain_no_scratch():
     return sizes
 
 
+def check_acq_staged_chain_tree_no_scratch():
+    """the staged kernels for chains with composed-kernel members (K_s x 3, value, gradient x 3; the census is acq_staged_chain.hip's):
+    every one without a private segment"""
+    sizes = private_segments("acq_staged_chain_tree.hip", "ffgp_acq_staged_chain_tree_")
+    assert len(sizes) == 7, sorted(sizes)
+    assert all(v == 0 for v in sizes.values()), sizes
+    return sizes
+
+
 def check_acq_chain_tree_no_scratch():
     """the one-launch kernel for chains with composed-kernel members (D + 1 <= 2, 8, 16): every instantiation without a private segment"""
     sizes = private_segments("acq_chain_tree.hip", "ffgp_chain_tree_acq_kernel")
@@ -133,3 +142,4 @@ if __name__ == "__main__":
     print("sb2st_chase: counter stores behind an explicit vmcnt(0):", check_chase_publish())
     print("acq_staged_chain.hip: private segment sizes:", check_acq_staged_chain_no_scratch())
     print("acq_chain_tree.hip: private segment sizes:", check_acq_chain_tree_no_scratch())
+    print("acq_staged_chain_tree.hip: private segment sizes:", check_acq_staged_chain_tree_no_scratch())
