@@ -161,6 +161,15 @@ FFGP_ACQ_MAX_MEMBERS = 8
 FFGP_ACQ_MAX_N, FFGP_ACQ_MAX_D, FFGP_ACQ_MAX_STEPS = 256, 16, 4096      # include/ffgp.h
 FFGP_ACQ_STAGED_MAX_N = 2048     # ffgp_acq_optimize_stack_staged: images in handle workspace, not in LDS
 
+FFGP_PREDICT_SMALL_MAX_N, FFGP_PREDICT_SMALL_MAX_D, FFGP_PREDICT_SMALL_MAX_d = 128, 16, 16      # ffgp_predict_small_batch (include/ffgp.h)
+FFGP_PREDICT_SMALL_MAX_F = 256
+
+
+class PredictMember(C.Structure):
+    """ffgp_predict_member: one model's test points and outputs in ffgp_predict_small_batch"""
+    _fields_ = [("Xs_dev", _dp), ("nt", C.c_int), ("mean_dev", _dp), ("var_dev", _dp), ("var_add_noise", C.c_int)]
+
+
 LINK_ID, LINK_INV_ABS_EPS, LINK_EXP_NEG, LINK_INV, LINK_ABS, LINK_EXP_SQ, LINK_SQUARE = range(7)
 
 
@@ -265,6 +274,8 @@ EXPORTS = {
     "ffgp_nlml_fused_async": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.POINTER(Grads)]),
     "ffgp_wait": (C.c_int, [C.c_void_p]),
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),
+    "ffgp_predict_small_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(PredictMember),
+                                           C.POINTER(C.c_int)]),
     "ffgp_last_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int,
                                     C.POINTER(C.c_int)]),
     "ffgp_syrk_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long),

@@ -70,6 +70,26 @@ def negative_log_likelihood_many(models, xs, ys):
     return torch.stack(out)
 
 
+def forward_many(models, xs, ys, x_tests, state=None):
+    """[(mean [nt_f, d], var [nt_f, 1])]: what `m.forward(x, y, x_test)` gives under torch.no_grad() for every model, the covariance
+    reduced to its diagonal (what Experiments/calculate_metrix.py:43 reads) -- the end of the reference's experiment drivers, one
+    `gpr(x_train, y_train, x_test)` per fidelity, seed and training size (Experiments/GAR_Aligned/exp_aligned.py:63-107, ResGP.py:48-65,
+    AR_autoRegression.py:56-89), as ONE library call (`ffgp_predict_small_batch`: every model factored in LDS, its test points in tiles of
+    16, all in one launch).  A model shares the call when `F.raw_many_ok(m.kernel, x, y, m.log_beta)` holds (one library kernel with
+    constant profile parameters -- a RationalQuadraticKernel's learnable alpha is not --, everything on one GPU in fp64), N <= 128,
+    D <= 16, d <= 16 and its test points are [nt, D] on that GPU in fp64; any other member (a SumKernel, 129 points, CPU tensors) runs its
+    own `forward`, in the caller's order.  `y` may be `[y, y_var]`: y_var is dropped, as `forward` drops it.  The fused results are
+    views of one flat allocation; the models' posterior caches are not touched by the fused route.  state (a dict) receives "fused"
+    (the indices that shared the call) and "status" (per model 0, or the first non-positive pivot of a Sigma that is not positive
+    definite: NaN results); without it such a model raises torch.linalg.LinAlgError."""
+    return F.forward_many(models, xs, ys, x_tests, state, lambda m: m.log_beta, F._lib.LINK_EXP_NEG, JITTER, True, False)
+
+
+def forward_many_fused(models, xs, ys, x_tests):
+    """the indices of the models `forward_many` would serve from its one library call (nothing is computed)"""
+    return F.forward_many_members(models, xs, ys, x_tests, lambda m: m.log_beta, False)[1]
+
+
 class cigp(F.PosteriorCacheMixin, nn.Module):
     def __init__(self, kernel, log_beta):
         super().__init__()

@@ -108,6 +108,43 @@ int main() {
       EXPECT(ffgp_train_wide_raw(fk, 1, &pw, &lk, &rw, &dt, 3, &ad, &x, 8, 0, &x, 3, &inf) == FFGP_ERR_ARG);
       EXPECT(inf == 7);      // (a refused call writes nothing)
     }
+    // the batched prediction: every refusal comes before the handle is dereferenced or anything is enqueued or written
+    {
+      ffgp_handle* fk = reinterpret_cast<ffgp_handle*>(0x1);
+      ffgp_problem pp;
+      std::memset(&pp, 0, sizeof pp);
+      pp.n = 8; pp.D = 2; pp.d = 3; pp.X_dev = pp.Y_dev = pp.w_dev = pp.amp_dev = pp.diag_add_dev = &x;
+      pp.kfun = FFGP_KFUN_SE; pp.kparam = 1.0;
+      double out[2] = {7.0, 7.0};
+      ffgp_predict_member pm = {&x, 5, &out[0], &out[1], 1};
+      int sp = 7;
+      EXPECT(ffgp_predict_small_batch(nullptr, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_batch(fk, 1, nullptr, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, nullptr, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_batch(fk, 0, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_batch(fk, FFGP_PREDICT_SMALL_MAX_F + 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      pm.nt = 0;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, nullptr, &pm, &sp) == FFGP_ERR_ARG);
+      pm.nt = 5; pm.mean_dev = nullptr;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, nullptr, &pm, &sp) == FFGP_ERR_ARG);
+      pm.mean_dev = &out[0]; pm.Xs_dev = nullptr;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, nullptr, &pm, &sp) == FFGP_ERR_ARG);
+      pm.Xs_dev = &x; pp.n = FFGP_PREDICT_SMALL_MAX_N + 1;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.n = 8; pp.D = FFGP_PREDICT_SMALL_MAX_D + 1;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.D = 2; pp.d = FFGP_PREDICT_SMALL_MAX_d + 1;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.d = 3; pp.diag_vec_dev = &x;      // the predict paths drop y_var
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.diag_vec_dev = nullptr; pp.add_all = 0.5;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.add_all = 0.0; pp.kfun = FFGP_KFUN_RQ + 1;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.kfun = FFGP_KFUN_SE; pp.Y_dev = nullptr;
+      EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(sp == 7 && out[0] == 7.0 && out[1] == 7.0);      // (a refused call writes nothing)
+    }
     ffgp_kdesc kd[2];
     ffgp_kdesc_grads kg[2];
     std::memset(kd, 0, sizeof kd);

@@ -27,6 +27,21 @@ def _split(y_train):
     return y_train, None
 
 
+def forward_many(models, xs, ys, x_tests, state=None):
+    """`cigp_v10.forward_many` for GP_basic models: [(mean [nt_f, d], var [nt_f, 1])], the posterior of `m.forward(x, y, x_test)` under
+    torch.no_grad() with the covariance reduced to its diagonal and the mean kept as [nt, d] (forward squeezes it).  Sigma = K +
+    noise_variance^2 I and nothing is added to the variance (gp_basic.py:78-84).  A member given `[y, y_var]` runs its own `forward`
+    (GP_basic adds the FULL y_var matrix to Sigma), as does any member outside the fused call's limits (`cigp_v10.forward_many`).  A
+    FidelityKernelMCMC kernel takes the raw or effective route `F.raw_many_ok` gives it; it has no `links()` -- its amplitude carries
+    the Monte-Carlo fidelity integral, formed on the host -- so today that is neither and such a member runs its own `forward`."""
+    return F.forward_many(models, xs, ys, x_tests, state, lambda m: m.noise_variance, F._lib.LINK_SQUARE, 0.0, False, True)
+
+
+def forward_many_fused(models, xs, ys, x_tests):
+    """the indices of the models `forward_many` would serve from its one library call (nothing is computed)"""
+    return F.forward_many_members(models, xs, ys, x_tests, lambda m: m.noise_variance, True)[1]
+
+
 class GP_basic(F.PosteriorCacheMixin, nn.Module):
     def __init__(self, kernel, noise_variance):
         super().__init__()

@@ -582,6 +582,118 @@ def predict(X, Y, Xs, w, amp, diag_add=None, diag_vec=None, add_mat=None, add_al
     return mean.to(device=Y.device, dtype=odt), var.to(device=Y.device, dtype=odt)
 
 
+def forward_many_route(kernel, x_train, y_train, x_test, noise_param):
+    """the kernel's `links()` when (x_train, y_train, x_test) of a model with this kernel and raw noise parameter can be a member of
+    `predict_raw_many` (ffgp_predict_small_batch), else None: `raw_many_ok` -- one radial-profile library kernel with constant profile
+    parameters, everything on one GPU in fp64 -- within the kernel's limits (n <= 128, D <= 16, d <= 16), and test points [nt >= 1, D] on
+    the same GPU in fp64"""
+    if not isinstance(x_train, torch.Tensor) or not isinstance(y_train, torch.Tensor) or not isinstance(x_test, torch.Tensor):
+        return None
+    with torch.no_grad():      # (prediction: parameters that require grad do not close the raw route)
+        lk = raw_many_ok(kernel, x_train, y_train, noise_param)
+    if lk is None:
+        return None
+    n, D = x_train.shape
+    if not 1 <= n <= _lib.FFGP_PREDICT_SMALL_MAX_N or not 1 <= D <= _lib.FFGP_PREDICT_SMALL_MAX_D:
+        return None
+    if not 1 <= y_train.shape[1] <= _lib.FFGP_PREDICT_SMALL_MAX_d:
+        return None
+    if not raw_ok(x_test) or x_test.device != x_train.device or x_test.dim() != 2 or x_test.shape[1] != D or x_test.shape[0] < 1:
+        return None
+    return lk
+
+
+@torch.no_grad()
+def predict_raw_many(items):
+    """items: dicts {X, Y, Xs, lk (the kernel's `links()`), rdadd, dadd_link, dadd_c, add_noise}, each passed by `forward_many_route`, all on
+    one GPU -- the posteriors of F small models at their own test points by ONE library call (ffgp_predict_small_batch; one call per
+    FFGP_PREDICT_SMALL_MAX_F members).  Returns ([(mean [nt, d], var [nt, 1])] as views of one flat allocation, [status]): a member
+    whose Sigma is not positive definite has its failing pivot as status and NaN outputs.  No host synchronisation, no torch kernel
+    and no `.item()` before the call: pointers and sizes only."""
+    nF = len(items)
+    dev = items[0]["X"].device
+    h = _lib.handle(dev.index, 0)
+    _lib.bind_stream(h, dev.index)
+    sizes = [(it["Xs"].shape[0], it["Y"].shape[1]) for it in items]
+    flat = torch.empty((sum(nt * (d + 1) for nt, d in sizes),), dtype=torch.float64, device=dev)
+    P, L, M = (Problem * nF)(), (_lib.Links * nF)(), (_lib.PredictMember * nF)()
+    out, off, base = [], 0, flat.data_ptr()
+    for f, it in enumerate(items):
+        X, Y, Xs, lk = it["X"], it["Y"], it["Xs"], it["lk"]
+        (n, D), (nt, d) = X.shape, sizes[f]
+        p, l, m = P[f], L[f], M[f]
+        p.n, p.D, p.d = n, D, d
+        p.X_dev, p.Y_dev, p.w_dev, p.amp_dev, p.diag_add_dev = X.data_ptr(), Y.data_ptr(), lk["w"].data_ptr(), lk["amp"].data_ptr(), it["rdadd"].data_ptr()
+        p.clamp_min, p.kfun = lk["clamp"], lk["kfun"]
+        kp = lk.get("kparam")
+        p.kparam = 1.0 if kp is None else float(kp)
+        p.ll_variant, p.pi_const = FFGP_LL_V1, PI_TRUNC
+        l.w_link, l.w_c, l.w_broadcast = lk["w_link"], lk["w_c"], 1 if lk["w"].numel() == 1 and D > 1 else 0
+        l.amp_link, l.amp_c = lk["amp_link"], 0.0
+        l.dadd_link, l.dadd_c, l.out_scale = it["dadd_link"], it["dadd_c"], 1.0
+        m.Xs_dev, m.nt = Xs.data_ptr(), nt
+        m.mean_dev, m.var_dev = base + 8 * off, base + 8 * (off + nt * d)
+        m.var_add_noise = 1 if it["add_noise"] else 0
+        out.append((flat[off:off + nt * d].view(nt, d), flat[off + nt * d:off + nt * (d + 1)].view(nt, 1)))
+        off += nt * (d + 1)
+    status = (C.c_int * nF)()
+    cap = _lib.FFGP_PREDICT_SMALL_MAX_F
+    for lo in range(0, nF, cap):
+        k = min(cap, nF - lo)
+        view = lambda arr, typ: C.cast(C.byref(arr, lo * C.sizeof(typ)), C.POINTER(typ))
+        check(lib.ffgp_predict_small_batch(h, k, view(P, Problem), view(L, _lib.Links), view(M, _lib.PredictMember), view(status, C.c_int)),
+              "ffgp_predict_small_batch")
+    return out, list(status)
+
+
+def forward_many_members(models, xs, ys, x_tests, noise_of, takes_y_var):
+    """(items, fused): the members of a `forward_many` call that share the library call -- those `forward_many_route` accepts, on the
+    GPU of the first one it accepts -- as `predict_raw_many` items without their noise link, and their indices in the caller's order"""
+    items, fused = [], []
+    for i, (m, x, y, xt) in enumerate(zip(models, xs, ys, x_tests)):
+        if isinstance(y, list):
+            if takes_y_var:
+                continue
+            y = y[0]
+        lk = forward_many_route(m.kernel, x, y, xt, noise_of(m))
+        if lk is None or (items and x.device != items[0]["X"].device):
+            continue
+        items.append({"X": x, "Y": y, "Xs": xt, "lk": lk, "rdadd": noise_of(m)})
+        fused.append(i)
+    return items, fused
+
+
+def forward_many(models, xs, ys, x_tests, state, noise_of, dadd_link, dadd_c, add_noise, takes_y_var):
+    """The body of `cigp_v10.forward_many` and `gp_basic.forward_many`: [(mean [nt_f, d], var [nt_f, 1])] in the caller's order.  Members
+    that `forward_many_route` accepts (all on the GPU of the first one that does) share ONE library call; the others run
+    `m.forward(x, y, x_test)` under no_grad, one after the other, and give its covariance's diagonal.  noise_of(m): the raw noise
+    parameter; takes_y_var: a `[y, y_var]` member's forward uses y_var (GP_basic adds the full matrix), so it falls back -- otherwise
+    y_var is dropped, as the module's forward drops it.  state (a dict, optional) receives "fused": the members that shared the call, and
+    "status": per member 0 or the first non-positive pivot of its Sigma (NaN results).  Without a state dict such a member raises
+    torch.linalg.LinAlgError, as the per-model loop would."""
+    items, fused = forward_many_members(models, xs, ys, x_tests, noise_of, takes_y_var)
+    for it in items:
+        it.update(dadd_link=dadd_link, dadd_c=dadd_c, add_noise=add_noise)
+    out = [None] * len(models)
+    status = [0] * len(models)
+    if items:
+        res, st = predict_raw_many(items)
+        for k, i in enumerate(fused):
+            out[i], status[i] = res[k], st[k]
+    with torch.no_grad():
+        for i, (m, x, y, xt) in enumerate(zip(models, xs, ys, x_tests)):
+            if out[i] is None:
+                mean, cov = m.forward(x, y, xt)
+                out[i] = (mean.reshape(xt.shape[0], -1), cov.diagonal().reshape(-1, 1))
+    if state is not None:
+        state["fused"], state["status"] = fused, status
+    else:
+        for i in fused:
+            if status[i] > 0:
+                _raise_not_pd(status[i], "linalg.cholesky (model %d of forward_many)" % i)
+    return out
+
+
 class _NLMLPair(torch.autograd.Function):
     """nlml() for a composed kernel: the composition is assembled straight into the factorisation's buffer and its gradient tile
     reads G once (ffgp_problem.tree / ffgp_grads.g_pair)."""

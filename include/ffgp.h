@@ -1210,6 +1210,37 @@ int ffgp_wait(ffgp_handle* h);
 int ffgp_predict(ffgp_handle* h, const ffgp_problem* p, const double* Xs_dev, int nt, int var_mode,
                  double var_add_all, double* mean_dev, double* var_dev, int ldv);
 
+/* The posteriors of F independent SMALL models at their own test points in ONE launch: what the reference's experiment drivers end with,
+   one `gpr(x_train, y_train, x_test)` per fidelity, seed and training size (Experiments/GAR_Aligned/exp_aligned.py:63-107, ResGP.py:48-65,
+   AR_autoRegression.py:56-89, CAR_ContinuousAutoRegression.py:94-114) -- after ffgp_train_raw the last per-model launch chain of a sweep.
+   p[f] / links[f] describe model f exactly as for ffgp_nlml_fused_small_batch (raw parameters with links, or links == NULL for
+   effective parameters); ll_variant and pi_const are ignored, as in ffgp_predict.  Limits per member: n <= FFGP_PREDICT_SMALL_MAX_N,
+   D <= FFGP_PREDICT_SMALL_MAX_D, d <= FFGP_PREDICT_SMALL_MAX_d, one radial-profile kernel (kfun SE ... RQ with a constant kparam),
+   diag_add as the only Sigma extra (no diag_vec / add_mat / add_all / mean_jitter, no caller-built covariance, no composed kernel: the
+   reference's predict paths drop y_var).  1 <= F <= FFGP_PREDICT_SMALL_MAX_F.
+   m[f]: the test points of model f and where its results go: mean_dev[nt, d] = K_s^T Sigma^-1 Y, var_dev[nt] = k(x, x) - colsum(V^2),
+   V = L^-1 K_s, plus -- var_add_noise = 1 -- the value of the diag_add link WITHOUT its constant dadd_c (cigp.forward's 1/beta,
+   cigp_v10.py:41-44, where Sigma carries 1/beta + jitter); 0 adds nothing (GP_basic.forward, gp_basic.py:78-84).
+   The grid is (F, S): each of the S workgroups of a model factors it in LDS (the stages of the one-launch trainer, csrc/train_tile.h)
+   and takes a fixed share of the model's tiles of 16 test points; S follows from F and the largest nt.  A point's mean and variance do not
+   depend on S, on its tile or on the other points of the call, bit for bit.  (FFGP_PREDICT_SPLIT=k in the environment, read at every
+   call, forces S = min(k, tiles): for tests.)
+   A member whose Sigma is not positive definite stops alone: status[f] (host, may be NULL) = the 1-based index of its first non-positive
+   pivot and its outputs are NaN; the others complete.  Returns the first non-zero status, or FFGP_ERR_ARG -- before anything is enqueued
+   or written -- for null pointers, a member outside the limits, nt < 1 or F outside its range.  Synchronous.                          */
+#define FFGP_PREDICT_SMALL_MAX_N 128
+#define FFGP_PREDICT_SMALL_MAX_D 16
+#define FFGP_PREDICT_SMALL_MAX_d 16
+#define FFGP_PREDICT_SMALL_MAX_F 256
+typedef struct ffgp_predict_member {
+  const double* Xs_dev; int nt;      /* [nt, D] test points of THIS model */
+  double* mean_dev;                  /* [nt, d] */
+  double* var_dev;                   /* [nt]  diagonal variance */
+  int var_add_noise;                 /* 1: add the diag_add link's value without its constant dadd_c; 0: add nothing */
+} ffgp_predict_member;
+int ffgp_predict_small_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, const ffgp_predict_member* m,
+                             int* status);
+
 /* ---- multi-GPU: the joint likelihood of sharded blocks --------------------------------------------------- */
 /* buf_dev[0..count) <- element-wise SUM over the ranks of `comm` (in place, fp64), enqueued on the handle's stream: the ONE
    collective of the per-fidelity sharding -- the F-vector of per-block values, `loss += cigp_list[f].compute_loss(...)`
