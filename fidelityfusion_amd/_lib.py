@@ -276,6 +276,8 @@ EXPORTS = {
     "ffgp_predict": (C.c_int, [C.c_void_p, C.POINTER(Problem), _dp, C.c_int, C.c_int, C.c_double, _dp, _dp, C.c_int]),
     "ffgp_predict_small_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(Links), C.POINTER(PredictMember),
                                            C.POINTER(C.c_int)]),
+    "ffgp_predict_small_tree_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Problem), C.POINTER(TreeLinks), C.POINTER(PredictMember),
+                                                C.POINTER(C.c_int)]),
     "ffgp_last_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.c_int,
                                     C.POINTER(C.c_int)]),
     "ffgp_syrk_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_long),

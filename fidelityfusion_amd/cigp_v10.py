@@ -90,6 +90,25 @@ def forward_many_fused(models, xs, ys, x_tests):
     return F.forward_many_members(models, xs, ys, x_tests, lambda m: m.log_beta, False)[1]
 
 
+def forward_many_composed(models, xs, ys, x_tests, state=None):
+    """`forward_many` with the composed-kernel members served from one launch too: the same return value, the radial members through
+    the same `ffgp_predict_small_batch` call (bit-identical results), and the SumKernel / ProductKernel members -- every cigp demo of
+    the reference runs on SumKernel(LinearKernel, MaternKernel), cigp_v10.py:81,111,147 -- through ONE `ffgp_predict_small_tree_batch`
+    call (per 256 members) instead of their own `forward`.  A composed member shares it when `kernel.tree_links()` applies (2-4 library
+    leaves, no learnable profile parameter), every leaf parameter, log_beta, x, y and x_test are fp64, contiguous and on one GPU,
+    N <= 128, D <= 16, d <= 16, nt >= 1; everything else runs its own `forward`.  No model's posterior cache is touched.  state (a dict)
+    receives "fused" (every member a library call served), "fused_composed" (those of the composed call) and "status" as
+    `forward_many`; without it a member whose Sigma is not positive definite raises torch.linalg.LinAlgError."""
+    return F.forward_many(models, xs, ys, x_tests, state, lambda m: m.log_beta, F._lib.LINK_EXP_NEG, JITTER, True, False, composed=True)
+
+
+def forward_many_composed_fused(models, xs, ys, x_tests):
+    """(fused, fused_composed): the indices `forward_many_composed` would serve from a library call, and those of them the
+    composed-kernel call would serve (nothing is computed)"""
+    _, fused, _, tfused = F.forward_many_composed_members(models, xs, ys, x_tests, lambda m: m.log_beta, False)
+    return sorted(fused + tfused), tfused
+
+
 class cigp(F.PosteriorCacheMixin, nn.Module):
     def __init__(self, kernel, log_beta):
         super().__init__()

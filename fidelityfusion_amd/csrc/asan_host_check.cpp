@@ -145,6 +145,62 @@ int main() {
       EXPECT(ffgp_predict_small_batch(fk, 1, &pp, &lk, &pm, &sp) == FFGP_ERR_ARG);
       EXPECT(sp == 7 && out[0] == 7.0 && out[1] == 7.0);      // (a refused call writes nothing)
     }
+    // ... and its composed-kernel form: the same refusals, and those about the tree
+    {
+      ffgp_handle* fk = reinterpret_cast<ffgp_handle*>(0x1);
+      ffgp_kdesc lf[5];
+      std::memset(lf, 0, sizeof lf);
+      for (auto& k : lf) { k.kfun = FFGP_KFUN_MATERN52; k.w_dev = k.amp_dev = &x; k.kparam = 1.0; }
+      lf[0].kfun = FFGP_KFUN_LINEAR; lf[0].center_dev = &x;
+      ffgp_ktree tq;
+      std::memset(&tq, 0, sizeof tq);
+      tq.n_leaves = 2; tq.leaf = lf;
+      ffgp_tree_links tlk;
+      std::memset(&tlk, 0, sizeof tlk);
+      ffgp_problem pp;
+      std::memset(&pp, 0, sizeof pp);
+      pp.n = 8; pp.D = 2; pp.d = 3; pp.X_dev = pp.Y_dev = pp.diag_add_dev = &x;
+      pp.tree = &tq;
+      double out[2] = {7.0, 7.0};
+      ffgp_predict_member pm = {&x, 5, &out[0], &out[1], 1};
+      int sp = 7;
+      EXPECT(ffgp_predict_small_tree_batch(nullptr, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, nullptr, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, nullptr, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_tree_batch(fk, 0, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(ffgp_predict_small_tree_batch(fk, FFGP_PREDICT_SMALL_MAX_F + 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pm.nt = 0;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, nullptr, &pm, &sp) == FFGP_ERR_ARG);
+      pm.nt = 5; pm.var_dev = nullptr;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, nullptr, &pm, &sp) == FFGP_ERR_ARG);
+      pm.var_dev = &out[1]; pp.n = FFGP_PREDICT_SMALL_MAX_N + 1;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.n = 8; pp.D = FFGP_PREDICT_SMALL_MAX_D + 1;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.D = 2; pp.d = FFGP_PREDICT_SMALL_MAX_d + 1;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.d = 3; pp.tree = nullptr;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.tree = &tq; tq.n_leaves = 5;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      tq.n_leaves = 4; tq.shape = 2;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      tq.shape = FFGP_TREE_BALANCED; tq.op[1] = 2;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      tq.op[1] = FFGP_KOP_PRODUCT; lf[3].kfun = FFGP_KFUN_RQ;      // a learnable profile parameter
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      lf[3].kfun = FFGP_KFUN_SE; lf[2].amp_dev = nullptr;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      lf[2].amp_dev = &x; pp.diag_vec_dev = &x;      // the predict paths drop y_var
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.diag_vec_dev = nullptr; pp.add_all = 0.5;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.add_all = 0.0; pp.diag_add_dev = nullptr;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, &tlk, &pm, &sp) == FFGP_ERR_ARG);
+      pp.diag_add_dev = &x; pp.Y_dev = nullptr;
+      EXPECT(ffgp_predict_small_tree_batch(fk, 1, &pp, nullptr, &pm, &sp) == FFGP_ERR_ARG);
+      EXPECT(sp == 7 && out[0] == 7.0 && out[1] == 7.0);      // (a refused call writes nothing)
+    }
     ffgp_kdesc kd[2];
     ffgp_kdesc_grads kg[2];
     std::memset(kd, 0, sizeof kd);

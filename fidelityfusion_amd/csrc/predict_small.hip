@@ -15,7 +15,7 @@
 // images: every sum that forms its mean and variance runs over the training points in an order fixed by the model's size alone, so the
 // results do not depend on S, on the point's tile or on the other points, bit for bit.
 // A member whose Sigma is not positive definite stops alone: NaN outputs, its status word set by its workgroup 0.
-#include "train_host.h"
+#include "predict_small.h"
 
 struct PredictModel {
   int n, D, d;
@@ -213,14 +213,12 @@ __global__ __launch_bounds__(TR_T) void ffgp_predict_small_kernel(const PredictM
 }
 
 static bool ps_member_ok(const ffgp_problem& q, const ffgp_predict_member& m) {
-  if (q.n <= 0 || q.n > FFGP_PREDICT_SMALL_MAX_N || q.D <= 0 || q.D > FFGP_PREDICT_SMALL_MAX_D || q.d <= 0 || q.d > FFGP_PREDICT_SMALL_MAX_d) return false;
+  if (!ps_sizes_ok(q, m)) return false;
   if (q.cov_dev || q.pair || q.tree || q.add_mat_dev || q.diag_vec_dev || q.add_all != 0.0 || q.mean_jitter != 0.0) return false;
   if (!q.X_dev || !q.Y_dev || !q.w_dev || !q.amp_dev) return false;
   if (q.kfun < FFGP_KFUN_SE || q.kfun > FFGP_KFUN_RQ) return false;
-  return m.Xs_dev && m.mean_dev && m.var_dev && m.nt >= 1;
+  return true;
 }
-
-static_assert(FFGP_PREDICT_SMALL_MAX_N == TR_N && FFGP_PREDICT_SMALL_MAX_D == TR_D && FFGP_PREDICT_SMALL_MAX_d == TR_Y, "the header's limits are the trainer's images");
 
 extern "C" int ffgp_predict_small_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* l, const ffgp_predict_member* m, int* status) {
   if (!h || !p || !m || F < 1 || F > FFGP_PREDICT_SMALL_MAX_F) return FFGP_ERR_ARG;
@@ -230,10 +228,7 @@ extern "C" int ffgp_predict_small_batch(ffgp_handle* h, int F, const ffgp_proble
     Dmax = std::max(Dmax, p[f].D);
     tiles = std::max(tiles, (m[f].nt + 15) / 16);
   }
-  // S: enough workgroups for the chip's 256 CUs when the models alone do not fill it, never more than the largest member has tiles
-  int split = std::min(tiles, std::max(1, 256 / F));
-  if (const char* e = getenv("FFGP_PREDICT_SPLIT"))
-    if (atoi(e) > 0) split = std::min(tiles, atoi(e));
+  const int split = ps_split(F, tiles);
   FFGP_HIP(hipSetDevice(h->device));
   // the call's block (train_host.h): the table of F models and the status words; no steps, no scratch
   TrainLayout lay;
@@ -269,14 +264,5 @@ extern "C" int ffgp_predict_small_batch(ffgp_handle* h, int F, const ffgp_proble
     hipLaunchKernelGGL(kernel, dim3(F, split), dim3(TR_T), lds_bytes, h->stream, tab, info);
     return hipGetLastError() == hipSuccess ? FFGP_OK : FFGP_ERR_HIP;
   }));
-  // the status words back (the models' parameters did not move: the handle's cached factors stay valid)
-  int* st = reinterpret_cast<int*>(blk.host + blk.info_off);
-  FFGP_HIP(hipMemcpyAsync(st, info, (size_t)F * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  FFGP_HIP(hipStreamSynchronize(h->stream));
-  int rc = FFGP_OK;
-  for (int f = 0; f < F; ++f) {
-    if (status) status[f] = st[f];
-    if (rc == FFGP_OK && st[f] != 0) rc = st[f];
-  }
-  return rc;
+  return ps_finish(h, blk, F, status);
 }

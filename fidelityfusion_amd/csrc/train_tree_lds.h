@@ -126,6 +126,24 @@ __device__ __forceinline__ double ttl_form(bool lin, const double* xi, const dou
     arr[3] = (e) == 3 ? (x) : arr[3]; \
   } while (0)
 
+// One entry of the composed covariance: per leaf the form on rows xi, xj, amp_e phi_e of it (a linear leaf: amp_e times the form), then the
+// tree -- the assembly's entry (phase P1 of ttl_body) and, in predict_small_tree.hip, Sigma's and K_s's.  tr: nl, shape, op[3]; kfi, lp, w2,
+// cen: the leaf tables in LDS.  The leaf loop is not unrolled: one leaf's form is live at a time.
+template <int DM, class TREE>
+__device__ __forceinline__ double ttl_entry(const TREE& tr, const int* kfi, const double* lp, const double* w2, const double* cen, const double* xi,
+                                            const double (&xj)[DM]) {
+  double v[TTL_L] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+  for (int e = 0; e < tr.nl; ++e) {
+    const int kf = tr_lds_int(kfi + e);
+    const bool lin = kf == FFGP_KFUN_LINEAR;
+    const double s = ttl_form<DM>(lin, xi, xj, w2 + e * TR_D, cen + e * TR_D);
+    const double val = lp[4 * e] * (lin ? s : ffgp_kfun_val(kf, lp[4 * e + 2], fmax(s, lp[4 * e + 1])));
+    TTL_PUT(v, e, val);
+  }
+  return ffgp_tree_eval(tr, v);
+}
+
 // DM: the input dimensions the per-entry loops are unrolled for (8 or 16: every model of the launch has D <= DM; the padded
 // dimensions hold zeros and add nothing, so a model's arithmetic does not depend on which instantiation runs it)
 // V2: the FFGP_LL_V2 likelihood (B = Sigma^-1 A by the two block chains once more; the targets' image receives B, so the targets are
@@ -304,17 +322,7 @@ __device__ __forceinline__ void ttl_body(const MODEL* __restrict__ tab, TtlCommo
 #pragma unroll 1
         for (int r = 0; r < 4; ++r) {
           const int i = bi * 16 + g + 4 * r;
-          const double* xi = Xs + i * (TR_D + 1);
-          double v[TTL_L] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 1
-          for (int e = 0; e < tr.nl; ++e) {
-            const int kf = tr_lds_int(kfi + e);
-            const bool lin = kf == FFGP_KFUN_LINEAR;
-            const double s = ttl_form<DM>(lin, xi, xj, w2 + e * TR_D, cen + e * TR_D);
-            const double val = lp[4 * e] * (lin ? s : ffgp_kfun_val(kf, lp[4 * e + 2], fmax(s, lp[4 * e + 1])));
-            TTL_PUT(v, e, val);
-          }
-          double kv = ffgp_tree_eval(tr, v);
+          double kv = ttl_entry<DM>(tr, kfi, lp, w2, cen, Xs + i * (TR_D + 1), xj);
           if (i == j) {
             kv += dadd;
             kv += dvec[i];

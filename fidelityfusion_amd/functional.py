@@ -25,7 +25,7 @@ from .linalg import (_CondGauss, _EighSmall, _GaussNLLFromCov, _gemm, _KernelMat
                      add_diagonal, cholesky, cholesky_with_rows, conditional_gaussian, eigh_small, gaussian_ll_v2,
                      gaussian_nll_from_cov, kernel_matrix, kernel_on_device, kernel_pair, matmul_nt, rows_in)
 from .nlml import (RAGGED_CHAIN_MAX_N, SMALL_BATCH_MAX_d, SMALL_BATCH_MAX_D, SMALL_BATCH_MAX_N, _NLML, _NLMLPair, _NLMLRaw, _NLMLRawMany, _problem, _raw_pending,
-                   _settle_raw, forward_many, forward_many_members, forward_many_route, many_batchable, nlml, nlml_many, nlml_pair, nlml_raw, nlml_raw_many, pair_inputs_plain, predict, predict_raw_many, raw_many_ok,
+                   _settle_raw, forward_many, forward_many_composed_members, forward_many_members, forward_many_route, forward_many_tree_route, many_batchable, nlml, nlml_many, nlml_pair, nlml_raw, nlml_raw_many, pair_inputs_plain, predict, predict_raw_many, predict_tree_many, raw_many_ok,
                    raw_ok, raw_path)
 from .posterior import Posterior, PosteriorCache, PosteriorCacheMixin, PosteriorChain, PosteriorStack, _PosteriorQuery
 

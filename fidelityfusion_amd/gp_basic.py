@@ -42,6 +42,20 @@ def forward_many_fused(models, xs, ys, x_tests):
     return F.forward_many_members(models, xs, ys, x_tests, lambda m: m.noise_variance, True)[1]
 
 
+def forward_many_composed(models, xs, ys, x_tests, state=None):
+    """`cigp_v10.forward_many_composed` for GP_basic models: the SumKernel / ProductKernel members share ONE
+    `ffgp_predict_small_tree_batch` call with Sigma = K + noise_variance^2 I (LINK_SQUARE, constant 0) and nothing added to the
+    variance; the radial members and the fall-backs are `forward_many`'s."""
+    return F.forward_many(models, xs, ys, x_tests, state, lambda m: m.noise_variance, F._lib.LINK_SQUARE, 0.0, False, True, composed=True)
+
+
+def forward_many_composed_fused(models, xs, ys, x_tests):
+    """(fused, fused_composed): the indices `forward_many_composed` would serve from a library call, and those of them the
+    composed-kernel call would serve (nothing is computed)"""
+    _, fused, _, tfused = F.forward_many_composed_members(models, xs, ys, x_tests, lambda m: m.noise_variance, True)
+    return sorted(fused + tfused), tfused
+
+
 class GP_basic(F.PosteriorCacheMixin, nn.Module):
     def __init__(self, kernel, noise_variance):
         super().__init__()

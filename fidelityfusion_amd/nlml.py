@@ -663,32 +663,146 @@ def forward_many_members(models, xs, ys, x_tests, noise_of, takes_y_var):
     return items, fused
 
 
-def forward_many(models, xs, ys, x_tests, state, noise_of, dadd_link, dadd_c, add_noise, takes_y_var):
+def forward_many_tree_route(kernel, x_train, y_train, x_test, noise_param):
+    """`kernel.tree_links()` when (x_train, y_train, x_test) of a model with this composed kernel and raw noise parameter can be a member
+    of `predict_tree_many` (ffgp_predict_small_tree_batch), else None: a SumKernel / ProductKernel composition with `tree_links()` (2-4
+    library leaves, no learnable profile parameter), every leaf parameter, the noise parameter, x, y and x_test fp64, contiguous and on
+    one GPU, n <= 128, D <= 16, d <= 16, nt >= 1, `w` of 1 or D entries and a centre of D entries.  `requires_grad` on parameters does not
+    matter: the route runs under no_grad."""
+    if not isinstance(x_train, torch.Tensor) or not isinstance(y_train, torch.Tensor) or not isinstance(x_test, torch.Tensor):
+        return None
+    tl = kernel.tree_links() if hasattr(kernel, "tree_links") else None
+    if tl is None:
+        return None
+    pars = [t for lk in tl[2] for t in (lk["w"], lk["amp"], lk.get("center")) if t is not None]
+    if not raw_ok(x_train, y_train, x_test, noise_param, *pars):
+        return None
+    if x_train.dim() != 2 or y_train.dim() != 2 or x_train.shape[0] != y_train.shape[0] or noise_param.numel() != 1:
+        return None
+    n, D = x_train.shape
+    if not 1 <= n <= _lib.FFGP_PREDICT_SMALL_MAX_N or not 1 <= D <= _lib.FFGP_PREDICT_SMALL_MAX_D:
+        return None
+    if not 1 <= y_train.shape[1] <= _lib.FFGP_PREDICT_SMALL_MAX_d:
+        return None
+    if x_test.dim() != 2 or x_test.shape[1] != D or x_test.shape[0] < 1:
+        return None
+    for lk in tl[2]:
+        if lk["w"].numel() not in (1, D) or lk["amp"].numel() != 1 or (lk.get("center") is not None and lk["center"].numel() != D):
+            return None
+    return tl
+
+
+@torch.no_grad()
+def predict_tree_many(items):
+    """`predict_raw_many` for composed-kernel members: items {X, Y, Xs, tl (the kernel's `tree_links()`), rdadd, dadd_link, dadd_c,
+    add_noise}, each passed by `forward_many_tree_route`, all on one GPU -- ONE ffgp_predict_small_tree_batch call per
+    FFGP_PREDICT_SMALL_MAX_F members, the leaves on their raw parameters.  Returns ([(mean [nt, d], var [nt, 1])] as views of one flat
+    allocation, [status]).  No host synchronisation, no torch kernel and no `.item()` before the call: pointers and sizes only."""
+    nF = len(items)
+    dev = items[0]["X"].device
+    h = _lib.handle(dev.index, 0)
+    _lib.bind_stream(h, dev.index)
+    sizes = [(it["Xs"].shape[0], it["Y"].shape[1]) for it in items]
+    flat = torch.empty((sum(nt * (d + 1) for nt, d in sizes),), dtype=torch.float64, device=dev)
+    P, L, M = (Problem * nF)(), (_lib.TreeLinks * nF)(), (_lib.PredictMember * nF)()
+    out, keep, off, base = [], [], 0, flat.data_ptr()
+    for f, it in enumerate(items):
+        X, Y, Xs = it["X"], it["Y"], it["Xs"]
+        _, (shape, ops), lks = it["tl"]
+        (n, D), (nt, d) = X.shape, sizes[f]
+        p, tk, m = P[f], L[f], M[f]
+        p.n, p.D, p.d = n, D, d
+        p.X_dev, p.Y_dev, p.diag_add_dev = X.data_ptr(), Y.data_ptr(), it["rdadd"].data_ptr()
+        p.ll_variant, p.pi_const = FFGP_LL_V1, PI_TRUNC
+        arr, tree = (KDesc * len(lks))(), _lib.KTree()
+        for e, lk in enumerate(lks):
+            arr[e].kfun, arr[e].clamp_min, arr[e].kparam = lk["kfun"], lk["clamp"], float(lk.get("kparam", 1.0))
+            arr[e].w_dev, arr[e].amp_dev = lk["w"].data_ptr(), lk["amp"].data_ptr()
+            le = tk.leaf[e]
+            le.w_link, le.w_c, le.w_broadcast = lk["w_link"], lk["w_c"], 1 if lk["w"].numel() == 1 and D > 1 else 0
+            le.amp_link, le.amp_c = lk["amp_link"], 0.0
+            if lk.get("center") is not None:
+                arr[e].center_dev = lk["center"].data_ptr()
+        tree.n_leaves, tree.shape, tree.leaf = len(lks), shape, arr
+        for i, o in enumerate(ops):
+            tree.op[i] = o
+        p.tree = C.pointer(tree)
+        keep += [arr, tree]
+        tk.dadd_link, tk.dadd_c, tk.out_scale = it["dadd_link"], it["dadd_c"], 1.0
+        m.Xs_dev, m.nt = Xs.data_ptr(), nt
+        m.mean_dev, m.var_dev = base + 8 * off, base + 8 * (off + nt * d)
+        m.var_add_noise = 1 if it["add_noise"] else 0
+        out.append((flat[off:off + nt * d].view(nt, d), flat[off + nt * d:off + nt * (d + 1)].view(nt, 1)))
+        off += nt * (d + 1)
+    status = (C.c_int * nF)()
+    cap = _lib.FFGP_PREDICT_SMALL_MAX_F
+    for lo in range(0, nF, cap):
+        k = min(cap, nF - lo)
+        view = lambda arr, typ: C.cast(C.byref(arr, lo * C.sizeof(typ)), C.POINTER(typ))
+        check(lib.ffgp_predict_small_tree_batch(h, k, view(P, Problem), view(L, _lib.TreeLinks), view(M, _lib.PredictMember),
+                                                view(status, C.c_int)), "ffgp_predict_small_tree_batch")
+    return out, list(status)
+
+
+def forward_many_composed_members(models, xs, ys, x_tests, noise_of, takes_y_var):
+    """(items, fused, tree items, fused_composed): `forward_many_members`' radial members, exactly as `forward_many` takes them, and the
+    composed-kernel members `forward_many_tree_route` accepts -- on the GPU of the first member either route accepted -- as
+    `predict_tree_many` items without their noise link, with their indices in the caller's order"""
+    items, fused = forward_many_members(models, xs, ys, x_tests, noise_of, takes_y_var)
+    titems, tfused = [], []
+    dev = items[0]["X"].device if items else None
+    for i, (m, x, y, xt) in enumerate(zip(models, xs, ys, x_tests)):
+        if i in fused:
+            continue
+        if isinstance(y, list):
+            if takes_y_var:
+                continue
+            y = y[0]
+        tl = forward_many_tree_route(m.kernel, x, y, xt, noise_of(m))
+        if tl is None or (dev is not None and x.device != dev):
+            continue
+        dev = x.device
+        titems.append({"X": x, "Y": y, "Xs": xt, "tl": tl, "rdadd": noise_of(m)})
+        tfused.append(i)
+    return items, fused, titems, tfused
+
+
+def forward_many(models, xs, ys, x_tests, state, noise_of, dadd_link, dadd_c, add_noise, takes_y_var, composed=False):
     """The body of `cigp_v10.forward_many` and `gp_basic.forward_many`: [(mean [nt_f, d], var [nt_f, 1])] in the caller's order.  Members
     that `forward_many_route` accepts (all on the GPU of the first one that does) share ONE library call; the others run
     `m.forward(x, y, x_test)` under no_grad, one after the other, and give its covariance's diagonal.  noise_of(m): the raw noise
     parameter; takes_y_var: a `[y, y_var]` member's forward uses y_var (GP_basic adds the full matrix), so it falls back -- otherwise
     y_var is dropped, as the module's forward drops it.  state (a dict, optional) receives "fused": the members that shared the call, and
     "status": per member 0 or the first non-positive pivot of its Sigma (NaN results).  Without a state dict such a member raises
-    torch.linalg.LinAlgError, as the per-model loop would."""
-    items, fused = forward_many_members(models, xs, ys, x_tests, noise_of, takes_y_var)
-    for it in items:
+    torch.linalg.LinAlgError, as the per-model loop would.
+    composed=True (`forward_many_composed`): the composed-kernel members `forward_many_tree_route` accepts share ONE call of their own
+    (`predict_tree_many`) instead of running their own forward; state["fused"] then lists the members either call served and
+    state["fused_composed"] those of the second."""
+    if composed:
+        items, fused, titems, tfused = forward_many_composed_members(models, xs, ys, x_tests, noise_of, takes_y_var)
+    else:
+        (items, fused), titems, tfused = forward_many_members(models, xs, ys, x_tests, noise_of, takes_y_var), [], []
+    for it in items + titems:
         it.update(dadd_link=dadd_link, dadd_c=dadd_c, add_noise=add_noise)
     out = [None] * len(models)
     status = [0] * len(models)
-    if items:
-        res, st = predict_raw_many(items)
-        for k, i in enumerate(fused):
-            out[i], status[i] = res[k], st[k]
+    for its, idx, call in ((items, fused, predict_raw_many), (titems, tfused, predict_tree_many)):
+        if its:
+            res, st = call(its)
+            for k, i in enumerate(idx):
+                out[i], status[i] = res[k], st[k]
     with torch.no_grad():
         for i, (m, x, y, xt) in enumerate(zip(models, xs, ys, x_tests)):
             if out[i] is None:
                 mean, cov = m.forward(x, y, xt)
                 out[i] = (mean.reshape(xt.shape[0], -1), cov.diagonal().reshape(-1, 1))
+    served = sorted(fused + tfused)
     if state is not None:
-        state["fused"], state["status"] = fused, status
+        state["fused"], state["status"] = served, status
+        if composed:
+            state["fused_composed"] = tfused
     else:
-        for i in fused:
+        for i in served:
             if status[i] > 0:
                 _raise_not_pd(status[i], "linalg.cholesky (model %d of forward_many)" % i)
     return out

@@ -1241,6 +1241,23 @@ typedef struct ffgp_predict_member {
 int ffgp_predict_small_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_links* links, const ffgp_predict_member* m,
                              int* status);
 
+/* ffgp_predict_small_batch for members on a COMPOSED kernel (csrc/predict_small_tree.hip): every p[f] carries `tree`, a ffgp_ktree of
+   2-4 leaves in the FFGP_TREE_CHAIN / FFGP_TREE_BALANCED shapes with Sum / Product nodes, leaves FFGP_KFUN_SE ... FFGP_KFUN_MATERN52
+   (w_dev one broadcast value or D) and FFGP_KFUN_LINEAR (centre at the origin, or given through center_dev) -- what
+   ffgp_train_tree_lds_raw trains, described the same way: the leaves on their RAW parameters with links[f] (center_train is not
+   read: a centre is used as it stands), or links == NULL for effective parameters and identity links (w_dev then holds D values).
+   The limits, ffgp_predict_member, var_add_noise, the status words, the return value, the grid (F, S) and FFGP_PREDICT_SPLIT are
+   ffgp_predict_small_batch's; diag_add_dev (required) is the only Sigma extra.  Sigma and K_s are formed entry by entry as the
+   one-launch tree trainer forms Sigma (X as given, per leaf sum_k w_ek^2 (x_ik - x_jk)^2 or sum_k w_ek^2 (x_ik - c_k)(x_jk - c_k),
+   then the tree node by node), and var_dev[nt] = k(x, x) - colsum(V^2) [+ noise] with k(x, x) the tree on the leaves' self values,
+   formed per test point (a linear leaf's depends on it).  A point's results do not depend on S, on its tile or on the other points
+   and members of the call, bit for bit; a member whose Sigma is not positive definite stops alone (status, NaN outputs).
+   FFGP_ERR_ARG -- before anything is enqueued or written -- for what ffgp_predict_small_batch refuses, tree == NULL or of another
+   form, a FFGP_KFUN_RQ leaf, a leaf without w_dev / amp_dev, diag_vec_dev, a missing diag_add_dev.  Synchronous; the handle's
+   cached factors stay valid.                                                                                                  */
+int ffgp_predict_small_tree_batch(ffgp_handle* h, int F, const ffgp_problem* p, const ffgp_tree_links* links, const ffgp_predict_member* m,
+                                  int* status);
+
 /* ---- multi-GPU: the joint likelihood of sharded blocks --------------------------------------------------- */
 /* buf_dev[0..count) <- element-wise SUM over the ranks of `comm` (in place, fp64), enqueued on the handle's stream: the ONE
    collective of the per-fidelity sharding -- the F-vector of per-block values, `loss += cigp_list[f].compute_loss(...)`
